@@ -1,7 +1,17 @@
 """Benchmark: Mrays/s of the MI355X wavefront path tracer on BASELINE.json's
 headline workload, next to the reference CPU algorithm timed on this host.
 
-    python bench.py [--gpus N --steps K --warmup W] [--workload C3|C2|C4|C5]
+    python bench.py [--gpus N --steps K --warmup W] [--workload C3|C2|C4|C5] [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times the K steps and prints the result line
+(the headline Mrays/s, ms_per_step, the event counts of the last timed render
+and the pipeline roofline derived from them).  --full adds what takes runs of
+its own: the CPU baseline and the parity check against the oracle, and the
+profiled render behind the k_extend roofline and the per-kernel times.
+--dump-outputs DIR writes the last timed step's float accumulator (rank 0:
+the frame assembled from the gather at N > 1) as DIR/accumulator.npy; the
+frames a step renders depend on --warmup and --steps only, so two builds run
+with the same arguments are comparable value for value.
 
 Workloads (BASELINE.json configs):
   C3  bundled indoor scene, 1280x720, 256 spp, unbounded bounces + Russian roulette (headline)
@@ -19,7 +29,7 @@ gathered to rank 0 over RCCL once per render; the total work is fixed, so
 scaling is "strong".  Mrays/s = W*H*spp*steps / seconds / 1e6 (main.cpp:431:
 camera samples per second).
 
-The CPU baseline (rank 0, N = 1) is the oracle's restatement of the
+The CPU baseline (--full; rank 0, N = 1) is the oracle's restatement of the
 reference's CPU renderer (oracle/cpu_ref_bench, OpenMP rows like
 renderer.cpp:163) on bounded samples of the last timed step's frames, timed
 twice: at the environment's thread share over every --cpu-row-step-th row (its
@@ -77,6 +87,10 @@ def parse():
     ap.add_argument("--steps", type=int, default=3, help="timed renders")
     ap.add_argument("--warmup", type=int, default=1, help="untimed renders before the timed region")
     ap.add_argument("--workload", choices=sorted(WORKLOADS), default="C3")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the CPU baseline + parity check and the profiled render (roofline, per-kernel ms)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="write the last timed step's accumulator as DIR/accumulator.npy (float32, H x W x 4)")
     ap.add_argument("--width", type=int, default=0, help="override the workload's width")
     ap.add_argument("--height", type=int, default=0, help="override the workload's height")
     ap.add_argument("--spp", type=int, default=0, help="override the workload's samples per pixel (frames per render)")
@@ -84,12 +98,12 @@ def parse():
                     help="N > 1: rows per interleaved shard block (1 spreads the long-path-heavy rows over all GPUs)")
     ap.add_argument("--cpu-threads", type=int, default=0, help="0: the lease's CPU share (OMP_NUM_THREADS, else the affinity mask)")
     ap.add_argument("--cpu-row-step", type=int, default=0, help="CPU sample: every n-th row of the last step's frames")
-    ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--no-cpu", action="store_true", help="--full without the CPU baseline and the parity check")
     ap.add_argument("--cpu-full-host", type=int, default=1,
                     help="also time the CPU baseline on every CPU of the affinity mask: 1 (default) unless the cgroup "
                          "CPU quota already equals the lease's threads, 2 always, 0 never")
     ap.add_argument("--profile-pass", type=int, default=1,
-                    help="renders re-run with per-kernel HIP events for the roofline (0 = none)")
+                    help="--full: renders re-run with per-kernel HIP events for the roofline (0 = none)")
     ap.add_argument("--tail", type=str, default="", help="tuning: drain policy 'threshold,lanes_per_wave,stage_segments'")
     ap.add_argument("--tail-coop", type=int, default=-1, help="tuning: cooperative drain when <= N paths remain")
     ap.add_argument("--pool", type=int, default=0, help="tuning: paths in flight (0: the library default, 5 frames)")
@@ -236,6 +250,8 @@ def rocprof_summary(workload):
 
 def main():
     args = parse()
+    if args.steps < 1 or args.warmup < 0:
+        sys.exit("bench.py: --steps must be >= 1 and --warmup >= 0")
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
@@ -316,15 +332,25 @@ def main():
         dist.all_reduce(evt)
         ev = {k: int(v) for k, v in zip(ev, evt.tolist())}
     gpu_acc = None
-    if rank == 0 and not args.no_cpu:
+    check = args.full and not args.no_cpu
+    if rank == 0 and (check or args.dump_outputs):
         # N > 1: the frame assembled from the last step's gather (every rank's rows)
         gpu_acc = r.accumulator() if world == 1 else gather.assemble()
+    dumped = None
+    if gpu_acc is not None and args.dump_outputs:
+        import numpy as np
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "accumulator.npy"), np.ascontiguousarray(gpu_acc, dtype=np.float32))
+        dumped = {"accumulator.npy": {"shape": list(gpu_acc.shape), "dtype": "float32",
+                                      "frames": [last_first, last_first + SPP]}}
+    if not check:
+        gpu_acc = None
     samples_per_render = W * H * SPP
     value = samples_per_render * args.steps / dt / 1e6
 
     # ---- roofline of the dominant wavefront kernel (k_extend), HIP events on the render stream ----
     roof = kernel_ms = None
-    if args.profile_pass > 0:
+    if args.full and args.profile_pass > 0:
         r.set_profiling(True)
         for i in range(args.profile_pass):
             r.clear_accumulator()
@@ -402,6 +428,7 @@ def main():
             "n_gpus": world,
             "steps": args.steps,
             "warmup": args.warmup,
+            "full": args.full,
             "ms_per_step": round(dt / args.steps * 1e3, 3),
             "higher_is_better": True,
             "scaling": "strong",
@@ -432,6 +459,7 @@ def main():
             "tail_paths_per_render": ev["tail_paths"],
             "kernel_ms_profile_pass": kernel_ms,
             "scene_build_s": round(scene_build_s, 3),
+            "dumped_outputs": dumped,
         }
         print(json.dumps(out))
     if dist_on:

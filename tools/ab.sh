@@ -3,7 +3,7 @@
 #   tools/ab.sh [-t] [-c] [-s] [-n] [-r REPS] OUT 'name|ENV=V,ENV=V|--bench-opts' ...
 #   -t  the -m gpu suite once first (defaults)       -c  lone-chain latency (tools/chain_probe.py)
 #   -s  8-shard shard-1 breakdown (tools/shard_breakdown.py 8 1)
-#   -n  no bench line (default: one bench.py line without the CPU leg: --steps 3 --warmup 1 + opts)
+#   -n  no bench line (default: one bench.py --full line without the CPU leg: --steps 3 --warmup 1 + opts)
 #   -r  repetitions of the whole variant list (interleaved A B A B ...)
 # A library build is a variant too: 'timing|SURF_HIP_LIB=surf-path-tracer_amd/lib/variants/timing.so|'.
 # Examples (DESIGN.md cites these): the two-level walk A/B
@@ -38,7 +38,7 @@ for rep in $(seq 1 "$reps"); do
       line="$line shard8/1_ms $(sed -n 3p "$OUT/$tag.shard.txt" | python3 -c 'import json,sys;print(json.loads(sys.stdin.read())["wall_ms"])')"
     fi
     if [ $bench = 1 ]; then
-      run timeout -k 10 400 python bench.py --no-cpu --steps 3 --warmup 1 $opts > "$OUT/$tag.json" 2> "$OUT/$tag.err" || exit 1
+      run timeout -k 10 400 python bench.py --full --no-cpu --steps 3 --warmup 1 $opts > "$OUT/$tag.json" 2> "$OUT/$tag.err" || exit 1
       line="$line $(python3 -c "import json;j=json.load(open('$OUT/$tag.json'));k=j['kernel_ms_profile_pass'];print(j['value'], 'ext', k['ms_extend'], 'shade', k['ms_shade'], 'conn', k['ms_connect'], 'tail', k['ms_tail'], k['tail_paths'], 'it', j['iterations_per_render'])")"
     fi
     echo "$line"

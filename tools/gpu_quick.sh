@@ -10,5 +10,5 @@ timeout -k 10 120 python tools/chain_probe.py > "$OUT/chain.txt" 2>&1 || exit 1
 tail -1 "$OUT/chain.txt"
 timeout -k 10 200 python tools/shard_breakdown.py 8 1 > "$OUT/shard.txt" 2>&1 || exit 1
 sed -n 2,3p "$OUT/shard.txt"
-timeout -k 10 300 python bench.py --no-cpu > "$OUT/bench.json" 2> "$OUT/bench.err" || exit 1
+timeout -k 10 300 python bench.py --full --no-cpu > "$OUT/bench.json" 2> "$OUT/bench.err" || exit 1
 python3 -c "import json;j=json.load(open('$OUT/bench.json'));print(j['value'], j['kernel_ms_profile_pass'])"

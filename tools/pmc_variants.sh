@@ -15,7 +15,7 @@ for v in "$@"; do
   for pass in "${PL[@]}"; do
     ( IFS=,; for e in $envs; do [ -n "$e" ] && export "$e"; done; unset IFS
       timeout -s KILL 240 rocprofv3 --pmc $pass --output-format csv -d "$OUT/${name}_p$k" -o run -- \
-        python3 bench.py --steps 1 --warmup 0 --no-cpu $opts > "$OUT/${name}_p$k.json" 2> "$OUT/${name}_p$k.err" ) || exit 1
+        python3 bench.py --full --steps 1 --warmup 0 --no-cpu $opts > "$OUT/${name}_p$k.json" 2> "$OUT/${name}_p$k.err" ) || exit 1
     k=$((k + 1))
   done
 done

@@ -38,14 +38,14 @@ line() {   # bench JSON -> one summary line
 benches() {
     local b=$OUT/bench
     mkdir -p "$b"
-    timeout -k 10 400 python bench.py > "$b/bench_c3.json" 2> "$b/bench_c3.err" || { tail -5 "$b/bench_c3.err"; return 1; }
+    timeout -k 10 400 python bench.py --full > "$b/bench_c3.json" 2> "$b/bench_c3.err" || { tail -5 "$b/bench_c3.err"; return 1; }
     line "$b/bench_c3.json" C3
     for wl in C2 C4 C5; do
-        timeout -k 10 500 python bench.py --workload $wl > "$b/bench_${wl,,}.json" 2> "$b/bench_${wl,,}.err" || { tail -5 "$b/bench_${wl,,}.err"; return 1; }
+        timeout -k 10 500 python bench.py --full --workload $wl > "$b/bench_${wl,,}.json" 2> "$b/bench_${wl,,}.err" || { tail -5 "$b/bench_${wl,,}.err"; return 1; }
         line "$b/bench_${wl,,}.json" $wl
     done
     SURF_BENCH_BACKEND=gloo timeout -k 10 400 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 \
-        --master-port 29517 bench.py --gpus 2 --steps 2 --warmup 1 > "$b/dist_n2.json" 2> "$b/dist_n2.err" || { tail -5 "$b/dist_n2.err"; return 1; }
+        --master-port 29517 bench.py --full --gpus 2 --steps 2 --warmup 1 > "$b/dist_n2.json" 2> "$b/dist_n2.err" || { tail -5 "$b/dist_n2.err"; return 1; }
     line "$b/dist_n2.json" N2
     timeout -k 10 300 python tools/shard_probe.py 8 > "$b/shards8_c3.txt" 2>&1 || return 1
     tail -1 "$b/shards8_c3.txt"
