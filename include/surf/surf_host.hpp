@@ -339,8 +339,13 @@ public:
     std::vector<U32> finalizeRGBA8();             /* width*height RGBA8 words */
     std::vector<U32> displayRGBA8();              /* finalize image through fs_quad.frag's sqrt gamma */
     void synchronize();                           /* waits until every frame rendered so far is accumulated */
+    /* first-hit feature buffers of the current camera and scene state (surf_read_aov;
+     * width*height*4 values each): a float plane (position, normal or albedo), and the id plane */
+    std::vector<F32> readAOV(surf_aov plane);
+    std::vector<U32> readAOVIds();
     surf_ctx* handle() const { return m_ctx; }
 private:
+    void pushSceneAndCamera();                    /* what render() re-reads per frame: instance updates, the camera */
     surf_ctx* m_ctx = nullptr;
     RendererConfig m_config;
     FramebufferSize m_resolution;

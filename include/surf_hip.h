@@ -314,6 +314,40 @@ int surf_pack_rgba8(const float* acc, uint32_t n, float inv_samples, int display
 int surf_get_stats(surf_ctx* ctx, surf_stats* out);
 int surf_synchronize(surf_ctx* ctx);
 
+/* ---- first-hit feature buffers (AOVs) ----
+ * What a denoiser, compositor or picking tool reads beside the radiance: per
+ * pixel, the first hit of the pixel's unjittered camera ray -- from the camera
+ * position through the pixel's corner ((x, row) / resolution on the view
+ * plane, the ray the issue order's pixel classes use), WITHOUT jitter and
+ * WITHOUT a lens sample even when the camera has a defocus angle: the planes
+ * are sharp and noise-free.  No reference counterpart.  Four planes of
+ * rows*width 16-byte records, shard row order like the accumulator:
+ *   SURF_AOV_POSITION float4  hit (o + t*d, t)                 miss (0, 0, 0, 1e30)
+ *   SURF_AOV_NORMAL   float4  hit (N, 0): the shading normal the path tracer
+ *                             uses -- M * (u*n0 + v*n2 + w*n1, 0) normalized as a
+ *                             vec4 (M, not its inverse transpose: Instance::normal),
+ *                             turned against the ray; emitters too -- miss 0
+ *   SURF_AOV_ALBEDO   float4  hit (albedo, 1); emitter (emission_strength *
+ *                             emission_color, 1); miss (background along d, 0)
+ *   SURF_AOV_ID       uint4   hit (instance, primitive, material index, 0)
+ *                             miss (~0, ~0, ~0, 0)
+ * All four are computed by one kernel on the first read and cached until
+ * surf_set_camera changes the camera, surf_upload_scene or
+ * surf_update_instances; the device buffers are allocated on first use
+ * (SURF_ERR_OOM when that fails, SURF_ERR_NO_SCENE before a scene and a camera
+ * are set, SURF_ERR_INVALID for a NULL argument or a plane outside 0..3).
+ * A read never changes the sample stream: the accumulator and the event
+ * counters after further renders are what they would be without it. */
+typedef enum {
+    SURF_AOV_POSITION = 0, SURF_AOV_NORMAL = 1, SURF_AOV_ALBEDO = 2, SURF_AOV_ID = 3, SURF_AOV_COUNT = 4
+} surf_aov;
+int surf_read_aov(surf_ctx* ctx, int plane, void* out);     /* host buffer, rows*width*16 bytes */
+/* Device-to-device copy of a plane (dst on the same device, rows*width*16 bytes). */
+int surf_copy_aov_device(surf_ctx* ctx, int plane, void* dst_device);
+/* Diagnostics: device time (HIP events) of the last feature-buffer kernel
+ * launch, 0 before the first.  No reference counterpart. */
+int surf_debug_aov_time(surf_ctx* ctx, float* kernel_ms);
+
 /* ---- traversal entry points (kernel-level parity tests) ----
  * n world-space rays, o/d 3 floats each.  closest: depth starts at 1e30;
  * writes t,u,v (floats) and inst,prim (u32, ~0 on miss).  any: tmax per ray,
@@ -350,6 +384,12 @@ void surf_scene_destroy(surf_scene* scene);
  * swapchain; these are its on-disk equivalent. */
 int surf_write_ppm(const char* path, uint32_t width, uint32_t height, const uint32_t* rgba8);
 int surf_write_png(const char* path, uint32_t width, uint32_t height, const uint32_t* rgba8);
+/* Float image file: a colour PFM ("PF\n<width> <height>\n-1.0\n", then the
+ * rows BOTTOM to top, RGB as little-endian f32) of an RGBA float image given
+ * rows top to bottom (the accumulator, a float feature plane); alpha is
+ * dropped, the values are written bit for bit.  SURF_ERR_IO when the path
+ * cannot be written. */
+int surf_write_pfm(const char* path, uint32_t width, uint32_t height, const float* rgba);
 
 /* Mesh::Mesh(path) (sources/mesh.cpp:69-154, tinyobjloader triangulate=true):
  * .obj or .obj.gz parsed in parallel chunks (threads = 0: default count).  The

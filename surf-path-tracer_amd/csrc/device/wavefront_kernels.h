@@ -2289,6 +2289,25 @@ __device__ __forceinline__ void sampleNEE(const DevScene& S, const ShadeTables& 
     }
 }
 
+/* Shading normal of a hit (Instance::normal, bvh.cpp: M (u n0 + v n2 + w n1, 0)
+ * -- M, not its inverse transpose -- then glm::normalize(vec4)), turned
+ * against the ray direction d (renderer.cpp's `if (dot(d, N) > 0) N = -N`).
+ * shadePath and k_aov share it. */
+__device__ __forceinline__ V3 hitNormal(const DevScene& S, const DevInstance& I, uint32_t prim, float hu, float hv, V3 d) {
+    const float4* nr = S.normals + 3u * (I.triOffset + prim);
+    const float4 n0 = nr[0], n1 = nr[1], n2 = nr[2];
+    const float w = (1.0f - hu) - hv;
+    const V3 no = add(add(lscl(hu, xyz(n0)), lscl(hv, xyz(n2))), lscl(w, xyz(n1)));
+    const float* M = I.M;
+    const float nx4 = mrow(M, 0, no.x, no.y, no.z, 0.0f), ny4 = mrow(M, 1, no.x, no.y, no.z, 0.0f);
+    const float nz4 = mrow(M, 2, no.x, no.y, no.z, 0.0f), nw4 = mrow(M, 3, no.x, no.y, no.z, 0.0f);
+    const float nn = (nx4 * nx4 + ny4 * ny4) + (nz4 * nz4 + nw4 * nw4);
+    const float ninv = 1.0f / sqrtf(nn);
+    V3 N = mk3(nx4 * ninv, ny4 * ninv, nz4 * ninv);
+    if (dot(d, N) > 0.0f) N = scl(N, -1.0f);
+    return N;
+}
+
 template <bool SPEC = false>
 __device__ __forceinline__ void shadePath(const DevScene& S, const ShadeTables& Tb, float4 o4, float4 d4, float4 T4, float4 h4,
                                           uint32_t inst, uint32_t maxSeg, uint32_t zeroCutoff, ShadeOut& r) {
@@ -2333,22 +2352,11 @@ __device__ __forceinline__ void shadePath(const DevScene& S, const ShadeTables& 
         medium = mk3(gExpf(m.absorb[0] * nd), gExpf(m.absorb[1] * nd), gExpf(m.absorb[2] * nd));
     }
     const V3 P = add(o, lscl(t, d));
-    /* Instance::normal: M (u n0 + v n2 + w n1, 0), glm::normalize(vec4) */
-    const float4* nr = S.normals + 3u * (I.triOffset + prim);
-    const float4 n0 = nr[0], n1 = nr[1], n2 = nr[2];
-    const float w = (1.0f - hu) - hv;
-    const V3 no = add(add(lscl(hu, xyz(n0)), lscl(hv, xyz(n2))), lscl(w, xyz(n1)));
-    const float* M = I.M;
-    const float nx4 = mrow(M, 0, no.x, no.y, no.z, 0.0f), ny4 = mrow(M, 1, no.x, no.y, no.z, 0.0f);
-    const float nz4 = mrow(M, 2, no.x, no.y, no.z, 0.0f), nw4 = mrow(M, 3, no.x, no.y, no.z, 0.0f);
-    const float nn = (nx4 * nx4 + ny4 * ny4) + (nz4 * nz4 + nw4 * nw4);
-    const float ninv = 1.0f / sqrtf(nn);
-    V3 N = mk3(nx4 * ninv, ny4 * ninv, nz4 * ninv);
+    const V3 N = hitNormal(S, I, prim, hu, hv, d);
     const float rng = rndF(seed);
     V3 R = mk3(0.0f, 0.0f, 0.0f);
     bool nextMedium = inMedium;
     bool alive = true;
-    if (dot(d, N) > 0.0f) N = scl(N, -1.0f);
     if (rng < m.refl) {
         R = sub(d, lscl(2.0f * dot(N, d), N));
         lastSpecular = true;
@@ -3251,6 +3259,79 @@ __global__ __launch_bounds__(kBlock) void k_trace_any(DevScene S, const float* _
     uint32_t inst = kUnset, prim = kUnset;
     occ[i] = traceScene<true, LW>(S, Tt, mk3(o[3 * i], o[3 * i + 1], o[3 * i + 2]), mk3(d[3 * i], d[3 * i + 1], d[3 * i + 2]),
                               depth, u, v, inst, prim, lds + threadIdx.x, blockDim.x) ? 1 : 0;
+}
+
+/* First-hit feature buffers (AOVs, surf_read_aov): one lane per shard pixel lp
+ * traces the pixel's unjittered camera ray -- through the pixel's corner
+ * (x, row), from the camera position: no jitter and no lens sample, also for a
+ * camera with a defocus angle, so the planes are sharp and carry no noise --
+ * and writes four planar 16-byte records:
+ *   pos[lp]  hit: (o + t d, t)                           miss: (0, 0, 0, 1e30)
+ *   nrm[lp]  hit: (shadePath's N, 0), emitters included   miss: 0
+ *   alb[lp]  hit: (albedo, 1); emitter: (strength * colour, 1)
+ *                                                        miss: (background along d, 0)
+ *   ids[lp]  hit: (instance, primitive, material, 0)     miss: (~0, ~0, ~0, 0)
+ * The expressions are shadePath's / classifyPixels' term by term (f32, no
+ * contraction), so a host restatement reproduces every plane bit for bit.
+ * The tables are staged as k_trace_closest (dynamic LDS: stack, TraceInst,
+ * TLAS order) and k_shade (static LDS) stage them, by every lane of the block
+ * before the lanes past the last pixel leave.  Reads the scene and the camera
+ * only: no Counters, no pool, nothing of the captured graph. */
+template <bool LDS, bool LW = false>
+__global__ __launch_bounds__(kBlock) void k_aov(DevScene S, DevCamera cam, const uint32_t* __restrict__ rows, uint32_t width,
+                                                uint32_t npx, float4* __restrict__ pos, float4* __restrict__ nrm,
+                                                float4* __restrict__ alb, uint4* __restrict__ ids, uint32_t stackWords) {
+    extern __shared__ uint32_t lds[];
+    __shared__ DevInstance sInst[LDS ? kLdsInst : 1];
+    __shared__ DevMaterial sMat[LDS ? kLdsMats : 1];
+    __shared__ uint2 sLights[LDS ? kLdsLights : 1];
+    const TraceTables Tt = traceTables<LDS>(S, lds, stackWords);
+    ShadeTables Tb{S.inst, S.mats, S.lights};
+    if (LDS) {
+        stageTables(S, sInst, sMat, sLights);
+        Tb = ShadeTables{sInst, sMat, sLights};
+    }
+    const uint32_t lp = blockIdx.x * blockDim.x + threadIdx.x;
+    if (lp >= npx) return;
+    const uint32_t rowi = lp / width;
+    const uint32_t x = lp - rowi * width;
+    const uint32_t row = rows[rowi];
+    const float u = (float)x * cam.invW, v = (float)row * cam.invH;
+    const V3 o = ld3(cam.pos);
+    const V3 dir = sub(add(add(ld3(cam.firstPixel), lscl(u, ld3(cam.uVec))), lscl(v, ld3(cam.vVec))), o);
+    const float len2 = ((0.0f + dir.x * dir.x) + dir.y * dir.y) + dir.z * dir.z;
+    const float inv = 1.0f / sqrtf(len2);
+    const V3 d = scl(dir, inv);
+    float depth = kFarAway, hu = 0.0f, hv = 0.0f;
+    uint32_t inst = kUnset, prim = kUnset;
+    const bool hit = traceScene<false, LW>(S, Tt, o, d, depth, hu, hv, inst, prim, lds + threadIdx.x, blockDim.x);
+    float4 oP = make_float4(0.0f, 0.0f, 0.0f, kFarAway), oN = make_float4(0.0f, 0.0f, 0.0f, 0.0f), oA;
+    uint4 oI = make_uint4(kUnset, kUnset, kUnset, 0u);
+    if (hit) {
+        const DevInstance& I = Tb.inst[inst];
+        const DevMaterial& m = Tb.mats[I.material];
+        const V3 P = add(o, lscl(depth, d));
+        const V3 N = hitNormal(S, I, prim, hu, hv, d);
+        const bool isLight = m.emit > 0.0f && (m.ec[0] > 0.0f || m.ec[1] > 0.0f || m.ec[2] > 0.0f);
+        const V3 a = isLight ? lscl(m.emit, ld3(m.ec)) : ld3(m.albedo);
+        oP = make_float4(P.x, P.y, P.z, depth);
+        oN = make_float4(N.x, N.y, N.z, 0.0f);
+        oA = make_float4(a.x, a.y, a.z, 1.0f);
+        oI = make_uint4(inst, prim, I.material, 0u);
+    } else {
+        /* SceneBackground along d (scene.cpp:35-51), shadePath's miss */
+        V3 bg = mk3(0.0f, 0.0f, 0.0f);
+        if (S.bgType == 0u) bg = ld3(S.bgColor);
+        else if (S.bgType == 1u) {
+            const float a = 0.5f * (1.0f + d.y);
+            bg = add(lscl(a, ld3(S.bgB)), lscl(1.0f - a, ld3(S.bgA)));
+        }
+        oA = make_float4(bg.x, bg.y, bg.z, 0.0f);
+    }
+    pos[lp] = oP;
+    nrm[lp] = oN;
+    alb[lp] = oA;
+    ids[lp] = oI;
 }
 
 /* Cooperative traversal entry points (one ray per 64-lane block, the

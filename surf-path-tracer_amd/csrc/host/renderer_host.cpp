@@ -42,7 +42,7 @@ void WaveFrontRenderer::clearAccumulator() {
     m_energyStale = false;
 }
 
-void WaveFrontRenderer::render(F32 /*deltaTime*/) {
+void WaveFrontRenderer::pushSceneAndCamera() {
     if (m_scene.generation() != m_sceneGeneration) {
         /* GPUScene::update (scene.cpp:267-282) re-uploads the instance records,
          * TLAS indices and TLAS nodes; geometry and BLASes stay resident */
@@ -54,6 +54,10 @@ void WaveFrontRenderer::render(F32 /*deltaTime*/) {
     }
     const CameraUBO ubo = m_camera.toUBO();
     check(surf_set_camera(m_ctx, &ubo), m_ctx, "surf_set_camera");
+}
+
+void WaveFrontRenderer::render(F32 /*deltaTime*/) {
+    pushSceneAndCamera();
     /* one frame of samplesPerFrame samples, seeded from the running sample
      * count, its samples chaining their RNG state (renderer.cpp:160-188) */
     const U32 spp = m_config.samplesPerFrame ? m_config.samplesPerFrame : 1u;
@@ -88,6 +92,24 @@ std::vector<F32> WaveFrontRenderer::readAccumulator() {
 std::vector<U32> WaveFrontRenderer::finalizeRGBA8() {
     std::vector<U32> out((size_t)m_resolution.width * m_resolution.height);
     check(surf_finalize_rgba8(m_ctx, out.data()), m_ctx, "surf_finalize_rgba8");
+    return out;
+}
+
+/* The feature buffers follow the camera and the scene as the next render()
+ * would see them (also before the first render() call). */
+std::vector<F32> WaveFrontRenderer::readAOV(surf_aov plane) {
+    if (plane != SURF_AOV_POSITION && plane != SURF_AOV_NORMAL && plane != SURF_AOV_ALBEDO)
+        throw std::runtime_error("readAOV: not a float plane (the id plane is readAOVIds)");
+    pushSceneAndCamera();
+    std::vector<F32> out((size_t)m_resolution.width * m_resolution.height * 4);
+    check(surf_read_aov(m_ctx, plane, out.data()), m_ctx, "surf_read_aov");
+    return out;
+}
+
+std::vector<U32> WaveFrontRenderer::readAOVIds() {
+    pushSceneAndCamera();
+    std::vector<U32> out((size_t)m_resolution.width * m_resolution.height * 4);
+    check(surf_read_aov(m_ctx, SURF_AOV_ID, out.data()), m_ctx, "surf_read_aov");
     return out;
 }
 

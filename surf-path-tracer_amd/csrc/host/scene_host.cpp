@@ -1259,6 +1259,26 @@ int surf_write_png(const char* path, uint32_t width, uint32_t height, const uint
     return (fclose(f) == 0 && ok) ? SURF_OK : SURF_ERR_IO;
 }
 
+int surf_write_pfm(const char* path, uint32_t width, uint32_t height, const float* rgba) {
+    if (!path || !rgba || width == 0 || height == 0) return SURF_ERR_INVALID;
+    FILE* f = fopen(path, "wb");
+    if (!f) return SURF_ERR_IO;
+    bool ok = fprintf(f, "PF\n%u %u\n-1.0\n", width, height) > 0;
+    /* f32 words as bytes, least significant first, whatever the host's order */
+    std::vector<unsigned char> row((size_t)width * 12);
+    for (uint32_t y = height; y-- > 0 && ok;) {
+        for (uint32_t x = 0; x < width; ++x)
+            for (uint32_t ch = 0; ch < 3; ++ch) {
+                uint32_t bits;
+                memcpy(&bits, &rgba[((size_t)y * width + x) * 4 + ch], 4);
+                unsigned char* b = &row[((size_t)x * 3 + ch) * 4];
+                b[0] = (unsigned char)bits; b[1] = (unsigned char)(bits >> 8); b[2] = (unsigned char)(bits >> 16); b[3] = (unsigned char)(bits >> 24);
+            }
+        ok = fwrite(row.data(), 1, row.size(), f) == row.size();
+    }
+    return (fclose(f) == 0 && ok) ? SURF_OK : SURF_ERR_IO;
+}
+
 struct surf_mesh { surf::Mesh mesh; };
 
 int surf_obj_load(const char* path, uint32_t threads, surf_mesh** out) {

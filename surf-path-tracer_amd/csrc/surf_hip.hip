@@ -105,6 +105,12 @@ struct surf_ctx {
     bool reorder = true;
     bool permValid = false;
     uint32_t* dPerm = nullptr;
+    /* first-hit feature buffers (surf_read_aov): four planes of npx 16-byte
+     * records, allocated on first use; valid until the camera, the scene or
+     * the instances change (where permValid is cleared) */
+    void* aov[SURF_AOV_COUNT] = {};
+    bool aovValid = false;
+    float aovKernelMs = 0.0f;      /* device time of the last k_aov launch (surf_debug_aov_time) */
     /* one-frame render calls may leave up to a pool of their stream unissued
      * (SURF_LOOP_LAG=0: issue each call's frame before returning) */
     bool loopLag = true;
@@ -697,6 +703,36 @@ int classifyPixels(surf_ctx* c) {
     return SURF_OK;
 }
 
+/* The four feature planes (k_aov), computed on first use and kept until the
+ * camera, the scene or the instances change.  One launch on the render
+ * stream, behind whatever replays are in flight: the kernel reads the scene
+ * and the camera only, so the sample stream is neither drained nor touched. */
+int ensureAov(surf_ctx* c) {
+    if (!c->hasScene) return fail(c, SURF_ERR_NO_SCENE, "no scene uploaded");
+    if (!c->hasCamera) return fail(c, SURF_ERR_NO_SCENE, "no camera set");
+    SURF_CHECK(c, hipSetDevice(c->device));
+    if (c->aovValid) return SURF_OK;
+    for (void*& p : c->aov)
+        if (!p && (hipMalloc(&p, (size_t)c->npx * 16) != hipSuccess || !p)) {
+            p = nullptr;
+            (void)hipGetLastError();
+            return fail(c, SURF_ERR_OOM, "hipMalloc of a feature plane (" + std::to_string((size_t)c->npx * 16) + " bytes) failed");
+        }
+    SURF_CHECK(c, hipEventRecord(c->ev0, c->stream));
+    hipLaunchKernelGGL(c->S.laneW ? (c->ldsTables ? k_aov<true, true> : k_aov<false, true>)
+                                  : (c->ldsTables ? k_aov<true, false> : k_aov<false, false>),
+                       dim3((c->npx + kBlock - 1) / kBlock), dim3(kBlock), traversalLds(c, kBlock), c->stream,
+                       c->S, c->cam, (const uint32_t*)c->dRows, c->width, c->npx, static_cast<float4*>(c->aov[SURF_AOV_POSITION]),
+                       static_cast<float4*>(c->aov[SURF_AOV_NORMAL]), static_cast<float4*>(c->aov[SURF_AOV_ALBEDO]),
+                       static_cast<uint4*>(c->aov[SURF_AOV_ID]), stackWords(c, kBlock));
+    SURF_CHECK(c, hipGetLastError());
+    SURF_CHECK(c, hipEventRecord(c->ev1, c->stream));
+    SURF_CHECK(c, hipEventSynchronize(c->ev1));
+    (void)hipEventElapsedTime(&c->aovKernelMs, c->ev0, c->ev1);
+    c->aovValid = true;
+    return SURF_OK;
+}
+
 /* ---- sample stream ------------------------------------------------------ */
 int startStream(surf_ctx* c, uint64_t baseFrame, uint32_t maxSeg, uint32_t frames, uint32_t spp) {
     Counters h{};
@@ -1280,6 +1316,7 @@ void surf_destroy(surf_ctx* c) {
     if (c->hPhaseN) (void)hipHostFree(c->hPhaseN);
     if (c->phaseLog) std::fclose(c->phaseLog);
     if (c->acc) (void)hipFree(c->acc);
+    for (void*& p : c->aov) { if (p) (void)hipFree(p); p = nullptr; }
     if (c->dRows) (void)hipFree(c->dRows);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
@@ -1428,6 +1465,7 @@ struct InstanceTables {
 void setKeys(surf_ctx* c, DevScene& S, const InstanceTables& T) {
     c->heavyInst.assign(T.hvInst, T.hvInst + T.nHeavy);
     c->permValid = false;                 /* the pixel classes follow the instances */
+    c->aovValid = false;                  /* ... and so do the feature buffers */
     S.nHeavy = T.nHeavy;
     for (uint32_t h = 0; h < 3; ++h) {
         S.hvLo[h] = h < T.nHeavy ? T.hvLo[h] : make_float4(0, 0, 0, 0);
@@ -1888,6 +1926,7 @@ int surf_set_camera(surf_ctx* c, const surf_camera_ubo* u) {
     k.diskV[0] = dv.x; k.diskV[1] = dv.y; k.diskV[2] = dv.z;
     c->cam = k;
     c->permValid = false;
+    c->aovValid = false;
     c->camUbo = *u;
     c->hasCamera = true;
     destroyGraph(c);     /* camera is a kernel argument of the captured graph */
@@ -1979,6 +2018,30 @@ int surf_copy_accumulator_device(surf_ctx* c, void* dst) {
     if (rc) return rc;
     SURF_CHECK(c, hipMemcpyAsync(dst, c->acc, (size_t)c->npx * sizeof(float4), hipMemcpyDeviceToDevice, c->stream));
     SURF_CHECK(c, hipStreamSynchronize(c->stream));
+    return SURF_OK;
+}
+
+int surf_read_aov(surf_ctx* c, int plane, void* out) {
+    if (!c || !out || plane < 0 || plane >= SURF_AOV_COUNT) return SURF_ERR_INVALID;
+    int rc = ensureAov(c);
+    if (rc) return rc;
+    SURF_CHECK(c, hipMemcpyAsync(out, c->aov[plane], (size_t)c->npx * 16, hipMemcpyDeviceToHost, c->stream));
+    SURF_CHECK(c, hipStreamSynchronize(c->stream));
+    return SURF_OK;
+}
+
+int surf_copy_aov_device(surf_ctx* c, int plane, void* dst) {
+    if (!c || !dst || plane < 0 || plane >= SURF_AOV_COUNT) return SURF_ERR_INVALID;
+    int rc = ensureAov(c);
+    if (rc) return rc;
+    SURF_CHECK(c, hipMemcpyAsync(dst, c->aov[plane], (size_t)c->npx * 16, hipMemcpyDeviceToDevice, c->stream));
+    SURF_CHECK(c, hipStreamSynchronize(c->stream));
+    return SURF_OK;
+}
+
+int surf_debug_aov_time(surf_ctx* c, float* kernel_ms) {
+    if (!c || !kernel_ms) return SURF_ERR_INVALID;
+    *kernel_ms = c->aovKernelMs;
     return SURF_OK;
 }
 

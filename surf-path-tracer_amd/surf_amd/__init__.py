@@ -12,6 +12,7 @@ Mirrors the reference interface for the hot path:
     .accumulator()             float RGBA accumulator (rows of this shard)
     .finalize_rgba8()          wavefront_finalize.comp + RgbaToU32
     .trace_closest/.trace_any  ray_extend / ray_connect traversal (tests)
+    .aov()                     first-hit feature buffers (no reference counterpart)
 """
 from __future__ import annotations
 
@@ -125,6 +126,9 @@ def load() -> C.CDLL:
         "surf_obj_load": ([C.c_char_p, U32, C.POINTER(P)], I32),
         "surf_write_ppm": ([C.c_char_p, U32, U32, P], I32), "surf_write_png": ([C.c_char_p, U32, U32, P], I32),
         "surf_display_rgba8": ([P, P], I32),
+        "surf_read_aov": ([P, I32, P], I32), "surf_copy_aov_device": ([P, I32, P], I32),
+        "surf_debug_aov_time": ([P, C.POINTER(F)], I32),
+        "surf_write_pfm": ([C.c_char_p, U32, U32, P], I32),
         "surf_mesh_data": ([P, C.POINTER(P), C.POINTER(P), C.POINTER(U32)], I32),
         "surf_mesh_destroy": ([P], None),
         "surf_ref_sinf": ([F], F), "surf_ref_cosf": ([F], F), "surf_ref_expf": ([F], F),
@@ -291,6 +295,20 @@ def write_image(path: str, rgba8: np.ndarray) -> None:
     h, w = img.shape
     fn = load().surf_write_ppm if path.lower().endswith(".ppm") else load().surf_write_png
     _check(fn(path.encode(), w, h, _ptr(img)), "surf_write_image")
+
+
+def write_pfm(path: str, rgba: np.ndarray) -> None:
+    """Writes an (H, W, 4) float32 image, rows top to bottom (the accumulator, a
+    float feature plane of Renderer.aov()), as a colour PFM (surf_write_pfm:
+    rows bottom to top, RGB as little-endian f32 bit for bit, alpha dropped)."""
+    img = np.ascontiguousarray(rgba, dtype=np.float32)
+    if img.ndim != 3 or img.shape[2] != 4:
+        raise ValueError(f"rgba shape {img.shape} is not (H, W, 4)")
+    h, w = img.shape[:2]
+    _check(load().surf_write_pfm(path.encode(), w, h, _ptr(img)), "surf_write_pfm")
+
+
+AOV_PLANES = ("position", "normal", "albedo", "id")      # surf_aov order
 
 
 def obj_load(path: str, threads: int = 0) -> tuple[np.ndarray, np.ndarray]:
@@ -472,6 +490,38 @@ class Renderer:
         out = np.zeros((len(self.rows), self.width, 4), dtype=np.float32)
         _check(load().surf_read_accumulator(self._h, _ptr(out)), "surf_read_accumulator", self._h)
         return out
+
+    def set_camera(self, ubo: bytes):
+        """surf_set_camera: a 128-byte CameraUBO (Scene.camera's layout).  A changed
+        camera ends the sample stream and drops the cached feature buffers."""
+        if len(ubo) != C.sizeof(CameraUBO):
+            raise ValueError(f"camera UBO is {len(ubo)} bytes, not {C.sizeof(CameraUBO)}")
+        buf = CameraUBO.from_buffer_copy(ubo)
+        _check(load().surf_set_camera(self._h, buf), "surf_set_camera", self._h)
+
+    def aov(self) -> dict:
+        """First-hit feature buffers of this shard's rows (surf_read_aov; the plane
+        definitions are in include/surf_hip.h): 'position', 'normal' and 'albedo'
+        as (rows, width, 4) float32, 'id' as (rows, width, 4) uint32 (instance,
+        primitive, material, 0; ~0 on a miss).  Computed on the first read, cached
+        until the camera, the scene or the instances change; the sample stream is
+        not touched.  Row shards assemble like accumulators (assemble_shards
+        works on float32: pass it the id plane as .view(np.float32))."""
+        out = {}
+        for k, name in enumerate(AOV_PLANES):
+            a = np.zeros((len(self.rows), self.width, 4), dtype=np.uint32 if name == "id" else np.float32)
+            _check(load().surf_read_aov(self._h, k, _ptr(a)), "surf_read_aov", self._h)
+            out[name] = a
+        return out
+
+    def copy_aov_to(self, plane: int, device_ptr: int):
+        _check(load().surf_copy_aov_device(self._h, plane, C.c_void_p(device_ptr)), "surf_copy_aov_device", self._h)
+
+    def debug_aov_time(self) -> float:
+        """Device milliseconds of the last feature-buffer kernel launch (surf_debug_aov_time)."""
+        ms = C.c_float()
+        _check(load().surf_debug_aov_time(self._h, C.byref(ms)), "surf_debug_aov_time", self._h)
+        return float(ms.value)
 
     def copy_accumulator_to(self, device_ptr: int):
         _check(load().surf_copy_accumulator_device(self._h, C.c_void_p(device_ptr)), "surf_copy_accumulator_device", self._h)
