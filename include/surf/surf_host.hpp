@@ -343,6 +343,12 @@ public:
      * width*height*4 values each): a float plane (position, normal or albedo), and the id plane */
     std::vector<F32> readAOV(surf_aov plane);
     std::vector<U32> readAOVIds();
+    /* the rendered radiance through the edge-avoiding a-trous filter (surf_denoise; width*height*4
+     * floats, w = 1): the accumulator and the feature buffers of the camera and scene of the last
+     * render() call; the accumulator is left untouched.  The form without arguments takes
+     * surf_denoise_default_params. */
+    std::vector<F32> denoise(const surf_denoise_params& params);
+    std::vector<F32> denoise();
     surf_ctx* handle() const { return m_ctx; }
 private:
     void pushSceneAndCamera();                    /* what render() re-reads per frame: instance updates, the camera */

@@ -348,6 +348,94 @@ int surf_copy_aov_device(surf_ctx* ctx, int plane, void* dst_device);
  * launch, 0 before the first.  No reference counterpart. */
 int surf_debug_aov_time(surf_ctx* ctx, float* kernel_ms);
 
+/* ---- denoiser: edge-avoiding a-trous wavelet filter on the feature buffers ----
+ * A pure post-process of the radiance (Dammertz et al. 2010, with albedo
+ * demodulation): it reads the accumulator and the first-hit feature planes
+ * and writes a new image; the accumulator, the sample stream and the event
+ * counters are what they would be without it.  No reference counterpart.
+ *
+ * The arithmetic is part of the interface: every operation is f32 and
+ * uncontracted, in exactly the order written here, so a host restatement
+ * reproduces the image bit for bit (surf_denoise_image_host is one).
+ *
+ * Inputs: a FULL frame of W x H pixels, rows top to bottom, as four float4
+ * planes: acc (radiance sum, w = the sample count), position, normal, albedo
+ * as surf_read_aov defines them (albedo.w == 0 marks a miss).  Parameters:
+ * iterations n in 1..6, sigma_color, sigma_normal, sigma_plane (each finite
+ * and > 0), demodulate (0 / 1).
+ *
+ * Prepare, per pixel p (k = x, y, z):
+ *   valid = albedo.w != 0
+ *   inv   = acc.w > 0 ? 1.0f / acc.w : 0.0f
+ *   c_k   = acc_k * inv
+ *   den_k = (valid && demodulate) ? (albedo_k > 0.01f ? albedo_k : 0.01f) : 1.0f
+ *   I0_k  = c_k / den_k
+ * Iteration i = 0..n-1, step s = 1 << i, with the f32 constants (host)
+ *   sc = sigma_color * ldexpf(1.0f, -i)      kc = 1.0f / (sc * sc)
+ *   kn = 1.0f / (sigma_normal * sigma_normal)
+ *   kp = 1.0f / (sigma_plane * sigma_plane)
+ * An invalid p copies I_i(p) to the next level unchanged.  A valid p starts
+ * from sumW = 0, sum = (0, 0, 0) and visits the 25 taps q = (x + dx*s,
+ * y + dy*s), dy = -2..2 the outer loop, dx = -2..2 the inner; a q outside the
+ * frame or invalid is skipped; for every other q, the centre included:
+ *   dC = Iq - Ip     dc = (dCx*dCx + dCy*dCy) + dCz*dCz
+ *   dN = Nq - Np     dn = (dNx*dNx + dNy*dNy) + dNz*dNz
+ *   dP = Pq - Pp     pl = (dPx*Npx + dPy*Npy) + dPz*Npz     dp = pl*pl
+ *   e  = (dc*kc + dn*kn) + dp*kp
+ *   e  = e < 100.0f ? e : 100.0f     (a NaN becomes 100; keeps the argument in
+ *                                     the range the expf restatement is verified on)
+ *   w  = (h[dy+2] * h[dx+2]) * expf(-e)     h = {0.0625, 0.25, 0.375, 0.25, 0.0625}
+ *                                           expf: glibc 2.35's, as the path tracer's
+ *   sumW  = sumW + w
+ *   sum_k = sum_k + w * Iq_k
+ * and then I_{i+1}(p)_k = sum_k / sumW (the centre tap makes sumW > 0).
+ * Output: (I_n * den, 1.0f) for a valid pixel, (c, 1.0f) for a miss; with
+ * w = 1, surf_pack_rgba8(out, n, 1.0f, display, ...) gives the displayable image.
+ *
+ * Known limit: the guides are the first hit of the sharp centre ray.  What is
+ * seen THROUGH the lens blur or in a mirror has no guide edges, only the
+ * colour term protects it; fireflies survive as well.
+ *
+ * One launch per iteration (the last fuses the remodulation) on a 32 x 8
+ * pixel tile per 256-thread block, in two variants with identical bits: taps
+ * from an LDS copy of the tile and its 2*s halo, or straight from global
+ * memory.  SURF_DENOISE_LDS=<largest step staged> (read at surf_create*; 0 =
+ * never; steps above 4 are never staged, their halo outgrows its reuse).
+ * Scratch images are allocated on first use and kept (no allocation in
+ * steady state), freed by surf_destroy. */
+typedef struct {
+    uint32_t iterations;
+    float sigma_color, sigma_normal, sigma_plane;
+    uint32_t demodulate;
+    uint32_t _pad[3];
+} surf_denoise_params;
+/* 5 iterations, sigma_color 1.0, sigma_normal 0.3, sigma_plane 0.1, demodulate 1 */
+int surf_denoise_default_params(surf_denoise_params* params);
+/* The context's accumulator filtered with its own (cached) feature planes, to
+ * a host buffer of width*height*4 floats.  Drains the stream, as every read
+ * does; leaves the accumulator untouched.  The context must own every row
+ * 0..height-1: on a row shard SURF_ERR_INVALID (surf_last_error points to
+ * surf_denoise_image -- a spatial filter needs its neighbours' rows).
+ * SURF_ERR_NO_SCENE before a scene and a camera are set, SURF_ERR_OOM when a
+ * scratch image cannot be allocated, SURF_ERR_INVALID for a NULL argument,
+ * iterations outside 1..6 or a sigma that is not finite and > 0. */
+int surf_denoise(surf_ctx* ctx, const surf_denoise_params* params, float* out_rgba);
+/* The same, to a buffer on the context's device (width*height*16 bytes). */
+int surf_denoise_copy_device(surf_ctx* ctx, const surf_denoise_params* params, void* dst_device);
+/* Host planes of any full frame (w*h*4 floats each), e.g. one assembled from
+ * row shards; needs no scene on the context.  SURF_ERR_INVALID also for w or
+ * h of 0. */
+int surf_denoise_image(surf_ctx* ctx, uint32_t w, uint32_t h, const float* acc, const float* position, const float* normal,
+                       const float* albedo, const surf_denoise_params* params, float* out);
+/* The CPU twin: the same per-pixel functions compiled for the host; needs no
+ * device.  Bit-identical to surf_denoise_image. */
+int surf_denoise_image_host(uint32_t w, uint32_t h, const float* acc, const float* position, const float* normal,
+                            const float* albedo, const surf_denoise_params* params, float* out);
+/* Diagnostics: device time (HIP events) of each kernel of the last denoise run
+ * on this context: kernel_ms[0] the prepare kernel, kernel_ms[1 + i]
+ * iteration i; entries past the run's iterations (and past 7) are 0. */
+int surf_debug_denoise_time(surf_ctx* ctx, float* kernel_ms, uint32_t count);
+
 /* ---- traversal entry points (kernel-level parity tests) ----
  * n world-space rays, o/d 3 floats each.  closest: depth starts at 1e30;
  * writes t,u,v (floats) and inst,prim (u32, ~0 on miss).  any: tmax per ray,

@@ -113,6 +113,22 @@ std::vector<U32> WaveFrontRenderer::readAOVIds() {
     return out;
 }
 
+/* The filter reads the accumulator beside the feature buffers, so it keeps
+ * the camera and the scene of the last render() call: those the accumulated
+ * samples saw. */
+std::vector<F32> WaveFrontRenderer::denoise(const surf_denoise_params& params) {
+    if (m_totalSamples == 0) throw std::runtime_error("denoise: nothing rendered since the last clear");
+    std::vector<F32> out((size_t)m_resolution.width * m_resolution.height * 4);
+    check(surf_denoise(m_ctx, &params, out.data()), m_ctx, "surf_denoise");
+    return out;
+}
+
+std::vector<F32> WaveFrontRenderer::denoise() {
+    surf_denoise_params params;
+    check(surf_denoise_default_params(&params), m_ctx, "surf_denoise_default_params");
+    return denoise(params);
+}
+
 std::vector<U32> WaveFrontRenderer::displayRGBA8() {
     std::vector<U32> out((size_t)m_resolution.width * m_resolution.height);
     check(surf_display_rgba8(m_ctx, out.data()), m_ctx, "surf_display_rgba8");

@@ -24,6 +24,7 @@
 
 #include "surf_hip.h"
 #include "device/wavefront_kernels.h"
+#include "device/denoise_kernels.h"
 
 using namespace surfdev;
 
@@ -111,6 +112,21 @@ struct surf_ctx {
     void* aov[SURF_AOV_COUNT] = {};
     bool aovValid = false;
     float aovKernelMs = 0.0f;      /* device time of the last k_aov launch (surf_debug_aov_time) */
+    /* the a-trous denoiser (surf_denoise*): scratch images of dnCap pixels --
+     * the two ping-pong levels, the packed normal and position guides -- and,
+     * for surf_denoise_image, the four uploaded planes; allocated on first use,
+     * grown only when a larger frame arrives, freed in surf_destroy */
+    float4* dn[4] = {};
+    size_t dnCap = 0;
+    float4* dnIn[4] = {};
+    size_t dnInCap = 0;
+    hipEvent_t dnEv[kDenoiseMaxIterations + 2] = {};
+    float dnMs[kDenoiseMaxIterations + 1] = {};   /* prepare, then the iterations of the last run (surf_debug_denoise_time) */
+    /* largest a-trous step whose tile is staged in LDS (SURF_DENOISE_LDS; 0 =
+     * every step reads its taps from global memory).  2: staging takes a third
+     * off the launches at steps 1 and 2 and adds 10 % at step 4 (MEASUREMENTS
+     * "Denoiser") */
+    uint32_t dnLdsMax = 2;
     /* one-frame render calls may leave up to a pool of their stream unissued
      * (SURF_LOOP_LAG=0: issue each call's frame before returning) */
     bool loopLag = true;
@@ -733,6 +749,111 @@ int ensureAov(surf_ctx* c) {
     return SURF_OK;
 }
 
+/* ---- a-trous denoiser ---------------------------------------------------- */
+const char* denoiseParamError(const surf_denoise_params* p) {
+    if (!p) return "params is NULL";
+    if (p->iterations < 1 || p->iterations > (uint32_t)kDenoiseMaxIterations) return "iterations outside 1..6";
+    for (float s : {p->sigma_color, p->sigma_normal, p->sigma_plane})
+        if (!(std::isfinite(s) && s > 0.0f)) return "a sigma is not finite and > 0";
+    return nullptr;
+}
+
+/* the per-iteration constants, computed in f32 on the host as the header states */
+struct DenoiseConsts { float kc, kn, kp; };
+DenoiseConsts denoiseConsts(const surf_denoise_params& p, uint32_t i) {
+    const float sc = p.sigma_color * ldexpf(1.0f, -(int)i);
+    DenoiseConsts k;
+    k.kc = 1.0f / (sc * sc);
+    k.kn = 1.0f / (p.sigma_normal * p.sigma_normal);
+    k.kp = 1.0f / (p.sigma_plane * p.sigma_plane);
+    return k;
+}
+
+int growPlanes(surf_ctx* c, float4** planes, int count, size_t& cap, size_t npx) {
+    if (npx <= cap) return SURF_OK;
+    for (int k = 0; k < count; ++k) {
+        if (planes[k]) (void)hipFree(planes[k]);
+        planes[k] = nullptr;
+    }
+    cap = 0;
+    for (int k = 0; k < count; ++k)
+        if (hipMalloc(reinterpret_cast<void**>(&planes[k]), npx * sizeof(float4)) != hipSuccess || !planes[k]) {
+            planes[k] = nullptr;
+            (void)hipGetLastError();
+            return fail(c, SURF_ERR_OOM, "hipMalloc of a denoiser image (" + std::to_string(npx * sizeof(float4)) + " bytes) failed");
+        }
+    cap = npx;
+    return SURF_OK;
+}
+
+/* Prepare + n a-trous launches on the context's stream over device planes of
+ * a full w x h frame; *result is the scratch image that holds the output
+ * (valid until the next denoise call).  Waits for the result. */
+int runDenoise(surf_ctx* c, uint32_t w, uint32_t h, const float4* acc, const float4* pos, const float4* nrm, const float4* alb,
+               const surf_denoise_params& P, const float4** result) {
+    const size_t npx = (size_t)w * h;
+    int rc = growPlanes(c, c->dn, 4, c->dnCap, npx);
+    if (rc) return rc;
+    for (auto& e : c->dnEv)
+        if (!e) SURF_CHECK(c, hipEventCreate(&e));
+    float4* lvl[2] = {c->dn[0], c->dn[1]};
+    float4* gN = c->dn[2];
+    float4* gP = c->dn[3];
+    SURF_CHECK(c, hipEventRecord(c->dnEv[0], c->stream));
+    hipLaunchKernelGGL(k_denoise_prepare, dim3((uint32_t)((npx + 255) / 256)), dim3(256), 0, c->stream, acc, pos, nrm, alb,
+                       P.demodulate ? 1u : 0u, (uint32_t)npx, lvl[0], gN, gP);
+    SURF_CHECK(c, hipGetLastError());
+    SURF_CHECK(c, hipEventRecord(c->dnEv[1], c->stream));
+    const dim3 grid((w + kDenoiseTileW - 1) / kDenoiseTileW, (h + kDenoiseTileH - 1) / kDenoiseTileH);
+    const uint32_t stagedMax = std::min<uint32_t>(c->dnLdsMax, (uint32_t)kDenoiseMaxStagedStep);
+    for (uint32_t i = 0; i < P.iterations; ++i) {
+        const int s = 1 << i;
+        const DenoiseConsts k = denoiseConsts(P, i);
+        const int last = i + 1 == P.iterations;
+        if ((uint32_t)s <= stagedMax) {
+            const size_t lds = (size_t)3 * sizeof(float4) * (kDenoiseTileW + 4 * s) * (kDenoiseTileH + 4 * s);
+            hipLaunchKernelGGL(k_atrous<true>, grid, dim3(256), lds, c->stream, (const float4*)lvl[i & 1], (const float4*)gN,
+                               (const float4*)gP, alb, lvl[(i & 1) ^ 1], (int)w, (int)h, s, k.kc, k.kn, k.kp,
+                               P.demodulate ? 1u : 0u, last);
+        } else {
+            hipLaunchKernelGGL(k_atrous<false>, grid, dim3(256), 0, c->stream, (const float4*)lvl[i & 1], (const float4*)gN,
+                               (const float4*)gP, alb, lvl[(i & 1) ^ 1], (int)w, (int)h, s, k.kc, k.kn, k.kp,
+                               P.demodulate ? 1u : 0u, last);
+        }
+        SURF_CHECK(c, hipGetLastError());
+        SURF_CHECK(c, hipEventRecord(c->dnEv[i + 2], c->stream));
+    }
+    SURF_CHECK(c, hipEventSynchronize(c->dnEv[P.iterations + 1]));
+    for (uint32_t k = 0; k <= (uint32_t)kDenoiseMaxIterations; ++k) {
+        c->dnMs[k] = 0.0f;
+        if (k <= P.iterations) (void)hipEventElapsedTime(&c->dnMs[k], c->dnEv[k], c->dnEv[k + 1]);
+    }
+    *result = lvl[P.iterations & 1];
+    return SURF_OK;
+}
+
+int ensureDrained(surf_ctx* c);
+
+/* surf_denoise / surf_denoise_copy_device: the context's own accumulator and
+ * cached feature planes, the result copied to the host or to a device buffer */
+int denoiseContext(surf_ctx* c, const surf_denoise_params* p, void* dst, hipMemcpyKind kind) {
+    if (!c || !dst) return SURF_ERR_INVALID;
+    if (const char* why = denoiseParamError(p)) return fail(c, SURF_ERR_INVALID, std::string("surf_denoise: ") + why);
+    if (c->rows.size() != c->height)
+        return fail(c, SURF_ERR_INVALID, "surf_denoise needs a context that owns every row of the frame: a spatial filter reads its "
+                                         "neighbours' rows; assemble the shards' accumulators and feature planes and call surf_denoise_image");
+    int rc = ensureAov(c);
+    if (rc) return rc;
+    if ((rc = ensureDrained(c))) return rc;
+    const float4* res = nullptr;
+    rc = runDenoise(c, c->width, c->height, c->acc, static_cast<const float4*>(c->aov[SURF_AOV_POSITION]),
+                    static_cast<const float4*>(c->aov[SURF_AOV_NORMAL]), static_cast<const float4*>(c->aov[SURF_AOV_ALBEDO]), *p, &res);
+    if (rc) return rc;
+    SURF_CHECK(c, hipMemcpyAsync(dst, res, (size_t)c->npx * sizeof(float4), kind, c->stream));
+    SURF_CHECK(c, hipStreamSynchronize(c->stream));
+    return SURF_OK;
+}
+
 /* ---- sample stream ------------------------------------------------------ */
 int startStream(surf_ctx* c, uint64_t baseFrame, uint32_t maxSeg, uint32_t frames, uint32_t spp) {
     Counters h{};
@@ -1243,6 +1364,7 @@ int createCtx(int dev, uint32_t w, uint32_t h, std::vector<uint32_t> rows, surf_
     if (const char* e = std::getenv("SURF_DRAIN_SHORT")) c->drainShort = e[0] == '1';
     if (const char* e = std::getenv("SURF_REGEN_FIRST")) c->regenFirst = e[0] == '1';
     if (const char* e = std::getenv("SURF_PIPELINE")) c->pipeline = e[0] != '0';
+    if (const char* e = std::getenv("SURF_DENOISE_LDS")) c->dnLdsMax = (uint32_t)std::max(0, std::atoi(e));
     c->width = w;
     c->height = h;
     c->rows = std::move(rows);
@@ -1317,6 +1439,9 @@ void surf_destroy(surf_ctx* c) {
     if (c->phaseLog) std::fclose(c->phaseLog);
     if (c->acc) (void)hipFree(c->acc);
     for (void*& p : c->aov) { if (p) (void)hipFree(p); p = nullptr; }
+    for (float4*& p : c->dn) { if (p) (void)hipFree(p); p = nullptr; }
+    for (float4*& p : c->dnIn) { if (p) (void)hipFree(p); p = nullptr; }
+    for (auto& e : c->dnEv) if (e) (void)hipEventDestroy(e);
     if (c->dRows) (void)hipFree(c->dRows);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
@@ -2042,6 +2167,87 @@ int surf_copy_aov_device(surf_ctx* c, int plane, void* dst) {
 int surf_debug_aov_time(surf_ctx* c, float* kernel_ms) {
     if (!c || !kernel_ms) return SURF_ERR_INVALID;
     *kernel_ms = c->aovKernelMs;
+    return SURF_OK;
+}
+
+int surf_denoise_default_params(surf_denoise_params* p) {
+    if (!p) return SURF_ERR_INVALID;
+    std::memset(p, 0, sizeof *p);
+    p->iterations = 5;
+    p->sigma_color = 1.0f;
+    p->sigma_normal = 0.3f;
+    p->sigma_plane = 0.1f;
+    p->demodulate = 1;
+    return SURF_OK;
+}
+
+int surf_denoise(surf_ctx* c, const surf_denoise_params* p, float* out) {
+    return denoiseContext(c, p, out, hipMemcpyDeviceToHost);
+}
+
+int surf_denoise_copy_device(surf_ctx* c, const surf_denoise_params* p, void* dst) {
+    return denoiseContext(c, p, dst, hipMemcpyDeviceToDevice);
+}
+
+int surf_denoise_image(surf_ctx* c, uint32_t w, uint32_t h, const float* acc, const float* position, const float* normal,
+                       const float* albedo, const surf_denoise_params* p, float* out) {
+    if (!c || !acc || !position || !normal || !albedo || !out) return SURF_ERR_INVALID;
+    if (w == 0 || h == 0 || (uint64_t)w * h > (1ull << 31)) return fail(c, SURF_ERR_INVALID, "surf_denoise_image: empty or too large a frame");
+    if (const char* why = denoiseParamError(p)) return fail(c, SURF_ERR_INVALID, std::string("surf_denoise_image: ") + why);
+    SURF_CHECK(c, hipSetDevice(c->device));
+    const size_t npx = (size_t)w * h;
+    int rc = growPlanes(c, c->dnIn, 4, c->dnInCap, npx);
+    if (rc) return rc;
+    const float* src[4] = {acc, position, normal, albedo};
+    for (int k = 0; k < 4; ++k)
+        SURF_CHECK(c, hipMemcpyAsync(c->dnIn[k], src[k], npx * sizeof(float4), hipMemcpyHostToDevice, c->stream));
+    const float4* res = nullptr;
+    if ((rc = runDenoise(c, w, h, c->dnIn[0], c->dnIn[1], c->dnIn[2], c->dnIn[3], *p, &res))) return rc;
+    SURF_CHECK(c, hipMemcpyAsync(out, res, npx * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
+    SURF_CHECK(c, hipStreamSynchronize(c->stream));
+    return SURF_OK;
+}
+
+/* The CPU twin: denoisePrepare / denoisePixel / denoiseStore of
+ * device/denoise_kernels.h compiled for the host, on host arrays. */
+int surf_denoise_image_host(uint32_t w, uint32_t h, const float* acc, const float* position, const float* normal,
+                            const float* albedo, const surf_denoise_params* p, float* out) {
+    if (!acc || !position || !normal || !albedo || !out) return fail(nullptr, SURF_ERR_INVALID, "surf_denoise_image_host: NULL argument");
+    if (w == 0 || h == 0 || (uint64_t)w * h > (1ull << 31)) return fail(nullptr, SURF_ERR_INVALID, "surf_denoise_image_host: empty or too large a frame");
+    if (const char* why = denoiseParamError(p)) return fail(nullptr, SURF_ERR_INVALID, std::string("surf_denoise_image_host: ") + why);
+    const size_t npx = (size_t)w * h;
+    const float4* A = reinterpret_cast<const float4*>(acc);
+    const float4* Ps = reinterpret_cast<const float4*>(position);
+    const float4* Ns = reinterpret_cast<const float4*>(normal);
+    const float4* Al = reinterpret_cast<const float4*>(albedo);
+    const uint32_t demod = p->demodulate ? 1u : 0u;
+    std::vector<float4> lvl[2], gN(npx), gP(npx);
+    lvl[0].resize(npx);
+    lvl[1].resize(npx);
+    for (size_t q = 0; q < npx; ++q) denoisePrepare(A[q], Ps[q], Ns[q], Al[q], demod, lvl[0][q], gN[q], gP[q]);
+    for (uint32_t i = 0; i < p->iterations; ++i) {
+        const int s = 1 << i;
+        const DenoiseConsts k = denoiseConsts(*p, i);
+        const bool last = i + 1 == p->iterations;
+        const std::vector<float4>& I = lvl[i & 1];
+        std::vector<float4>& O = lvl[(i & 1) ^ 1];
+        const DenoiseFetchPlanes fetch{I.data(), gN.data(), gP.data(), (int)w};
+        for (int y = 0; y < (int)h; ++y)
+            for (int x = 0; x < (int)w; ++x) {
+                const size_t q = (size_t)y * w + x;
+                const bool valid = gN[q].w != 0.0f;
+                V3 f = mk3(0.0f, 0.0f, 0.0f);
+                if (valid) f = denoisePixel(x, y, (int)w, (int)h, s, k.kc, k.kn, k.kp, I[q], gN[q], gP[q], fetch);
+                O[q] = denoiseStore(valid, I[q], f, last, Al[q], demod);
+            }
+    }
+    std::memcpy(out, lvl[p->iterations & 1].data(), npx * sizeof(float4));
+    return SURF_OK;
+}
+
+int surf_debug_denoise_time(surf_ctx* c, float* kernel_ms, uint32_t count) {
+    if (!c || !kernel_ms) return SURF_ERR_INVALID;
+    for (uint32_t k = 0; k < count; ++k) kernel_ms[k] = k <= (uint32_t)kDenoiseMaxIterations ? c->dnMs[k] : 0.0f;
     return SURF_OK;
 }
 

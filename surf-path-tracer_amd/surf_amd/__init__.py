@@ -13,6 +13,7 @@ Mirrors the reference interface for the hot path:
     .finalize_rgba8()          wavefront_finalize.comp + RgbaToU32
     .trace_closest/.trace_any  ray_extend / ray_connect traversal (tests)
     .aov()                     first-hit feature buffers (no reference counterpart)
+    .denoise()                 edge-avoiding a-trous filter on them (no reference counterpart)
 """
 from __future__ import annotations
 
@@ -73,6 +74,12 @@ class Stats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_ if not k.startswith("_")}
 
 
+class DenoiseParams(C.Structure):
+    """surf_denoise_params (include/surf_hip.h gives the filter's arithmetic)."""
+    _fields_ = [("iterations", C.c_uint32), ("sigma_color", C.c_float), ("sigma_normal", C.c_float),
+                ("sigma_plane", C.c_float), ("demodulate", C.c_uint32), ("_pad", C.c_uint32 * 3)]
+
+
 CameraUBO = C.c_uint8 * 128
 
 _lib = None
@@ -129,6 +136,12 @@ def load() -> C.CDLL:
         "surf_read_aov": ([P, I32, P], I32), "surf_copy_aov_device": ([P, I32, P], I32),
         "surf_debug_aov_time": ([P, C.POINTER(F)], I32),
         "surf_write_pfm": ([C.c_char_p, U32, U32, P], I32),
+        "surf_denoise_default_params": ([C.POINTER(DenoiseParams)], I32),
+        "surf_denoise": ([P, C.POINTER(DenoiseParams), P], I32),
+        "surf_denoise_copy_device": ([P, C.POINTER(DenoiseParams), P], I32),
+        "surf_denoise_image": ([P, U32, U32, P, P, P, P, C.POINTER(DenoiseParams), P], I32),
+        "surf_denoise_image_host": ([U32, U32, P, P, P, P, C.POINTER(DenoiseParams), P], I32),
+        "surf_debug_denoise_time": ([P, C.POINTER(F), U32], I32),
         "surf_mesh_data": ([P, C.POINTER(P), C.POINTER(P), C.POINTER(U32)], I32),
         "surf_mesh_destroy": ([P], None),
         "surf_ref_sinf": ([F], F), "surf_ref_cosf": ([F], F), "surf_ref_expf": ([F], F),
@@ -309,6 +322,41 @@ def write_pfm(path: str, rgba: np.ndarray) -> None:
 
 
 AOV_PLANES = ("position", "normal", "albedo", "id")      # surf_aov order
+
+
+def denoise_params(**params) -> DenoiseParams:
+    """surf_denoise_default_params (5 iterations, sigma_color 1.0, sigma_normal
+    0.3, sigma_plane 0.1, demodulate 1) with the given fields replaced."""
+    p = DenoiseParams()
+    _check(load().surf_denoise_default_params(C.byref(p)), "surf_denoise_default_params")
+    for k, v in params.items():
+        if k not in ("iterations", "sigma_color", "sigma_normal", "sigma_plane", "demodulate"):
+            raise TypeError(f"unknown denoise parameter {k!r}")
+        setattr(p, k, int(v) if k in ("iterations", "demodulate") else float(v))
+    return p
+
+
+def _denoise_planes(acc, planes):
+    """(w, h, [acc, position, normal, albedo]) as contiguous (H, W, 4) float32; planes
+    is Renderer.aov()'s dict (the id plane is not needed) or a (position, normal, albedo) sequence."""
+    if isinstance(planes, dict):
+        planes = [planes[k] for k in ("position", "normal", "albedo")]
+    arrs = [np.ascontiguousarray(a, dtype=np.float32) for a in (acc, *planes)]
+    if len(arrs) != 4 or arrs[0].ndim != 3 or arrs[0].shape[2] != 4 or any(a.shape != arrs[0].shape for a in arrs):
+        raise ValueError(f"denoise planes {[a.shape for a in arrs]} are not four (H, W, 4) images of one size")
+    h, w = arrs[0].shape[:2]
+    return w, h, arrs
+
+
+def denoise_image_host(acc: np.ndarray, planes, **params) -> np.ndarray:
+    """The CPU twin of Renderer.denoise_image (surf_denoise_image_host): the
+    same per-pixel functions compiled for the host, bit-identical; no device."""
+    w, h, a = _denoise_planes(acc, planes)
+    p = denoise_params(**params)
+    out = np.zeros((h, w, 4), np.float32)
+    _check(load().surf_denoise_image_host(w, h, _ptr(a[0]), _ptr(a[1]), _ptr(a[2]), _ptr(a[3]), C.byref(p), _ptr(out)),
+           "surf_denoise_image_host")
+    return out
 
 
 def obj_load(path: str, threads: int = 0) -> tuple[np.ndarray, np.ndarray]:
@@ -522,6 +570,40 @@ class Renderer:
         ms = C.c_float()
         _check(load().surf_debug_aov_time(self._h, C.byref(ms)), "surf_debug_aov_time", self._h)
         return float(ms.value)
+
+    def denoise(self, **params) -> np.ndarray:
+        """The accumulated radiance through the edge-avoiding a-trous filter
+        (surf_denoise; parameters as denoise_params): (H, W, 4) float32 radiance
+        with w = 1 -- pack_rgba8(img, 1, display=True) is the displayable image.
+        Reads the accumulator and the cached feature planes on the device and
+        leaves both untouched.  Raises SURF_ERR_INVALID on a row shard: assemble
+        the shards' accumulators and planes and call denoise_image."""
+        p = denoise_params(**params)
+        out = np.zeros((self.height, self.width, 4), dtype=np.float32)
+        _check(load().surf_denoise(self._h, C.byref(p), _ptr(out)), "surf_denoise", self._h)
+        return out
+
+    def denoise_image(self, acc: np.ndarray, planes, **params) -> np.ndarray:
+        """The same filter on host planes of any full frame (surf_denoise_image):
+        acc (H, W, 4) with w = the sample count, planes Renderer.aov()'s dict or
+        (position, normal, albedo)."""
+        w, h, a = _denoise_planes(acc, planes)
+        p = denoise_params(**params)
+        out = np.zeros((h, w, 4), np.float32)
+        _check(load().surf_denoise_image(self._h, w, h, _ptr(a[0]), _ptr(a[1]), _ptr(a[2]), _ptr(a[3]), C.byref(p), _ptr(out)),
+               "surf_denoise_image", self._h)
+        return out
+
+    def copy_denoised_to(self, device_ptr: int, **params):
+        p = denoise_params(**params)
+        _check(load().surf_denoise_copy_device(self._h, C.byref(p), C.c_void_p(device_ptr)), "surf_denoise_copy_device", self._h)
+
+    def debug_denoise_time(self) -> list:
+        """Device milliseconds of the last denoise run's kernels (surf_debug_denoise_time):
+        the prepare kernel, then each iteration (0 past the run's iterations)."""
+        ms = (C.c_float * 7)()
+        _check(load().surf_debug_denoise_time(self._h, ms, 7), "surf_debug_denoise_time", self._h)
+        return [float(v) for v in ms]
 
     def copy_accumulator_to(self, device_ptr: int):
         _check(load().surf_copy_accumulator_device(self._h, C.c_void_p(device_ptr)), "surf_copy_accumulator_device", self._h)
