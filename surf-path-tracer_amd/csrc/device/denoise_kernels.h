@@ -14,11 +14,11 @@
  */
 #pragma once
 #include "surf_math.h"
+#include "types.h"          /* kDenoiseMaxIterations */
 
 namespace surfdev {
 
 constexpr int kDenoiseTileW = 32, kDenoiseTileH = 8;      /* one 256-thread block */
-constexpr int kDenoiseMaxIterations = 6;
 /* largest step the LDS variant stages: the tile plus its 2*s halo is
  * (32+4s) x (8+4s) texels of 48 B -- 20.3 / 30 / 54 KiB at s = 1 / 2 / 4.  At
  * s = 8 it would be 120 KiB for 2.5 uses per staged texel, at s = 16 more

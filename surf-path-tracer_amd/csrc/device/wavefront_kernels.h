@@ -31,12 +31,10 @@
 #include <hip/hip_runtime.h>
 #include <type_traits>
 #include "surf_math.h"
+#include "types.h"          /* the records shared with the host; lds_layout.h: where the kernels' dynamic LDS regions lie */
 
 namespace surfdev {
 
-constexpr uint32_t kUnset = 0xffffffffu;
-constexpr uint32_t kFlagMedium = 1u, kFlagSpecular = 2u;
-constexpr int kBlock = 256;
 /* Minimum waves per SIMD the register allocator must allow (occupancy). */
 #ifndef SURF_SHADE_WAVES
 #define SURF_SHADE_WAVES 4
@@ -62,107 +60,8 @@ constexpr int kBlock = 256;
 #define SURF_COOP_WAVES 4          /* k_tail_coop waves per SIMD (launch bounds; 3: 136 VGPRs, 5: spills) */
 #endif
 
-struct DevInstance {          /* 160 B */
-    float Minv[16];
-    float M[16];
-    uint32_t triOffset, idxOffset, nodeOffset, material;
-    float area;
-    uint32_t affineInv;       /* Minv row 3 == (0,0,0,1): w == 1 exactly for finite points */
-    uint32_t affine;          /* M row 3 == (0,0,0,1) */
-    uint32_t _pad;
-};
-
-struct DevMaterial {          /* = Material (64 B) */
-    float emit, refl, refr, ior;
-    float ec[4], albedo[4], absorb[4];
-};
-
-/* Per-instance traversal record (144 B), host-built at upload: rows of M^-1
- * (row i = m[i], m[4+i], m[8+i], m[12+i]), offsets, and the BLAS root record.
- * Kernels stage the table in LDS, so the per-instance loop of every ray reads
- * LDS instead of paying two dependent memory trips per instance. */
-struct TraceInst {
-    float4 m0, m1, m2, m3;
-    uint4 meta;               /* nodeOffset, idxOffset, affineInv, instance id */
-    float4 r0, r1, r2, r3;    /* root node record */
-    float4 wlo, whi;          /* conservative world box of the BLAS's triangles (wlo.w != 0: usable) */
-};
-constexpr uint32_t kLdsTraceInst = 64;   /* instances staged in LDS (9 KB) */
-
-struct DevScene {
-    const TraceInst* tinst;   /* [nInst], instance-id order */
-    const float4* nodes;      /* BLAS: 4 float4 per node (see upload) */
-    const float4* tris;       /* 3 float4 per BLAS index slot: (v0, prim), e1, e2 */
-    const float4* normals;    /* 3 float4 per global triangle: n0, n1, n2 */
-    const float4* verts;      /* reference Triangle records (v0, v1, v2, centroid) */
-    const float4* tlasNodes;  /* 4 float4 per TLAS node */
-    const uint32_t* tlasIdx;
-    const DevInstance* inst;
-    const DevMaterial* mats;
-    const uint2* lights;      /* (instance, primitive count) */
-    uint32_t nLights;
-    /* the emitters' BLAS k_connect stages in LDS (sbRecN = 0: none): the
-     * instances whose BLAS root is node sbNode0 walk its sbRecN interior records
-     * in compact form (sbRec: the children's boxes, each child an interior
-     * record index or a leaf's triangle range -- no leaf records) and its sbTriN
-     * triangle slots (S.tris + 3 * sbTri0) from LDS */
-    uint32_t sbNode0, sbRecN, sbTri0, sbTriN;
-    const float4* sbRec;
-    uint32_t nInst, nMats;
-    uint32_t tlasLeafCount;   /* TLAS root is a leaf with this many instances (0: general TLAS) */
-    uint32_t finiteBoxes;     /* every BLAS node box is finite: slabFinite is exact */
-    uint32_t nodes4G;         /* every BLAS-local record offset (64 B each) fits 32 bits: the asm wave walk's buffer offsets */
-    const float* wnodes;      /* two-level records (48 floats per BLAS node, see surf_upload_scene), or null */
-    uint32_t nWnodes;         /* nodes in wnodes (every 192-B offset fits 32 bits) */
-    uint32_t laneW;           /* the one-ray-per-lane traversal walks the two-level records too (HBM-resident BVHs) */
-    uint32_t bgType;
-    float bgColor[3], bgA[3], bgB[3];
-    float cellLo[3], cellScale[3];   /* ray-order cells: the TLAS root box split in 2 per axis (scale 0: one cell) */
-    /* ray-order membership key (single-leaf TLAS): the world boxes of the (at
-     * most 3) instances with the largest BLASes; keyMode 1: pool key by them */
-    uint32_t nHeavy, keyMode;
-    float4 hvLo[3], hvHi[3];
-};
-
-struct DevCamera {
-    float pos[3], firstPixel[3], uVec[3], vVec[3], diskU[3], diskV[3];
-    float invW, invH;
-    uint32_t defocus;
-};
-
-/* Path pool: od[2i] = (origin, sample id), od[2i + 1] = (direction, flags) --
- * the ray a traversal reads is one 32-B piece of one cache line, also when it
- * is gathered through the ray order -- T[i] = (throughput, rng state),
- * key[i] = ray-order bin (start instance). */
-struct Pool { float4* od; float4* T; uint8_t* key; };
 /* Where a path that used up its segment budget goes. */
 struct Sink { Pool q; uint32_t* n; uint32_t cap; };
-/* Shadow queue: od[2i] = (origin, tmax), od[2i + 1] = (direction, sample id)
- * -- the ray k_connect traverses is one 32-B piece of one cache line --
- * c[i] = (T * Ld, 0), read only for an unoccluded ray.  k_shade appends each
- * shadow ray straight into the region of its order bin (shadowKey: kShBins
- * regions of `region` slots, then an overflow region of the pool's capacity
- * for a bin that outgrows its region), so k_connect reads the rays in bin
- * order sequentially: no sort pass and no gather through an order array. */
-constexpr uint32_t kShBins = 16;     /* shadow-ray order bins: light slot (mod 2) x octant cell */
-/* Each bin's cursor and region are split by XCD (SURF_SH_XCDS parts, the
- * appending workgroup's HW_REG_XCC_ID) and the cursors lie SURF_SH_STRIDE words
- * apart: every workgroup iteration of k_shade reserves once per non-empty bin,
- * and same-address device atomics serialize. */
-#ifndef SURF_SH_XCDS
-#define SURF_SH_XCDS 1
-#endif
-#ifndef SURF_SH_STRIDE
-#define SURF_SH_STRIDE 32
-#endif
-constexpr uint32_t kShXcds = SURF_SH_XCDS, kShStride = SURF_SH_STRIDE;
-constexpr uint32_t kShSegs = kShBins * kShXcds + 1u;      /* queue segments: (bin, XCD) regions, then the overflow */
-struct ShadowQ {
-    float4* od; float4* c;
-    uint32_t* cur;        /* [2 parities][kShSegs] cursors, kShStride words apart (may count past a region's end) */
-    uint32_t region;      /* slots per (bin, XCD) region */
-    uint32_t bins;        /* kShBins, or 1: no shadow order (SURF_SORT=0/2) */
-};
 __device__ __forceinline__ uint32_t* shCursor(const ShadowQ& Q, int par, uint32_t seg) {
     return Q.cur + ((size_t)par * kShSegs + seg) * kShStride;
 }
@@ -172,42 +71,6 @@ __device__ __forceinline__ uint32_t xccId() {
     asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID, 0, 4)" : "=s"(x));
     return x % kShXcds;
 }
-
-/* Device counters of the sample stream.  Double-buffered by phase parity so no
- * kernel writes a word another block of the same launch still reads. */
-struct Counters {
-    uint32_t nIn[2];                 /* paths in pool[p] when a phase reads it */
-    uint32_t app[2];                 /* phase parity p: paths appended to pool[p^1] (the shadow
-                                        queue's cursors are ShadowQ::cur) */
-    uint32_t maxSeg;                 /* 0 = unbounded */
-    uint32_t zeroCutoff;             /* end paths whose throughput is exactly 0 (radiance-neutral) */
-    uint32_t segMax;                 /* longest finished path (extension rays), diagnostics */
-    uint32_t survN;                  /* k_tail survivors appended (may exceed survCap) */
-    uint32_t survCap;
-    uint32_t rowNext;                /* k_tail_pair path queue: next path to hand out */
-    /* issue order of the stream's first permFrames frames: every frame's
-     * samples of the permA pixels listed first in StreamGeom::perm, then each
-     * frame's other pixels frame by frame (0: frame-major throughout) */
-    uint32_t permFrames, permA;
-    /* samples per frame (config().samplesPerFrame, renderer.cpp:171): a frame's
-     * samples of one pixel form a chain -- sample k + 1 starts from the RNG state
-     * sample k's path left -- so k_regen issues only the first sample of each
-     * (frame, pixel) and the kernel that ends a sample's path starts the next */
-    uint32_t spp;
-    unsigned long long issued[2];    /* stream chains issued (first samples of (frame, pixel)), per parity */
-    unsigned long long limit;        /* host-written issue limit (frame window) */
-    unsigned long long baseFrame;    /* absolute frame index of stream frame 0 */
-    unsigned long long ev[16];       /* ext, hit, cont, shadow, acc, unocc, tail paths, capped paths, wavefront ext, resumed rays */
-    uint32_t capped[64];             /* sample ids of paths ended by the segment cap, slot blockIdx % 64 (diagnostics, ~0 = none) */
-    /* event counts striped over kStripes cache lines (block b adds to stripe
-     * b % kStripes): a counter shared by every block of a launch serializes its
-     * atomics (~12 ns each, measured); totals = ev + sum over stripes */
-    unsigned long long evS[32][16];
-    unsigned long long dbg[8];       /* SURF_SEG_TIMING builds: k_tail_coop cycles (extend, shade, connect, segments) */
-    uint32_t resumeN[2];             /* capped lane walks: resume records written by k_extend of parity p (k_regen zeroes) */
-};
-constexpr uint32_t kStripes = 32;    /* frameDone and event-count stripes */
-constexpr int kEvents = 10;          /* event kinds counted (ev / evS index; 9: rays k_extend_cont finished) */
 
 /* A path ended by the segment cap: counted in the event stripes; its sample
  * id is also stored in slot blockIdx % 64 (diagnostics: a racy overwrite, so
@@ -221,16 +84,6 @@ __device__ __forceinline__ void noteCapped(Counters* C, uint32_t sid) {
     atomicAdd(&C->evS[blockIdx.x % kStripes][7], 1ull);
     noteCappedSid(true, C, sid);
 }
-
-/* Where a stream sample lives: radiance slot sid = (pass % window) * npx + pixel,
- * pass = the sample's index in the stream (frame * spp + its place in the
- * frame; window is a multiple of spp, so a frame's samples occupy consecutive
- * slots and slot % spp is the place in the frame). */
-struct StreamGeom {
-    const uint32_t* rows;            /* shard rows */
-    uint32_t width, npx, window;
-    const uint32_t* perm;            /* local pixels, class A (Counters::permA of them) first */
-};
 
 SURF_HD V3 ld3(const float* p) { return mk3(p[0], p[1], p[2]); }
 
@@ -342,7 +195,6 @@ __device__ __forceinline__ float boxDist(float4 lo, float4 hi, V3 o, V3 rd, floa
  * at its parent and never again, bvh.cpp:193-253); the answer is an OR over
  * them, so testing a hit leaf's triangles as soon as its parent is visited --
  * no leaf record, no stack entry -- returns what blasTrace<true> does. */
-constexpr uint32_t kLeafTagC = 0x80000000u;
 __device__ __forceinline__ bool leafAnyStaged(const float4* sT, uint32_t ref, V3 o, V3 d, float depth) {
     const uint32_t cnt = (ref >> 16) & 0x7fffu, lf = ref & 0xffffu;
     for (uint32_t k = 0; k < cnt; ++k) {
@@ -505,7 +357,6 @@ __device__ __forceinline__ bool blasTrace(const DevScene& S, const TraceInst& I,
  * exact, as no leaf lies between the levels (the depth is the same).  Stack
  * entries are node indices, or packed leaf references (a popped leaf needs no
  * record). */
-constexpr uint32_t kLeafTag = 0x80000000u;
 struct WRow { float4 a, b, c, d; };
 template <bool FIN>
 __device__ __forceinline__ void wBoxes(const WRow& r, V3 o, V3 rd, float depth, float& d0, float& d1) {
@@ -661,10 +512,11 @@ struct TraceTables {
     const uint32_t* order;    /* TLAS leaf index array (tlasIndices) */
 };
 
-/* Dynamic LDS layout of the traversal kernels: [stack: depth x blockDim u32]
- * [TraceInst x nInst][tlasIdx x nInst].  Every thread of the block calls this. */
-__device__ __forceinline__ TraceTables stageTrace(const DevScene& S, uint32_t* lds, uint32_t stackWords) {
-    TraceInst* tab = reinterpret_cast<TraceInst*>(lds + stackWords);
+/* Stages the trace tables at LDS word `at` (lds_layout.h: where each kernel's
+ * tables start): [TraceInst x nInst][tlasIdx x nInst], layout::traceTableWords
+ * in all.  Every thread of the block calls this. */
+__device__ __forceinline__ TraceTables stageTrace(const DevScene& S, uint32_t* lds, uint32_t at) {
+    TraceInst* tab = reinterpret_cast<TraceInst*>(lds + at);
     uint32_t* order = reinterpret_cast<uint32_t*>(tab + S.nInst);
     const uint32_t n16 = S.nInst * (uint32_t)(sizeof(TraceInst) / 16);
     for (uint32_t k = threadIdx.x; k < n16; k += blockDim.x) reinterpret_cast<float4*>(tab)[k] = reinterpret_cast<const float4*>(S.tinst)[k];
@@ -674,8 +526,8 @@ __device__ __forceinline__ TraceTables stageTrace(const DevScene& S, uint32_t* l
 }
 
 template <bool LDS_INST>
-__device__ __forceinline__ TraceTables traceTables(const DevScene& S, uint32_t* lds, uint32_t stackWords) {
-    if (LDS_INST) return stageTrace(S, lds, stackWords);
+__device__ __forceinline__ TraceTables traceTables(const DevScene& S, uint32_t* lds, uint32_t at) {
+    if (LDS_INST) return stageTrace(S, lds, at);
     return TraceTables{S.tinst, S.tlasIdx};
 }
 
@@ -1581,7 +1433,6 @@ __device__ __forceinline__ bool leafWaveW(float st, uint32_t cnt, V3 o, V3 d, fl
     }
     return any;
 }
-constexpr uint32_t kLeafInW = 3;     /* triangles a two-level leaf record holds */
 
 /* blasWalk with two-level visits (S.wnodes): the DFS below one BLAS root from
  * W(root) -- its first visit re-tests the root's children at the current
@@ -1623,9 +1474,6 @@ __device__ __forceinline__ bool blasWalk2(const DevScene& S, uint32_t nodeOff, c
         st = rs[sp / 4u + lane];
     }
 }
-
-/* LDS prologue table of the wave traversal: 16 floats per instance */
-__device__ __forceinline__ uint32_t proWords(const DevScene& S) { return 16u * S.nInst; }
 
 /* Prologue entry of one instance (lane-parallel: one instance per lane): its
  * object-space ray, 1/d, the slab ranges of its BLAS root's two children and
@@ -2058,7 +1906,6 @@ __global__ __launch_bounds__(kSortThreads) void k_binscatter(const uint8_t* __re
 /* ------------------------------------------------------------------ kernels */
 /* SK: the traversal stack's entry type -- 16-bit when every BLAS and TLAS
  * node index fits (half the stack's LDS: more resident workgroups) */
-constexpr uint32_t kResumeHead = 10;   /* words of a resume record before its stack refs (64 words in all) */
 /* CAP (single-leaf TLAS): a lane leaves a ray after capIters node visits of
  * one BLAS walk (W-record visits in the two-level walk; LaneCap) and writes
  * its resume record (64 words: slot i, pool index j, TLAS turn, next node,
@@ -2078,7 +1925,7 @@ __global__ __launch_bounds__(kBlock, LW ? SURF_TRACE_WAVES : (CAP ? SURF_TRACE_W
      * what it traces, not the fixed grid's LDS staging */
     if (blockIdx.x * blockDim.x >= n) return;
     /* (stackWords: 32-bit words of the stack; a 16-bit stack uses half of them) */
-    const TraceTables Tt = traceTables<LDS>(S, lds, sizeof(SK) == 2 ? (stackWords + 1u) / 2u : stackWords);
+    const TraceTables Tt = traceTables<LDS>(S, lds, layout::laneTablesAt(stackWords, sizeof(SK) == 2));
     const uint32_t stride = blockDim.x;
     SK* stk = reinterpret_cast<SK*>(lds) + threadIdx.x;
     LaneCap lc;
@@ -2124,7 +1971,7 @@ __global__ __launch_bounds__(kBlock, SURF_TRACE_WAVES) void k_extend_cont(DevSce
     extern __shared__ uint32_t lds[];
     const uint32_t n = min(C->resumeN[par], recCap);
     if (blockIdx.x * blockDim.x >= n) return;
-    const TraceTables Tt = traceTables<LDS>(S, lds, sizeof(SK) == 2 ? (stackWords + 1u) / 2u : stackWords);
+    const TraceTables Tt = traceTables<LDS>(S, lds, layout::laneTablesAt(stackWords, sizeof(SK) == 2));
     const uint32_t stride = blockDim.x;
     SK* stk = reinterpret_cast<SK*>(lds) + threadIdx.x;
     uint32_t done = 0u;
@@ -2211,8 +2058,6 @@ struct ShadeTables {
     const uint2* lights;
 };
 
-constexpr uint32_t kLdsInst = 64, kLdsMats = 64, kLdsLights = 64;
-
 __device__ __forceinline__ void stageTables(const DevScene& S, DevInstance* sInst, DevMaterial* sMat, uint2* sLights) {
     const uint32_t nI = S.nInst * (sizeof(DevInstance) / 16), nM = S.nMats * (sizeof(DevMaterial) / 16);
     for (uint32_t k = threadIdx.x; k < nI; k += blockDim.x) reinterpret_cast<float4*>(sInst)[k] = reinterpret_cast<const float4*>(S.inst)[k];
@@ -2224,7 +2069,7 @@ __device__ __forceinline__ void stageTables(const DevScene& S, DevInstance* sIns
 /* The cooperative (one path per wave) kernels stage the trace and shading
  * tables in LDS when they fit; with more instances / materials / lights they
  * read them from global memory (wave-uniform reads).  The host sizes the
- * dynamic LDS the same way (surf_hip.hip coopLds / coopTailLds). */
+ * dynamic LDS from the same layout (lds_layout.h, one ray per wave). */
 /* (a compile-time choice: through a pointer that may be LDS or global, a
  * table load is a flat load the compiler cannot prove wave-uniform, and the
  * walk's scalar operands derive from those loads) */
@@ -2641,15 +2486,15 @@ __global__ __launch_bounds__(kBlock, STG ? 5 : SURF_TRACE_WAVES) void k_connect(
      * that BLAS down to its sampled triangle) staged after a stack of 16-bit
      * entries (every node index < 65536) and the trace tables; stageTrace's
      * barrier publishes them */
-    const uint32_t stackWordsUsed = STG ? stackWords / 2u : stackWords;
+    const uint32_t tablesAt = STG ? layout::stagedTablesAt(stackWords) : layout::laneTablesAt(stackWords, false);
     float4* sN = nullptr;
     if (STG) {
-        sN = reinterpret_cast<float4*>(lds + ((stackWordsUsed + S.nInst * (uint32_t)((sizeof(TraceInst) + 4u) / 4u) + 3u) & ~3u));
+        sN = reinterpret_cast<float4*>(lds + layout::stagedBlasAt(stackWords, S.nInst));
         for (uint32_t k = threadIdx.x; k < 4u * S.sbRecN; k += blockDim.x) sN[k] = S.sbRec[k];
-        float4* const sT = sN + 4u * S.sbRecN;
+        float4* const sT = sN + 4u * S.sbRecN;           /* layout::stagedTrisAt, as blasAnyStaged finds them: behind the records */
         for (uint32_t k = threadIdx.x; k < 3u * S.sbTriN; k += blockDim.x) sT[k] = S.tris[3u * S.sbTri0 + k];
     }
-    const TraceTables Tt = traceTables<LDS>(S, lds, stackWordsUsed);
+    const TraceTables Tt = traceTables<LDS>(S, lds, tablesAt);
     const uint32_t stride = blockDim.x;
     using SK = typename std::conditional<STG, uint16_t, uint32_t>::type;
     SK* stk = reinterpret_cast<SK*>(lds) + threadIdx.x;
@@ -2867,7 +2712,7 @@ __global__ __launch_bounds__(64, SURF_TAIL_WAVES) void k_tail(DevScene S, Pool c
                                              uint32_t stackWords, uint32_t firstCounted, uint32_t budget, Pool surv,
                                              DevCamera cam, StreamGeom G) {
     extern __shared__ uint32_t lds[];
-    const TraceTables Tt = traceTables<LDS_TABLES>(S, lds, stackWords);
+    const TraceTables Tt = traceTables<LDS_TABLES>(S, lds, layout::laneTablesAt(stackWords, false));
     __shared__ DevInstance sInst[LDS_TABLES ? kLdsInst : 1];
     __shared__ DevMaterial sMat[LDS_TABLES ? kLdsMats : 1];
     __shared__ uint2 sLights[LDS_TABLES ? kLdsLights : 1];
@@ -2897,15 +2742,15 @@ __global__ __launch_bounds__(64, SURF_COOP_WAVES) void k_tail_coop(DevScene S, P
                                                   uint32_t* __restrict__ frameDone, uint32_t npx, uint32_t window, Counters* C,
                                                   uint32_t stackWords, uint32_t firstCounted, DevCamera cam, StreamGeom G) {
     extern __shared__ uint32_t lds[];
-    const TraceTables Tt = coopTrace<LDS>(S, lds, stackWords + proWords(S));
+    const TraceTables Tt = coopTrace<LDS>(S, lds, layout::waveTablesAt(stackWords, S.nInst, 1u));
     /* shading's instance / material / light tables in LDS too: a path's
      * segments read them on its dependent chain (the drain's latency floor) */
-    const ShadeTables Tb = coopShade<LDS>(S, lds, (stackWords + proWords(S) + S.nInst * (uint32_t)((sizeof(TraceInst) + 4u) / 4u) + 3u) & ~3u);
+    const ShadeTables Tb = coopShade<LDS>(S, lds, layout::waveShadeAt(stackWords, S.nInst, 1u));
     const uint32_t i = blockIdx.x;
     if (i >= n) return;
     const bool lead = threadIdx.x == 0;
     float* rstk = reinterpret_cast<float*>(lds);     /* the record stack (16 words per entry) */
-    float4* pro = reinterpret_cast<float4*>(lds + stackWords);
+    float4* pro = reinterpret_cast<float4*>(lds + layout::waveProAt(stackWords, S.nInst, 0u));
     const uint32_t maxSeg = C->maxSeg, zeroCutoff = C->zeroCutoff, spp = C->spp;
     const uint32_t st = blockIdx.x % kStripes;
     float4 o4 = cur.od[2u * (i)], d4 = cur.od[2u * (i) + 1u], T4 = cur.T[i];
@@ -3113,18 +2958,17 @@ __global__ __launch_bounds__(128, SURF_COOP_WAVES) void k_tail_pair(DevScene S, 
     extern __shared__ uint32_t lds[];
     __shared__ PairBox box;
     /* LDS: [record stack | prologue table] per wave, then the trace tables and the shading tables */
-    const uint32_t per = stackWords + proWords(S);
     if (threadIdx.x < 2u) {
         box.run[threadIdx.x] = 1u; box.help[threadIdx.x] = 0u;
         box.post[threadIdx.x] = 0u; box.done[threadIdx.x] = 0u; box.occ[threadIdx.x] = 0u;
     }
-    const TraceTables Tt = coopTrace<LDS>(S, lds, 2u * per);
-    const ShadeTables Tb = coopShade<LDS>(S, lds, (2u * per + S.nInst * (uint32_t)((sizeof(TraceInst) + 4u) / 4u) + 3u) & ~3u);
+    const TraceTables Tt = coopTrace<LDS>(S, lds, layout::waveTablesAt(stackWords, S.nInst, 2u));
+    const ShadeTables Tb = coopShade<LDS>(S, lds, layout::waveShadeAt(stackWords, S.nInst, 2u));
     __syncthreads();                                  /* the mailboxes are initialised (global tables: no staging barrier) */
     const uint32_t w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   /* wave-uniform: the walk's LDS bases are scalar */
     const bool lead = (threadIdx.x & 63u) == 0u;
-    float* rstk = reinterpret_cast<float*>(lds + w * per);
-    float4* pro = reinterpret_cast<float4*>(lds + w * per + stackWords);
+    float* rstk = reinterpret_cast<float*>(lds + layout::waveStackAt(stackWords, S.nInst, w));
+    float4* pro = reinterpret_cast<float4*>(lds + layout::waveProAt(stackWords, S.nInst, w));
     PairCounts pc{0, 0, 0, 0, 0, 0, 0, 0};
     uint32_t posted = 0u;                             /* == box.post[w] */
     for (;;) {
@@ -3237,7 +3081,7 @@ __global__ __launch_bounds__(kBlock) void k_trace_closest(DevScene S, const floa
                                                           uint32_t n, float4* __restrict__ tuv, uint2* __restrict__ ip,
                                                           uint32_t stackWords) {
     extern __shared__ uint32_t lds[];
-    const TraceTables Tt = traceTables<LDS>(S, lds, stackWords);
+    const TraceTables Tt = traceTables<LDS>(S, lds, layout::laneTablesAt(stackWords, false));
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     float depth = kFarAway, u = 0.0f, v = 0.0f;
@@ -3252,7 +3096,7 @@ __global__ __launch_bounds__(kBlock) void k_trace_any(DevScene S, const float* _
                                                       const float* __restrict__ tmaxv, uint32_t n, uint8_t* __restrict__ occ,
                                                       uint32_t stackWords) {
     extern __shared__ uint32_t lds[];
-    const TraceTables Tt = traceTables<LDS>(S, lds, stackWords);
+    const TraceTables Tt = traceTables<LDS>(S, lds, layout::laneTablesAt(stackWords, false));
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     float depth = tmaxv[i], u = 0.0f, v = 0.0f;
@@ -3285,7 +3129,7 @@ __global__ __launch_bounds__(kBlock) void k_aov(DevScene S, DevCamera cam, const
     __shared__ DevInstance sInst[LDS ? kLdsInst : 1];
     __shared__ DevMaterial sMat[LDS ? kLdsMats : 1];
     __shared__ uint2 sLights[LDS ? kLdsLights : 1];
-    const TraceTables Tt = traceTables<LDS>(S, lds, stackWords);
+    const TraceTables Tt = traceTables<LDS>(S, lds, layout::laneTablesAt(stackWords, false));
     ShadeTables Tb{S.inst, S.mats, S.lights};
     if (LDS) {
         stageTables(S, sInst, sMat, sLights);
@@ -3342,14 +3186,14 @@ __global__ __launch_bounds__(64) void k_trace_closest_coop(DevScene S, const flo
                                                            uint32_t n, float4* __restrict__ tuv, uint2* __restrict__ ip,
                                                            uint32_t stackWords) {
     extern __shared__ uint32_t lds[];
-    const TraceTables Tt = coopTrace<LDS>(S, lds, stackWords + proWords(S));
+    const TraceTables Tt = coopTrace<LDS>(S, lds, layout::waveTablesAt(stackWords, S.nInst, 1u));
     const uint32_t i = blockIdx.x;
     if (i >= n) return;
     float depth = kFarAway, u = 0.0f, v = 0.0f;
     uint32_t inst = kUnset, prim = kUnset;
     const V3 ro = mk3(o[3 * i], o[3 * i + 1], o[3 * i + 2]), rdir = mk3(d[3 * i], d[3 * i + 1], d[3 * i + 2]);
     const bool hit = traceWave<false, W2>(S, Tt, ro, rdir, depth, u, v, inst, prim, reinterpret_cast<float*>(lds),
-                                      reinterpret_cast<float4*>(lds + stackWords));
+                                      reinterpret_cast<float4*>(lds + layout::waveProAt(stackWords, S.nInst, 0u)));
     if (threadIdx.x == 0) {
         tuv[i] = make_float4(depth, hit ? u : 0.0f, hit ? v : 0.0f, 0.0f);
         ip[i] = make_uint2(hit ? inst : kUnset, hit ? prim : kUnset);
@@ -3360,14 +3204,14 @@ __global__ __launch_bounds__(64) void k_trace_any_coop(DevScene S, const float* 
                                                        const float* __restrict__ tmaxv, uint32_t n, uint8_t* __restrict__ occ,
                                                        uint32_t stackWords) {
     extern __shared__ uint32_t lds[];
-    const TraceTables Tt = coopTrace<LDS>(S, lds, stackWords + proWords(S));
+    const TraceTables Tt = coopTrace<LDS>(S, lds, layout::waveTablesAt(stackWords, S.nInst, 1u));
     const uint32_t i = blockIdx.x;
     if (i >= n) return;
     const V3 ro = mk3(o[3 * i], o[3 * i + 1], o[3 * i + 2]), rdir = mk3(d[3 * i], d[3 * i + 1], d[3 * i + 2]);
     float depth = tmaxv[i], u = 0.0f, v = 0.0f;
     uint32_t inst = kUnset, prim = kUnset;
     const bool oc = traceWave<true, W2>(S, Tt, ro, rdir, depth, u, v, inst, prim, reinterpret_cast<float*>(lds),
-                                    reinterpret_cast<float4*>(lds + stackWords));
+                                    reinterpret_cast<float4*>(lds + layout::waveProAt(stackWords, S.nInst, 0u)));
     if (threadIdx.x == 0) occ[i] = oc ? 1 : 0;
 }
 
@@ -3390,10 +3234,10 @@ template <bool LDS, bool W2>
 __global__ __launch_bounds__(64) void k_segment_cycles(DevScene S, float4 o4, float4 d4, float4 T4, uint32_t reps,
                                                        unsigned long long* __restrict__ cyc, uint32_t stackWords) {
     extern __shared__ uint32_t lds[];
-    const TraceTables Tt = coopTrace<LDS>(S, lds, stackWords + proWords(S));
-    const ShadeTables Tb = coopShade<LDS>(S, lds, (stackWords + proWords(S) + S.nInst * (uint32_t)((sizeof(TraceInst) + 4u) / 4u) + 3u) & ~3u);
+    const TraceTables Tt = coopTrace<LDS>(S, lds, layout::waveTablesAt(stackWords, S.nInst, 1u));
+    const ShadeTables Tb = coopShade<LDS>(S, lds, layout::waveShadeAt(stackWords, S.nInst, 1u));
     float* rstk = reinterpret_cast<float*>(lds);
-    float4* pro = reinterpret_cast<float4*>(lds + stackWords);
+    float4* pro = reinterpret_cast<float4*>(lds + layout::waveProAt(stackWords, S.nInst, 0u));
     unsigned long long c[6] = {0, 0, 0, 0, 0, 0};
     uint32_t sink = 0;
     if (reps & 0x80000000u) {

@@ -1,0 +1,254 @@
+/*
+ * surf_ctx.h -- internal: the device context behind include/surf_hip.h and the
+ * helpers every host translation unit of the library uses (error reporting,
+ * device allocation lists, scene-table upload).  Includes no kernel.
+ */
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <array>
+#include <cstdio>
+#include <map>
+#include <string>
+#include <tuple>
+#include <vector>
+
+#include "surf_hip.h"
+#include "device/types.h"
+
+using namespace surfdev;                     /* internal header: the host code names the shared records unqualified */
+
+constexpr uint32_t kMaxStack = 120;         /* LDS stack entries per ray (block 256 -> 120 KiB max) */
+
+struct surf_ctx {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    uint32_t width = 0, height = 0;
+    std::vector<uint32_t> rows;
+    uint32_t npx = 0;
+    uint32_t capacity = 0;
+    uint32_t window = 0;           /* frames whose samples may be in flight (radiance slots; ensureWindow) */
+    bool windowFixed = false;      /* set by surf_set_frame_batch */
+    bool profiling = false;
+    std::string err;
+
+    /* scene */
+    bool hasScene = false;
+    uint32_t extBlock = 128;       /* k_extend workgroup size (SURF_EXTEND_BLOCK=128|256): 128 measured 5 % faster on k_extend */
+    bool connectGlobal = false;    /* k_connect reads its tables from global memory (SURF_CONNECT_GLOBAL=1, tuning) */
+    bool extStack16 = true;        /* k_extend's stack in 16-bit entries when node indices fit (SURF_EXT_STACK16=0: 32-bit) */
+    bool regenCount = true;        /* k_regen_count fills the next pool and counts it for its sort (SURF_REGEN_COUNT=0: k_regen + k_bincount) */
+    /* the lane walk leaves a ray after laneCap node visits of one BLAS walk
+     * to k_extend_cont (SURF_LANE_CAP; 0 = off, the default: measured slower) */
+    uint32_t laneCap = 0;
+    uint32_t* resumeRec = nullptr;  /* resume records, 64 words each (allocated with the first capped graph) */
+    uint32_t resumeCap = 0;
+    bool ldsTables = false;        /* instance/material/light tables fit the per-workgroup LDS copy */
+    DevScene S{};
+    std::vector<void*> sceneAllocs;
+    uint32_t stackDepth = 0;
+    uint32_t nInstances = 0, nTriangles = 0, nBlasNodes = 0;
+    /* what surf_update_instances may change: instance records, TLAS, lights */
+    uint32_t nMaterials = 0, nLightsUp = 0, tlasNodeCount = 0, maxBlasDepth = 0;
+    std::map<std::tuple<uint32_t, uint32_t, uint32_t>, std::array<float4, 4>> blasRoots;  /* (node, idx, tri offset) -> root record */
+    std::map<uint32_t, std::array<double, 6>> blasBounds;   /* tri offset -> bounds of its BLAS's triangles (v0, v0+e1, v0+e2) */
+    std::map<uint32_t, uint32_t> blasSlots;                  /* tri offset -> index slots (triangles) of its BLAS */
+    /* issue order: the pixels whose centre ray first hits a heavy instance
+     * (long Russian-roulette paths start there) are issued for all frames of a
+     * multi-frame stream before the rest (SURF_REORDER=0: frame-major) */
+    bool reorder = true;
+    bool permValid = false;
+    uint32_t* dPerm = nullptr;
+    /* first-hit feature buffers (surf_read_aov): four planes of npx 16-byte
+     * records, allocated on first use; valid until the camera, the scene or
+     * the instances change (where permValid is cleared) */
+    void* aov[SURF_AOV_COUNT] = {};
+    bool aovValid = false;
+    float aovKernelMs = 0.0f;      /* device time of the last k_aov launch (surf_debug_aov_time) */
+    /* the a-trous denoiser (surf_denoise*): scratch images of dnCap pixels --
+     * the two ping-pong levels, the packed normal and position guides -- and,
+     * for surf_denoise_image, the four uploaded planes; allocated on first use,
+     * grown only when a larger frame arrives, freed in surf_destroy */
+    float4* dn[4] = {};
+    size_t dnCap = 0;
+    float4* dnIn[4] = {};
+    size_t dnInCap = 0;
+    hipEvent_t dnEv[kDenoiseMaxIterations + 2] = {};
+    float dnMs[kDenoiseMaxIterations + 1] = {};   /* prepare, then the iterations of the last run (surf_debug_denoise_time) */
+    /* largest a-trous step whose tile is staged in LDS (SURF_DENOISE_LDS; 0 =
+     * every step reads its taps from global memory).  2: staging takes a third
+     * off the launches at steps 1 and 2 and adds 10 % at step 4 (MEASUREMENTS
+     * "Denoiser") */
+    uint32_t dnLdsMax = 2;
+    /* one-frame render calls may leave up to a pool of their stream unissued
+     * (SURF_LOOP_LAG=0: issue each call's frame before returning) */
+    bool loopLag = true;
+    /* occupancy probes: extra dynamic LDS per k_extend / k_connect workgroup (SURF_EXT_LDS_PAD / SURF_CON_LDS_PAD bytes) */
+    size_t extLdsPad = 0, conLdsPad = 0;
+    /* k_connect stages the emitters' BLAS node records in LDS when they are
+     * few and every BLAS node index fits 16 bits (SURF_LDS_LIGHTBLAS=0: never) */
+    bool ldsLightBlas = true;
+    /* small BLASes in the compact form k_connect stages (blasAnyStaged): BLAS
+     * node offset -> interior records on the device, their count, index offset, triangle slots */
+    struct StagedBlas { const float4* rec; uint32_t recN, tri0, triN; };
+    std::map<uint32_t, StagedBlas> stagedBlas;
+    uint32_t permA = 0, permFrames = 0;
+    std::vector<uint32_t> heavyInst;
+    /* pool ray-order key (SURF_KEY): 2 heavy-instance mask x quadrant, most
+     * heavy instances first (the default: the costliest rays are dealt to the
+     * first-dispatched workgroups, DESIGN 4 "Pool sizing"), 1 the same key
+     * ascending, 0 start instance x quadrant */
+    uint32_t keyMode = 2;
+    /* camera */
+    bool hasCamera = false;
+    DevCamera cam{};
+    surf_camera_ubo camUbo{};
+
+    /* wavefront state */
+    bool allocated = false;
+    Pool pool[2]{};
+    float4* hitTUV = nullptr;
+    uint32_t* hitInst = nullptr;
+    ShadowQ Q{};
+    float4* rad = nullptr;
+    float4* acc = nullptr;
+    uint32_t* dRows = nullptr;
+    Counters* ctr = nullptr;
+    Counters* hctr = nullptr;      /* pinned: the counters as of the last consumed snapshot */
+    uint32_t* frameDone = nullptr; /* [kStripes][window] completions per frame slot */
+    /* host snapshots of the counters and of the open passes' completion
+     * stripes, each taken after a graph replay; a lagged one-frame call may
+     * return with up to kSnaps of them (and their replays) in flight, so the
+     * GPU keeps working while the application runs its loop (pump) */
+    struct Snap { Counters* h = nullptr; uint32_t* fd = nullptr; uint64_t acc = 0, open = 0; int phases = 0; hipEvent_t ev = nullptr; };
+    static constexpr int kSnaps = 2;
+    Snap snap[kSnaps];
+    int snapHead = 0, snapCount = 0;
+    uint64_t issuePerPhase = 0;    /* chains a phase issued in the last unstarved snapshot of this stream: what the replays in flight will issue */
+    bool pipeline = true;          /* SURF_PIPELINE=0: every replay waited for before the next (and before a call returns) */
+    /* issue limits pushed to the device: a ring of pinned sources, so a later
+     * push never rewrites the bytes an earlier, still queued copy reads */
+    static constexpr uint32_t kLimitRing = 16;
+    uint64_t* hLimit = nullptr;
+    uint32_t hLimitNext = 0;
+    /* device time of calls that return with replays in flight: two event
+     * pairs used in turn, read once their end has passed */
+    hipEvent_t tev[2][2] = {};
+    bool tevPending[2] = {false, false};
+    int tevCur = 0;
+    uint32_t* dOutRGBA = nullptr;
+    std::vector<void*> wfAllocs;
+    uint64_t totalSamples = 0;     /* frames rendered since the last clear (samples per pixel) */
+
+    /* sample stream: targetFrames frames of spp samples per pixel requested,
+     * i.e. passes (samples per pixel) [0, targetFrames * spp) after the
+     * baseFrame samples rendered before the stream; pass q lives in radiance
+     * slot q % window (window a multiple of spp) */
+    bool streamActive = false;
+    uint64_t baseFrame = 0;        /* sample count before the stream (the reference's totalSamples) */
+    uint64_t targetFrames = 0;     /* frames requested (chains per pixel) */
+    uint64_t accPasses = 0;        /* passes accumulated (in order) */
+    uint32_t spp = 1;              /* samples per frame of the stream (a frame's samples chain their RNG state) */
+    uint32_t streamMaxSeg = 0;
+    int zeroCutoff = -1;           /* early end of paths with throughput < FLT_MIN: 1 on, 0 off, -1 automatic (on for 1-sample frames) */
+    uint64_t pushedLimit = 0;
+    uint32_t tailPaths = 0;        /* drain policy (surf_set_tail_policy), 0 = automatic */
+    uint32_t tailBudget = 16;      /* per-stage segment budget of the drain tail (0 = one stage); 16: measured fastest */
+    Pool surv[2]{};                /* drain survivors, ping-pong between stages */
+    uint32_t survCap = 0;
+    uint32_t coopMax = 0;          /* survivors handled by the cooperative tail (one path per wave) */
+    uint32_t coopAll = 150000;     /* drain paths left to the cooperative tail (surf_set_tail_coop); C3 drain 176-184 ms at 60000, 172-178 at 150000 */
+    int drainReplays = 1;          /* graph replays per host poll while draining (SURF_DRAIN_REPLAYS) */
+    bool drainShort = false;       /* short replays once nothing is left to issue (SURF_DRAIN_SHORT=1; measured slower, MEASUREMENTS round 5) */
+    bool regenFirst = false;       /* k_regen before the connect fork (SURF_REGEN_FIRST=1; measured equal, MEASUREMENTS round 5) */
+    int traceMode = 0;             /* surf_trace_closest/_any: 0 one ray per lane, 1 one ray per wave */
+    bool connectStaged = false;    /* the last k_connect launched walked the emitters' BLAS from LDS (surf_debug_connect_staging) */
+    bool tailPair = true;          /* cooperative drain on k_tail_pair (partner waves trace the shadow rays; SURF_TAIL_PAIR=0: k_tail_coop) */
+    uint32_t cus = 256;            /* compute units of the device */
+    bool sortRays = true;          /* order each phase's rays by start instance (SURF_SORT=0: off) */
+    bool sortPool = true;
+    bool sortShadow = true;        /* ... and the shadow queue by light (SURF_SORT=2: pool only, 3: shadow queue only) */
+    /* ray order: counts from k_regen_count (or k_bincount), then k_binscatter each phase */
+    uint32_t* order = nullptr;
+    uint32_t* binHist = nullptr;
+    /* connect overlapped with the next phase's regen / pool sort / extend
+     * (SURF_OVERLAP=0: one stream): its own stream in the graph capture, its
+     * own shadow order and histograms */
+    bool overlap = true;
+    hipStream_t side = nullptr;
+    std::vector<hipEvent_t> capEv;   /* two per phase of a full replay (sized by createCtx) */
+    uint32_t tailLanes = 0;
+    uint32_t segMaxBase = 0;       /* longest path of finished streams */
+    uint64_t tailFirstRays = 0;    /* first extension rays of drained paths: counted by regen, traced by the tail */
+
+    /* graph */
+    hipGraphExec_t graphExec = nullptr, graphExecShort = nullptr;
+    hipGraph_t graph = nullptr, graphShort = nullptr;
+    uint32_t gridWork = 0, gridRegen = 0, gridExtend = 0, gridConnect = 0;
+
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    std::vector<hipEvent_t> pev;   /* profiling: kPhaseEvents per phase of a full replay + the end (sized by createCtx) */
+    uint32_t* hPhaseN = nullptr;   /* profiling + SURF_PHASE_LOG: paths each phase extends (pinned) */
+    FILE* phaseLog = nullptr;      /* SURF_PHASE_LOG=<file>: one line per profiled phase (size, kernel ms) */
+    surf_stats stats{};
+    unsigned long long evBase[kEvents] = {};   /* event counts of finished streams since the last clear */
+};
+
+/* the helpers, and what one host translation unit of the library defines for
+ * the others (a namespace of their own: the library's C++ symbols stay clear
+ * of an application's) */
+namespace surfhost {
+/* the last error of any context, for surf_last_error(NULL) */
+void setGlobalError(const std::string& e);
+/* defined beside the sample stream (surf_hip.hip): whatever replaces scene
+ * tables first ends the stream that reads them and drops the captured graphs,
+ * whose kernel arguments carry the scene descriptor */
+int endStream(surf_ctx* c);
+void destroyGraph(surf_ctx* c);
+
+#define SURF_CHECK(ctx, call)                                                             \
+    do {                                                                                  \
+        hipError_t e_ = (call);                                                           \
+        if (e_ != hipSuccess) {                                                           \
+            (ctx)->err = std::string(#call) + ": " + hipGetErrorString(e_);               \
+            setGlobalError((ctx)->err);                                                   \
+            return SURF_ERR_HIP;                                                          \
+        }                                                                                 \
+    } while (0)
+
+inline int fail(surf_ctx* c, int code, const std::string& msg) {
+    if (c) c->err = msg;
+    setGlobalError(msg);
+    return code;
+}
+
+template <class T>
+int devAlloc(surf_ctx* c, std::vector<void*>& list, T** out, size_t count) {
+    *out = nullptr;
+    if (count == 0) count = 1;
+    void* p = nullptr;
+    if (hipMalloc(&p, count * sizeof(T)) != hipSuccess || !p) {
+        return fail(c, SURF_ERR_OOM, "hipMalloc of " + std::to_string(count * sizeof(T)) + " bytes failed");
+    }
+    list.push_back(p);
+    *out = static_cast<T*>(p);
+    return SURF_OK;
+}
+
+inline void freeList(std::vector<void*>& list) {
+    for (void* p : list) (void)hipFree(p);
+    list.clear();
+}
+
+template <class T>
+int upload(surf_ctx* c, const std::vector<T>& host, const T** devOut) {
+    T* d = nullptr;
+    int rc = devAlloc(c, c->sceneAllocs, &d, host.size());
+    if (rc) return rc;
+    if (!host.empty()) SURF_CHECK(c, hipMemcpy(d, host.data(), host.size() * sizeof(T), hipMemcpyHostToDevice));
+    *devOut = d;
+    return SURF_OK;
+}
+
+}  // namespace surfhost
+using namespace surfhost;

@@ -1,32 +1,24 @@
 /*
- * surf_hip.hip -- C-ABI implementation (include/surf_hip.h): device context,
- * scene upload + re-layout, the wavefront render loop (hipGraph-captured
- * phases), readback.  Replaces WaveFrontRenderer's Vulkan orchestration
+ * surf_hip.hip -- the kernels' translation unit: kernel selection, the
+ * wavefront render loop (hipGraph-captured phases), the sample stream's pump
+ * and drain, feature buffers, denoiser and the C ABI (include/surf_hip.h)
+ * around them.  Replaces WaveFrontRenderer's Vulkan orchestration
  * (renderer.cpp:604-1454) -- without its per-bounce host round trip: the
  * host only polls a pinned counter block once per replayed graph of
- * kPhasesPerGraph phases.
+ * kPhasesPerGraph phases.  Scene validation and re-layout launch no kernel
+ * and live in host/scene_upload.hip.
  */
-#include <hip/hip_runtime.h>
+#include "host/surf_ctx.h"
 
 #include <algorithm>
 #include <chrono>
 #include <cmath>
-#include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <cfloat>
-#include <array>
-#include <map>
 #include <mutex>
-#include <tuple>
-#include <string>
-#include <vector>
 
-#include "surf_hip.h"
 #include "device/wavefront_kernels.h"
 #include "device/denoise_kernels.h"
-
-using namespace surfdev;
 
 namespace {
 
@@ -40,8 +32,8 @@ constexpr int kPhasesPerGraph = SURF_PHASES_GRAPH;   /* even: parity returns to 
 static_assert(kPhasesPerGraph % 2 == 0, "even: parity returns to 0 after a replay");
 /* The short graph: a render call with at most one frame left to issue (the
  * drop-in loop's 1-spp render(), main.cpp:381-446) replays 4 phases per host
- * poll instead of 8, so a per-frame call does not keep the pool a quarter full
- * for 8 phases per frame.  4096 one-frame calls at 1280x720: 625 / 641 / 637
+ * poll instead of 16, so a per-frame call does not keep the pool a quarter full
+ * for 16 phases per frame.  4096 one-frame calls at 1280x720: 625 / 641 / 637
  * Mrays/s with 2 / 4 / 8 phases (each replay's end joins its last k_connect,
  * which then overlaps nothing; MEASUREMENTS round 5). */
 #ifndef SURF_PHASES_SHORT
@@ -50,234 +42,16 @@ static_assert(kPhasesPerGraph % 2 == 0, "even: parity returns to 0 after a repla
 constexpr int kPhasesShort = SURF_PHASES_SHORT;
 static_assert(kPhasesShort % 2 == 0 && kPhasesShort <= kPhasesPerGraph, "even: parity returns to 0 after a replay");
 constexpr int kPhaseEvents = 6;             /* profiling events per phase: sort, extend, shade, sort, connect, regen */
-constexpr uint32_t kMaxStack = 120;          /* LDS stack entries per ray (block 256 -> 120 KiB max) */
 constexpr uint64_t kMaxIterations = 1ull << 22;  /* safety net: a path longer than this is a bug */
 
 std::mutex gErrMutex;
 std::string gLastError;
 
-void setGlobalError(const std::string& e) { std::lock_guard<std::mutex> l(gErrMutex); gLastError = e; }
-
-template <class T>
-struct DevBuf {
-    T* p = nullptr;
-    size_t n = 0;
-    void release() { if (p) (void)hipFree(p); p = nullptr; n = 0; }
-};
-
 }  // namespace
 
-struct surf_ctx {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    uint32_t width = 0, height = 0;
-    std::vector<uint32_t> rows;
-    uint32_t npx = 0;
-    uint32_t capacity = 0;
-    uint32_t window = 0;           /* frames whose samples may be in flight (radiance slots; ensureWindow) */
-    bool windowFixed = false;      /* set by surf_set_frame_batch */
-    bool profiling = false;
-    std::string err;
+void surfhost::setGlobalError(const std::string& e) { std::lock_guard<std::mutex> l(gErrMutex); gLastError = e; }
 
-    /* scene */
-    bool hasScene = false;
-    uint32_t extBlock = 128;       /* k_extend workgroup size (SURF_EXTEND_BLOCK=128|256): 128 measured 5 % faster on k_extend */
-    bool connectGlobal = false;    /* k_connect reads its tables from global memory (SURF_CONNECT_GLOBAL=1, tuning) */
-    bool extStack16 = true;        /* k_extend's stack in 16-bit entries when node indices fit (SURF_EXT_STACK16=0: 32-bit) */
-    bool regenCount = true;        /* k_regen_count fills the next pool and counts it for its sort (SURF_REGEN_COUNT=0: k_regen + k_bincount) */
-    /* the lane walk leaves a ray after laneCap node visits of one BLAS walk
-     * to k_extend_cont (SURF_LANE_CAP; 0 = off, the default: measured slower) */
-    uint32_t laneCap = 0;
-    uint32_t* resumeRec = nullptr;  /* resume records, 64 words each (allocated with the first capped graph) */
-    uint32_t resumeCap = 0;
-    bool ldsTables = false;        /* instance/material/light tables fit the per-workgroup LDS copy */
-    DevScene S{};
-    std::vector<void*> sceneAllocs;
-    uint32_t stackDepth = 0;
-    uint32_t nInstances = 0, nTriangles = 0, nBlasNodes = 0;
-    /* what surf_update_instances may change: instance records, TLAS, lights */
-    uint32_t nMaterials = 0, nLightsUp = 0, tlasNodeCount = 0, maxBlasDepth = 0;
-    std::map<std::tuple<uint32_t, uint32_t, uint32_t>, std::array<float4, 4>> blasRoots;  /* (node, idx, tri offset) -> root record */
-    std::map<uint32_t, std::array<double, 6>> blasBounds;   /* tri offset -> bounds of its BLAS's triangles (v0, v0+e1, v0+e2) */
-    std::map<uint32_t, uint32_t> blasSlots;                  /* tri offset -> index slots (triangles) of its BLAS */
-    /* issue order: the pixels whose centre ray first hits a heavy instance
-     * (long Russian-roulette paths start there) are issued for all frames of a
-     * multi-frame stream before the rest (SURF_REORDER=0: frame-major) */
-    bool reorder = true;
-    bool permValid = false;
-    uint32_t* dPerm = nullptr;
-    /* first-hit feature buffers (surf_read_aov): four planes of npx 16-byte
-     * records, allocated on first use; valid until the camera, the scene or
-     * the instances change (where permValid is cleared) */
-    void* aov[SURF_AOV_COUNT] = {};
-    bool aovValid = false;
-    float aovKernelMs = 0.0f;      /* device time of the last k_aov launch (surf_debug_aov_time) */
-    /* the a-trous denoiser (surf_denoise*): scratch images of dnCap pixels --
-     * the two ping-pong levels, the packed normal and position guides -- and,
-     * for surf_denoise_image, the four uploaded planes; allocated on first use,
-     * grown only when a larger frame arrives, freed in surf_destroy */
-    float4* dn[4] = {};
-    size_t dnCap = 0;
-    float4* dnIn[4] = {};
-    size_t dnInCap = 0;
-    hipEvent_t dnEv[kDenoiseMaxIterations + 2] = {};
-    float dnMs[kDenoiseMaxIterations + 1] = {};   /* prepare, then the iterations of the last run (surf_debug_denoise_time) */
-    /* largest a-trous step whose tile is staged in LDS (SURF_DENOISE_LDS; 0 =
-     * every step reads its taps from global memory).  2: staging takes a third
-     * off the launches at steps 1 and 2 and adds 10 % at step 4 (MEASUREMENTS
-     * "Denoiser") */
-    uint32_t dnLdsMax = 2;
-    /* one-frame render calls may leave up to a pool of their stream unissued
-     * (SURF_LOOP_LAG=0: issue each call's frame before returning) */
-    bool loopLag = true;
-    /* occupancy probes: extra dynamic LDS per k_extend / k_connect workgroup (SURF_EXT_LDS_PAD / SURF_CON_LDS_PAD bytes) */
-    size_t extLdsPad = 0, conLdsPad = 0;
-    /* k_connect stages the emitters' BLAS node records in LDS when they are
-     * few and every BLAS node index fits 16 bits (SURF_LDS_LIGHTBLAS=0: never) */
-    bool ldsLightBlas = true;
-    /* small BLASes in the compact form k_connect stages (blasAnyStaged): BLAS
-     * node offset -> interior records on the device, their count, index offset, triangle slots */
-    struct StagedBlas { const float4* rec; uint32_t recN, tri0, triN; };
-    std::map<uint32_t, StagedBlas> stagedBlas;
-    uint32_t permA = 0, permFrames = 0;
-    std::vector<uint32_t> heavyInst;
-    /* pool ray-order key (SURF_KEY): 2 heavy-instance mask x quadrant, most
-     * heavy instances first (the default: the costliest rays are dealt to the
-     * first-dispatched workgroups, DESIGN 4 "Pool sizing"), 1 the same key
-     * ascending, 0 start instance x quadrant */
-    uint32_t keyMode = 2;
-    /* camera */
-    bool hasCamera = false;
-    DevCamera cam{};
-    surf_camera_ubo camUbo{};
-
-    /* wavefront state */
-    bool allocated = false;
-    Pool pool[2]{};
-    float4* hitTUV = nullptr;
-    uint32_t* hitInst = nullptr;
-    ShadowQ Q{};
-    float4* rad = nullptr;
-    float4* acc = nullptr;
-    uint32_t* dRows = nullptr;
-    Counters* ctr = nullptr;
-    Counters* hctr = nullptr;      /* pinned: the counters as of the last consumed snapshot */
-    uint32_t* frameDone = nullptr; /* [kStripes][window] completions per frame slot */
-    /* host snapshots of the counters and of the open passes' completion
-     * stripes, each taken after a graph replay; a lagged one-frame call may
-     * return with up to kSnaps of them (and their replays) in flight, so the
-     * GPU keeps working while the application runs its loop (pump) */
-    struct Snap { Counters* h = nullptr; uint32_t* fd = nullptr; uint64_t acc = 0, open = 0; int phases = 0; hipEvent_t ev = nullptr; };
-    static constexpr int kSnaps = 2;
-    Snap snap[kSnaps];
-    int snapHead = 0, snapCount = 0;
-    uint64_t issuePerPhase = 0;    /* chains a phase issued in the last unstarved snapshot of this stream: what the replays in flight will issue */
-    bool pipeline = true;          /* SURF_PIPELINE=0: every replay waited for before the next (and before a call returns) */
-    /* issue limits pushed to the device: a ring of pinned sources, so a later
-     * push never rewrites the bytes an earlier, still queued copy reads */
-    static constexpr uint32_t kLimitRing = 16;
-    uint64_t* hLimit = nullptr;
-    uint32_t hLimitNext = 0;
-    /* device time of calls that return with replays in flight: two event
-     * pairs used in turn, read once their end has passed */
-    hipEvent_t tev[2][2] = {};
-    bool tevPending[2] = {false, false};
-    int tevCur = 0;
-    uint32_t* dOutRGBA = nullptr;
-    std::vector<void*> wfAllocs;
-    uint64_t totalSamples = 0;     /* frames rendered since the last clear (samples per pixel) */
-
-    /* sample stream: targetFrames frames of spp samples per pixel requested,
-     * i.e. passes (samples per pixel) [0, targetFrames * spp) after the
-     * baseFrame samples rendered before the stream; pass q lives in radiance
-     * slot q % window (window a multiple of spp) */
-    bool streamActive = false;
-    uint64_t baseFrame = 0;        /* sample count before the stream (the reference's totalSamples) */
-    uint64_t targetFrames = 0;     /* frames requested (chains per pixel) */
-    uint64_t accPasses = 0;        /* passes accumulated (in order) */
-    uint32_t spp = 1;              /* samples per frame of the stream (a frame's samples chain their RNG state) */
-    uint32_t streamMaxSeg = 0;
-    int zeroCutoff = -1;           /* early end of paths with throughput < FLT_MIN: 1 on, 0 off, -1 automatic (on for 1-sample frames) */
-    uint64_t pushedLimit = 0;
-    uint32_t tailPaths = 0;        /* drain policy (surf_set_tail_policy), 0 = automatic */
-    uint32_t tailBudget = 16;      /* per-stage segment budget of the drain tail (0 = one stage); 16: measured fastest */
-    Pool surv[2]{};                /* drain survivors, ping-pong between stages */
-    uint32_t survCap = 0;
-    uint32_t coopMax = 0;          /* survivors handled by the cooperative tail (one path per wave) */
-    uint32_t coopAll = 150000;     /* drain paths left to the cooperative tail (surf_set_tail_coop); C3 drain 176-184 ms at 60000, 172-178 at 150000 */
-    int drainReplays = 1;          /* graph replays per host poll while draining (SURF_DRAIN_REPLAYS) */
-    bool drainShort = false;       /* short replays once nothing is left to issue (SURF_DRAIN_SHORT=1; measured slower, MEASUREMENTS round 5) */
-    bool regenFirst = false;       /* k_regen before the connect fork (SURF_REGEN_FIRST=1; measured equal, MEASUREMENTS round 5) */
-    int traceMode = 0;             /* surf_trace_closest/_any: 0 one ray per lane, 1 one ray per wave */
-    bool connectStaged = false;    /* the last k_connect launched walked the emitters' BLAS from LDS (surf_debug_connect_staging) */
-    bool tailPair = true;          /* cooperative drain on k_tail_pair (partner waves trace the shadow rays; SURF_TAIL_PAIR=0: k_tail_coop) */
-    uint32_t cus = 256;            /* compute units of the device */
-    bool sortRays = true;          /* order each phase's rays by start instance (SURF_SORT=0: off) */
-    bool sortPool = true;
-    bool sortShadow = true;        /* ... and the shadow queue by light (SURF_SORT=2: pool only, 3: shadow queue only) */
-    /* ray order: counts from k_regen_count (or k_bincount), then k_binscatter each phase */
-    uint32_t* order = nullptr;
-    uint32_t* binHist = nullptr;
-    /* connect overlapped with the next phase's regen / pool sort / extend
-     * (SURF_OVERLAP=0: one stream): its own stream in the graph capture, its
-     * own shadow order and histograms */
-    bool overlap = true;
-    hipStream_t side = nullptr;
-    hipEvent_t capEv[2 * kPhasesPerGraph] = {};
-    uint32_t tailLanes = 0;
-    uint32_t segMaxBase = 0;       /* longest path of finished streams */
-    uint64_t tailFirstRays = 0;    /* first extension rays of drained paths: counted by regen, traced by the tail */
-
-    /* graph */
-    hipGraphExec_t graphExec = nullptr, graphExecShort = nullptr;
-    hipGraph_t graph = nullptr, graphShort = nullptr;
-    uint32_t gridWork = 0, gridRegen = 0, gridExtend = 0, gridConnect = 0;
-
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    hipEvent_t pev[kPhasesPerGraph * kPhaseEvents + 1] = {};   /* profiling: kPhaseEvents per phase + the end */
-    uint32_t* hPhaseN = nullptr;   /* profiling + SURF_PHASE_LOG: paths each phase extends (pinned) */
-    FILE* phaseLog = nullptr;      /* SURF_PHASE_LOG=<file>: one line per profiled phase (size, kernel ms) */
-    surf_stats stats{};
-    unsigned long long evBase[kEvents] = {};   /* event counts of finished streams since the last clear */
-};
-
-#define SURF_CHECK(ctx, call)                                                             \
-    do {                                                                                  \
-        hipError_t e_ = (call);                                                           \
-        if (e_ != hipSuccess) {                                                           \
-            (ctx)->err = std::string(#call) + ": " + hipGetErrorString(e_);               \
-            setGlobalError((ctx)->err);                                                   \
-            return SURF_ERR_HIP;                                                          \
-        }                                                                                 \
-    } while (0)
-
-namespace {
-
-int fail(surf_ctx* c, int code, const std::string& msg) {
-    if (c) c->err = msg;
-    setGlobalError(msg);
-    return code;
-}
-
-template <class T>
-int devAlloc(surf_ctx* c, std::vector<void*>& list, T** out, size_t count) {
-    *out = nullptr;
-    if (count == 0) count = 1;
-    void* p = nullptr;
-    if (hipMalloc(&p, count * sizeof(T)) != hipSuccess || !p) {
-        return fail(c, SURF_ERR_OOM, "hipMalloc of " + std::to_string(count * sizeof(T)) + " bytes failed");
-    }
-    list.push_back(p);
-    *out = static_cast<T*>(p);
-    return SURF_OK;
-}
-
-void freeList(std::vector<void*>& list) {
-    for (void* p : list) (void)hipFree(p);
-    list.clear();
-}
-
-void destroyGraph(surf_ctx* c) {
+void surfhost::destroyGraph(surf_ctx* c) {
     if (c->graphExec) (void)hipGraphExecDestroy(c->graphExec);
     if (c->graph) (void)hipGraphDestroy(c->graph);
     if (c->graphExecShort) (void)hipGraphExecDestroy(c->graphExecShort);
@@ -286,91 +60,122 @@ void destroyGraph(surf_ctx* c) {
     c->graph = c->graphShort = nullptr;
 }
 
-/* Dynamic LDS of a traversal kernel with `block` threads: the per-lane stack,
- * then (LDS tables) the TraceInst table and the TLAS index array. */
-uint32_t stackWords(const surf_ctx* c, uint32_t block) { return c->stackDepth * block; }
-/* one-ray-per-wave traversal (traceWave): a stack of node records, 16 words per
- * entry -- 64 with two-level records (blasWalk2 pushes whole W records) */
-uint32_t recStackWords(const surf_ctx* c) { return c->stackDepth * (c->S.wnodes ? 64u : 16u); }
-/* Dynamic LDS of the one-ray-per-wave kernels: the record stack, the prologue
- * table (16 words per instance), then the trace tables; k_tail_coop adds the
- * shading tables (coopTailLds). */
-/* (tables staged only when they fit: coopLdsTables in the kernels) */
-size_t coopLds(const surf_ctx* c) {
-    return ((size_t)recStackWords(c) + 16u * c->nInstances) * sizeof(float) +
-           (c->ldsTables ? (size_t)c->nInstances * (sizeof(TraceInst) + sizeof(uint32_t)) : 0);
+namespace {
+
+/* ---- kernel selection -----------------------------------------------------
+ * Everything the context decides about a launch is decided here: the facts
+ * that pick an instantiation (Variant), one selector per kernel family, and
+ * with each choice the dynamic LDS it needs -- taken from the layout the
+ * kernel itself reads (device/lds_layout.h), so an instantiation and its LDS
+ * size cannot be paired wrongly at a call site.  Nothing below this section
+ * spells a kernel's template arguments. */
+
+/* an instantiation and the dynamic LDS bytes a launch of it needs */
+template <class F>
+struct Kernel { F fn; size_t lds; };
+template <class F>
+Kernel<F> kernel(F fn, size_t lds) { return {fn, lds}; }
+
+size_t ldsBytes(uint32_t words) { return (size_t)words * sizeof(uint32_t); }
+
+/* the kernels' `stackWords` argument: the lane kernels' stack with 32-bit
+ * entries, the wave kernels' stack of node records */
+uint32_t stackWords(const surf_ctx* c, uint32_t block) { return layout::laneStack32(c->stackDepth, block); }
+uint32_t recStackWords(const surf_ctx* c) { return layout::recStackWords(c->stackDepth, c->S.wnodes != nullptr); }
+
+size_t laneLds(const surf_ctx* c, uint32_t block, bool entries16, bool tables) {
+    return ldsBytes(layout::laneTotal(stackWords(c, block), entries16, tables, c->nInstances));
 }
-size_t coopTailLds(const surf_ctx* c) {
-    if (!c->ldsTables) return coopLds(c);
-    return ((coopLds(c) + 15) & ~(size_t)15) + (size_t)c->nInstances * sizeof(DevInstance) + (size_t)c->nMaterials * sizeof(DevMaterial) +
-           (size_t)c->nLightsUp * sizeof(uint2);
+size_t stagedLds(const surf_ctx* c) {
+    return ldsBytes(layout::stagedTotal(stackWords(c, kBlock), c->nInstances, c->S.sbRecN, c->S.sbTriN));
 }
-/* k_tail_pair: a record stack and a prologue table per wave (two waves), then the tables */
-size_t pairTailLds(const surf_ctx* c) {
-    return coopTailLds(c) + ((size_t)recStackWords(c) + 16u * c->nInstances) * sizeof(float);
+size_t waveTraceLds(const surf_ctx* c) { return ldsBytes(layout::waveTraceTotal(recStackWords(c), c->nInstances, c->ldsTables)); }
+size_t waveTailLds(const surf_ctx* c, uint32_t waves) {
+    return ldsBytes(layout::waveTailTotal(recStackWords(c), c->nInstances, c->nMaterials, c->nLightsUp, c->ldsTables, waves));
 }
-/* the one-ray-per-wave kernels' LDS: stack + prologue table per wave (+ tables) within 64 KiB */
-bool coopLdsOk(const surf_ctx* c) { return pairTailLds(c) <= 65536; }
-size_t traversalLds(const surf_ctx* c, uint32_t block) {
-    size_t b = (size_t)stackWords(c, block) * sizeof(uint32_t);
-    if (c->ldsTables) b += (size_t)c->nInstances * (sizeof(TraceInst) + sizeof(uint32_t));
-    return b;
+/* the one-ray-per-wave kernels fit the LDS: the largest of them, k_tail_pair, within 64 KiB */
+bool coopLdsOk(const surf_ctx* c) { return waveTailLds(c, 2u) <= 65536; }
+
+/* The capped lane walk (LaneCap): a TLAS of one leaf of <= 64 instances and
+ * a stack that fits a resume record */
+bool laneCapOn(const surf_ctx* c) {
+    return c->laneCap > 0u && c->S.tlasLeafCount >= 1u && c->S.tlasLeafCount <= 64u && c->stackDepth <= 64u - kResumeHead;
 }
 
-/* ----------------------------------------------------------- scene upload
- * Walks every BLAS/TLAS from its root: validates indices (no kernel can
- * fault on a malformed scene), measures depth, and emits the device node
- * record that carries the children's boxes. */
-struct TreeWalk {
-    uint32_t depth = 0;
-    bool ok = true;
-    std::string why;
+struct Variant {
+    bool lds;      /* the trace and shading tables fit the per-workgroup LDS copy */
+    bool laneW;    /* the lane walk over the two-level records (HBM-resident BVHs) */
+    bool w2;       /* the wave walk over the two-level records */
+    bool sk16;     /* k_extend's stack in 16-bit entries: every node index fits (the two-level lane walk stacks 32-bit packed leaf references) */
+    bool cap;      /* the capped lane walk */
+    bool ldsC;     /* k_connect's tables in LDS (else global: LDS holds only its stack) */
+    bool stg;      /* ... and the emitters' BLAS beside them, behind a 16-bit stack */
 };
-
-TreeWalk walkTree(const surf_bvh_node* nodes, uint32_t nodeCount, uint32_t offset, uint32_t idxCount, uint32_t idxOffset,
-                  std::vector<float4>& out, std::vector<uint8_t>& leafSeen, std::vector<uint32_t>* owner = nullptr) {
-    TreeWalk w;
-    std::vector<std::pair<uint32_t, uint32_t>> st{{0u, 0u}};
-    size_t visits = 0;
-    while (!st.empty()) {
-        auto [local, dep] = st.back();
-        st.pop_back();
-        if (++visits > (size_t)nodeCount + 1 || dep > 4096) { w.ok = false; w.why = "BVH has a cycle"; return w; }
-        const uint64_t g = (uint64_t)offset + local;
-        if (g >= nodeCount) { w.ok = false; w.why = "BVH node index out of range"; return w; }
-        const surf_bvh_node& n = nodes[g];
-        float4* rec = &out[4 * g];
-        if (owner) (*owner)[g] = offset;
-        rec[0].w = u2f(n.left_first);
-        rec[1].w = u2f(n.count);
-        if (n.count != 0) {
-            if ((uint64_t)idxOffset + n.left_first + n.count > idxCount) { w.ok = false; w.why = "BVH leaf range out of range"; return w; }
-            for (uint32_t k = 0; k < n.count; ++k) leafSeen[idxOffset + n.left_first + k] = 1;
-            w.depth = std::max(w.depth, dep);
-            continue;
-        }
-        const uint64_t l = (uint64_t)offset + n.left_first;
-        if (l + 1 >= nodeCount) { w.ok = false; w.why = "BVH child index out of range"; return w; }
-        const surf_bvh_node& L = nodes[l];
-        const surf_bvh_node& R = nodes[l + 1];
-        rec[0] = make_float4(L.bb_min.x, L.bb_min.y, L.bb_min.z, rec[0].w);
-        rec[1] = make_float4(L.bb_max.x, L.bb_max.y, L.bb_max.z, rec[1].w);
-        rec[2] = make_float4(R.bb_min.x, R.bb_min.y, R.bb_min.z, 0.0f);
-        rec[3] = make_float4(R.bb_max.x, R.bb_max.y, R.bb_max.z, 0.0f);
-        st.push_back({n.left_first + 1, dep + 1});
-        st.push_back({n.left_first, dep + 1});
-    }
-    return w;
+Variant variantOf(const surf_ctx* c) {
+    Variant v;
+    v.lds = c->ldsTables;
+    v.laneW = c->S.laneW != 0u;
+    v.w2 = c->S.wnodes != nullptr;
+    v.sk16 = c->extStack16 && !v.laneW && c->nBlasNodes < 65536u && c->tlasNodeCount < 65536u;
+    v.cap = laneCapOn(c);
+    v.ldsC = v.lds && !c->connectGlobal;
+    /* staged only where the copy still leaves 5 workgroups of 256 per CU
+     * (k_connect's residency; 144 B of static LDS each) */
+    v.stg = v.ldsC && !v.laneW && c->S.sbRecN > 0u && (stagedLds(c) + 256) * 5 <= 163840;
+    return v;
 }
 
-template <class T>
-int upload(surf_ctx* c, const std::vector<T>& host, const T** devOut) {
-    T* d = nullptr;
-    int rc = devAlloc(c, c->sceneAllocs, &d, host.size());
-    if (rc) return rc;
-    if (!host.empty()) SURF_CHECK(c, hipMemcpy(d, host.data(), host.size() * sizeof(T), hipMemcpyHostToDevice));
-    *devOut = d;
-    return SURF_OK;
+/* the four instantiations of a kernel template over two bools */
+#define SURF_PICK2(K, a, b) ((a) ? ((b) ? K<true, true> : K<true, false>) : ((b) ? K<false, true> : K<false, false>))
+
+/* k_extend<LDS, LW, SK, CAP>: 12 of the 16 -- the two-level lane walk never takes a 16-bit stack */
+template <bool LDS>
+auto extendFn(const Variant& v) {
+    if (v.laneW) return v.cap ? k_extend<LDS, true, uint32_t, true> : k_extend<LDS, true, uint32_t, false>;
+    if (v.sk16) return v.cap ? k_extend<LDS, false, uint16_t, true> : k_extend<LDS, false, uint16_t, false>;
+    return v.cap ? k_extend<LDS, false, uint32_t, true> : k_extend<LDS, false, uint32_t, false>;
+}
+auto extendKernel(const surf_ctx* c, const Variant& v) {
+    return kernel(v.lds ? extendFn<true>(v) : extendFn<false>(v), laneLds(c, c->extBlock, v.sk16, v.lds) + c->extLdsPad);
+}
+
+/* k_extend_cont<LDS, LW, SK>: the capped walk's second pass, the stack as k_extend has it */
+template <bool LDS>
+auto extendContFn(const Variant& v) {
+    if (v.laneW) return k_extend_cont<LDS, true, uint32_t>;
+    return v.sk16 ? k_extend_cont<LDS, false, uint16_t> : k_extend_cont<LDS, false, uint32_t>;
+}
+auto extendContKernel(const surf_ctx* c, const Variant& v) {
+    return kernel(v.lds ? extendContFn<true>(v) : extendContFn<false>(v), laneLds(c, kBlock, v.sk16, v.lds));
+}
+
+auto shadeKernel(const Variant& v) { return v.lds ? k_shade<true> : k_shade<false>; }
+
+/* k_connect<LDS, LW, STG>: staged only over LDS tables and one-level records */
+auto connectKernel(const surf_ctx* c, const Variant& v) {
+    const auto fn = v.laneW ? (v.ldsC ? k_connect<true, true, false> : k_connect<false, true, false>)
+                   : v.stg ? k_connect<true, false, true>
+                           : (v.ldsC ? k_connect<true, false, false> : k_connect<false, false, false>);
+    return kernel(fn, (v.stg ? stagedLds(c) : laneLds(c, kBlock, false, v.ldsC)) + c->conLdsPad);
+}
+
+/* the lane kernels of 256 threads over <LDS, LW>, and k_tail's 64 */
+auto traceClosestKernel(const surf_ctx* c, const Variant& v) { return kernel(SURF_PICK2(k_trace_closest, v.lds, v.laneW), laneLds(c, kBlock, false, v.lds)); }
+auto traceAnyKernel(const surf_ctx* c, const Variant& v) { return kernel(SURF_PICK2(k_trace_any, v.lds, v.laneW), laneLds(c, kBlock, false, v.lds)); }
+auto aovKernel(const surf_ctx* c, const Variant& v) { return kernel(SURF_PICK2(k_aov, v.lds, v.laneW), laneLds(c, kBlock, false, v.lds)); }
+auto tailKernel(const surf_ctx* c, const Variant& v) { return kernel(v.lds ? k_tail<true> : k_tail<false>, laneLds(c, 64, false, v.lds)); }
+
+/* the one-ray-per-wave kernels over <LDS, W2> */
+auto tailPairKernel(const surf_ctx* c, const Variant& v) { return kernel(SURF_PICK2(k_tail_pair, v.lds, v.w2), waveTailLds(c, 2u)); }
+auto tailCoopKernel(const surf_ctx* c, const Variant& v) { return kernel(SURF_PICK2(k_tail_coop, v.lds, v.w2), waveTailLds(c, 1u)); }
+auto segmentCyclesKernel(const surf_ctx* c, const Variant& v) { return kernel(SURF_PICK2(k_segment_cycles, v.lds, v.w2), waveTailLds(c, 1u)); }
+auto traceClosestCoopKernel(const surf_ctx* c, const Variant& v) { return kernel(SURF_PICK2(k_trace_closest_coop, v.lds, v.w2), waveTraceLds(c)); }
+auto traceAnyCoopKernel(const surf_ctx* c, const Variant& v) { return kernel(SURF_PICK2(k_trace_any_coop, v.lds, v.w2), waveTraceLds(c)); }
+
+/* k_atrous<STAGED> at step s: the staged one holds the tile and its 2 s halo, three float4 planes */
+auto atrousKernel(bool staged, int s) {
+    return kernel(staged ? k_atrous<true> : k_atrous<false>,
+                  staged ? (size_t)3 * sizeof(float4) * (kDenoiseTileW + 4 * s) * (kDenoiseTileH + 4 * s) : 0);
 }
 
 int allocWavefront(surf_ctx* c) {
@@ -478,7 +283,6 @@ int allocWavefront(surf_ctx* c) {
  * later, longer stream grows the ring; a window set by surf_set_frame_batch
  * is kept as given. */
 constexpr uint64_t kWindowFloor = 256, kLoopFloor = 4096;
-constexpr uint64_t kLdsLightBlas = 20480;     /* k_connect's staged emitter BLAS (compact records + triangles), bytes at most */
 int ensureWindow(surf_ctx* c, uint64_t frames, uint32_t spp) {
     const uint64_t passes = frames * spp;
     const uint64_t floor = frames == 1 ? kLoopFloor : kWindowFloor;
@@ -523,12 +327,6 @@ int ensureWindow(surf_ctx* c, uint64_t frames, uint32_t spp) {
 
 StreamGeom geom(const surf_ctx* c) { return StreamGeom{c->dRows, c->width, c->npx, c->window, c->dPerm}; }
 
-/* The capped lane walk (LaneCap): a TLAS of one leaf of <= 64 instances and
- * a stack that fits a resume record */
-bool laneCapOn(const surf_ctx* c) {
-    return c->laneCap > 0u && c->S.tlasLeafCount >= 1u && c->S.tlasLeafCount <= 64u && c->stackDepth <= 64u - kResumeHead;
-}
-
 /* Counting sort of the pool (which 0) or shadow queue (which 1) of phase par
  * by its 4-bit key into c->order. */
 void launchSort(surf_ctx* c, const uint8_t* key, int par, int which, hipStream_t st, uint32_t* hist, uint32_t* out, bool count = true) {
@@ -553,7 +351,7 @@ void launchSort(surf_ctx* c, const uint8_t* key, int par, int which, hipStream_t
  * contribution of bounce i must be added before what bounce i+1 adds. */
 void launchPhase(surf_ctx* c, int ph, hipEvent_t* ev) {
     const int par = ph & 1;
-    const uint32_t sw = stackWords(c, kBlock);
+    const Variant v = variantOf(c);
     const bool ovl = !ev && c->overlap;
     hipStream_t s0 = c->stream, s1 = ovl ? c->side : c->stream;
     if (ev && c->phaseLog)
@@ -576,40 +374,21 @@ void launchPhase(surf_ctx* c, int ph, hipEvent_t* ev) {
     };
     if (ev) (void)hipEventRecord(ev[1], s0);
     const Pool cur = c->pool[par];                 /* the pool k_extend / k_shade read */
-    /* LW: the two-level records in the lane traversal (HBM-resident BVHs, S.laneW) */
-    /* 16-bit stack entries when every node index fits (the lane walk over
-     * two-level records stacks 32-bit packed leaf references) */
-    const bool sk16 = c->extStack16 && !c->S.laneW && c->nBlasNodes < 65536u && c->tlasNodeCount < 65536u;
-    const bool capW = laneCapOn(c);
-    auto extendK = c->S.laneW ? (capW ? (c->ldsTables ? k_extend<true, true, uint32_t, true> : k_extend<false, true, uint32_t, true>)
-                                      : (c->ldsTables ? k_extend<true, true> : k_extend<false, true>))
-                   : capW ? (sk16 ? (c->ldsTables ? k_extend<true, false, uint16_t, true> : k_extend<false, false, uint16_t, true>)
-                                  : (c->ldsTables ? k_extend<true, false, uint32_t, true> : k_extend<false, false, uint32_t, true>))
-                          : sk16 ? (c->ldsTables ? k_extend<true, false, uint16_t> : k_extend<false, false, uint16_t>)
-                                 : (c->ldsTables ? k_extend<true, false> : k_extend<false, false>);
-    const size_t extLds = traversalLds(c, c->extBlock) - (sk16 ? (size_t)stackWords(c, c->extBlock) * 2u : 0u);
-    hipLaunchKernelGGL(extendK, dim3(c->gridExtend), dim3(c->extBlock), extLds + c->extLdsPad, s0, c->S,
+    const auto extend = extendKernel(c, v);
+    hipLaunchKernelGGL(extend.fn, dim3(c->gridExtend), dim3(c->extBlock), extend.lds, s0, c->S,
                        cur, c->hitTUV, c->hitInst, (const Counters*)c->ctr, par, stackWords(c, c->extBlock), order,
                        c->laneCap, c->resumeRec, c->resumeCap);
-    if (capW) {   /* the rays the capped lane walk left, 64 to a wave again (LaneCap) */
-        auto contK = c->S.laneW ? (c->ldsTables ? k_extend_cont<true, true, uint32_t> : k_extend_cont<false, true, uint32_t>)
-                     : sk16 ? (c->ldsTables ? k_extend_cont<true, false, uint16_t> : k_extend_cont<false, false, uint16_t>)
-                            : (c->ldsTables ? k_extend_cont<true, false, uint32_t> : k_extend_cont<false, false, uint32_t>);
-        hipLaunchKernelGGL(contK, dim3(std::min<uint32_t>((c->resumeCap + kBlock - 1) / kBlock, c->cus * 8u)), dim3(kBlock),
-                           traversalLds(c, kBlock) - (sk16 ? (size_t)stackWords(c, kBlock) * 2u : 0u), s0, c->S, cur, c->hitTUV,
-                           c->hitInst, (const Counters*)c->ctr, par, stackWords(c, kBlock), (const uint32_t*)c->resumeRec,
-                           c->resumeCap);
+    if (v.cap) {   /* the rays the capped lane walk left, 64 to a wave again (LaneCap) */
+        const auto cont = extendContKernel(c, v);
+        hipLaunchKernelGGL(cont.fn, dim3(std::min<uint32_t>((c->resumeCap + kBlock - 1) / kBlock, c->cus * 8u)), dim3(kBlock),
+                           cont.lds, s0, c->S, cur, c->hitTUV, c->hitInst, (const Counters*)c->ctr, par, stackWords(c, kBlock),
+                           (const uint32_t*)c->resumeRec, c->resumeCap);
     }
     if (ev) (void)hipEventRecord(ev[2], s0);
     if (ovl && ph > 0) (void)hipStreamWaitEvent(s0, c->capEv[2 * (ph - 1) + 1], 0);   /* the previous phase's connect */
-    if (c->ldsTables)
-        hipLaunchKernelGGL(k_shade<true>, dim3(c->gridWork), dim3(kBlock), 0, s0, c->S, cur, c->pool[par ^ 1],
-                           c->hitTUV, (const uint32_t*)c->hitInst, c->Q, c->rad, c->frameDone, c->npx, c->window, c->ctr, par, order,
-                           c->cam, geom(c));
-    else
-        hipLaunchKernelGGL(k_shade<false>, dim3(c->gridWork), dim3(kBlock), 0, s0, c->S, cur, c->pool[par ^ 1],
-                           c->hitTUV, (const uint32_t*)c->hitInst, c->Q, c->rad, c->frameDone, c->npx, c->window, c->ctr, par, order,
-                           c->cam, geom(c));
+    hipLaunchKernelGGL(shadeKernel(v), dim3(c->gridWork), dim3(kBlock), 0, s0, c->S, cur, c->pool[par ^ 1],
+                       c->hitTUV, (const uint32_t*)c->hitInst, c->Q, c->rad, c->frameDone, c->npx, c->window, c->ctr, par, order,
+                       c->cam, geom(c));
     if (ev) (void)hipEventRecord(ev[3], s0);
     /* k_regen before the fork (SURF_REGEN_FIRST): alone it takes ~17 us, beside
      * k_connect it waits for CU slots on the next phase's critical path */
@@ -621,20 +400,13 @@ void launchPhase(surf_ctx* c, int ph, hipEvent_t* ev) {
     /* (the shadow rays are already in bin order: k_shade appends each to its
      * bin's region of the queue -- no sort pass) */
     if (ev) (void)hipEventRecord(ev[4], s0);
-    const bool ldsC = c->ldsTables && !c->connectGlobal;   /* else global tables: LDS holds only the traversal stack */
-    /* the emitters' BLAS in LDS (S.sbRecN > 0): after the stack and the tables, 16-B aligned */
-    const size_t stgLds = ((((size_t)sw * sizeof(uint16_t) + (size_t)c->nInstances * (sizeof(TraceInst) + sizeof(uint32_t))) + 15) & ~(size_t)15) +
-                          (size_t)c->S.sbRecN * 64 + (size_t)c->S.sbTriN * 48;
-    /* staged only where the copy still leaves 5 workgroups of 256 per CU
-     * (k_connect's residency; 144 B of static LDS each) */
-    const bool stg = ldsC && !c->S.laneW && c->S.sbRecN > 0u && (stgLds + 256) * 5 <= 163840;
-    c->connectStaged = stg;
-    auto connectK = c->S.laneW ? (ldsC ? k_connect<true, true> : k_connect<false, true>)
-                               : (ldsC ? (stg ? k_connect<true, false, true> : k_connect<true, false>) : k_connect<false, false>);
-    /* staged: 16-bit stack entries (half the stack's LDS) leave room for the
-     * copy beside 5 workgroups of 256 per CU, the residency k_connect runs at */
-    const size_t connectLds = (!ldsC ? (size_t)sw * sizeof(uint32_t) : stg ? stgLds : traversalLds(c, kBlock)) + c->conLdsPad;
-    hipLaunchKernelGGL(connectK, dim3(c->gridConnect), dim3(kBlock), connectLds, s1, c->S, c->Q, c->rad, c->ctr, par, sw);
+    /* staged (the emitters' BLAS in LDS): 16-bit stack entries (half the
+     * stack's LDS) leave room for the copy beside 5 workgroups of 256 per CU,
+     * the residency k_connect runs at */
+    c->connectStaged = v.stg;
+    const auto connect = connectKernel(c, v);
+    hipLaunchKernelGGL(connect.fn, dim3(c->gridConnect), dim3(kBlock), connect.lds, s1, c->S, c->Q, c->rad, c->ctr, par,
+                       stackWords(c, kBlock));
     if (ovl) (void)hipEventRecord(c->capEv[2 * ph + 1], s1);
     if (ev) (void)hipEventRecord(ev[5], s0);
     if (!c->regenFirst) regen();
@@ -664,6 +436,42 @@ int buildGraph(surf_ctx* c) {
     return SURF_OK;
 }
 
+/* Closest hits of n host rays (o, d: 3 floats per ray) on the context's
+ * stream: upload, k_trace_closest -- one ray per lane, or per wave (perWave:
+ * k_trace_closest_coop) -- and the records read back: (instance, primitive)
+ * into ip and, when asked for, (t, u, v) into tuv.  `what` names the caller
+ * in an error. */
+int traceClosestRays(surf_ctx* c, uint32_t n, const float* o, const float* d, bool perWave, std::vector<float4>* tuv,
+                     std::vector<uint2>& ip, const char* what) {
+    std::vector<void*> tmp;
+    float *dO, *dD; float4* dT; uint2* dI;
+    int rc;
+    if ((rc = devAlloc(c, tmp, &dO, 3 * (size_t)n)) || (rc = devAlloc(c, tmp, &dD, 3 * (size_t)n)) ||
+        (rc = devAlloc(c, tmp, &dT, n)) || (rc = devAlloc(c, tmp, &dI, n))) { freeList(tmp); return rc; }
+    (void)hipMemcpyAsync(dO, o, 12 * (size_t)n, hipMemcpyHostToDevice, c->stream);
+    (void)hipMemcpyAsync(dD, d, 12 * (size_t)n, hipMemcpyHostToDevice, c->stream);
+    const Variant v = variantOf(c);
+    if (perWave) {
+        const auto k = traceClosestCoopKernel(c, v);
+        hipLaunchKernelGGL(k.fn, dim3(n), dim3(64), k.lds, c->stream, c->S, (const float*)dO, (const float*)dD, n, dT, dI,
+                           recStackWords(c));
+    } else {
+        const auto k = traceClosestKernel(c, v);
+        hipLaunchKernelGGL(k.fn, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), k.lds, c->stream, c->S, (const float*)dO,
+                           (const float*)dD, n, dT, dI, stackWords(c, kBlock));
+    }
+    ip.resize(n);
+    if (tuv) {
+        tuv->resize(n);
+        (void)hipMemcpyAsync(tuv->data(), dT, sizeof(float4) * (size_t)n, hipMemcpyDeviceToHost, c->stream);
+    }
+    (void)hipMemcpyAsync(ip.data(), dI, sizeof(uint2) * (size_t)n, hipMemcpyDeviceToHost, c->stream);
+    const hipError_t e = hipStreamSynchronize(c->stream);
+    freeList(tmp);
+    if (e != hipSuccess) return fail(c, SURF_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
+    return SURF_OK;
+}
+
 /* Pixel classes of the issue order (cached until the camera, the scene or
  * the instances change): class A = the local pixels whose centre camera ray
  * first hits one of the heavy instances (setKeys).  Long Russian-roulette
@@ -688,22 +496,8 @@ int classifyPixels(surf_ctx* c) {
         const float inv = 1.0f / std::sqrt(len2);
         for (int a = 0; a < 3; ++a) { o[3 * (size_t)lp + a] = k.pos[a]; d[3 * (size_t)lp + a] = dir[a] * inv; }
     }
-    std::vector<void*> tmp;
-    float *dO, *dD; float4* dT; uint2* dI;
-    int rc;
-    if ((rc = devAlloc(c, tmp, &dO, 3 * (size_t)n)) || (rc = devAlloc(c, tmp, &dD, 3 * (size_t)n)) ||
-        (rc = devAlloc(c, tmp, &dT, n)) || (rc = devAlloc(c, tmp, &dI, n))) { freeList(tmp); return rc; }
-    std::vector<uint2> ip(n);
-    (void)hipMemcpyAsync(dO, o.data(), 12 * (size_t)n, hipMemcpyHostToDevice, c->stream);
-    (void)hipMemcpyAsync(dD, d.data(), 12 * (size_t)n, hipMemcpyHostToDevice, c->stream);
-    hipLaunchKernelGGL(c->S.laneW ? (c->ldsTables ? k_trace_closest<true, true> : k_trace_closest<false, true>)
-                                  : (c->ldsTables ? k_trace_closest<true, false> : k_trace_closest<false, false>),
-                       dim3((n + kBlock - 1) / kBlock), dim3(kBlock), traversalLds(c, kBlock), c->stream,
-                       c->S, (const float*)dO, (const float*)dD, n, dT, dI, stackWords(c, kBlock));
-    (void)hipMemcpyAsync(ip.data(), dI, sizeof(uint2) * (size_t)n, hipMemcpyDeviceToHost, c->stream);
-    const hipError_t e = hipStreamSynchronize(c->stream);
-    freeList(tmp);
-    if (e != hipSuccess) return fail(c, SURF_ERR_HIP, std::string("pixel classification: ") + hipGetErrorString(e));
+    std::vector<uint2> ip;
+    if (int rc = traceClosestRays(c, n, o.data(), d.data(), false, nullptr, ip, "pixel classification")) return rc;
     std::vector<uint32_t> perm;
     perm.reserve(n);
     for (int cls = 0; cls < 2; ++cls)
@@ -735,10 +529,8 @@ int ensureAov(surf_ctx* c) {
             return fail(c, SURF_ERR_OOM, "hipMalloc of a feature plane (" + std::to_string((size_t)c->npx * 16) + " bytes) failed");
         }
     SURF_CHECK(c, hipEventRecord(c->ev0, c->stream));
-    hipLaunchKernelGGL(c->S.laneW ? (c->ldsTables ? k_aov<true, true> : k_aov<false, true>)
-                                  : (c->ldsTables ? k_aov<true, false> : k_aov<false, false>),
-                       dim3((c->npx + kBlock - 1) / kBlock), dim3(kBlock), traversalLds(c, kBlock), c->stream,
-                       c->S, c->cam, (const uint32_t*)c->dRows, c->width, c->npx, static_cast<float4*>(c->aov[SURF_AOV_POSITION]),
+    const auto aov = aovKernel(c, variantOf(c));
+    hipLaunchKernelGGL(aov.fn, dim3((c->npx + kBlock - 1) / kBlock), dim3(kBlock), aov.lds, c->stream, c->S, c->cam, (const uint32_t*)c->dRows, c->width, c->npx, static_cast<float4*>(c->aov[SURF_AOV_POSITION]),
                        static_cast<float4*>(c->aov[SURF_AOV_NORMAL]), static_cast<float4*>(c->aov[SURF_AOV_ALBEDO]),
                        static_cast<uint4*>(c->aov[SURF_AOV_ID]), stackWords(c, kBlock));
     SURF_CHECK(c, hipGetLastError());
@@ -810,16 +602,9 @@ int runDenoise(surf_ctx* c, uint32_t w, uint32_t h, const float4* acc, const flo
         const int s = 1 << i;
         const DenoiseConsts k = denoiseConsts(P, i);
         const int last = i + 1 == P.iterations;
-        if ((uint32_t)s <= stagedMax) {
-            const size_t lds = (size_t)3 * sizeof(float4) * (kDenoiseTileW + 4 * s) * (kDenoiseTileH + 4 * s);
-            hipLaunchKernelGGL(k_atrous<true>, grid, dim3(256), lds, c->stream, (const float4*)lvl[i & 1], (const float4*)gN,
-                               (const float4*)gP, alb, lvl[(i & 1) ^ 1], (int)w, (int)h, s, k.kc, k.kn, k.kp,
-                               P.demodulate ? 1u : 0u, last);
-        } else {
-            hipLaunchKernelGGL(k_atrous<false>, grid, dim3(256), 0, c->stream, (const float4*)lvl[i & 1], (const float4*)gN,
-                               (const float4*)gP, alb, lvl[(i & 1) ^ 1], (int)w, (int)h, s, k.kc, k.kn, k.kp,
-                               P.demodulate ? 1u : 0u, last);
-        }
+        const auto atrous = atrousKernel((uint32_t)s <= stagedMax, s);
+        hipLaunchKernelGGL(atrous.fn, grid, dim3(256), atrous.lds, c->stream, (const float4*)lvl[i & 1], (const float4*)gN,
+                           (const float4*)gP, alb, lvl[(i & 1) ^ 1], (int)w, (int)h, s, k.kc, k.kn, k.kp, P.demodulate ? 1u : 0u, last);
         SURF_CHECK(c, hipGetLastError());
         SURF_CHECK(c, hipEventRecord(c->dnEv[i + 2], c->stream));
     }
@@ -875,6 +660,11 @@ int startStream(surf_ctx* c, uint64_t baseFrame, uint32_t maxSeg, uint32_t frame
     h.spp = spp;
     h.baseFrame = baseFrame;
     h.survCap = c->survCap;
+    /* The fused count (k_regen_count) relies on this: binHist is valid only
+     * for the pool the previous phase's k_regen_count produced, and the first
+     * phase's sort does not recount it.  So every pool change outside the
+     * graph zeroes nIn -- here both pools start empty (h is zeroed), so the
+     * stale counts order no path. */
     *c->hctr = h;
     SURF_CHECK(c, hipMemcpyAsync(c->ctr, c->hctr, sizeof(Counters), hipMemcpyHostToDevice, c->stream));
     SURF_CHECK(c, hipMemsetAsync(c->frameDone, 0, (size_t)kStripes * c->window * sizeof(uint32_t), c->stream));
@@ -1047,13 +837,9 @@ int advance(surf_ctx* c, bool shortRun = false) {
  * phase boundary: pool 0 is the next to be extended, nothing else pending). */
 void launchTail(surf_ctx* c, Pool in, uint32_t n, uint32_t lpw, uint32_t firstCounted, uint32_t budget, Pool out) {
     const uint32_t blocks = (n + lpw - 1) / lpw;
-    const size_t lds = traversalLds(c, 64);
-    if (c->ldsTables)
-        hipLaunchKernelGGL(k_tail<true>, dim3(blocks), dim3(64), lds, c->stream, c->S, in, n, lpw, c->rad, c->frameDone,
-                           c->npx, c->window, c->ctr, stackWords(c, 64), firstCounted, budget, out, c->cam, geom(c));
-    else
-        hipLaunchKernelGGL(k_tail<false>, dim3(blocks), dim3(64), lds, c->stream, c->S, in, n, lpw, c->rad, c->frameDone,
-                           c->npx, c->window, c->ctr, stackWords(c, 64), firstCounted, budget, out, c->cam, geom(c));
+    const auto tail = tailKernel(c, variantOf(c));
+    hipLaunchKernelGGL(tail.fn, dim3(blocks), dim3(64), tail.lds, c->stream, c->S, in, n, lpw, c->rad, c->frameDone,
+                       c->npx, c->window, c->ctr, stackWords(c, 64), firstCounted, budget, out, c->cam, geom(c));
 }
 
 /* Finishes every path of pool 0 (counters at an even phase boundary: pool 0 is
@@ -1075,6 +861,7 @@ int runTail(surf_ctx* c) {
     if (n == 0) return SURF_OK;
     if (c->profiling) SURF_CHECK(c, hipEventRecord(c->pev[0], c->stream));
     Pool in = c->pool[0];
+    const Variant v = variantOf(c);
     uint32_t cnt = n, firstCounted = 1u;
     c->tailFirstRays += n;
     int buf = 0;
@@ -1091,25 +878,20 @@ int runTail(surf_ctx* c) {
              * taking paths from the queue; idle waves trace their sibling's
              * shadow rays once the queue is empty */
             int per = 0;
-            const bool w2 = c->S.wnodes != nullptr;
-            auto kern = c->ldsTables ? (w2 ? k_tail_pair<true, true> : k_tail_pair<true, false>)
-                                     : (w2 ? k_tail_pair<false, true> : k_tail_pair<false, false>);
-            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, kern, 128, pairTailLds(c)) != hipSuccess || per < 1)
+            const auto pair = tailPairKernel(c, v);
+            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, pair.fn, 128, pair.lds) != hipSuccess || per < 1)
                 per = 2 * SURF_COOP_WAVES;
             const uint32_t blocks = std::max<uint32_t>(1u, std::min<uint32_t>((cnt + 1u) / 2u, c->cus * (uint32_t)per));
             SURF_CHECK(c, hipMemsetAsync(&c->ctr->rowNext, 0, sizeof(uint32_t), c->stream));
-            hipLaunchKernelGGL(kern, dim3(blocks), dim3(128), pairTailLds(c), c->stream, c->S, in, cnt, c->rad, c->frameDone,
+            hipLaunchKernelGGL(pair.fn, dim3(blocks), dim3(128), pair.lds, c->stream, c->S, in, cnt, c->rad, c->frameDone,
                                c->npx, c->window, c->ctr, recStackWords(c), firstCounted, c->cam, geom(c));
             SURF_CHECK(c, hipGetLastError());
             c->stats.tail_survivors += cnt;
             break;
         }
         if (waveEligible(c) && cnt <= c->coopAll) {
-            const bool w2 = c->S.wnodes != nullptr;
-            hipLaunchKernelGGL(c->ldsTables ? (w2 ? k_tail_coop<true, true> : k_tail_coop<true, false>)
-                                            : (w2 ? k_tail_coop<false, true> : k_tail_coop<false, false>),
-                               dim3(cnt), dim3(64), coopTailLds(c), c->stream,
-                               c->S, in, cnt, c->rad, c->frameDone,
+            const auto coop = tailCoopKernel(c, v);
+            hipLaunchKernelGGL(coop.fn, dim3(cnt), dim3(64), coop.lds, c->stream, c->S, in, cnt, c->rad, c->frameDone,
                                c->npx, c->window, c->ctr, recStackWords(c), firstCounted, c->cam, geom(c));
             SURF_CHECK(c, hipGetLastError());
             c->stats.tail_survivors += cnt;
@@ -1174,7 +956,11 @@ int runTail(surf_ctx* c) {
         SURF_CHECK(c, hipMemcpyToSymbol(HIP_SYMBOL(g_segStats), zero, sizeof(zero)));   /* per drain, like the counters */
     }
 #endif
-    /* pool 0 is now empty: the next phase starts from regen's refill */
+    /* pool 0 is now empty: the next phase starts from regen's refill.  The
+     * fused count relies on this too: binHist still holds k_regen_count's
+     * counts of the pool the tail just finished, valid for no other pool, and
+     * the next replay's first sort does not recount -- with nIn zeroed it
+     * orders no path, and that phase's k_regen_count counts the refill. */
     c->hctr->nIn[0] = 0;
     SURF_CHECK(c, hipMemcpyAsync(&c->ctr->nIn[0], &c->hctr->nIn[0], sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
     SURF_CHECK(c, hipStreamSynchronize(c->stream));
@@ -1243,7 +1029,7 @@ int pump(surf_ctx* c, bool drain, uint64_t lag) {
             /* a per-frame render call (lagged, or at most one frame left to
              * issue): short replays (SURF_DRAIN_SHORT=1: also once nothing is
              * left to issue, so the drain takes over within kPhasesShort phases instead
-             * of up to 8 -- measured slower) */
+             * of up to kPhasesPerGraph (16) -- measured slower) */
             const bool shortRun = (!drain && (lag > 0 || target - issued <= c->npx)) || (starved && c->drainShort);
             for (int k = 0; k < reps; ++k)
                 if ((rc = advance(c, shortRun))) return rc;
@@ -1296,8 +1082,10 @@ int ensureDrained(surf_ctx* c) {
     return SURF_OK;
 }
 
+}  // namespace
+
 /* A stream ends when its pool is empty and all its frames are accumulated. */
-int endStream(surf_ctx* c) {
+int surfhost::endStream(surf_ctx* c) {
     int rc = ensureDrained(c);
     if (rc) return rc;
     if (c->streamActive) {
@@ -1309,6 +1097,8 @@ int endStream(surf_ctx* c) {
     c->streamActive = false;
     return SURF_OK;
 }
+
+namespace {
 
 /* Which rows a shard owns. */
 std::vector<uint32_t> shardRows(uint32_t height, uint32_t shard, uint32_t shards, uint32_t block) {
@@ -1342,6 +1132,8 @@ int createCtx(int dev, uint32_t w, uint32_t h, std::vector<uint32_t> rows, surf_
         extBlock = (uint32_t)b;
     }
     auto* c = new surf_ctx();
+    c->capEv.assign(2 * kPhasesPerGraph, nullptr);
+    c->pev.assign(kPhasesPerGraph * kPhaseEvents + 1, nullptr);
     c->device = dev;
     c->extBlock = extBlock;
     if (const char* e = std::getenv("SURF_SORT")) {
@@ -1568,461 +1360,6 @@ int surf_set_profiling(surf_ctx* c, int enabled) {
     int rc = endStream(c);
     if (rc) return rc;
     c->profiling = enabled != 0;
-    return SURF_OK;
-}
-
-/* Instance-dependent tables (GPUScene::update re-uploads exactly these,
- * scene.cpp:267-282): DevInstance + TraceInst per instance, the TLAS node
- * records and index array, the light list.  BLAS roots come from the upload. */
-struct InstanceTables {
-    std::vector<DevInstance> inst;
-    std::vector<TraceInst> tinst;
-    std::vector<float4> tnodes;
-    std::vector<uint32_t> tidx;
-    std::vector<uint2> lights;
-    uint32_t tlasDepth = 0, tlasLeafCount = 0;
-    uint32_t nHeavy = 0;
-    float4 hvLo[3], hvHi[3];
-    uint32_t hvInst[3] = {0, 0, 0};
-};
-
-/* The heavy-instance boxes of the ray-order keys (kernel arguments). */
-void setKeys(surf_ctx* c, DevScene& S, const InstanceTables& T) {
-    c->heavyInst.assign(T.hvInst, T.hvInst + T.nHeavy);
-    c->permValid = false;                 /* the pixel classes follow the instances */
-    c->aovValid = false;                  /* ... and so do the feature buffers */
-    S.nHeavy = T.nHeavy;
-    for (uint32_t h = 0; h < 3; ++h) {
-        S.hvLo[h] = h < T.nHeavy ? T.hvLo[h] : make_float4(0, 0, 0, 0);
-        S.hvHi[h] = h < T.nHeavy ? T.hvHi[h] : make_float4(0, 0, 0, 0);
-    }
-    S.keyMode = T.nHeavy ? c->keyMode : 0u;
-    /* the emitters' BLAS, when every light instance uses one BLAS and its
-     * node records fit kLdsLightBlas bytes: k_connect stages them */
-    S.sbNode0 = S.sbRecN = S.sbTri0 = S.sbTriN = 0u;
-    S.sbRec = nullptr;
-    if (c->ldsLightBlas && !T.lights.empty()) {
-        bool one = true;
-        const DevInstance* L0 = T.lights[0].x < T.inst.size() ? &T.inst[T.lights[0].x] : nullptr;
-        for (const uint2& L : T.lights)
-            one = one && L0 && L.x < T.inst.size() && T.inst[L.x].nodeOffset == L0->nodeOffset &&
-                  T.inst[L.x].idxOffset == L0->idxOffset && T.inst[L.x].triOffset == L0->triOffset;
-        const auto sb = one ? c->stagedBlas.find(L0->nodeOffset) : c->stagedBlas.end();
-        /* 16-bit stack entries: every BLAS and TLAS node index below 65536 */
-        const bool small = c->nBlasNodes < 65536u && T.tnodes.size() / 4 < 65536u;
-        if (small && sb != c->stagedBlas.end() && sb->second.tri0 == L0->idxOffset) {
-            S.sbNode0 = sb->first; S.sbRec = sb->second.rec; S.sbRecN = sb->second.recN;
-            S.sbTri0 = sb->second.tri0; S.sbTriN = sb->second.triN;
-        }
-    }
-}
-
-int buildInstanceTables(surf_ctx* c, const surf_gpu_instance* instances, uint32_t n, const uint32_t* tlasIdx,
-                        const surf_bvh_node* tlasNodes, uint32_t nTlas, const surf_light* lights, uint32_t nLights, InstanceTables& T) {
-    auto affine = [](const float* m) { return m[3] == 0.0f && m[7] == 0.0f && m[11] == 0.0f && m[15] == 1.0f; };
-    T.inst.resize(n);
-    T.tinst.resize(n);
-    for (uint32_t i = 0; i < n; ++i) {
-        const surf_gpu_instance& g = instances[i];
-        const auto root = c->blasRoots.find(std::make_tuple(g.bvh_node_offset, g.bvh_idx_offset, g.tri_offset));
-        if (root == c->blasRoots.end() || g.material_offset >= c->nMaterials)
-            return fail(c, SURF_ERR_INVALID, "instance " + std::to_string(i) + ": offsets do not name an uploaded BLAS/material");
-        DevInstance& D = T.inst[i];
-        std::memcpy(D.Minv, g.inv_transform, sizeof D.Minv);
-        std::memcpy(D.M, g.transform, sizeof D.M);
-        D.triOffset = g.tri_offset; D.idxOffset = g.bvh_idx_offset; D.nodeOffset = g.bvh_node_offset; D.material = g.material_offset;
-        D.area = g.area;
-        /* row 3 of a column-major matrix: elements 3, 7, 11, 15 */
-        D.affineInv = affine(g.inv_transform) ? 1u : 0u;
-        D.affine = affine(g.transform) ? 1u : 0u;
-        const float* m = D.Minv;
-        TraceInst& R = T.tinst[i];
-        R.m0 = make_float4(m[0], m[4], m[8], m[12]);
-        R.m1 = make_float4(m[1], m[5], m[9], m[13]);
-        R.m2 = make_float4(m[2], m[6], m[10], m[14]);
-        R.m3 = make_float4(m[3], m[7], m[11], m[15]);
-        R.meta = make_uint4(D.nodeOffset, D.idxOffset, D.affineInv, i);
-        R.r0 = root->second[0]; R.r1 = root->second[1]; R.r2 = root->second[2]; R.r3 = root->second[3];
-        /* conservative world box: the triangle bounds' corners mapped to world
-         * space by the inverse of the M^-1 the traversal applies (inverted in
-         * double, so the box matches the object-space rays whatever M says),
-         * padded by 1e-4 of the box's coordinate magnitude times the matrix's
-         * condition number (~1000x the float rounding of the ray transform,
-         * slab terms and triangle test); not usable (never culls) for a
-         * projective or singular M^-1 or non-finite bounds */
-        R.wlo = make_float4(0, 0, 0, 0);
-        R.whi = make_float4(0, 0, 0, 0);
-        const auto bb = c->blasBounds.find(g.tri_offset);
-        double A[3][3], t[3], B[3][3];      /* M^-1 = [A t; 0 1] (column-major input), B = A^-1 */
-        for (int r = 0; r < 3; ++r) {
-            for (int q = 0; q < 3; ++q) A[r][q] = (double)g.inv_transform[4 * q + r];
-            t[r] = (double)g.inv_transform[12 + r];
-        }
-        const double det = A[0][0] * (A[1][1] * A[2][2] - A[1][2] * A[2][1]) - A[0][1] * (A[1][0] * A[2][2] - A[1][2] * A[2][0]) +
-                           A[0][2] * (A[1][0] * A[2][1] - A[1][1] * A[2][0]);
-        if (bb != c->blasBounds.end() && D.affineInv && std::isfinite(det) && det != 0.0) {
-            B[0][0] = (A[1][1] * A[2][2] - A[1][2] * A[2][1]) / det; B[0][1] = (A[0][2] * A[2][1] - A[0][1] * A[2][2]) / det;
-            B[0][2] = (A[0][1] * A[1][2] - A[0][2] * A[1][1]) / det; B[1][0] = (A[1][2] * A[2][0] - A[1][0] * A[2][2]) / det;
-            B[1][1] = (A[0][0] * A[2][2] - A[0][2] * A[2][0]) / det; B[1][2] = (A[0][2] * A[1][0] - A[0][0] * A[1][2]) / det;
-            B[2][0] = (A[1][0] * A[2][1] - A[1][1] * A[2][0]) / det; B[2][1] = (A[0][1] * A[2][0] - A[0][0] * A[2][1]) / det;
-            B[2][2] = (A[0][0] * A[1][1] - A[0][1] * A[1][0]) / det;
-            double na = 0.0, nb = 0.0;
-            for (int r = 0; r < 3; ++r)
-                for (int q = 0; q < 3; ++q) { na += A[r][q] * A[r][q]; nb += B[r][q] * B[r][q]; }
-            const double cond = std::sqrt(na * nb);
-            double lo[3] = {HUGE_VAL, HUGE_VAL, HUGE_VAL}, hi[3] = {-HUGE_VAL, -HUGE_VAL, -HUGE_VAL};
-            for (int corner = 0; corner < 8; ++corner) {
-                const double p[3] = {bb->second[(corner & 1) ? 3 : 0] - t[0], bb->second[(corner & 2) ? 4 : 1] - t[1],
-                                     bb->second[(corner & 4) ? 5 : 2] - t[2]};
-                for (int r = 0; r < 3; ++r) {
-                    const double w = B[r][0] * p[0] + B[r][1] * p[1] + B[r][2] * p[2];
-                    lo[r] = std::min(lo[r], w); hi[r] = std::max(hi[r], w);
-                }
-            }
-            double mag = 0.0;
-            for (int r = 0; r < 3; ++r) mag = std::max({mag, std::fabs(lo[r]), std::fabs(hi[r]), hi[r] - lo[r]});
-            const double pad = 1e-4 * mag * std::max(1.0, cond) + 1e-6;
-            bool ok = std::isfinite(mag) && mag < 1e30;
-            float flo[3], fhi[3];
-            for (int r = 0; r < 3; ++r) {
-                flo[r] = (float)(lo[r] - pad); fhi[r] = (float)(hi[r] + pad);
-                ok = ok && std::isfinite(flo[r]) && std::isfinite(fhi[r]);
-            }
-            if (ok) {
-                R.wlo = make_float4(flo[0], flo[1], flo[2], 1.0f);
-                R.whi = make_float4(fhi[0], fhi[1], fhi[2], 0.0f);
-            }
-        }
-    }
-    T.tnodes.assign((size_t)nTlas * 4, make_float4(0, 0, 0, 0));
-    std::vector<uint8_t> tseen(n, 0);
-    TreeWalk tw = walkTree(tlasNodes, nTlas, 0, n, 0, T.tnodes, tseen);
-    if (!tw.ok) return fail(c, SURF_ERR_INVALID, "TLAS: " + tw.why);
-    T.tlasDepth = tw.depth;
-    T.tidx.assign(tlasIdx, tlasIdx + n);
-    for (uint32_t v : T.tidx) if (v >= n) return fail(c, SURF_ERR_INVALID, "TLAS index out of range");
-    T.tlasLeafCount = tlasNodes[0].count;        /* root leaf: wave-uniform instance loop */
-    if (T.tlasLeafCount && tlasNodes[0].left_first != 0) T.tlasLeafCount = 0;   /* general path unless indices start at 0 */
-    /* ray-order membership key: the (at most 3) instances of a single-leaf
-     * TLAS with the largest BLASes (>= 64 triangles) and a usable world box */
-    if (T.tlasLeafCount) {
-        std::vector<std::pair<uint32_t, uint32_t>> big;     /* (triangles, instance) */
-        for (uint32_t i = 0; i < n; ++i) {
-            const auto it = c->blasSlots.find(instances[i].tri_offset);
-            const uint32_t tris = it == c->blasSlots.end() ? 0u : it->second;
-            if (tris >= 64 && T.tinst[i].wlo.w != 0.0f) big.push_back({tris, i});
-        }
-        std::stable_sort(big.begin(), big.end(), [](const auto& a, const auto& b) { return a.first > b.first; });
-        for (size_t h = 0; h < big.size() && h < 3; ++h) {
-            T.hvLo[h] = T.tinst[big[h].second].wlo;
-            T.hvHi[h] = T.tinst[big[h].second].whi;
-            T.hvInst[h] = big[h].second;
-            T.nHeavy = (uint32_t)h + 1;
-        }
-    }
-    T.lights.resize(nLights);
-    for (uint32_t l = 0; l < nLights; ++l) {
-        const surf_light& L = lights[l];
-        if (L.light_instance_idx >= n || L.primitive_count == 0 ||
-            (uint64_t)instances[L.light_instance_idx].tri_offset + L.primitive_count > c->nTriangles)
-            return fail(c, SURF_ERR_INVALID, "light " + std::to_string(l) + " out of range");
-        T.lights[l] = make_uint2(L.light_instance_idx, L.primitive_count);
-    }
-    return SURF_OK;
-}
-
-int surf_upload_scene(surf_ctx* c, const surf_scene_desc* d) {
-    if (!c || !d) return SURF_ERR_INVALID;
-    if (d->triangle_count == 0 || !d->triangles || !d->tri_ext || !d->blas_indices || !d->blas_nodes || !d->materials ||
-        !d->instances || d->instance_count == 0 || !d->tlas_indices || !d->tlas_nodes || d->tlas_node_count == 0 ||
-        !d->background || d->material_count == 0 || d->blas_node_count == 0 || d->blas_index_count == 0 ||
-        (d->light_count && !d->lights))
-        return fail(c, SURF_ERR_INVALID, "incomplete scene descriptor");
-    /* the kernels index records with 32-bit element offsets (16 floats per node,
-     * 12 per BLAS index slot, 16 per triangle record) */
-    if (d->blas_node_count >= (1u << 28) || d->blas_index_count >= (1u << 28) || d->triangle_count >= (1u << 28))
-        return fail(c, SURF_ERR_LIMIT, "scene larger than 2^28 BVH nodes / index slots / triangles");
-    SURF_CHECK(c, hipSetDevice(c->device));
-    int rc0 = endStream(c);
-    if (rc0) return rc0;
-    SURF_CHECK(c, hipStreamSynchronize(c->stream));
-    destroyGraph(c);
-    freeList(c->sceneAllocs);
-    c->hasScene = false;
-
-    /* instances */
-    std::vector<DevInstance> inst(d->instance_count);
-    std::vector<int64_t> idxTri(d->blas_index_count, -1);   /* idx slot -> tri offset owner */
-    std::vector<float4> nodes((size_t)d->blas_node_count * 4, make_float4(0, 0, 0, 0));
-    std::vector<uint8_t> seen(d->blas_index_count, 0), walked(d->blas_node_count, 0);
-    std::vector<uint32_t> owner(d->blas_node_count, kUnset);    /* BLAS node offset of every reachable node */
-    uint32_t maxBlasDepth = 0;
-    for (uint32_t i = 0; i < d->instance_count; ++i) {
-        const surf_gpu_instance& g = d->instances[i];
-        if (g.tri_offset >= d->triangle_count || g.material_offset >= d->material_count ||
-            g.bvh_node_offset >= d->blas_node_count || g.bvh_idx_offset >= d->blas_index_count)
-            return fail(c, SURF_ERR_INVALID, "instance " + std::to_string(i) + " offsets out of range");
-        DevInstance& D = inst[i];
-        std::memcpy(D.Minv, g.inv_transform, sizeof D.Minv);
-        std::memcpy(D.M, g.transform, sizeof D.M);
-        D.triOffset = g.tri_offset; D.idxOffset = g.bvh_idx_offset; D.nodeOffset = g.bvh_node_offset; D.material = g.material_offset;
-        D.area = g.area;
-        /* row 3 of a column-major matrix: elements 3, 7, 11, 15 */
-        auto affine = [](const float* m) { return m[3] == 0.0f && m[7] == 0.0f && m[11] == 0.0f && m[15] == 1.0f; };
-        D.affineInv = affine(g.inv_transform) ? 1u : 0u;
-        D.affine = affine(g.transform) ? 1u : 0u;
-        if (!walked[g.bvh_node_offset]) {
-            std::vector<uint8_t> leaf(d->blas_index_count, 0);
-            TreeWalk w = walkTree(d->blas_nodes, d->blas_node_count, g.bvh_node_offset, d->blas_index_count, g.bvh_idx_offset, nodes, leaf,
-                                  &owner);
-            if (!w.ok) return fail(c, SURF_ERR_INVALID, "instance " + std::to_string(i) + ": " + w.why);
-            maxBlasDepth = std::max(maxBlasDepth, w.depth);
-            walked[g.bvh_node_offset] = 1;
-            for (uint32_t k = 0; k < d->blas_index_count; ++k)
-                if (leaf[k]) {
-                    if (idxTri[k] >= 0 && idxTri[k] != (int64_t)g.tri_offset) return fail(c, SURF_ERR_INVALID, "BLAS index range shared by two meshes");
-                    idxTri[k] = g.tri_offset;
-                }
-        }
-    }
-    c->nBlasNodes = d->blas_node_count;
-    /* the compact form of every small BLAS (k_connect stages the emitters' one,
-     * blasAnyStaged): its interior records in DFS order from the root (record 0),
-     * each child an interior record index or a leaf's kLeafTagC | count << 16 |
-     * leftFirst; and the span of its triangle slots */
-    std::map<uint32_t, std::vector<float4>> compact;
-    std::map<uint32_t, std::array<uint32_t, 2>> compactTris;   /* node offset -> (index offset, slots) */
-    for (uint32_t i = 0; i < d->instance_count; ++i) {
-        const uint32_t root = d->instances[i].bvh_node_offset;
-        if (compact.count(root) || d->blas_nodes[root].count != 0) continue;
-        std::vector<float4> recs;
-        std::vector<uint32_t> order{root};                     /* interior nodes by record index */
-        uint32_t slots = 0;
-        bool ok = true;
-        for (size_t k = 0; k < order.size() && ok; ++k) {
-            const uint32_t g = order[k];
-            const float4* r = &nodes[4 * (size_t)g];
-            uint32_t ref[2];
-            for (int ch = 0; ch < 2; ++ch) {
-                const uint32_t cg = root + f2u(r[0].w) + (uint32_t)ch;
-                const surf_bvh_node& q = d->blas_nodes[cg];
-                if (q.count != 0) {
-                    ok = ok && q.count < 32768u && q.left_first < 65536u;
-                    ref[ch] = kLeafTagC | (q.count << 16) | (q.left_first & 0xffffu);
-                    slots = std::max(slots, q.left_first + q.count);
-                } else {
-                    ok = ok && order.size() < 32768u;
-                    ref[ch] = (uint32_t)order.size();
-                    order.push_back(cg);
-                }
-            }
-            recs.push_back(make_float4(r[0].x, r[0].y, r[0].z, u2f(ref[0])));
-            recs.push_back(make_float4(r[1].x, r[1].y, r[1].z, u2f(ref[1])));
-            recs.push_back(make_float4(r[2].x, r[2].y, r[2].z, 0.0f));
-            recs.push_back(make_float4(r[3].x, r[3].y, r[3].z, 0.0f));
-            ok = ok && (recs.size() / 4) * 64 + (uint64_t)slots * 48 <= kLdsLightBlas;
-        }
-        if (ok) { compact[root] = std::move(recs); compactTris[root] = {d->instances[i].bvh_idx_offset, slots}; }
-    }
-    c->blasRoots.clear();
-    for (uint32_t i = 0; i < d->instance_count; ++i) {
-        const surf_gpu_instance& g = d->instances[i];
-        const size_t r = 4 * (size_t)g.bvh_node_offset;
-        c->blasRoots[std::make_tuple(g.bvh_node_offset, g.bvh_idx_offset, g.tri_offset)] = {nodes[r], nodes[r + 1], nodes[r + 2], nodes[r + 3]};
-    }
-    c->nTriangles = d->triangle_count;
-    c->nMaterials = d->material_count;
-    /* BVH-ordered triangles: (v0, prim), e1 = v1 - v0, e2 = v2 - v0 (mesh.cpp:25-26) */
-    std::vector<float4> tris((size_t)d->blas_index_count * 3, make_float4(0, 0, 0, 0));
-    for (uint32_t k = 0; k < d->blas_index_count; ++k) {
-        if (idxTri[k] < 0) continue;
-        const uint64_t t = (uint64_t)idxTri[k] + d->blas_indices[k];
-        if (t >= d->triangle_count) return fail(c, SURF_ERR_INVALID, "BLAS index " + std::to_string(k) + " out of range");
-        const surf_triangle& T = d->triangles[t];
-        tris[3 * (size_t)k + 0] = make_float4(T.v0.x, T.v0.y, T.v0.z, u2f(d->blas_indices[k]));
-        tris[3 * (size_t)k + 1] = make_float4(T.v1.x - T.v0.x, T.v1.y - T.v0.y, T.v1.z - T.v0.z, 0.0f);
-        tris[3 * (size_t)k + 2] = make_float4(T.v2.x - T.v0.x, T.v2.y - T.v0.y, T.v2.z - T.v0.z, 0.0f);
-    }
-    /* object-space bounds of each BLAS's triangles as the traversal sees them
-     * (v0, v0 + e1, v0 + e2 of the slot records), for the world-box cull */
-    c->blasBounds.clear();
-    c->blasSlots.clear();
-    for (uint32_t k = 0; k < d->blas_index_count; ++k) {
-        if (idxTri[k] < 0) continue;
-        ++c->blasSlots[(uint32_t)idxTri[k]];
-        auto it = c->blasBounds.emplace((uint32_t)idxTri[k], std::array<double, 6>{HUGE_VAL, HUGE_VAL, HUGE_VAL, -HUGE_VAL, -HUGE_VAL, -HUGE_VAL}).first;
-        const float4 a = tris[3 * (size_t)k], e1 = tris[3 * (size_t)k + 1], e2 = tris[3 * (size_t)k + 2];
-        const double v[3][3] = {{a.x, a.y, a.z}, {(double)a.x + e1.x, (double)a.y + e1.y, (double)a.z + e1.z},
-                                {(double)a.x + e2.x, (double)a.y + e2.y, (double)a.z + e2.z}};
-        for (const auto& p : v)
-            for (int q = 0; q < 3; ++q) { it->second[q] = std::min(it->second[q], p[q]); it->second[3 + q] = std::max(it->second[3 + q], p[q]); }
-    }
-    std::vector<float4> normals((size_t)d->triangle_count * 3), verts((size_t)d->triangle_count * 4);
-    for (uint32_t t = 0; t < d->triangle_count; ++t) {
-        const surf_tri_extension& x = d->tri_ext[t];
-        normals[3 * (size_t)t + 0] = make_float4(x.n0.x, x.n0.y, x.n0.z, 0.0f);
-        normals[3 * (size_t)t + 1] = make_float4(x.n1.x, x.n1.y, x.n1.z, 0.0f);
-        normals[3 * (size_t)t + 2] = make_float4(x.n2.x, x.n2.y, x.n2.z, 0.0f);
-        const surf_triangle& T = d->triangles[t];
-        verts[4 * (size_t)t + 0] = make_float4(T.v0.x, T.v0.y, T.v0.z, 0.0f);
-        verts[4 * (size_t)t + 1] = make_float4(T.v1.x, T.v1.y, T.v1.z, 0.0f);
-        verts[4 * (size_t)t + 2] = make_float4(T.v2.x, T.v2.y, T.v2.z, 0.0f);
-        verts[4 * (size_t)t + 3] = make_float4(T.centroid.x, T.centroid.y, T.centroid.z, 0.0f);
-    }
-    InstanceTables IT;
-    int rcT = buildInstanceTables(c, d->instances, d->instance_count, d->tlas_indices, d->tlas_nodes, d->tlas_node_count,
-                                  d->lights, d->light_count, IT);
-    if (rcT) return rcT;
-    std::vector<DevMaterial> mats(d->material_count);
-    std::memcpy(mats.data(), d->materials, d->material_count * sizeof(DevMaterial));
-
-    const uint32_t depth = IT.tlasDepth + maxBlasDepth + 1;
-    if (depth > kMaxStack) return fail(c, SURF_ERR_LIMIT, "BVH too deep for the LDS traversal stack (" + std::to_string(depth) + " entries)");
-
-    DevScene S{};
-    int rc;
-    if ((rc = upload(c, nodes, &S.nodes))) return rc;
-    /* two-level records for the wave walk (blasWalk2): W(g) = the records of g
-     * and of its two children, each in the lanes-as-planes order (lane l of a
-     * row = dword planeDword(l) of the 64-B record), 48 floats; a leaf's W holds
-     * its own record.  192-B offsets are 32-bit buffer offsets: at most 22.3 M nodes. */
-    const bool walk2 = !(std::getenv("SURF_WALK2") && std::getenv("SURF_WALK2")[0] == '0');   /* A/B: 0 = one-level walk (read per upload) */
-    if (walk2 && (uint64_t)d->blas_node_count * 192u < (1ull << 32)) {
-        std::vector<float> W((size_t)d->blas_node_count * 48, 0.0f);
-        /* lanes 14 / 15 of a row (unused by the wave walk): the row node's two
-         * children as packed leaf references for the lane walk (blasTraceW):
-         * kLeafTag | count << 24 | leftFirst, 0 when not a leaf or too large */
-        auto packLeaf = [&](uint64_t m) -> uint32_t {
-            const surf_bvh_node& q = d->blas_nodes[m];
-            return (q.count != 0 && q.count < 128u && q.left_first < (1u << 24)) ? (kLeafTag | (q.count << 24) | q.left_first) : 0u;
-        };
-        auto putRec = [&](size_t g, size_t row, uint64_t src) {
-            const float* r = reinterpret_cast<const float*>(&nodes[4 * src]);
-            for (uint32_t l = 0; l < 14; ++l) {
-                const uint32_t dw = l < 12u ? (l / 6u) * 8u + (l & 1u) * 4u + ((l % 6u) >> 1) : (l == 12u ? 3u : 7u);
-                W[48 * g + 16 * row + l] = r[dw];
-            }
-            const surf_bvh_node& q = d->blas_nodes[src];
-            if (q.count == 0 && owner[src] != kUnset) {
-                W[48 * g + 16 * row + 14] = u2f(packLeaf((uint64_t)owner[src] + q.left_first));
-                W[48 * g + 16 * row + 15] = u2f(packLeaf((uint64_t)owner[src] + q.left_first + 1));
-            }
-        };
-        /* a leaf's W holds its own record in row 0 and, for <= kLeafInW
-         * triangles, the triangles themselves (row j: lanes 0..2 v0, 3..5 e1,
-         * 6..8 e2, 9 prim -- the BVH-ordered records of its index slots), so the
-         * wave walk tests them from the record its visit loaded (leafWaveW) */
-        std::map<uint32_t, uint32_t> idxOfNode;                      /* BLAS node offset -> index offset */
-        for (uint32_t i = 0; i < d->instance_count; ++i) idxOfNode[d->instances[i].bvh_node_offset] = d->instances[i].bvh_idx_offset;
-        for (uint32_t g = 0; g < d->blas_node_count; ++g) {
-            if (owner[g] == kUnset) continue;
-            putRec(g, 0, g);
-            const surf_bvh_node& n = d->blas_nodes[g];
-            if (n.count == 0) {
-                putRec(g, 1, (uint64_t)owner[g] + n.left_first);
-                putRec(g, 2, (uint64_t)owner[g] + n.left_first + 1);
-            } else if (n.count <= kLeafInW) {
-                const uint64_t slot0 = (uint64_t)idxOfNode[owner[g]] + n.left_first;
-                for (uint32_t j = 0; j < n.count; ++j) {
-                    const float4* t = &tris[3 * (slot0 + j)];
-                    float* w = &W[48 * (size_t)g + 16 * j];
-                    w[0] = t[0].x; w[1] = t[0].y; w[2] = t[0].z;
-                    w[3] = t[1].x; w[4] = t[1].y; w[5] = t[1].z;
-                    w[6] = t[2].x; w[7] = t[2].y; w[8] = t[2].z;
-                    w[9] = t[0].w;
-                }
-            }
-        }
-        const float* dW = nullptr;
-        if ((rc = upload(c, W, &dW))) return rc;
-        S.wnodes = dW;
-        S.nWnodes = d->blas_node_count;
-        /* the lane traversal walks them too when the BVH cannot stay in the
-         * caches (nodes + triangles past the 256 MB of MALL): one DRAM round
-         * trip per two levels instead of one per level (SURF_LANEW=0|1: A/B) */
-        const uint64_t bvhBytes = (uint64_t)d->blas_node_count * 64u + (uint64_t)d->blas_index_count * 48u;
-        S.laneW = bvhBytes > (256ull << 20) ? 1u : 0u;
-        if (const char* e = std::getenv("SURF_LANEW")) S.laneW = e[0] == '1' ? 1u : 0u;
-    }
-    if ((rc = upload(c, tris, &S.tris))) return rc;
-    if ((rc = upload(c, normals, &S.normals))) return rc;
-    if ((rc = upload(c, verts, &S.verts))) return rc;
-    if ((rc = upload(c, IT.tnodes, &S.tlasNodes))) return rc;
-    if ((rc = upload(c, IT.tidx, &S.tlasIdx))) return rc;
-    if ((rc = upload(c, IT.inst, &S.inst))) return rc;
-    if ((rc = upload(c, IT.tinst, &S.tinst))) return rc;
-    if ((rc = upload(c, mats, &S.mats))) return rc;
-    if ((rc = upload(c, IT.lights, &S.lights))) return rc;
-    S.nLights = d->light_count;
-    S.nInst = d->instance_count;
-    S.nMats = d->material_count;
-    S.nodes4G = d->blas_node_count < (1u << 26) ? 1u : 0u;
-    S.finiteBoxes = 1u;
-    for (const float4& q : nodes)
-        if (!(std::fabs(q.x) <= FLT_MAX && std::fabs(q.y) <= FLT_MAX && std::fabs(q.z) <= FLT_MAX)) { S.finiteBoxes = 0u; break; }
-    S.tlasLeafCount = IT.tlasLeafCount;
-    c->stagedBlas.clear();
-    for (const auto& kv : compact) {
-        const float4* dR = nullptr;
-        if ((rc = upload(c, kv.second, &dR))) return rc;
-        c->stagedBlas[kv.first] = surf_ctx::StagedBlas{dR, (uint32_t)(kv.second.size() / 4), compactTris[kv.first][0],
-                                                        compactTris[kv.first][1]};
-    }
-    setKeys(c, S, IT);
-    const surf_background& bg = *d->background;
-    S.bgType = bg.type;
-    S.bgColor[0] = bg.color.x; S.bgColor[1] = bg.color.y; S.bgColor[2] = bg.color.z;
-    S.bgA[0] = bg.gradient_a.x; S.bgA[1] = bg.gradient_a.y; S.bgA[2] = bg.gradient_a.z;
-    S.bgB[0] = bg.gradient_b.x; S.bgB[1] = bg.gradient_b.y; S.bgB[2] = bg.gradient_b.z;
-    {
-        /* ray-order cells (a sort key only: any value is correct, a stale box after refits too) */
-        const surf_bvh_node& root = d->tlas_nodes[0];
-        const float lo[3] = {root.bb_min.x, root.bb_min.y, root.bb_min.z}, hi[3] = {root.bb_max.x, root.bb_max.y, root.bb_max.z};
-        for (int a = 0; a < 3; ++a) {
-            const float ext = hi[a] - lo[a];
-            const bool ok = std::isfinite(lo[a]) && std::isfinite(ext) && ext > 0.0f;
-            S.cellLo[a] = ok ? lo[a] : 0.0f;
-            S.cellScale[a] = ok ? 2.0f / ext : 0.0f;
-        }
-    }
-    c->S = S;
-    c->ldsTables = d->instance_count <= kLdsInst && d->instance_count <= kLdsTraceInst && d->material_count <= kLdsMats &&
-                   d->light_count <= kLdsLights;
-    c->stackDepth = depth;
-    c->nInstances = d->instance_count;
-    c->nLightsUp = d->light_count;
-    c->tlasNodeCount = d->tlas_node_count;
-    c->maxBlasDepth = maxBlasDepth;
-    c->hasScene = true;
-    return SURF_OK;
-}
-
-int surf_update_instances(surf_ctx* c, const surf_gpu_instance* instances, uint32_t n, const uint32_t* tlasIdx,
-                          const surf_bvh_node* tlasNodes, uint32_t nTlas, const surf_light* lights, uint32_t nLights) {
-    if (!c || !instances || !tlasIdx || !tlasNodes || (nLights && !lights)) return SURF_ERR_INVALID;
-    if (!c->hasScene) return fail(c, SURF_ERR_NO_SCENE, "no scene uploaded");
-    if (n != c->nInstances || nTlas != c->tlasNodeCount || nLights != c->nLightsUp)
-        return fail(c, SURF_ERR_INVALID, "instance/TLAS/light counts differ from the uploaded scene: use surf_upload_scene");
-    SURF_CHECK(c, hipSetDevice(c->device));
-    int rc = endStream(c);            /* in-flight paths belong to the old transforms */
-    if (rc) return rc;
-    InstanceTables IT;
-    if ((rc = buildInstanceTables(c, instances, n, tlasIdx, tlasNodes, nTlas, lights, nLights, IT))) return rc;
-    const uint32_t depth = IT.tlasDepth + c->maxBlasDepth + 1;
-    if (depth > kMaxStack) return fail(c, SURF_ERR_LIMIT, "BVH too deep for the LDS traversal stack (" + std::to_string(depth) + " entries)");
-    SURF_CHECK(c, hipStreamSynchronize(c->stream));
-    auto put = [&](const void* dst, const void* src, size_t bytes) {
-        return hipMemcpy(const_cast<void*>(dst), src, bytes, hipMemcpyHostToDevice);
-    };
-    SURF_CHECK(c, put(c->S.inst, IT.inst.data(), IT.inst.size() * sizeof(DevInstance)));
-    SURF_CHECK(c, put(c->S.tinst, IT.tinst.data(), IT.tinst.size() * sizeof(TraceInst)));
-    SURF_CHECK(c, put(c->S.tlasNodes, IT.tnodes.data(), IT.tnodes.size() * sizeof(float4)));
-    SURF_CHECK(c, put(c->S.tlasIdx, IT.tidx.data(), IT.tidx.size() * sizeof(uint32_t)));
-    if (nLights) SURF_CHECK(c, put(c->S.lights, IT.lights.data(), IT.lights.size() * sizeof(uint2)));
-    c->S.tlasLeafCount = IT.tlasLeafCount;
-    setKeys(c, c->S, IT);
-    c->stackDepth = std::max(c->stackDepth, depth);
-    destroyGraph(c);                  /* kernel arguments carry the scene descriptor */
     return SURF_OK;
 }
 
@@ -2336,31 +1673,9 @@ int surf_trace_closest(surf_ctx* c, uint32_t n, const float* o, const float* d, 
     if (c->traceMode == 1 && !waveEligible(c))
         return fail(c, SURF_ERR_INVALID, "scene no longer fits the selected cooperative traversal");
     SURF_CHECK(c, hipSetDevice(c->device));
-    std::vector<void*> tmp;
-    float *dO, *dD; float4* dT; uint2* dI;
-    int rc;
-    if ((rc = devAlloc(c, tmp, &dO, 3 * (size_t)n)) || (rc = devAlloc(c, tmp, &dD, 3 * (size_t)n)) ||
-        (rc = devAlloc(c, tmp, &dT, n)) || (rc = devAlloc(c, tmp, &dI, n))) { freeList(tmp); return rc; }
-    (void)hipMemcpyAsync(dO, o, 12 * (size_t)n, hipMemcpyHostToDevice, c->stream);
-    (void)hipMemcpyAsync(dD, d, 12 * (size_t)n, hipMemcpyHostToDevice, c->stream);
-    if (c->traceMode == 1)
-        hipLaunchKernelGGL(c->ldsTables ? (c->S.wnodes ? k_trace_closest_coop<true, true> : k_trace_closest_coop<true, false>)
-                                        : (c->S.wnodes ? k_trace_closest_coop<false, true> : k_trace_closest_coop<false, false>),
-                           dim3(n), dim3(64), coopLds(c),
-                           c->stream, c->S, (const float*)dO, (const float*)dD,
-                           n, dT, dI, recStackWords(c));
-    else
-        hipLaunchKernelGGL(c->S.laneW ? (c->ldsTables ? k_trace_closest<true, true> : k_trace_closest<false, true>)
-                                      : (c->ldsTables ? k_trace_closest<true, false> : k_trace_closest<false, false>),
-                           dim3((n + kBlock - 1) / kBlock), dim3(kBlock), traversalLds(c, kBlock), c->stream,
-                           c->S, (const float*)dO, (const float*)dD, n, dT, dI, stackWords(c, kBlock));
-    std::vector<float4> t(n);
-    std::vector<uint2> ip(n);
-    (void)hipMemcpyAsync(t.data(), dT, 16 * (size_t)n, hipMemcpyDeviceToHost, c->stream);
-    (void)hipMemcpyAsync(ip.data(), dI, 8 * (size_t)n, hipMemcpyDeviceToHost, c->stream);
-    hipError_t e = hipStreamSynchronize(c->stream);
-    freeList(tmp);
-    if (e != hipSuccess) return fail(c, SURF_ERR_HIP, std::string("trace_closest: ") + hipGetErrorString(e));
+    std::vector<float4> t;
+    std::vector<uint2> ip;
+    if (int rc = traceClosestRays(c, n, o, d, c->traceMode == 1, &t, ip, "trace_closest")) return rc;
     for (uint32_t i = 0; i < n; ++i) { ot[i] = t[i].x; ou[i] = t[i].y; ov[i] = t[i].z; oi[i] = ip[i].x; op[i] = ip[i].y; }
     return SURF_OK;
 }
@@ -2380,17 +1695,16 @@ int surf_trace_any(surf_ctx* c, uint32_t n, const float* o, const float* d, cons
     (void)hipMemcpyAsync(dO, o, 12 * (size_t)n, hipMemcpyHostToDevice, c->stream);
     (void)hipMemcpyAsync(dD, d, 12 * (size_t)n, hipMemcpyHostToDevice, c->stream);
     (void)hipMemcpyAsync(dM, tm, 4 * (size_t)n, hipMemcpyHostToDevice, c->stream);
-    if (c->traceMode == 1)
-        hipLaunchKernelGGL(c->ldsTables ? (c->S.wnodes ? k_trace_any_coop<true, true> : k_trace_any_coop<true, false>)
-                                        : (c->S.wnodes ? k_trace_any_coop<false, true> : k_trace_any_coop<false, false>),
-                           dim3(n), dim3(64), coopLds(c), c->stream,
-                           c->S, (const float*)dO, (const float*)dD,
-                           (const float*)dM, n, dR, recStackWords(c));
-    else
-        hipLaunchKernelGGL(c->S.laneW ? (c->ldsTables ? k_trace_any<true, true> : k_trace_any<false, true>)
-                                      : (c->ldsTables ? k_trace_any<true, false> : k_trace_any<false, false>),
-                           dim3((n + kBlock - 1) / kBlock), dim3(kBlock), traversalLds(c, kBlock), c->stream,
-                           c->S, (const float*)dO, (const float*)dD, (const float*)dM, n, dR, stackWords(c, kBlock));
+    const Variant v = variantOf(c);
+    if (c->traceMode == 1) {
+        const auto k = traceAnyCoopKernel(c, v);
+        hipLaunchKernelGGL(k.fn, dim3(n), dim3(64), k.lds, c->stream, c->S, (const float*)dO, (const float*)dD, (const float*)dM, n,
+                           dR, recStackWords(c));
+    } else {
+        const auto k = traceAnyKernel(c, v);
+        hipLaunchKernelGGL(k.fn, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), k.lds, c->stream, c->S, (const float*)dO,
+                           (const float*)dD, (const float*)dM, n, dR, stackWords(c, kBlock));
+    }
     (void)hipMemcpyAsync(occ, dR, n, hipMemcpyDeviceToHost, c->stream);
     hipError_t e = hipStreamSynchronize(c->stream);
     freeList(tmp);
@@ -2425,10 +1739,8 @@ int surf_debug_segment_cycles(surf_ctx* c, const float* path12, uint32_t reps, u
     const float4 o4 = make_float4(path12[0], path12[1], path12[2], path12[3]);
     const float4 d4 = make_float4(path12[4], path12[5], path12[6], path12[7]);
     const float4 T4 = make_float4(path12[8], path12[9], path12[10], path12[11]);
-    const bool w2 = c->S.wnodes != nullptr;
-    hipLaunchKernelGGL(c->ldsTables ? (w2 ? k_segment_cycles<true, true> : k_segment_cycles<true, false>)
-                                    : (w2 ? k_segment_cycles<false, true> : k_segment_cycles<false, false>),
-                       dim3(1), dim3(64), coopTailLds(c), c->stream, c->S, o4, d4, T4, reps, d, recStackWords(c));
+    const auto k = segmentCyclesKernel(c, variantOf(c));
+    hipLaunchKernelGGL(k.fn, dim3(1), dim3(64), k.lds, c->stream, c->S, o4, d4, T4, reps, d, recStackWords(c));
     hipError_t e = hipMemcpyAsync(cycles15, d, 15 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     (void)hipFree(d);

@@ -254,6 +254,33 @@ def test_ray_order_and_launch_shapes_bitexact(oracle_scene, product_scene, sort,
     r.close()
 
 
+@pytest.mark.parametrize("env", [{"SURF_REGEN_COUNT": "0"}, {"SURF_EXT_STACK16": "0"}, {"SURF_REGEN_FIRST": "1"},
+                                 {"SURF_REGEN_COUNT": "0", "SURF_EXT_STACK16": "0", "SURF_REGEN_FIRST": "1"}],
+                         ids=["regen+bincount", "extend-stack-32bit", "regen-before-connect", "all-three"])
+def test_kernel_selection_switches_bitexact(oracle_scene, product_scene, env, monkeypatch):
+    """The host-side selection switches off their defaults pick other kernels
+    and another launch order for the same samples: k_regen + k_bincount instead
+    of the fused k_regen_count (SURF_REGEN_COUNT=0), k_extend with a 32-bit
+    stack (SURF_EXT_STACK16=0), k_regen before the connect fork
+    (SURF_REGEN_FIRST=1), and all three together give the oracle's radiance and
+    event counts bit for bit."""
+    W, H, F = 96, 64, 4
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    r = surf_amd.Renderer(product_scene, W, H, pool_capacity=4096)
+    r.render(F, 0, 0)
+    g = r.accumulator()
+    st = r.stats()
+    oracle.set_zero_cutoff(True)
+    try:
+        c2, cnt, _ = oracle_scene.render(W, H, F)
+    finally:
+        oracle.set_zero_cutoff(False)
+    _assert_bitexact(g, c2, f"selection switches {env}")
+    _assert_counts(st, cnt)
+    r.close()
+
+
 @pytest.mark.parametrize("reorder,key,overlap", [("1", "2", "1"), ("0", "2", "1"), ("1", "1", "1"), ("1", "0", "1"),
                                                  ("1", "2", "0")],
                          ids=["default", "frame-major-issue", "ascending-mask-key", "start-instance-key", "connect-serialized"])
