@@ -33,7 +33,7 @@ SURF_LDS_HD uint32_t align4(uint32_t words) { return (words + 3u) & ~3u; }
 SURF_LDS_HD uint32_t traceTableWords(uint32_t nInst) { return nInst * kTraceEntryWords; }
 
 /* ---- lane traversal: [stack: depth x block entries][trace tables]
- * (k_extend, k_extend_cont, k_connect, k_trace_*, k_aov, k_tail).  The kernels
+ * (k_extend, k_connect, k_trace_*, k_aov, k_tail).  The kernels
  * get the stack as `stack32`, its words with 32-bit entries. */
 SURF_LDS_HD uint32_t laneStack32(uint32_t depth, uint32_t block) { return depth * block; }
 SURF_LDS_HD uint32_t laneStackWords(uint32_t stack32, bool entries16) { return entries16 ? (stack32 + 1u) / 2u : stack32; }

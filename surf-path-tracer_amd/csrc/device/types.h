@@ -140,17 +140,16 @@ struct Counters {
     unsigned long long issued[2];    /* stream chains issued (first samples of (frame, pixel)), per parity */
     unsigned long long limit;        /* host-written issue limit (frame window) */
     unsigned long long baseFrame;    /* absolute frame index of stream frame 0 */
-    unsigned long long ev[16];       /* ext, hit, cont, shadow, acc, unocc, tail paths, capped paths, wavefront ext, resumed rays */
+    unsigned long long ev[16];       /* ext, hit, cont, shadow, acc, unocc, tail paths, capped paths, wavefront ext */
     uint32_t capped[64];             /* sample ids of paths ended by the segment cap, slot blockIdx % 64 (diagnostics, ~0 = none) */
     /* event counts striped over kStripes cache lines (block b adds to stripe
      * b % kStripes): a counter shared by every block of a launch serializes its
      * atomics (~12 ns each, measured); totals = ev + sum over stripes */
     unsigned long long evS[32][16];
     unsigned long long dbg[8];       /* SURF_SEG_TIMING builds: k_tail_coop cycles (extend, shade, connect, segments) */
-    uint32_t resumeN[2];             /* capped lane walks: resume records written by k_extend of parity p (k_regen zeroes) */
 };
 constexpr uint32_t kStripes = 32;    /* frameDone and event-count stripes */
-constexpr int kEvents = 10;          /* event kinds counted (ev / evS index; 9: rays k_extend_cont finished) */
+constexpr int kEvents = 9;           /* event kinds counted (ev / evS index) */
 
 /* Where a stream sample lives: radiance slot sid = (pass % window) * npx + pixel,
  * pass = the sample's index in the stream (frame * spp + its place in the
@@ -166,7 +165,6 @@ struct StreamGeom {
 constexpr uint32_t kLeafTagC = 0x80000000u;   /* compact staged BLAS (blasAnyStaged): a child that is a leaf */
 constexpr uint32_t kLeafTag = 0x80000000u;    /* two-level records (blasTraceW): a packed leaf reference */
 constexpr uint32_t kLeafInW = 3;     /* triangles a two-level leaf record holds */
-constexpr uint32_t kResumeHead = 10;   /* words of a resume record before its stack refs (64 words in all) */
 
 /* shading tables staged in LDS when the scene has at most this many (ShadeTables) */
 constexpr uint32_t kLdsInst = 64, kLdsMats = 64, kLdsLights = 64;

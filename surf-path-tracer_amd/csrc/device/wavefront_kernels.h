@@ -239,30 +239,15 @@ __device__ __forceinline__ bool blasAnyStaged(uint32_t recN, const float4* sR, V
     }
 }
 
-/* The capped lane walk (k_extend with a cap): a lane whose BLAS walk has
- * taken its `left` iterations (node visits; W-record visits in the two-level
- * walk) reserves a resume record and stops, its state here -- the node (ref)
- * it was about to visit -- and the entries below it still on its LDS stack;
- * k_extend writes the record and k_extend_cont continues the walk from that
- * state, 64 such rays to a wave.  Exact: the continuation takes the
- * reference's decisions from the same state (same boxes, order, pruning and
- * leaf order), so the ray ends as the uncapped walk would end it. */
-struct LaneCap {
-    uint32_t left;        /* iterations the lane may still take */
-    uint32_t ref, depthN, turn;
-    bool capped;
-};
-
 /* FIN: o, rd and every box finite (slabFinite is exact); else the reference's
  * ternary slab with its NaN behaviour. */
 /* STG: the BLAS is the emitters' one staged in LDS (S.sbNode0, sN; any-hit
  * only: blasAnyStaged).  SK: the stack entry type (16-bit when every node
  * index fits). */
-template <bool ANY, bool FIN, bool STG = false, typename SK = uint32_t, bool CAP = false, bool RES = false>
+template <bool ANY, bool FIN, bool STG = false, typename SK = uint32_t>
 __device__ __forceinline__ bool blasTrace(const DevScene& S, const TraceInst& I, V3 o, V3 d, V3 rd, float& depth,
                                           float& hu, float& hv, uint32_t& hprim,
-                                          SK* stk, uint32_t stride, uint32_t base, const float4* sN = nullptr,
-                                          LaneCap* lc = nullptr, uint32_t ref0 = 0u, uint32_t n0 = 0u) {
+                                          SK* stk, uint32_t stride, uint32_t base, const float4* sN = nullptr) {
     const uint32_t nodeOff = I.meta.x;
     const float4* tri = S.tris + 3u * I.meta.y;
     /* root: never box-tested (bvh.cpp:131), only its children are */
@@ -275,10 +260,12 @@ __device__ __forceinline__ bool blasTrace(const DevScene& S, const TraceInst& I,
     SK* sp = bottom;
     uint32_t node;
     bool any = false;
-    if (RES) {
-        node = ref0;
-        sp = bottom + n0 * stride;
-    } else {
+    /* The root's children.  The block scope is kept on purpose, for the emitted
+     * code and not for the names: with these locals at function scope, where
+     * their lifetimes span the loop and its early returns, the any-hit kernels
+     * (k_connect, k_trace_any, k_tail) compile to a different instruction
+     * stream.  Compare the device assembly before flattening it. */
+    {
         const float4 r2 = I.r2, r3 = I.r3;
         float dn = boxDist<FIN>(r0, r1, o, rd, depth);
         float df = boxDist<FIN>(r2, r3, o, rd, depth);
@@ -297,13 +284,6 @@ __device__ __forceinline__ bool blasTrace(const DevScene& S, const TraceInst& I,
         }
     }
     for (;;) {
-        if (CAP) {
-            if (lc->left == 0u) {
-                lc->ref = node; lc->depthN = (uint32_t)((sp - bottom) / stride); lc->capped = true;
-                return any;
-            }
-            --lc->left;
-        }
         const float4* nd = S.nodes + 4u * node;
         float4 q0 = nd[0], q1 = nd[1], q2 = nd[2], q3 = nd[3];
         pin(q0); pin(q1); pin(q2); pin(q3);
@@ -368,29 +348,19 @@ __device__ __forceinline__ WRow wSel(bool c, const WRow& x, const WRow& y) {
     r.a = c ? y.a : x.a; r.b = c ? y.b : x.b; r.c = c ? y.c : x.c; r.d = c ? y.d : x.d;
     return r;
 }
-/* RES (k_extend_cont): the walk continues from a capped lane's state -- ref0
- * next, n0 refs already on the stack -- instead of from the root. */
-template <bool ANY, bool FIN, bool CAP = false, bool RES = false>
+template <bool ANY, bool FIN>
 __device__ __forceinline__ bool blasTraceW(const DevScene& S, const TraceInst& I, V3 o, V3 d, V3 rd, float& depth,
-                                           float& hu, float& hv, uint32_t& hprim, uint32_t* stk, uint32_t stride, uint32_t base,
-                                           LaneCap* lc = nullptr, uint32_t ref0 = 0u, uint32_t n0 = 0u) {
+                                           float& hu, float& hv, uint32_t& hprim, uint32_t* stk, uint32_t stride, uint32_t base) {
     const uint32_t nodeOff = I.meta.x;
     const float4* tri = S.tris + 3u * I.meta.y;
     const uint32_t rlf = f2u(I.r0.w), rcnt = f2u(I.r1.w);
     if (rcnt != 0u) return leafTestUniform<ANY>(tri, rlf, rcnt, o, d, depth, hu, hv, hprim);
     const float4* W = reinterpret_cast<const float4*>(S.wnodes);
     uint32_t* const bottom = stk + base * stride;
-    uint32_t* sp = RES ? bottom + n0 * stride : bottom;
-    uint32_t ref = RES ? ref0 : nodeOff;    /* the root: its children are tested in its first visit */
+    uint32_t* sp = bottom;
+    uint32_t ref = nodeOff;    /* the root: its children are tested in its first visit */
     bool any = false;
     for (;;) {
-        if (CAP) {
-            if (lc->left == 0u) {
-                lc->ref = ref; lc->depthN = (uint32_t)((sp - bottom) / stride); lc->capped = true;
-                return any;
-            }
-            --lc->left;
-        }
         uint32_t lf = 0u, cnt = 0u;
         if (ref & kLeafTag) {
             lf = ref & 0xFFFFFFu; cnt = (ref >> 24) & 0x7Fu;
@@ -467,32 +437,19 @@ __device__ __forceinline__ float rowDot(float4 r, float x, float y, float z, flo
     return a + b;
 }
 
-template <bool ANY, bool LW = false, bool STG = false, typename SK = uint32_t, bool CAP = false>
-__device__ __forceinline__ bool instanceTrace(const DevScene& S, const TraceInst& I, V3 o, V3 d, float& depth, float& hu,
-                                              float& hv, uint32_t& hprim, SK* stk, uint32_t stride, uint32_t base,
-                                              const float4* sN = nullptr, LaneCap* lc = nullptr);
-/* The rest of a capped lane walk's BLAS walk (k_extend_cont): the instance's
- * object-space ray formed as instanceTrace forms it, then blasTraceW from the
- * saved ref with the saved refs on the stack (a capped walk was a finite one) */
-template <bool LW, typename SK>
-__device__ __forceinline__ bool instanceResume(const DevScene& S, const TraceInst& I, V3 o, V3 d, float& depth, float& hu, float& hv,
-                                               uint32_t& hprim, SK* stk, uint32_t stride, uint32_t ref0, uint32_t n0) {
-    V3 oo = mk3(rowDot(I.m0, o.x, o.y, o.z, 1.0f), rowDot(I.m1, o.x, o.y, o.z, 1.0f), rowDot(I.m2, o.x, o.y, o.z, 1.0f));
+/* Object-space ray of instance I (Instance::intersect, bvh.cpp:481-513). */
+__device__ __forceinline__ void instanceRay(const TraceInst& I, V3 o, V3 d, V3& oo, V3& dd) {
+    oo = mk3(rowDot(I.m0, o.x, o.y, o.z, 1.0f), rowDot(I.m1, o.x, o.y, o.z, 1.0f), rowDot(I.m2, o.x, o.y, o.z, 1.0f));
     if (!I.meta.z) oo = divs(oo, rowDot(I.m3, o.x, o.y, o.z, 1.0f));
-    const V3 dd = mk3(rowDot(I.m0, d.x, d.y, d.z, 0.0f), rowDot(I.m1, d.x, d.y, d.z, 0.0f), rowDot(I.m2, d.x, d.y, d.z, 0.0f));
-    const V3 rd = mk3(1.0f / dd.x, 1.0f / dd.y, 1.0f / dd.z);
-    if constexpr (LW)
-        return blasTraceW<false, true, false, true>(S, I, oo, dd, rd, depth, hu, hv, hprim, stk, stride, 0u, nullptr, ref0, n0);
-    return blasTrace<false, true, false, SK, false, true>(S, I, oo, dd, rd, depth, hu, hv, hprim, stk, stride, 0u, nullptr, nullptr,
-                                                         ref0, n0);
+    dd = mk3(rowDot(I.m0, d.x, d.y, d.z, 0.0f), rowDot(I.m1, d.x, d.y, d.z, 0.0f), rowDot(I.m2, d.x, d.y, d.z, 0.0f));
 }
-template <bool ANY, bool LW, bool STG, typename SK, bool CAP>
+
+template <bool ANY, bool LW = false, bool STG = false, typename SK = uint32_t>
 __device__ __forceinline__ bool instanceTrace(const DevScene& S, const TraceInst& I, V3 o, V3 d, float& depth, float& hu,
                                               float& hv, uint32_t& hprim, SK* stk, uint32_t stride, uint32_t base,
-                                              const float4* sN, LaneCap* lc) {
-    V3 oo = mk3(rowDot(I.m0, o.x, o.y, o.z, 1.0f), rowDot(I.m1, o.x, o.y, o.z, 1.0f), rowDot(I.m2, o.x, o.y, o.z, 1.0f));
-    if (!I.meta.z) oo = divs(oo, rowDot(I.m3, o.x, o.y, o.z, 1.0f));
-    const V3 dd = mk3(rowDot(I.m0, d.x, d.y, d.z, 0.0f), rowDot(I.m1, d.x, d.y, d.z, 0.0f), rowDot(I.m2, d.x, d.y, d.z, 0.0f));
+                                              const float4* sN = nullptr) {
+    V3 oo, dd;
+    instanceRay(I, o, d, oo, dd);
     /* a root leaf (the room's walls) needs no 1/d: its triangles are tested directly */
     if (f2u(I.r1.w) != 0u)
         return leafTestUniform<ANY>(S.tris + 3u * I.meta.y, f2u(I.r0.w), f2u(I.r1.w), oo, dd, depth, hu, hv, hprim);
@@ -500,9 +457,9 @@ __device__ __forceinline__ bool instanceTrace(const DevScene& S, const TraceInst
     /* S.finiteBoxes: every BLAS box is finite (checked at upload) */
     const bool fin = S.finiteBoxes && finite3(oo) && finite3(rd);
     if constexpr (LW)
-        return fin ? blasTraceW<ANY, true, CAP>(S, I, oo, dd, rd, depth, hu, hv, hprim, stk, stride, base, lc)
+        return fin ? blasTraceW<ANY, true>(S, I, oo, dd, rd, depth, hu, hv, hprim, stk, stride, base)
                    : blasTraceW<ANY, false>(S, I, oo, dd, rd, depth, hu, hv, hprim, stk, stride, base);
-    if (fin) return blasTrace<ANY, true, STG, SK, CAP>(S, I, oo, dd, rd, depth, hu, hv, hprim, stk, stride, base, sN, lc);
+    if (fin) return blasTrace<ANY, true, STG, SK>(S, I, oo, dd, rd, depth, hu, hv, hprim, stk, stride, base, sN);
     return blasTrace<ANY, false, STG, SK>(S, I, oo, dd, rd, depth, hu, hv, hprim, stk, stride, base, sN);
 }
 
@@ -532,23 +489,10 @@ __device__ __forceinline__ TraceTables traceTables(const DevScene& S, uint32_t* 
 }
 
 /* BvhTLAS::intersect / intersectAny (bvh.cpp:654-778). */
-/* CAP (single-leaf TLAS, LW): the walk stops where the lane's cap ran out
- * (LaneCap); lc->turn is then the instance's place in TLAS order */
-/* RES (closest hit, LW): continue a capped lane's walk -- the instance at
- * TLAS place lc->turn from lc->ref / lc->depthN (instanceResume), then the
- * instances after it; any / hinst come in as the lane left them */
-template <bool ANY, bool LW = false, bool STG = false, typename SK = uint32_t, bool CAP = false, bool RES = false>
+template <bool ANY, bool LW = false, bool STG = false, typename SK = uint32_t>
 __device__ __forceinline__ bool traceScene(const DevScene& S, const TraceTables& Tt, V3 o, V3 d, float& depth, float& hu, float& hv,
-                                           uint32_t& hinst, uint32_t& hprim, SK* stk, uint32_t stride, const float4* sN = nullptr,
-                                           LaneCap* lc = nullptr, bool any0 = false) {
-    bool any = any0;
-    if (RES) {
-        const uint32_t ii = Tt.order[lc->turn];
-        if (instanceResume<LW, SK>(S, Tt.inst[ii], o, d, depth, hu, hv, hprim, stk, stride, lc->ref, lc->depthN)) {
-            any = true;
-            hinst = ii;
-        }
-    }
+                                           uint32_t& hinst, uint32_t& hprim, SK* stk, uint32_t stride, const float4* sN = nullptr) {
+    bool any = false;
     if (S.tlasLeafCount) {
         /* single-leaf TLAS (the bundled scene): every lane visits the same
          * instances in the same order -> wave-uniform loop over LDS records.
@@ -560,7 +504,7 @@ __device__ __forceinline__ bool traceScene(const DevScene& S, const TraceTables&
          * shadow queue is ordered by light and origin cell). */
         const V3 rdw = mk3(1.0f / d.x, 1.0f / d.y, 1.0f / d.z);
         const bool cullOk = finite3(o) && finite3(rdw);
-        for (uint32_t k = RES ? lc->turn + 1u : 0u; k < S.tlasLeafCount; ++k) {
+        for (uint32_t k = 0; k < S.tlasLeafCount; ++k) {
             const uint32_t ii = Tt.order[k];
             const TraceInst& I = Tt.inst[ii];
             if (cullOk && I.wlo.w != 0.0f) {
@@ -575,13 +519,12 @@ __device__ __forceinline__ bool traceScene(const DevScene& S, const TraceTables&
              * staged triangles are those at S.sbTri0, so both offsets must match) */
             const bool hitI = (STG && !LW && I.meta.x == S.sbNode0 && I.meta.y == S.sbTri0)
                                   ? instanceTrace<ANY, false, true, SK>(S, I, o, d, depth, hu, hv, hprim, stk, stride, 0u, sN)
-                                  : instanceTrace<ANY, LW, false, SK, CAP>(S, I, o, d, depth, hu, hv, hprim, stk, stride, 0u, nullptr, lc);
+                                  : instanceTrace<ANY, LW, false, SK>(S, I, o, d, depth, hu, hv, hprim, stk, stride, 0u);
             if (hitI) {
                 if (ANY) return true;
                 any = true;
                 hinst = ii;
             }
-            if (CAP && lc->capped) { lc->turn = k; return any; }
         }
         return any;
     }
@@ -618,13 +561,6 @@ __device__ __forceinline__ bool traceScene(const DevScene& S, const TraceTables&
         }
     }
     return any;
-}
-
-/* Object-space ray of instance I (Instance::intersect, bvh.cpp:481-513). */
-__device__ __forceinline__ void instanceRay(const TraceInst& I, V3 o, V3 d, V3& oo, V3& dd) {
-    oo = mk3(rowDot(I.m0, o.x, o.y, o.z, 1.0f), rowDot(I.m1, o.x, o.y, o.z, 1.0f), rowDot(I.m2, o.x, o.y, o.z, 1.0f));
-    if (!I.meta.z) oo = divs(oo, rowDot(I.m3, o.x, o.y, o.z, 1.0f));
-    dd = mk3(rowDot(I.m0, d.x, d.y, d.z, 0.0f), rowDot(I.m1, d.x, d.y, d.z, 0.0f), rowDot(I.m2, d.x, d.y, d.z, 0.0f));
 }
 
 /* ------------------------------------------------- one ray per wave, lanes as planes
@@ -1906,19 +1842,10 @@ __global__ __launch_bounds__(kSortThreads) void k_binscatter(const uint8_t* __re
 /* ------------------------------------------------------------------ kernels */
 /* SK: the traversal stack's entry type -- 16-bit when every BLAS and TLAS
  * node index fits (half the stack's LDS: more resident workgroups) */
-/* CAP (single-leaf TLAS): a lane leaves a ray after capIters node visits of
- * one BLAS walk (W-record visits in the two-level walk; LaneCap) and writes
- * its resume record (64 words: slot i, pool index j, TLAS turn, next node,
- * stack depth, depth, u, v, prim, instance, then the stack's entries bottom
- * first); k_extend_cont finishes those rays and writes their hit records. */
-#ifndef SURF_TRACE_WAVES_CAP
-#define SURF_TRACE_WAVES_CAP SURF_TRACE_WAVES_EXT
-#endif
-template <bool LDS, bool LW = false, typename SK = uint32_t, bool CAP = false>
-__global__ __launch_bounds__(kBlock, LW ? SURF_TRACE_WAVES : (CAP ? SURF_TRACE_WAVES_CAP : SURF_TRACE_WAVES_EXT)) void k_extend(DevScene S, Pool cur, float4* __restrict__ hitTUV,
+template <bool LDS, bool LW = false, typename SK = uint32_t>
+__global__ __launch_bounds__(kBlock, LW ? SURF_TRACE_WAVES : SURF_TRACE_WAVES_EXT) void k_extend(DevScene S, Pool cur, float4* __restrict__ hitTUV,
                                                    uint32_t* __restrict__ hitInst, const Counters* C, int par, uint32_t stackWords,
-                                                   const uint32_t* __restrict__ order, uint32_t capIters, uint32_t* __restrict__ resumeRec,
-                                                   uint32_t resumeCap) {
+                                                   const uint32_t* __restrict__ order) {
     extern __shared__ uint32_t lds[];
     const uint32_t n = C->nIn[par];
     /* blocks past the pool exit before staging: a small pool (the drain) costs
@@ -1928,68 +1855,15 @@ __global__ __launch_bounds__(kBlock, LW ? SURF_TRACE_WAVES : (CAP ? SURF_TRACE_W
     const TraceTables Tt = traceTables<LDS>(S, lds, layout::laneTablesAt(stackWords, sizeof(SK) == 2));
     const uint32_t stride = blockDim.x;
     SK* stk = reinterpret_cast<SK*>(lds) + threadIdx.x;
-    LaneCap lc;
     for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
         const uint32_t j = order ? order[i] : i;       /* ray order: hit records stay in order i */
         const float4 o = ldS(&cur.od[2u * (j)]), d = ldS(&cur.od[2u * (j) + 1u]);
         float depth = kFarAway, u = 0.0f, v = 0.0f;
         uint32_t inst = kUnset, prim = kUnset;
-        if (CAP) { lc.left = capIters; lc.capped = false; }
-        const bool hit = traceScene<false, LW, false, SK, CAP>(S, Tt, xyz(o), xyz(d), depth, u, v, inst, prim, stk, stride, nullptr,
-                                                               CAP ? &lc : nullptr);
-        /* (the records hold a whole pool: every lane that stops has one) */
-        uint32_t slot = 0u;
-        if (CAP) {   /* one atomic per wave, by its first active lane (lanes past the pool have left the loop) */
-            const unsigned long long m = __ballot(lc.capped);
-            const int lead = __ffsll((long long)__ballot(true)) - 1;
-            uint32_t base = 0u;
-            if ((int)__lane_id() == lead && m) base = atomicAdd(&const_cast<Counters*>(C)->resumeN[par], (uint32_t)__popcll(m));
-            slot = (uint32_t)__shfl((int)base, lead) + rankBelow(m);
-        }
-        if (CAP && lc.capped) {
-            uint32_t* r = resumeRec + 64u * (size_t)slot;
-            r[0] = i; r[1] = j; r[2] = lc.turn; r[3] = lc.ref; r[4] = lc.depthN;
-            r[5] = f2u(depth); r[6] = f2u(u); r[7] = f2u(v); r[8] = prim; r[9] = inst;
-            for (uint32_t e = 0; e < lc.depthN; ++e) r[kResumeHead + e] = (uint32_t)stk[e * stride];
-            continue;
-        }
+        const bool hit = traceScene<false, LW, false, SK>(S, Tt, xyz(o), xyz(d), depth, u, v, inst, prim, stk, stride);
         stS(&hitTUV[i], make_float4(depth, u, v, u2f(prim)));
         stSu(&hitInst[i], hit ? inst : kUnset);
     }
-}
-
-/* The second pass of the capped lane walk (LaneCap): each lane takes one
- * resume record of this phase, puts the capped lane's stack into its own LDS
- * column and continues that walk (traceScene RES) -- the rays that outlived
- * the cap, 64 to a wave again -- then writes the hit record k_extend would
- * have written.  Same traversal code and decisions: exact. */
-template <bool LDS, bool LW, typename SK>
-__global__ __launch_bounds__(kBlock, SURF_TRACE_WAVES) void k_extend_cont(DevScene S, Pool cur, float4* __restrict__ hitTUV,
-                                                                         uint32_t* __restrict__ hitInst, const Counters* C, int par,
-                                                                         uint32_t stackWords, const uint32_t* __restrict__ rec,
-                                                                         uint32_t recCap) {
-    extern __shared__ uint32_t lds[];
-    const uint32_t n = min(C->resumeN[par], recCap);
-    if (blockIdx.x * blockDim.x >= n) return;
-    const TraceTables Tt = traceTables<LDS>(S, lds, layout::laneTablesAt(stackWords, sizeof(SK) == 2));
-    const uint32_t stride = blockDim.x;
-    SK* stk = reinterpret_cast<SK*>(lds) + threadIdx.x;
-    uint32_t done = 0u;
-    for (uint32_t q = blockIdx.x * blockDim.x + threadIdx.x; q < n; q += gridDim.x * blockDim.x, ++done) {
-        const uint32_t* r = rec + 64u * (size_t)q;
-        const uint32_t i = r[0], j = r[1];
-        LaneCap lc;
-        lc.turn = r[2]; lc.ref = r[3]; lc.depthN = r[4];
-        float depth = u2f(r[5]), u = u2f(r[6]), v = u2f(r[7]);
-        uint32_t prim = r[8], inst = r[9];
-        for (uint32_t e = 0; e < lc.depthN; ++e) stk[e * stride] = (SK)r[kResumeHead + e];
-        const float4 o = ldS(&cur.od[2u * j]), d = ldS(&cur.od[2u * j + 1u]);
-        const bool hit = traceScene<false, LW, false, SK, false, true>(S, Tt, xyz(o), xyz(d), depth, u, v, inst, prim, stk, stride,
-                                                                    nullptr, &lc, inst != kUnset);
-        stS(&hitTUV[i], make_float4(depth, u, v, u2f(prim)));
-        stSu(&hitInst[i], hit ? inst : kUnset);
-    }
-    if (done) atomicAdd(&const_cast<Counters*>(C)->evS[blockIdx.x % kStripes][9], (unsigned long long)done);
 }
 
 /* randomOnHemisphereCosineWeighted, surf_math.cpp:116-134 (retry loop for R.N == 0) */
@@ -2576,7 +2450,6 @@ __device__ __forceinline__ void regenSample(const DevCamera& cam, const Pool& nx
 /* The counters of the phase after par (one thread). */
 __device__ __forceinline__ void regenCounters(Counters* C, int par, const RegenPlan& R) {
     const int nx = par ^ 1;
-    C->resumeN[par] = 0u;          /* this phase's k_extend_cont has run */
     C->nIn[nx] = R.cont + R.nnew;
     C->issued[nx] = R.iss + R.nnew;
     C->app[nx] = 0u;               /* next phase's append cursor */

@@ -38,11 +38,6 @@ struct surf_ctx {
     bool connectGlobal = false;    /* k_connect reads its tables from global memory (SURF_CONNECT_GLOBAL=1, tuning) */
     bool extStack16 = true;        /* k_extend's stack in 16-bit entries when node indices fit (SURF_EXT_STACK16=0: 32-bit) */
     bool regenCount = true;        /* k_regen_count fills the next pool and counts it for its sort (SURF_REGEN_COUNT=0: k_regen + k_bincount) */
-    /* the lane walk leaves a ray after laneCap node visits of one BLAS walk
-     * to k_extend_cont (SURF_LANE_CAP; 0 = off, the default: measured slower) */
-    uint32_t laneCap = 0;
-    uint32_t* resumeRec = nullptr;  /* resume records, 64 words each (allocated with the first capped graph) */
-    uint32_t resumeCap = 0;
     bool ldsTables = false;        /* instance/material/light tables fit the per-workgroup LDS copy */
     DevScene S{};
     std::vector<void*> sceneAllocs;

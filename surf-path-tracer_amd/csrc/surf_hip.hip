@@ -96,18 +96,11 @@ size_t waveTailLds(const surf_ctx* c, uint32_t waves) {
 /* the one-ray-per-wave kernels fit the LDS: the largest of them, k_tail_pair, within 64 KiB */
 bool coopLdsOk(const surf_ctx* c) { return waveTailLds(c, 2u) <= 65536; }
 
-/* The capped lane walk (LaneCap): a TLAS of one leaf of <= 64 instances and
- * a stack that fits a resume record */
-bool laneCapOn(const surf_ctx* c) {
-    return c->laneCap > 0u && c->S.tlasLeafCount >= 1u && c->S.tlasLeafCount <= 64u && c->stackDepth <= 64u - kResumeHead;
-}
-
 struct Variant {
     bool lds;      /* the trace and shading tables fit the per-workgroup LDS copy */
     bool laneW;    /* the lane walk over the two-level records (HBM-resident BVHs) */
     bool w2;       /* the wave walk over the two-level records */
     bool sk16;     /* k_extend's stack in 16-bit entries: every node index fits (the two-level lane walk stacks 32-bit packed leaf references) */
-    bool cap;      /* the capped lane walk */
     bool ldsC;     /* k_connect's tables in LDS (else global: LDS holds only its stack) */
     bool stg;      /* ... and the emitters' BLAS beside them, behind a 16-bit stack */
 };
@@ -117,7 +110,6 @@ Variant variantOf(const surf_ctx* c) {
     v.laneW = c->S.laneW != 0u;
     v.w2 = c->S.wnodes != nullptr;
     v.sk16 = c->extStack16 && !v.laneW && c->nBlasNodes < 65536u && c->tlasNodeCount < 65536u;
-    v.cap = laneCapOn(c);
     v.ldsC = v.lds && !c->connectGlobal;
     /* staged only where the copy still leaves 5 workgroups of 256 per CU
      * (k_connect's residency; 144 B of static LDS each) */
@@ -128,25 +120,15 @@ Variant variantOf(const surf_ctx* c) {
 /* the four instantiations of a kernel template over two bools */
 #define SURF_PICK2(K, a, b) ((a) ? ((b) ? K<true, true> : K<true, false>) : ((b) ? K<false, true> : K<false, false>))
 
-/* k_extend<LDS, LW, SK, CAP>: 12 of the 16 -- the two-level lane walk never takes a 16-bit stack */
+/* k_extend<LDS, LW, SK>: 6 of the 8 -- the two-level lane walk never takes a 16-bit stack */
 template <bool LDS>
 auto extendFn(const Variant& v) {
-    if (v.laneW) return v.cap ? k_extend<LDS, true, uint32_t, true> : k_extend<LDS, true, uint32_t, false>;
-    if (v.sk16) return v.cap ? k_extend<LDS, false, uint16_t, true> : k_extend<LDS, false, uint16_t, false>;
-    return v.cap ? k_extend<LDS, false, uint32_t, true> : k_extend<LDS, false, uint32_t, false>;
+    if (v.laneW) return k_extend<LDS, true, uint32_t>;
+    if (v.sk16) return k_extend<LDS, false, uint16_t>;
+    return k_extend<LDS, false, uint32_t>;
 }
 auto extendKernel(const surf_ctx* c, const Variant& v) {
     return kernel(v.lds ? extendFn<true>(v) : extendFn<false>(v), laneLds(c, c->extBlock, v.sk16, v.lds) + c->extLdsPad);
-}
-
-/* k_extend_cont<LDS, LW, SK>: the capped walk's second pass, the stack as k_extend has it */
-template <bool LDS>
-auto extendContFn(const Variant& v) {
-    if (v.laneW) return k_extend_cont<LDS, true, uint32_t>;
-    return v.sk16 ? k_extend_cont<LDS, false, uint16_t> : k_extend_cont<LDS, false, uint32_t>;
-}
-auto extendContKernel(const surf_ctx* c, const Variant& v) {
-    return kernel(v.lds ? extendContFn<true>(v) : extendContFn<false>(v), laneLds(c, kBlock, v.sk16, v.lds));
 }
 
 auto shadeKernel(const Variant& v) { return v.lds ? k_shade<true> : k_shade<false>; }
@@ -376,14 +358,7 @@ void launchPhase(surf_ctx* c, int ph, hipEvent_t* ev) {
     const Pool cur = c->pool[par];                 /* the pool k_extend / k_shade read */
     const auto extend = extendKernel(c, v);
     hipLaunchKernelGGL(extend.fn, dim3(c->gridExtend), dim3(c->extBlock), extend.lds, s0, c->S,
-                       cur, c->hitTUV, c->hitInst, (const Counters*)c->ctr, par, stackWords(c, c->extBlock), order,
-                       c->laneCap, c->resumeRec, c->resumeCap);
-    if (v.cap) {   /* the rays the capped lane walk left, 64 to a wave again (LaneCap) */
-        const auto cont = extendContKernel(c, v);
-        hipLaunchKernelGGL(cont.fn, dim3(std::min<uint32_t>((c->resumeCap + kBlock - 1) / kBlock, c->cus * 8u)), dim3(kBlock),
-                           cont.lds, s0, c->S, cur, c->hitTUV, c->hitInst, (const Counters*)c->ctr, par, stackWords(c, kBlock),
-                           (const uint32_t*)c->resumeRec, c->resumeCap);
-    }
+                       cur, c->hitTUV, c->hitInst, (const Counters*)c->ctr, par, stackWords(c, c->extBlock), order);
     if (ev) (void)hipEventRecord(ev[2], s0);
     if (ovl && ph > 0) (void)hipStreamWaitEvent(s0, c->capEv[2 * (ph - 1) + 1], 0);   /* the previous phase's connect */
     hipLaunchKernelGGL(shadeKernel(v), dim3(c->gridWork), dim3(kBlock), 0, s0, c->S, cur, c->pool[par ^ 1],
@@ -412,17 +387,8 @@ void launchPhase(surf_ctx* c, int ph, hipEvent_t* ev) {
     if (!c->regenFirst) regen();
 }
 
-/* The resume records of the capped lane walk, before the first phase that
- * may write them: one per pool slot (every ray of a phase may stop once) */
-int ensureResume(surf_ctx* c) {
-    if (!laneCapOn(c) || c->resumeRec) return SURF_OK;
-    c->resumeCap = c->capacity;
-    return devAlloc(c, c->wfAllocs, &c->resumeRec, (size_t)c->resumeCap * 64u);
-}
-
 int buildGraph(surf_ctx* c) {
     if (c->graphExec) return SURF_OK;
-    if (int rc = ensureResume(c)) return rc;
     for (int shortG = 0; shortG < 2; ++shortG) {
         SURF_CHECK(c, hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
         const int nph = shortG ? kPhasesShort : kPhasesPerGraph;
@@ -806,7 +772,6 @@ int syncAndAccumulate(surf_ctx* c, int phases = 0) {
 int advance(surf_ctx* c, bool shortRun = false) {
     const int phases = shortRun ? kPhasesShort : kPhasesPerGraph;
     if (c->profiling) {
-        if (int rc = ensureResume(c)) return rc;
         for (int ph = 0; ph < phases; ++ph) launchPhase(c, ph, &c->pev[kPhaseEvents * ph]);
         SURF_CHECK(c, hipEventRecord(c->pev[kPhaseEvents * phases], c->stream));
         SURF_CHECK(c, hipGetLastError());
@@ -1144,7 +1109,6 @@ int createCtx(int dev, uint32_t w, uint32_t h, std::vector<uint32_t> rows, surf_
     if (const char* e = std::getenv("SURF_CONNECT_GLOBAL")) c->connectGlobal = e[0] != '0';
     if (const char* e = std::getenv("SURF_EXT_STACK16")) c->extStack16 = e[0] != '0';
     if (const char* e = std::getenv("SURF_REGEN_COUNT")) c->regenCount = e[0] != '0';
-    if (const char* e = std::getenv("SURF_LANE_CAP")) c->laneCap = (uint32_t)std::max(0, std::atoi(e));
     if (const char* e = std::getenv("SURF_KEY")) c->keyMode = e[0] == '0' ? 0u : (e[0] == '1' ? 1u : 2u);
     if (const char* e = std::getenv("SURF_OVERLAP")) c->overlap = e[0] != '0';
     if (const char* e = std::getenv("SURF_LOOP_LAG")) c->loopLag = e[0] != '0';
@@ -1709,16 +1673,6 @@ int surf_trace_any(surf_ctx* c, uint32_t n, const float* o, const float* d, cons
     hipError_t e = hipStreamSynchronize(c->stream);
     freeList(tmp);
     if (e != hipSuccess) return fail(c, SURF_ERR_HIP, std::string("trace_any: ") + hipGetErrorString(e));
-    return SURF_OK;
-}
-
-int surf_debug_lane_resumed(surf_ctx* c, uint64_t* rays) {
-    if (!c || !rays) return SURF_ERR_INVALID;
-    int rc = ensureDrained(c);
-    if (rc) return rc;
-    unsigned long long cur[kEvents] = {};
-    if (c->streamActive && c->hctr) streamEvents(*c->hctr, cur);
-    *rays = c->evBase[9] + cur[9];
     return SURF_OK;
 }
 

@@ -112,7 +112,6 @@ def load() -> C.CDLL:
         "surf_debug_capped": ([P, P, U32, C.POINTER(C.c_uint64)], I32),
         "surf_debug_issue_order": ([P, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)], I32),
         "surf_debug_connect_staging": ([P, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)], I32),
-        "surf_debug_lane_resumed": ([P, C.POINTER(C.c_uint64)], I32),
         "surf_debug_segment_cycles": ([P, P, U32, P], I32),
         "surf_upload_scene": ([P, C.POINTER(SceneDesc)], I32),
         "surf_set_camera": ([P, P], I32),
@@ -459,13 +458,6 @@ class Renderer:
         a, f = C.c_uint32(), C.c_uint32()
         _check(load().surf_debug_issue_order(self._h, C.byref(a), C.byref(f)), "surf_debug_issue_order", self._h)
         return int(a.value), int(f.value)
-
-    def debug_lane_resumed(self):
-        """Extension rays the capped lane walk left to k_extend_cont (SURF_LANE_CAP)
-        since the accumulator was last cleared (surf_debug_lane_resumed)."""
-        n = C.c_uint64()
-        _check(load().surf_debug_lane_resumed(self._h, C.byref(n)), "surf_debug_lane_resumed", self._h)
-        return int(n.value)
 
     def debug_connect_staging(self):
         """(records, triangles) of the emitters' BLAS the last k_connect launch

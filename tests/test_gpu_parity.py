@@ -132,38 +132,6 @@ def test_lane_two_level_walk_bitexact(oracle_scene, monkeypatch):
         p.close()
 
 
-@pytest.mark.parametrize("walk,cap", [("one-level", "4"), ("one-level", "24"), ("two-level", "2"), ("two-level", "12")])
-def test_lane_walk_cap_resume_bitexact(oracle_scene, monkeypatch, walk, cap):
-    """The capped lane walk (SURF_LANE_CAP): a ray whose BLAS walk takes more
-    than `cap` node visits (W-record visits in the two-level walk, forced on
-    the bundled scene by SURF_LANEW=1) is finished from the lane's state (its
-    next node, its stack, depth and hit so far, then the instances after it)
-    by k_extend_cont, the lane walk again with 64 such rays to a wave.  With
-    caps small enough that many rays hand over: a render and its event counts
-    equal the oracle's, and rays were resumed."""
-    monkeypatch.setenv("SURF_LANEW", "1" if walk == "two-level" else "0")
-    monkeypatch.setenv("SURF_LANE_CAP", cap)
-    p = surf_amd.Scene.indoor()
-    try:
-        W = H = 96
-        r = surf_amd.Renderer(p, W, H)
-        r.render(4, 0, 0)
-        g = r.accumulator()
-        stats = r.stats()
-        resumed = r.debug_lane_resumed()
-        r.close()
-        oracle.set_zero_cutoff(True)
-        try:
-            c, cnt, _ = oracle_scene.render(W, H, 4)
-        finally:
-            oracle.set_zero_cutoff(False)
-        _assert_bitexact(g, c, f"capped lane walk (cap {cap}) 96x96x4")
-        _assert_counts(stats, cnt)
-        assert resumed > 1000, resumed
-    finally:
-        p.close()
-
-
 def _render_both(oracle_scene, product_scene, W, H, frames, first=0, max_seg=0, **kw):
     """GPU render (zero-throughput cutoff on, the product default) against the
     oracle in reference semantics (no cutoff) for radiance, and against the
