@@ -349,6 +349,18 @@ public:
      * surf_denoise_default_params. */
     std::vector<F32> denoise(const surf_denoise_params& params);
     std::vector<F32> denoise();
+    /* temporal accumulation for animated frames (surf_temporal_accumulate; width*height*4 floats,
+     * w = 1): the samples since the last clear blended with the reprojected result of the previous
+     * call.  Per displayed frame: move the scene and the camera, clearAccumulatorKeepSeed(),
+     * render(), temporal().  spatial non-NULL: the returned image also went through the a-trous
+     * filter.  The form without arguments takes surf_temporal_default_params and no spatial filter. */
+    std::vector<F32> temporal(const surf_temporal_params& params, const surf_denoise_params* spatial);
+    std::vector<F32> temporal();
+    void resetTemporal();                         /* the next temporal() is a first frame */
+    /* clearAccumulator() for that loop: the next render() goes on with the sample indices after
+     * those already rendered instead of repeating the cleared frame's sample stream (a plain
+     * clearAccumulator() starts again from sample 0, as the reference does) */
+    void clearAccumulatorKeepSeed();
     surf_ctx* handle() const { return m_ctx; }
 private:
     void pushSceneAndCamera();                    /* what render() re-reads per frame: instance updates, the camera */
@@ -359,6 +371,7 @@ private:
     GPUScene& m_scene;
     U32 m_sceneGeneration = 0;
     U32 m_totalSamples = 0;
+    U32 m_firstSample = 0;                        /* sample index of the first sample after the last clear */
     FrameInstrumentationData m_frameInfo;
     bool m_energyStale = false;
 };

@@ -432,6 +432,149 @@ int surf_denoise_image_host(uint32_t w, uint32_t h, const float* acc, const floa
  * iteration i; entries past the run's iterations (and past 7) are 0. */
 int surf_debug_denoise_time(surf_ctx* ctx, float* kernel_ms, uint32_t count);
 
+/* ---- temporal accumulation with reprojection ----
+ * The temporal half of SVGF (Schied et al. 2017), the partner of the a-trous
+ * filter above: when the camera or an instance moves and the application
+ * clears the accumulator, last frame's result is reprojected onto this
+ * frame's pixels through the first-hit feature buffers and blended with this
+ * frame's samples, instead of starting again from one noisy sample set.  A
+ * pure post-process: the accumulator, the sample stream and the event
+ * counters are what they would be without it.  No reference counterpart.
+ * Per displayed frame: update the scene and the camera, surf_clear_accumulator,
+ * surf_render(1, first_sample_index, 0, spp), surf_temporal_accumulate.
+ *
+ * The arithmetic is part of the interface: every operation is f32 and
+ * uncontracted, / and sqrtf are IEEE, rintf (to nearest even) and floorf are
+ * exact, in exactly the order written here (surf_temporal_image_host is a
+ * host restatement).  dot(a, b) below is (ax*bx + ay*by) + az*bz.
+ *
+ * Inputs, per pixel p = (x, y) of a FULL frame of W x H pixels, rows top to
+ * bottom: A the accumulator (rgb sum, w = samples), P the position plane
+ * (xyz, w = the ray depth t), N the normal plane, ID the id plane (x = the
+ * instance, ~0 on a miss), as surf_read_aov defines them.  Of the previous
+ * frame: the history Hq = (rgb, n) with n the history length as a float, its
+ * position plane Pq, normal plane Nq and instance ids, its camera, and both
+ * frames' instance records (the same count).
+ * Host, per instance i: moved_i = its transform or its inv_transform differs
+ * bytewise between the two frames; V = this frame's inv_transform, T = the
+ * previous frame's transform (16 floats, column-major).  An id that is not
+ * below the instance count counts as not moved.
+ * Host, from the previous camera (C = position, F0 = first_pixel, U =
+ * u_vector, V = v_vector, res = resolution):
+ *   G  = F0 - C                 n = U x V  (nx = Uy*Vz - Uz*Vy, ny = Uz*Vx - Ux*Vz, nz = Ux*Vy - Uy*Vx)
+ *   g  = dot(G, n)              iu = 1.0f / dot(U, U)      iv = 1.0f / dot(V, V)
+ * Parameters: alpha_min in [0, 1], max_history >= 1, normal_min in [-1, 1],
+ * plane_tol and min_weight finite and > 0, snap in [0, 0.5).
+ *
+ * 1. Colour: inv = A.w > 0 ? 1.0f / A.w : 0.0f, c = A.rgb * inv.
+ * 2. Miss (ID.x == ~0): out = (c, 1), hist = (c, 0); nothing else.
+ * 3. Previous position and normal.  Not moved: Pprev = P.xyz, Nprev = N.xyz.
+ *    Moved, k = 0..2:
+ *      q_k     = ((V[k]*Px + V[4+k]*Py) + V[8+k]*Pz) + V[12+k]
+ *      Pprev_k = ((T[k]*qx + T[4+k]*qy) + T[8+k]*qz) + T[12+k]
+ *      qn_k    = (V[k]*Nx + V[4+k]*Ny) + V[8+k]*Nz
+ *      m_k     = (T[k]*qnx + T[4+k]*qny) + T[8+k]*qnz
+ *      il      = 1.0f / sqrtf((mx*mx + my*my) + mz*mz)       Nprev_k = m_k * il
+ * 4. Projection into the previous frame:
+ *      D = Pprev - C      dn = dot(D, n)      s = g / dn      H_k = D_k*s - G_k
+ *      fx = (dot(H, U) * iu) * res.x          fy = (dot(H, V) * iv) * res.y
+ *    No history unless s > 0, -1 < fx < W and -1 < fy < H (a NaN fails).
+ * 5. Snap: rx = rintf(fx); if fabsf(fx - rx) <= snap then fx = rx; fy alike.
+ *    (An unmoved pixel under an unmoved camera lands within 1e-4 px of itself:
+ *    the snap makes its history a single tap of weight 1, so a still image
+ *    does not blur a little more every frame.)
+ * 6. Taps: ix = (int)floorf(fx), tx = fx - floorf(fx); iy, ty alike.  From
+ *    sumW = sumN = 0, sumC = 0 the texels (ix, iy), (ix+1, iy), (ix, iy+1),
+ *    (ix+1, iy+1) in this order, with the weights w = (1-tx)*(1-ty),
+ *    tx*(1-ty), (1-tx)*ty, tx*ty.  A tap q is used when it is inside the
+ *    frame, w > 0, its previous instance id equals ID.x, Hq.w > 0,
+ *    dot(Nq, Nprev) >= normal_min and
+ *    fabsf(dot(Pprev - Pq, Nq)) <= plane_tol * P.w; then
+ *      sumW = sumW + w     sumC_k = sumC_k + w*Hq_k     sumN = sumN + w*Hq.w
+ * 7. Blend, with have = sumW > min_weight, hc = sumC / sumW, hn = sumN / sumW:
+ *      have, A.w > 0:   n' = hn + 1.0f, at most (float)max_history;
+ *                       a = 1.0f / n', at least alpha_min;
+ *                       r_k = hc_k + (c_k - hc_k) * a
+ *      have, A.w == 0:  r = hc, n' = hn
+ *      not have:        r = c,  n' = A.w > 0 ? 1 : 0
+ *    Without a previous frame every hit pixel takes "not have".
+ * 8. out = (r, 1), hist = (r, n').
+ *
+ * Known limits: shadows and reflections OF a moving object lag behind it
+ * until max_history or alpha_min ages them out; the guides are the sharp
+ * first hit, so what is seen through the lens or in a mirror reprojects by
+ * its glass or mirror surface; misses keep no history.
+ *
+ * One launch per frame, 256 threads on a 32 x 8 pixel tile; taps are read
+ * straight from global memory (three 16-byte loads each), and so is the
+ * motion table (25 floats per instance) whatever the instance count: an LDS
+ * copy of it was measured and is slower. */
+typedef struct {
+    float alpha_min;
+    uint32_t max_history;
+    float normal_min, plane_tol, snap, min_weight;
+    uint32_t _pad[2];
+} surf_temporal_params;
+/* alpha_min 0.0, max_history 32, normal_min 0.9, plane_tol 0.01, snap 1/64, min_weight 0.01 */
+int surf_temporal_default_params(surf_temporal_params* params);
+/* One frame of the loop above: the context's accumulator and (cached) feature
+ * planes blended with the state the previous call stored, to a host buffer of
+ * width*height*4 floats; then this frame's history (always the unfiltered
+ * blend), copies of its guides, its camera and its instance records are
+ * stored on the context for the next call.  With `spatial` non-NULL the
+ * returned image is surf_denoise's filter applied to the blend as the
+ * accumulator (w = 1) with this frame's planes; NULL: the blend itself.
+ * Drains the stream, as every read does.  The stored state survives
+ * surf_clear_accumulator, surf_set_camera and surf_update_instances (that is
+ * the point); surf_upload_scene and surf_temporal_reset drop it.  Buffers
+ * are allocated on first use and kept, freed by surf_destroy.
+ * SURF_ERR_INVALID on a row shard (surf_last_error points to
+ * surf_temporal_image), for a NULL argument, alpha_min outside [0, 1],
+ * max_history 0, normal_min outside [-1, 1], plane_tol or min_weight not
+ * finite and > 0, snap outside [0, 0.5), invalid spatial parameters;
+ * SURF_ERR_NO_SCENE before a scene and a camera are set; SURF_ERR_OOM. */
+int surf_temporal_accumulate(surf_ctx* ctx, const surf_temporal_params* params, const surf_denoise_params* spatial, float* out_rgba);
+/* The same, to a buffer on the context's device (width*height*16 bytes). */
+int surf_temporal_copy_device(surf_ctx* ctx, const surf_temporal_params* params, const surf_denoise_params* spatial, void* dst_device);
+/* Drops the stored state: the next surf_temporal_accumulate is a first frame. */
+int surf_temporal_reset(surf_ctx* ctx);
+/* (rgb, n) of the stored history, width*height*4 floats; SURF_ERR_INVALID before the first accumulate. */
+int surf_temporal_history(surf_ctx* ctx, float* out_rgbn);
+/* Host planes of any two full frames (w*h*16 bytes each), e.g. assembled from
+ * row shards; needs no scene on the context and neither reads nor changes its
+ * stored state.  instances: surf_gpu_instance records (their transforms are
+ * what is read; NULL with a count of 0). */
+typedef struct {
+    const float* acc;
+    const float* position;
+    const float* normal;
+    const uint32_t* id;
+    const surf_gpu_instance* instances;
+    uint32_t instance_count;
+    uint32_t _pad;
+} surf_temporal_frame;
+typedef struct {
+    const float* history;
+    const float* position;
+    const float* normal;
+    const uint32_t* id;
+    const surf_gpu_instance* instances;
+    uint32_t instance_count;
+    uint32_t _pad;
+    surf_camera_ubo camera;
+} surf_temporal_prev;
+/* prev NULL: a first frame.  out_rgba and out_history: w*h*4 floats each.
+ * SURF_ERR_INVALID also for w or h of 0, a NULL plane and instance counts
+ * that differ between the two frames. */
+int surf_temporal_image(surf_ctx* ctx, uint32_t w, uint32_t h, const surf_temporal_frame* cur, const surf_temporal_prev* prev,
+                        const surf_temporal_params* params, float* out_rgba, float* out_history);
+/* The CPU twin: the same per-pixel function compiled for the host; needs no
+ * device.  Bit-identical to surf_temporal_image. */
+int surf_temporal_image_host(uint32_t w, uint32_t h, const surf_temporal_frame* cur, const surf_temporal_prev* prev,
+                             const surf_temporal_params* params, float* out_rgba, float* out_history);
+/* Diagnostics: device time (HIP events) of the last k_temporal launch on this context, 0 before the first. */
+int surf_debug_temporal_time(surf_ctx* ctx, float* kernel_ms);
+
 /* ---- traversal entry points (kernel-level parity tests) ----
  * n world-space rays, o/d 3 floats each.  closest: depth starts at 1e30;
  * writes t,u,v (floats) and inst,prim (u32, ~0 on miss).  any: tmax per ray,

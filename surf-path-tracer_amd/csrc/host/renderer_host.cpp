@@ -38,8 +38,15 @@ WaveFrontRenderer::~WaveFrontRenderer() { surf_destroy(m_ctx); }
 void WaveFrontRenderer::clearAccumulator() {
     check(surf_clear_accumulator(m_ctx), m_ctx, "surf_clear_accumulator");
     m_totalSamples = 0;
+    m_firstSample = 0;
     m_frameInfo = FrameInstrumentationData{};
     m_energyStale = false;
+}
+
+void WaveFrontRenderer::clearAccumulatorKeepSeed() {
+    const U32 next = m_firstSample + m_totalSamples;
+    clearAccumulator();
+    m_firstSample = next;
 }
 
 void WaveFrontRenderer::pushSceneAndCamera() {
@@ -61,7 +68,7 @@ void WaveFrontRenderer::render(F32 /*deltaTime*/) {
     /* one frame of samplesPerFrame samples, seeded from the running sample
      * count, its samples chaining their RNG state (renderer.cpp:160-188) */
     const U32 spp = m_config.samplesPerFrame ? m_config.samplesPerFrame : 1u;
-    check(surf_render(m_ctx, 1, m_totalSamples, m_config.maxSegments, spp), m_ctx, "surf_render");
+    check(surf_render(m_ctx, 1, m_firstSample + m_totalSamples, m_config.maxSegments, spp), m_ctx, "surf_render");
     m_totalSamples += spp;
     m_frameInfo.totalSamples = m_totalSamples;
     m_energyStale = true;       /* render() itself never waits for the stream (no per-frame drain) */
@@ -128,6 +135,22 @@ std::vector<F32> WaveFrontRenderer::denoise() {
     check(surf_denoise_default_params(&params), m_ctx, "surf_denoise_default_params");
     return denoise(params);
 }
+
+/* Like denoise(), the blend keeps the camera and the scene of the last render() call. */
+std::vector<F32> WaveFrontRenderer::temporal(const surf_temporal_params& params, const surf_denoise_params* spatial) {
+    if (m_totalSamples == 0) throw std::runtime_error("temporal: nothing rendered since the last clear");
+    std::vector<F32> out((size_t)m_resolution.width * m_resolution.height * 4);
+    check(surf_temporal_accumulate(m_ctx, &params, spatial, out.data()), m_ctx, "surf_temporal_accumulate");
+    return out;
+}
+
+std::vector<F32> WaveFrontRenderer::temporal() {
+    surf_temporal_params params;
+    check(surf_temporal_default_params(&params), m_ctx, "surf_temporal_default_params");
+    return temporal(params, nullptr);
+}
+
+void WaveFrontRenderer::resetTemporal() { check(surf_temporal_reset(m_ctx), m_ctx, "surf_temporal_reset"); }
 
 std::vector<U32> WaveFrontRenderer::displayRGBA8() {
     std::vector<U32> out((size_t)m_resolution.width * m_resolution.height);

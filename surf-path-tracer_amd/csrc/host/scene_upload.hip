@@ -530,6 +530,8 @@ int surf_upload_scene(surf_ctx* c, const surf_scene_desc* d) {
     c->nLightsUp = d->light_count;
     c->tlasNodeCount = d->tlas_node_count;
     c->maxBlasDepth = B.maxDepth;
+    c->instHost.assign(d->instances, d->instances + d->instance_count);
+    c->tpHave = false;                /* another scene: the temporal history starts again */
     c->hasScene = true;
     return SURF_OK;
 }
@@ -559,6 +561,7 @@ int surf_update_instances(surf_ctx* c, const surf_gpu_instance* instances, uint3
     c->S.tlasLeafCount = IT.tlasLeafCount;
     setKeys(c, c->S, IT);
     c->stackDepth = std::max(c->stackDepth, depth);
+    c->instHost.assign(instances, instances + n);
     destroyGraph(c);                  /* kernel arguments carry the scene descriptor */
     return SURF_OK;
 }

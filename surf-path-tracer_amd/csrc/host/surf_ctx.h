@@ -75,6 +75,28 @@ struct surf_ctx {
      * off the launches at steps 1 and 2 and adds 10 % at step 4 (MEASUREMENTS
      * "Denoiser") */
     uint32_t dnLdsMax = 2;
+    /* temporal accumulation (surf_temporal*, host/temporal.hip): the state a
+     * frame leaves for the next -- history (rgb, n), position and the packed
+     * normal + instance id, as two sets of three images used in turn
+     * (tp[3 * tpCur ..] is the stored one), tp[6] the blended output -- then
+     * the camera and the instance records that frame saw.  surf_temporal_image
+     * has images of its own (four current planes, three previous, two
+     * outputs).  Allocated on first use, kept, freed in surf_destroy. */
+    float4* tp[7] = {};
+    size_t tpCap = 0;
+    int tpCur = 0;
+    bool tpHave = false;           /* a previous frame is stored (dropped by surf_upload_scene and surf_temporal_reset) */
+    surf_camera_ubo tpCam{};
+    std::vector<surf_gpu_instance> tpInst;
+    float4* tpIn[9] = {};
+    size_t tpInCap = 0;
+    float* tpMotion = nullptr;     /* the motion table on the device, tpMotionCap records */
+    uint32_t tpMotionCap = 0;
+    std::vector<float> tpMotionHost;
+    hipEvent_t tpEv[2] = {};
+    float tpMs = 0.0f;             /* device time of the last k_temporal launch (surf_debug_temporal_time) */
+    /* the instance records as last uploaded (surf_upload_scene, surf_update_instances): their transforms move the history */
+    std::vector<surf_gpu_instance> instHost;
     /* one-frame render calls may leave up to a pool of their stream unissued
      * (SURF_LOOP_LAG=0: issue each call's frame before returning) */
     bool loopLag = true;
@@ -200,6 +222,19 @@ void setGlobalError(const std::string& e);
  * whose kernel arguments carry the scene descriptor */
 int endStream(surf_ctx* c);
 void destroyGraph(surf_ctx* c);
+/* ... and for the temporal filter (host/temporal.hip) what a read of the
+ * context needs: the sample stream drained, the cached feature planes
+ * computed (c->aov), images of `count` x npx pixels grown, and the a-trous
+ * filter on device planes (*result: its scratch image holding the output) */
+int drainStream(surf_ctx* c);
+int featurePlanes(surf_ctx* c);
+int growImages(surf_ctx* c, float4** planes, int count, size_t& cap, size_t npx);
+int denoisePlanes(surf_ctx* c, uint32_t w, uint32_t h, const float4* acc, const float4* pos, const float4* nrm, const float4* alb,
+                  const surf_denoise_params& P, const float4** result);
+/* NULL when the parameters are valid, else what is wrong with them */
+const char* denoiseParamsError(const surf_denoise_params* p);
+/* defined in host/temporal.hip: surf_destroy's part for the temporal state */
+void freeTemporal(surf_ctx* c);
 
 #define SURF_CHECK(ctx, call)                                                             \
     do {                                                                                  \

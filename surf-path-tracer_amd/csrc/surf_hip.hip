@@ -1049,6 +1049,15 @@ int ensureDrained(surf_ctx* c) {
 
 }  // namespace
 
+int surfhost::drainStream(surf_ctx* c) { return ensureDrained(c); }
+int surfhost::featurePlanes(surf_ctx* c) { return ensureAov(c); }
+int surfhost::growImages(surf_ctx* c, float4** planes, int count, size_t& cap, size_t npx) { return growPlanes(c, planes, count, cap, npx); }
+int surfhost::denoisePlanes(surf_ctx* c, uint32_t w, uint32_t h, const float4* acc, const float4* pos, const float4* nrm,
+                            const float4* alb, const surf_denoise_params& P, const float4** result) {
+    return runDenoise(c, w, h, acc, pos, nrm, alb, P, result);
+}
+const char* surfhost::denoiseParamsError(const surf_denoise_params* p) { return denoiseParamError(p); }
+
 /* A stream ends when its pool is empty and all its frames are accumulated. */
 int surfhost::endStream(surf_ctx* c) {
     int rc = ensureDrained(c);
@@ -1198,6 +1207,7 @@ void surf_destroy(surf_ctx* c) {
     for (float4*& p : c->dn) { if (p) (void)hipFree(p); p = nullptr; }
     for (float4*& p : c->dnIn) { if (p) (void)hipFree(p); p = nullptr; }
     for (auto& e : c->dnEv) if (e) (void)hipEventDestroy(e);
+    freeTemporal(c);
     if (c->dRows) (void)hipFree(c->dRows);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);

@@ -14,6 +14,7 @@ Mirrors the reference interface for the hot path:
     .trace_closest/.trace_any  ray_extend / ray_connect traversal (tests)
     .aov()                     first-hit feature buffers (no reference counterpart)
     .denoise()                 edge-avoiding a-trous filter on them (no reference counterpart)
+    .temporal()                temporal accumulation with reprojection across cleared frames (no reference counterpart)
 """
 from __future__ import annotations
 
@@ -80,7 +81,25 @@ class DenoiseParams(C.Structure):
                 ("sigma_plane", C.c_float), ("demodulate", C.c_uint32), ("_pad", C.c_uint32 * 3)]
 
 
+class TemporalParams(C.Structure):
+    """surf_temporal_params (include/surf_hip.h gives the arithmetic)."""
+    _fields_ = [("alpha_min", C.c_float), ("max_history", C.c_uint32), ("normal_min", C.c_float), ("plane_tol", C.c_float),
+                ("snap", C.c_float), ("min_weight", C.c_float), ("_pad", C.c_uint32 * 2)]
+
+
 CameraUBO = C.c_uint8 * 128
+
+
+class TemporalFrame(C.Structure):
+    """surf_temporal_frame: host planes of the current frame."""
+    _fields_ = [("acc", C.c_void_p), ("position", C.c_void_p), ("normal", C.c_void_p), ("id", C.c_void_p),
+                ("instances", C.c_void_p), ("instance_count", C.c_uint32), ("_pad", C.c_uint32)]
+
+
+class TemporalPrev(C.Structure):
+    """surf_temporal_prev: host planes, instance records and camera of the previous frame."""
+    _fields_ = [("history", C.c_void_p), ("position", C.c_void_p), ("normal", C.c_void_p), ("id", C.c_void_p),
+                ("instances", C.c_void_p), ("instance_count", C.c_uint32), ("_pad", C.c_uint32), ("camera", CameraUBO)]
 
 _lib = None
 
@@ -141,6 +160,13 @@ def load() -> C.CDLL:
         "surf_denoise_image": ([P, U32, U32, P, P, P, P, C.POINTER(DenoiseParams), P], I32),
         "surf_denoise_image_host": ([U32, U32, P, P, P, P, C.POINTER(DenoiseParams), P], I32),
         "surf_debug_denoise_time": ([P, C.POINTER(F), U32], I32),
+        "surf_temporal_default_params": ([C.POINTER(TemporalParams)], I32),
+        "surf_temporal_accumulate": ([P, C.POINTER(TemporalParams), C.POINTER(DenoiseParams), P], I32),
+        "surf_temporal_copy_device": ([P, C.POINTER(TemporalParams), C.POINTER(DenoiseParams), P], I32),
+        "surf_temporal_reset": ([P], I32), "surf_temporal_history": ([P, P], I32),
+        "surf_temporal_image": ([P, U32, U32, C.POINTER(TemporalFrame), C.POINTER(TemporalPrev), C.POINTER(TemporalParams), P, P], I32),
+        "surf_temporal_image_host": ([U32, U32, C.POINTER(TemporalFrame), C.POINTER(TemporalPrev), C.POINTER(TemporalParams), P, P], I32),
+        "surf_debug_temporal_time": ([P, C.POINTER(F)], I32),
         "surf_mesh_data": ([P, C.POINTER(P), C.POINTER(P), C.POINTER(U32)], I32),
         "surf_mesh_destroy": ([P], None),
         "surf_ref_sinf": ([F], F), "surf_ref_cosf": ([F], F), "surf_ref_expf": ([F], F),
@@ -356,6 +382,69 @@ def denoise_image_host(acc: np.ndarray, planes, **params) -> np.ndarray:
     _check(load().surf_denoise_image_host(w, h, _ptr(a[0]), _ptr(a[1]), _ptr(a[2]), _ptr(a[3]), C.byref(p), _ptr(out)),
            "surf_denoise_image_host")
     return out
+
+
+def temporal_params(**params) -> TemporalParams:
+    """surf_temporal_default_params (alpha_min 0, max_history 32, normal_min 0.9,
+    plane_tol 0.01, snap 1/64, min_weight 0.01) with the given fields replaced."""
+    p = TemporalParams()
+    _check(load().surf_temporal_default_params(C.byref(p)), "surf_temporal_default_params")
+    for k, v in params.items():
+        if k not in ("alpha_min", "max_history", "normal_min", "plane_tol", "snap", "min_weight"):
+            raise TypeError(f"unknown temporal parameter {k!r}")
+        setattr(p, k, int(v) if k == "max_history" else float(v))
+    return p
+
+
+def _spatial_params(spatial):
+    """None, True (the denoiser's defaults) or a dict of denoiser parameters -> DenoiseParams or None."""
+    if spatial is None or spatial is False:
+        return None
+    return denoise_params(**({} if spatial is True else spatial))
+
+
+def _temporal_frames(cur, prev):
+    """(w, h, TemporalFrame, TemporalPrev or None, the arrays they point into).  cur: a
+    dict with 'acc', 'position', 'normal' ((H, W, 4) float32), 'id' ((H, W, 4) uint32)
+    and 'instances' (the surf_gpu_instance records as bytes, Scene.buffers()['instances']);
+    prev: None for a first frame, or a dict with 'history', 'position', 'normal',
+    'id', 'instances' and 'camera' (the 128-byte camera UBO)."""
+    def planes(d, first):
+        arrs = [np.ascontiguousarray(d[k], dtype=np.float32) for k in (first, "position", "normal")]
+        arrs.append(np.ascontiguousarray(d["id"], dtype=np.uint32))
+        inst = np.frombuffer(bytes(d.get("instances", b"")), np.uint8).copy()
+        if len(inst) % RECORD_BYTES["instances"]:
+            raise ValueError(f"instances: {len(inst)} bytes are no multiple of {RECORD_BYTES['instances']}")
+        return arrs, inst
+    ca, ci = planes(cur, "acc")
+    if ca[0].ndim != 3 or ca[0].shape[2] != 4 or any(a.shape != ca[0].shape for a in ca):
+        raise ValueError(f"temporal planes {[a.shape for a in ca]} are not four (H, W, 4) images of one size")
+    h, w = ca[0].shape[:2]
+    f = TemporalFrame(*[_ptr(a) for a in ca], _ptr(ci) if len(ci) else None, len(ci) // RECORD_BYTES["instances"], 0)
+    keep = [ca, ci]
+    q = None
+    if prev is not None:
+        pa, pi = planes(prev, "history")
+        if any(a.shape != ca[0].shape for a in pa):
+            raise ValueError(f"previous planes {[a.shape for a in pa]} differ from the current frame's {ca[0].shape}")
+        if len(prev["camera"]) != C.sizeof(CameraUBO):
+            raise ValueError(f"camera UBO is {len(prev['camera'])} bytes, not {C.sizeof(CameraUBO)}")
+        q = TemporalPrev(*[_ptr(a) for a in pa], _ptr(pi) if len(pi) else None, len(pi) // RECORD_BYTES["instances"], 0,
+                         CameraUBO.from_buffer_copy(prev["camera"]))
+        keep += [pa, pi]
+    return w, h, f, q, keep
+
+
+def temporal_image_host(cur, prev, **params):
+    """The CPU twin of Renderer.temporal_image (surf_temporal_image_host): the same
+    per-pixel function compiled for the host, bit-identical; no device.
+    Returns (out, history), each (H, W, 4) float32."""
+    w, h, f, q, _keep = _temporal_frames(cur, prev)
+    p = temporal_params(**params)
+    out, hist = np.zeros((h, w, 4), np.float32), np.zeros((h, w, 4), np.float32)
+    _check(load().surf_temporal_image_host(w, h, C.byref(f), C.byref(q) if q is not None else None, C.byref(p), _ptr(out), _ptr(hist)),
+           "surf_temporal_image_host")
+    return out, hist
 
 
 def obj_load(path: str, threads: int = 0) -> tuple[np.ndarray, np.ndarray]:
@@ -596,6 +685,53 @@ class Renderer:
         ms = (C.c_float * 7)()
         _check(load().surf_debug_denoise_time(self._h, ms, 7), "surf_debug_denoise_time", self._h)
         return [float(v) for v in ms]
+
+    def temporal(self, spatial=None, **params) -> np.ndarray:
+        """One frame of temporal accumulation (surf_temporal_accumulate; parameters
+        as temporal_params): the accumulator blended with the reprojected result
+        of the previous call, (H, W, 4) float32 with w = 1.  The loop per displayed
+        frame: move the scene / camera, clear_accumulator(), render(1, first, spp=),
+        temporal().  spatial: None, True (the denoiser's defaults) or a dict of
+        denoiser parameters -- the returned image then went through the a-trous
+        filter; the stored history is always the unfiltered blend.  Raises
+        SURF_ERR_INVALID on a row shard (see temporal_image)."""
+        p, sp = temporal_params(**params), _spatial_params(spatial)
+        out = np.zeros((self.height, self.width, 4), dtype=np.float32)
+        _check(load().surf_temporal_accumulate(self._h, C.byref(p), C.byref(sp) if sp is not None else None, _ptr(out)),
+               "surf_temporal_accumulate", self._h)
+        return out
+
+    def temporal_reset(self):
+        """Drops the stored history: the next temporal() is a first frame."""
+        _check(load().surf_temporal_reset(self._h), "surf_temporal_reset", self._h)
+
+    def temporal_history(self) -> np.ndarray:
+        """(rgb, n) of the stored history (surf_temporal_history), n the history length."""
+        out = np.zeros((self.height, self.width, 4), dtype=np.float32)
+        _check(load().surf_temporal_history(self._h, _ptr(out)), "surf_temporal_history", self._h)
+        return out
+
+    def temporal_image(self, cur, prev, **params):
+        """The same blend on host planes of any two full frames (surf_temporal_image;
+        cur and prev as _temporal_frames describes them, prev None for a first
+        frame).  Returns (out, history)."""
+        w, h, f, q, _keep = _temporal_frames(cur, prev)
+        p = temporal_params(**params)
+        out, hist = np.zeros((h, w, 4), np.float32), np.zeros((h, w, 4), np.float32)
+        _check(load().surf_temporal_image(self._h, w, h, C.byref(f), C.byref(q) if q is not None else None, C.byref(p), _ptr(out),
+                                          _ptr(hist)), "surf_temporal_image", self._h)
+        return out, hist
+
+    def copy_temporal_to(self, device_ptr: int, spatial=None, **params):
+        p, sp = temporal_params(**params), _spatial_params(spatial)
+        _check(load().surf_temporal_copy_device(self._h, C.byref(p), C.byref(sp) if sp is not None else None, C.c_void_p(device_ptr)),
+               "surf_temporal_copy_device", self._h)
+
+    def debug_temporal_time(self) -> float:
+        """Device milliseconds of the last k_temporal launch (surf_debug_temporal_time)."""
+        ms = C.c_float()
+        _check(load().surf_debug_temporal_time(self._h, C.byref(ms)), "surf_debug_temporal_time", self._h)
+        return float(ms.value)
 
     def copy_accumulator_to(self, device_ptr: int):
         _check(load().surf_copy_accumulator_device(self._h, C.c_void_p(device_ptr)), "surf_copy_accumulator_device", self._h)
