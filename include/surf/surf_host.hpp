@@ -357,6 +357,10 @@ public:
     std::vector<F32> temporal(const surf_temporal_params& params, const surf_denoise_params* spatial);
     std::vector<F32> temporal();
     void resetTemporal();                         /* the next temporal() is a first frame */
+    /* the same loop through the variance-guided filter (surf_svgf_accumulate): it shares temporal()'s
+     * stored state, the two may be mixed.  The form without arguments takes both sets of default parameters. */
+    std::vector<F32> svgf(const surf_temporal_params& params, const surf_svgf_params& filter);
+    std::vector<F32> svgf();
     /* clearAccumulator() for that loop: the next render() goes on with the sample indices after
      * those already rendered instead of repeating the cleared frame's sample stream (a plain
      * clearAccumulator() starts again from sample 0, as the reference does) */

@@ -575,6 +575,165 @@ int surf_temporal_image_host(uint32_t w, uint32_t h, const surf_temporal_frame* 
 /* Diagnostics: device time (HIP events) of the last k_temporal launch on this context, 0 before the first. */
 int surf_debug_temporal_time(surf_ctx* ctx, float* kernel_ms);
 
+/* ---- variance-guided filter ----
+ * The piece of SVGF that joins the two halves above: the first and second
+ * moment of luminance ride the temporal accumulation's reprojection, become a
+ * per-pixel variance (estimated spatially where the history is too short to
+ * trust), and that variance -- not one global sigma_color -- sets the a-trous
+ * filter's colour edge-stopping width and is filtered along with the colour.
+ * A pixel disoccluded this frame, or every pixel after a cut or a
+ * surf_temporal_reset, gets a wide filter; a pixel with a long history a
+ * narrow one.  A pure post-process, like the two above; no reference
+ * counterpart.  The loop is surf_temporal_accumulate's with
+ * surf_svgf_accumulate in its place.
+ *
+ * The arithmetic is part of the interface (f32, uncontracted, / and sqrtf
+ * IEEE, expf glibc 2.35's, in exactly this order; surf_svgf_image_host is a
+ * host restatement).  lum(v) = (0.2126f*vx + 0.7152f*vy) + 0.0722f*vz.
+ * Inputs: those of the temporal accumulation and the albedo plane (albedo.w
+ * == 0 marks an invalid pixel, as for the denoiser), and of the previous
+ * frame its moments plane Mq = (mu1, mu2, m, 0): the running first and second
+ * moment of luminance and the moments' own history length (none: every m = 0).
+ * Parameters: surf_temporal_params, and iterations n in 1..6, sigma_lum,
+ * sigma_normal, sigma_plane and variance_eps finite and > 0, demodulate
+ * 0 / 1, spatial_below >= 1.  den is the denoiser's (Prepare above) with this
+ * call's demodulate; kn, kp are the denoiser's from sigma_normal, sigma_plane.
+ *
+ * A. Moments through time.  Steps 1 - 8 of the temporal accumulation run
+ *    unchanged: out = (r, 1) and hist = (r, n') are bit for bit what
+ *    surf_temporal_accumulate gives.  Beside them, from sumWm = 0, sumM = 0:
+ *    for every tap q that step 6 uses, when Mq.z > 0:
+ *      sumWm = sumWm + w     sumM_k = sumM_k + w*Mq_k   (k = x, y, z)
+ *    With the quotients taken first, d_k = c_k / den_k and l = lum(d); with
+ *    haveM = have && sumWm > min_weight and hm = sumM / sumWm:
+ *      haveM, A.w > 0:   m' = hm.z + 1.0f, at most (float)max_history;
+ *                        am = 1.0f / m', at least alpha_min;
+ *                        mu1' = hm.x + (l - hm.x) * am
+ *                        mu2' = hm.y + (l*l - hm.y) * am
+ *      haveM, A.w == 0:  M' = (hm.x, hm.y, hm.z, 0)
+ *      not haveM:        M' = A.w > 0 ? (l, l*l, 1, 0) : (0, 0, 0, 0)
+ *      a miss (step 2):  M' = (0, 0, 0, 0)
+ * B. Variance.  An invalid pixel: v = 0.  A valid pixel p with m' = M'(p).z
+ *    and sb = (float)spatial_below:
+ *      m' >= sb:  t = mu2' - mu1'*mu1';  v = t > 0 ? t : 0
+ *      m' <  sb:  from sw = s1 = s2 = 0 the 49 taps q = (x + dx, y + dy),
+ *                 dy = -3..3 the outer loop, dx = -3..3 the inner; a q outside
+ *                 the frame, invalid or with M'(q).z == 0 is skipped; for
+ *                 every other q, the centre included, dn and dp as the
+ *                 denoiser's (dN = Nq - Np, dP = Pq - Pp, pl = dot(dP, Np)):
+ *                   e = dn*kn + dp*kp;  e = e < 100.0f ? e : 100.0f
+ *                   wq = expf(-e)
+ *                   sw = sw + wq   s1 = s1 + wq*M'(q).x   s2 = s2 + wq*M'(q).y
+ *                 sw > 0:  a1 = s1 / sw, a2 = s2 / sw, t = a2 - a1*a1,
+ *                          t = t > 0 ? t : 0, b = sb / (m' > 1.0f ? m' : 1.0f)
+ *                          (the quotient first), v = t * b
+ *                 else     v = 0
+ *    Level 0 of the filtered image is I0 = (r / den, v): the variance rides in
+ *    the image's w.  (An invalid pixel has den = 1: (r, 0).)
+ * C. Iteration i = 0..n-1, step s = 1 << i.  An invalid p copies I_i(p) to the
+ *    next level.  A valid p first takes, from gs = gw = 0, the 3 x 3 taps
+ *    q = (x + dx, y + dy), dy = -1..1 outer, dx = -1..1 inner, inside the frame
+ *    and valid, with g = {1/16, 1/8, 1/16;  1/8, 1/4, 1/8;  1/16, 1/8, 1/16}:
+ *      gs = gs + g*Iq.w     gw = gw + g
+ *    then gv = gs / gw and kl = 1.0f / (sigma_lum * sqrtf(gv) + variance_eps)
+ *    (sigma_lum is not halved per iteration: the shrinking variance does that),
+ *    then the denoiser's 25 taps with its skips, dn, dp and h, and
+ *      dl = fabsf(lum(Iq) - lum(Ip))
+ *      e  = (dl*kl + dn*kn) + dp*kp;  e = e < 100.0f ? e : 100.0f
+ *      w  = (h[dy+2] * h[dx+2]) * expf(-e)
+ *      sumW = sumW + w   sum_k = sum_k + w*Iq_k   sumV = sumV + (w*w)*Iq.w
+ *    and I_{i+1}(p) = (sum / sumW, sumV / (sumW*sumW)).
+ *    Output: (I_n.rgb * den, 1) for a valid pixel, (I_n.rgb, 1) otherwise.
+ *
+ * Not done: the paper feeds the first filtered iteration back into the
+ * history; here the history stays the unfiltered blend.  No firefly clamp:
+ * one very bright sample in a short history means a large variance and a
+ * wide filter around it.  The guides' limits are the denoiser's.
+ *
+ * Launches per frame, 256 threads on a 32 x 8 pixel tile each: k_temporal's
+ * moments instantiation (a fourth 16-byte load per used tap), the packed
+ * guides, the variance estimate, n iterations.  The variance kernel exists
+ * in two variants with identical bits: the tile and its halo of 3 -- 38 x 14
+ * texels of normal, position and moments, 25 536 bytes -- staged in LDS
+ * (the default), or its taps straight from global memory (SURF_SVGF_LDS=0,
+ * read at surf_create*).  SURF_DENOISE_LDS governs the iterations as it does
+ * the denoiser's; their staged tile has the same layout, the image's w now
+ * carrying the variance.  Buffers are allocated on first use and kept. */
+typedef struct {
+    uint32_t iterations;
+    float sigma_lum;
+    float sigma_normal, sigma_plane;
+    uint32_t demodulate;
+    uint32_t spatial_below;
+    float variance_eps;
+    uint32_t _pad;
+} surf_svgf_params;
+/* 5 iterations, sigma_lum 4.0, sigma_normal 0.3, sigma_plane 0.1, demodulate 1, spatial_below 4, variance_eps 1e-10 */
+int surf_svgf_default_params(surf_svgf_params* params);
+/* One frame of the loop, as surf_temporal_accumulate: the context's
+ * accumulator and (cached) feature planes against the stored state, the
+ * filtered image to a host buffer of width*height*4 floats.  It shares the
+ * stored temporal state with surf_temporal_accumulate -- history (always the
+ * unfiltered blend), guide copies, camera, instance records, with the same
+ * lifetime -- and adds the moments.  The two calls may be mixed:
+ * surf_temporal_accumulate leaves the stored moments marked absent, so the
+ * next surf_svgf_accumulate sees m = 0 everywhere and estimates spatially
+ * until the moments have a history again.  surf_temporal_reset and
+ * surf_upload_scene drop the moments with the history.  Status codes as
+ * surf_temporal_accumulate (on a row shard surf_last_error points to
+ * surf_svgf_image); SURF_ERR_INVALID also for iterations outside 1..6,
+ * spatial_below 0, and a sigma or variance_eps that is not finite and > 0. */
+int surf_svgf_accumulate(surf_ctx* ctx, const surf_temporal_params* params, const surf_svgf_params* svgf, float* out_rgba);
+/* The same, to a buffer on the context's device (width*height*16 bytes). */
+int surf_svgf_copy_device(surf_ctx* ctx, const surf_temporal_params* params, const surf_svgf_params* svgf, void* dst_device);
+/* The stored moments (mu1, mu2, m, 0), width*height*4 floats; SURF_ERR_INVALID
+ * when none are stored (before the first surf_svgf_accumulate, after a
+ * surf_temporal_accumulate, a reset or a scene upload). */
+int surf_svgf_moments(surf_ctx* ctx, float* out);
+/* Of the last surf_svgf_accumulate, per pixel: x = the variance entering the
+ * filter (I0.w), y = the variance leaving it (I_n.w, 0 for an invalid pixel),
+ * z = w = 0.  SURF_ERR_INVALID as surf_svgf_moments. */
+int surf_svgf_variance(surf_ctx* ctx, float* out);
+/* Host planes of any two full frames, as surf_temporal_image: the temporal
+ * structs plus the albedo plane and the previous moments (NULL: every m = 0). */
+typedef struct {
+    const float* acc;
+    const float* position;
+    const float* normal;
+    const uint32_t* id;
+    const surf_gpu_instance* instances;
+    uint32_t instance_count;
+    uint32_t _pad;
+    const float* albedo;
+} surf_svgf_frame;
+typedef struct {
+    const float* history;
+    const float* position;
+    const float* normal;
+    const uint32_t* id;
+    const surf_gpu_instance* instances;
+    uint32_t instance_count;
+    uint32_t _pad;
+    surf_camera_ubo camera;
+    const float* moments;
+} surf_svgf_prev;
+/* prev NULL: a first frame.  Four outputs of w*h*4 floats each: the filtered
+ * image, the history (rgb, n'), the moments M' and the variances as
+ * surf_svgf_variance returns them.  Needs no scene on the context and neither
+ * reads nor changes its stored state. */
+int surf_svgf_image(surf_ctx* ctx, uint32_t w, uint32_t h, const surf_svgf_frame* cur, const surf_svgf_prev* prev,
+                    const surf_temporal_params* params, const surf_svgf_params* svgf, float* out_rgba, float* out_history,
+                    float* out_moments, float* out_variance);
+/* The CPU twin: the same per-pixel functions compiled for the host; needs no
+ * device.  Bit-identical to surf_svgf_image. */
+int surf_svgf_image_host(uint32_t w, uint32_t h, const surf_svgf_frame* cur, const surf_svgf_prev* prev,
+                         const surf_temporal_params* params, const surf_svgf_params* svgf, float* out_rgba, float* out_history,
+                         float* out_moments, float* out_variance);
+/* Diagnostics: device time (HIP events) of the kernels of the last svgf run on
+ * this context: [0] k_temporal, [1] the guides and the variance estimate,
+ * [2 + i] iteration i; entries past the run's iterations (and past 8) are 0. */
+int surf_debug_svgf_time(surf_ctx* ctx, float* kernel_ms, uint32_t count);
+
 /* ---- traversal entry points (kernel-level parity tests) ----
  * n world-space rays, o/d 3 floats each.  closest: depth starts at 1e30;
  * writes t,u,v (floats) and inst,prim (u32, ~0 on miss).  any: tmax per ray,

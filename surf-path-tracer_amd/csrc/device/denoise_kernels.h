@@ -123,8 +123,10 @@ struct DenoiseFetchTile {
     __device__ __forceinline__ float4 p(int qx, int qy) const { return P[(qy - y0) * tw + (qx - x0)]; }
 };
 
-/* Elementwise: level 0 and the packed guides of n pixels. */
-__global__ __launch_bounds__(256) void k_denoise_prepare(const float4* __restrict__ acc, const float4* __restrict__ pos,
+/* Elementwise: level 0 and the packed guides of n pixels.  (static: the
+ * header is included by more than one translation unit; the one that
+ * launches it owns it.) */
+static __global__ __launch_bounds__(256) void k_denoise_prepare(const float4* __restrict__ acc, const float4* __restrict__ pos,
                                                          const float4* __restrict__ nrm, const float4* __restrict__ alb,
                                                          uint32_t demodulate, uint32_t n, float4* __restrict__ I0,
                                                          float4* __restrict__ gN, float4* __restrict__ gP) {

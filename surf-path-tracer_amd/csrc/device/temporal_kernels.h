@@ -16,6 +16,7 @@
 #pragma once
 #include <string.h>
 
+#include "denoise_kernels.h"      /* denoiseDen: the moments are those of the demodulated colour */
 #include "surf_math.h"
 #include "types.h"
 
@@ -61,23 +62,34 @@ inline void temporalMotionRecord(const float* curTransform, const float* curInv,
 SURF_HD float temporalRowPoint(const float* r, float x, float y, float z) { return ((r[0] * x + r[1] * y) + r[2] * z) + r[3]; }
 SURF_HD float temporalRowDir(const float* r, float x, float y, float z) { return (r[0] * x + r[1] * y) + r[2] * z; }
 
+/* luminance, of the demodulated colour and of a level of the filtered image */
+SURF_HD float svgfLum(float x, float y, float z) { return (0.2126f * x + 0.7152f * y) + 0.0722f * z; }
+
 /* One pixel: A the accumulator (rgb sum, w = samples), P, N the position and
  * normal planes' records, id the id plane's x (~0 on a miss).  prev.g / .h /
  * .p (qx, qy) return the guide, the history and the position of an in-frame
  * texel of the previous frame; history and position of a tap whose instance
- * id differs are never fetched.  out = (r, 1), hist = (r, n'). */
-template <class Prev>
+ * id differs are never fetched.  out = (r, 1), hist = (r, n').
+ * MOMENTS (the variance-guided filter, surf_svgf*): the luminance moments
+ * (mu1, mu2, m, 0) ride the same taps -- prev.m (qx, qy), read for used taps
+ * only -- and blend with this frame's luminance of c / den into mom; the
+ * colour path is the same arithmetic either way.  Without MOMENTS den is not
+ * read, mom not written, prev.m not called. */
+template <bool MOMENTS, class Prev>
 SURF_HD void temporalPixel(int W, int H, float4 A, float4 P, float4 N, uint32_t id, const TemporalConsts& K, const float* motion,
-                           const Prev& prev, float4& out, float4& hist) {
+                           const Prev& prev, float4& out, float4& hist, V3 den, float4& mom) {
     const float inv = A.w > 0.0f ? 1.0f / A.w : 0.0f;
     const V3 c = mk3(A.x * inv, A.y * inv, A.z * inv);
     if (id == 0xFFFFFFFFu) {
         out = make_float4(c.x, c.y, c.z, 1.0f);
         hist = make_float4(c.x, c.y, c.z, 0.0f);
+        if (MOMENTS) mom = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
         return;
     }
     float sumW = 0.0f, sumN = 0.0f;
     V3 sumC = mk3(0.0f, 0.0f, 0.0f);
+    float sumWm = 0.0f;
+    V3 sumM = mk3(0.0f, 0.0f, 0.0f);
     if (K.havePrev) {
         V3 Pp = mk3(P.x, P.y, P.z), Np = mk3(N.x, N.y, N.z);
         const float* m = motion + (size_t)kTemporalMotionWords * (id < K.nInst ? id : 0u);
@@ -124,6 +136,15 @@ SURF_HD void temporalPixel(int W, int H, float4 A, float4 P, float4 N, uint32_t 
                 sumC.y = sumC.y + w * Hq.y;
                 sumC.z = sumC.z + w * Hq.z;
                 sumN = sumN + w * Hq.w;
+                if (MOMENTS) {
+                    const float4 Mq = prev.m(qx, qy);
+                    if (Mq.z > 0.0f) {
+                        sumWm = sumWm + w;
+                        sumM.x = sumM.x + w * Mq.x;
+                        sumM.y = sumM.y + w * Mq.y;
+                        sumM.z = sumM.z + w * Mq.z;
+                    }
+                }
             }
         }
     }
@@ -145,6 +166,23 @@ SURF_HD void temporalPixel(int W, int H, float4 A, float4 P, float4 N, uint32_t 
     }
     out = make_float4(r.x, r.y, r.z, 1.0f);
     hist = make_float4(r.x, r.y, r.z, n1);
+    if (MOMENTS) {
+        const float l = svgfLum(c.x / den.x, c.y / den.y, c.z / den.z);
+        if (sumW > K.minWeight && sumWm > K.minWeight) {
+            const V3 hm = mk3(sumM.x / sumWm, sumM.y / sumWm, sumM.z / sumWm);
+            if (A.w > 0.0f) {
+                const float mm = hm.z + 1.0f;
+                const float m1 = mm < K.maxHistory ? mm : K.maxHistory;
+                float am = 1.0f / m1;
+                am = am < K.alphaMin ? K.alphaMin : am;
+                mom = make_float4(hm.x + (l - hm.x) * am, hm.y + (l * l - hm.y) * am, m1, 0.0f);
+            } else {
+                mom = make_float4(hm.x, hm.y, hm.z, 0.0f);
+            }
+        } else {
+            mom = A.w > 0.0f ? make_float4(l, l * l, 1.0f, 0.0f) : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        }
+    }
 }
 
 /* taps from the previous frame's full-frame planes in memory (device global memory, host arrays) */
@@ -153,6 +191,8 @@ struct TemporalFetchPlanes {
     const float4* Ps;
     const TemporalGuide* Gs;
     int W;
+    const float4* Ms;                        /* the moments plane (MOMENTS only); NULL: every m = 0 */
+    SURF_HD float4 m(int qx, int qy) const { return Ms ? Ms[(size_t)qy * W + qx] : make_float4(0.0f, 0.0f, 0.0f, 0.0f); }
     SURF_HD TemporalGuide g(int qx, int qy) const { return Gs[(size_t)qy * W + qx]; }
     SURF_HD float4 h(int qx, int qy) const { return Hs[(size_t)qy * W + qx]; }
     SURF_HD float4 p(int qx, int qy) const { return Ps[(size_t)qy * W + qx]; }
@@ -173,25 +213,39 @@ struct TemporalFetchPlanes {
  * at 1280 x 720 in a same-session A/B, MEASUREMENTS "Temporal accumulation") -- a hit pixel reads one word of it,
  * a moved pixel 25, all lanes of a wave mostly the same record, and the copy
  * and its barrier cost more than those cached loads.  No LDS.  Without a
- * previous frame pH, pP, pG and motion are never read. */
+ * previous frame pH, pP, pG and motion are never read.
+ * MOMENTS: the albedo plane in (the demodulation divisor), the previous
+ * moments in (a fourth 16-byte load per used tap; NULL: none stored) and
+ * this frame's moments out; the other instantiation never touches mo. */
+struct TemporalMomentPlanes {
+    const float4* alb;
+    const float4* pM;
+    float4* outM;
+    uint32_t demodulate;
+};
+
+template <bool MOMENTS>
 __global__ __launch_bounds__(256) void k_temporal(const float4* __restrict__ A, const float4* __restrict__ P,
                                                   const float4* __restrict__ N, const uint4* __restrict__ ID,
                                                   const float4* __restrict__ pH, const float4* __restrict__ pP,
                                                   const TemporalGuide* __restrict__ pG, const float* __restrict__ motion,
                                                   TemporalConsts K, int W, int H, float4* __restrict__ out,
                                                   float4* __restrict__ hist, float4* __restrict__ gP,
-                                                  TemporalGuide* __restrict__ gN) {
+                                                  TemporalGuide* __restrict__ gN, TemporalMomentPlanes mo) {
     const int x = (int)blockIdx.x * kTemporalTileW + (int)(threadIdx.x & (kTemporalTileW - 1));
     const int y = (int)blockIdx.y * kTemporalTileH + (int)(threadIdx.x / kTemporalTileW);
     if (x >= W || y >= H) return;
     const size_t p = (size_t)y * W + x;
     const float4 a = A[p], pos = P[p], nrm = N[p];
     const uint32_t id = ID[p].x;
-    const TemporalFetchPlanes prev{pH, pP, pG, W};
-    float4 o, h;
-    temporalPixel(W, H, a, pos, nrm, id, K, motion, prev, o, h);
+    const TemporalFetchPlanes prev{pH, pP, pG, W, MOMENTS ? mo.pM : nullptr};
+    float4 o, h, m;
+    V3 den = mk3(1.0f, 1.0f, 1.0f);
+    if (MOMENTS) den = denoiseDen(mo.alb[p], mo.demodulate);
+    temporalPixel<MOMENTS>(W, H, a, pos, nrm, id, K, motion, prev, o, h, den, m);
     out[p] = o;
     hist[p] = h;
+    if (MOMENTS) mo.outM[p] = m;
     if (gP) {
         gP[p] = pos;
         TemporalGuide g;

@@ -150,6 +150,21 @@ std::vector<F32> WaveFrontRenderer::temporal() {
     return temporal(params, nullptr);
 }
 
+std::vector<F32> WaveFrontRenderer::svgf(const surf_temporal_params& params, const surf_svgf_params& filter) {
+    if (m_totalSamples == 0) throw std::runtime_error("svgf: nothing rendered since the last clear");
+    std::vector<F32> out((size_t)m_resolution.width * m_resolution.height * 4);
+    check(surf_svgf_accumulate(m_ctx, &params, &filter, out.data()), m_ctx, "surf_svgf_accumulate");
+    return out;
+}
+
+std::vector<F32> WaveFrontRenderer::svgf() {
+    surf_temporal_params params;
+    surf_svgf_params filter;
+    check(surf_temporal_default_params(&params), m_ctx, "surf_temporal_default_params");
+    check(surf_svgf_default_params(&filter), m_ctx, "surf_svgf_default_params");
+    return svgf(params, filter);
+}
+
 void WaveFrontRenderer::resetTemporal() { check(surf_temporal_reset(m_ctx), m_ctx, "surf_temporal_reset"); }
 
 std::vector<U32> WaveFrontRenderer::displayRGBA8() {

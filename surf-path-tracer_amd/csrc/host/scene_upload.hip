@@ -532,6 +532,7 @@ int surf_upload_scene(surf_ctx* c, const surf_scene_desc* d) {
     c->maxBlasDepth = B.maxDepth;
     c->instHost.assign(d->instances, d->instances + d->instance_count);
     c->tpHave = false;                /* another scene: the temporal history starts again */
+    c->svHave = false;                /* ... and the luminance moments with it */
     c->hasScene = true;
     return SURF_OK;
 }

@@ -95,6 +95,25 @@ struct surf_ctx {
     std::vector<float> tpMotionHost;
     hipEvent_t tpEv[2] = {};
     float tpMs = 0.0f;             /* device time of the last k_temporal launch (surf_debug_temporal_time) */
+    /* the variance-guided filter (surf_svgf*, host/svgf.hip) shares the
+     * temporal state above and the denoiser's scratch (dn) and adds: the
+     * luminance moments as a plane pair used in turn (sv[svCur] the stored
+     * one; svHave: it belongs to the stored history -- surf_temporal_accumulate
+     * clears it) and sv[2], two float planes: the variance entering and leaving
+     * the filter.  surf_svgf_image has images of its own beside tpIn: albedo,
+     * previous moments, moments out, the two variances.  Allocated on first
+     * use, kept, freed in surf_destroy. */
+    float4* sv[3] = {};
+    size_t svCap = 0;
+    int svCur = 0;
+    bool svHave = false;
+    float4* svIn[4] = {};
+    size_t svInCap = 0;
+    hipEvent_t svEv[kDenoiseMaxIterations + 3] = {};
+    float svMs[kDenoiseMaxIterations + 2] = {};   /* k_temporal, guides + variance, then the iterations of the last run (surf_debug_svgf_time) */
+    /* the variance kernel takes its 7 x 7 taps from an LDS copy of the tile
+     * (SURF_SVGF_LDS=0: from global memory; MEASUREMENTS "Variance-guided filter") */
+    bool svVarStaged = true;
     /* the instance records as last uploaded (surf_upload_scene, surf_update_instances): their transforms move the history */
     std::vector<surf_gpu_instance> instHost;
     /* one-frame render calls may leave up to a pool of their stream unissued
@@ -235,6 +254,8 @@ int denoisePlanes(surf_ctx* c, uint32_t w, uint32_t h, const float4* acc, const 
 const char* denoiseParamsError(const surf_denoise_params* p);
 /* defined in host/temporal.hip: surf_destroy's part for the temporal state */
 void freeTemporal(surf_ctx* c);
+/* defined in host/svgf.hip: freeTemporal's part for the variance-guided filter's state */
+void freeSvgf(surf_ctx* c);
 
 #define SURF_CHECK(ctx, call)                                                             \
     do {                                                                                  \

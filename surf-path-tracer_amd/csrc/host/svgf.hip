@@ -1,0 +1,363 @@
+/*
+ * svgf.hip -- the variance-guided filter (surf_svgf*, include/surf_hip.h):
+ * parameter checks, the launches of one frame -- k_temporal with the moments
+ * switched on, the guides and the variance estimate, the variance-guided
+ * a-trous iterations -- the moments a frame leaves on the context beside the
+ * temporal state, and the CPU twin.  The arithmetic lives in
+ * device/temporal_kernels.h and device/svgf_kernels.h.
+ */
+#include "host/temporal_host.h"
+
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+
+#include "device/svgf_kernels.h"
+
+namespace {
+
+const char* svgfParamError(const surf_svgf_params* p) {
+    if (!p) return "svgf params is NULL";
+    if (p->iterations < 1 || p->iterations > (uint32_t)kDenoiseMaxIterations) return "iterations outside 1..6";
+    for (float s : {p->sigma_lum, p->sigma_normal, p->sigma_plane})
+        if (!(std::isfinite(s) && s > 0.0f)) return "a sigma is not finite and > 0";
+    if (p->spatial_below == 0) return "spatial_below is 0";
+    if (!(std::isfinite(p->variance_eps) && p->variance_eps > 0.0f)) return "variance_eps is not finite and > 0";
+    return nullptr;
+}
+
+/* the constants of a call, computed in f32 on the host as the header states */
+SvgfConsts svgfConsts(const surf_svgf_params& p) {
+    SvgfConsts k;
+    k.kn = 1.0f / (p.sigma_normal * p.sigma_normal);
+    k.kp = 1.0f / (p.sigma_plane * p.sigma_plane);
+    k.sigmaLum = p.sigma_lum;
+    k.varEps = p.variance_eps;
+    k.spatialBelow = (float)p.spatial_below;
+    return k;
+}
+
+/* k_svgf_variance<STAGED> and k_atrous_var<STAGED> at step s with their dynamic LDS */
+template <class F>
+struct Launch { F fn; size_t lds; };
+auto varianceKernel(bool staged) {
+    return Launch<decltype(&k_svgf_variance<true>)>{staged ? k_svgf_variance<true> : k_svgf_variance<false>, staged ? kSvgfVarLdsBytes : 0};
+}
+auto atrousVarKernel(bool staged, int s) {
+    return Launch<decltype(&k_atrous_var<true>)>{staged ? k_atrous_var<true> : k_atrous_var<false>,
+                                                 staged ? (size_t)3 * sizeof(float4) * (kDenoiseTileW + 4 * s) * (kDenoiseTileH + 4 * s) : 0};
+}
+
+/* the device planes of one frame: the current frame's, the previous frame's
+ * (NULL with K.havePrev 0; pM NULL: no moments stored) and what is written */
+struct SvgfPlanes {
+    const float4 *A, *P, *N, *alb;
+    const uint4* ID;
+    const float4 *pH, *pP;
+    const TemporalGuide* pG;
+    const float4* pM;
+    float4 *blend, *hist, *gP;
+    TemporalGuide* gN;
+    float4* outM;
+    float* var;                  /* 2 * npx floats: the variance entering the filter, then leaving it */
+};
+
+/* All launches of a frame on the context's stream over device planes of a
+ * full w x h frame; *result is the scratch image that holds the output.
+ * Waits for the result. */
+int runSvgf(surf_ctx* c, uint32_t w, uint32_t h, const SvgfPlanes& pl, const TemporalConsts& K, const surf_svgf_params& P,
+            const float4** result) {
+    const size_t npx = (size_t)w * h;
+    int rc = growImages(c, c->dn, 4, c->dnCap, npx);
+    if (rc) return rc;
+    for (auto& e : c->svEv)
+        if (!e) SURF_CHECK(c, hipEventCreate(&e));
+    if ((rc = temporalMotionUpload(c, K))) return rc;
+    const uint32_t demod = P.demodulate ? 1u : 0u;
+    const SvgfConsts S = svgfConsts(P);
+    float4* lvl[2] = {c->dn[0], c->dn[1]};
+    float4* gN = c->dn[2];
+    float4* gP = c->dn[3];
+    const dim3 grid((w + kDenoiseTileW - 1) / kDenoiseTileW, (h + kDenoiseTileH - 1) / kDenoiseTileH);
+    static_assert(kDenoiseTileW == kTemporalTileW && kDenoiseTileH == kTemporalTileH, "one grid for every kernel of the frame");
+    SURF_CHECK(c, hipEventRecord(c->svEv[0], c->stream));
+    hipLaunchKernelGGL(k_temporal<true>, grid, dim3(256), 0, c->stream, pl.A, pl.P, pl.N, pl.ID, pl.pH, pl.pP, pl.pG, (const float*)c->tpMotion, K,
+                       (int)w, (int)h, pl.blend, pl.hist, pl.gP, pl.gN, TemporalMomentPlanes{pl.alb, pl.pM, pl.outM, demod});
+    SURF_CHECK(c, hipGetLastError());
+    SURF_CHECK(c, hipEventRecord(c->svEv[1], c->stream));
+    hipLaunchKernelGGL(k_svgf_guides, dim3((uint32_t)((npx + 255) / 256)), dim3(256), 0, c->stream, pl.P, pl.N, pl.alb, (uint32_t)npx, gN, gP);
+    SURF_CHECK(c, hipGetLastError());
+    const auto variance = varianceKernel(c->svVarStaged);
+    hipLaunchKernelGGL(variance.fn, grid, dim3(256), variance.lds, c->stream, (const float4*)pl.blend, pl.alb, (const float4*)gN, (const float4*)gP,
+                       (const float4*)pl.outM, lvl[0], pl.var, (int)w, (int)h, S, demod);
+    SURF_CHECK(c, hipGetLastError());
+    SURF_CHECK(c, hipEventRecord(c->svEv[2], c->stream));
+    const uint32_t stagedMax = std::min<uint32_t>(c->dnLdsMax, (uint32_t)kDenoiseMaxStagedStep);
+    for (uint32_t i = 0; i < P.iterations; ++i) {
+        const int s = 1 << i;
+        const int last = i + 1 == P.iterations;
+        const auto atrous = atrousVarKernel((uint32_t)s <= stagedMax, s);
+        hipLaunchKernelGGL(atrous.fn, grid, dim3(256), atrous.lds, c->stream, (const float4*)lvl[i & 1], (const float4*)gN, (const float4*)gP, pl.alb,
+                           lvl[(i & 1) ^ 1], pl.var + npx, (int)w, (int)h, s, S, demod, last);
+        SURF_CHECK(c, hipGetLastError());
+        SURF_CHECK(c, hipEventRecord(c->svEv[i + 3], c->stream));
+    }
+    SURF_CHECK(c, hipEventSynchronize(c->svEv[P.iterations + 2]));
+    for (uint32_t k = 0; k < (uint32_t)kDenoiseMaxIterations + 2; ++k) {
+        c->svMs[k] = 0.0f;
+        if (k < P.iterations + 2) (void)hipEventElapsedTime(&c->svMs[k], c->svEv[k], c->svEv[k + 1]);
+    }
+    *result = lvl[P.iterations & 1];
+    return SURF_OK;
+}
+
+/* surf_svgf_accumulate / _copy_device: the context's own accumulator and
+ * cached feature planes against the stored state, which this frame's replaces */
+int svgfContext(surf_ctx* c, const surf_temporal_params* p, const surf_svgf_params* sp, void* dst, hipMemcpyKind kind) {
+    if (!c || !dst) return SURF_ERR_INVALID;
+    if (const char* why = temporalParamError(p)) return fail(c, SURF_ERR_INVALID, std::string("surf_svgf_accumulate: ") + why);
+    if (const char* why = svgfParamError(sp)) return fail(c, SURF_ERR_INVALID, std::string("surf_svgf_accumulate: ") + why);
+    if (c->rows.size() != c->height)
+        return fail(c, SURF_ERR_INVALID, "surf_svgf_accumulate needs a context that owns every row of the frame: a reprojected pixel and "
+                                         "a spatial filter read other rows; assemble the shards' accumulators and feature planes and call "
+                                         "surf_svgf_image");
+    int rc = featurePlanes(c);
+    if (rc) return rc;
+    if ((rc = drainStream(c))) return rc;
+    if ((rc = growImages(c, c->tp, 7, c->tpCap, c->npx))) { c->tpHave = false; return rc; }
+    if ((rc = growImages(c, c->sv, 3, c->svCap, c->npx))) { c->svHave = false; return rc; }
+    const bool have = c->tpHave && c->tpInst.size() == c->instHost.size();
+    const uint32_t nInst = (uint32_t)c->instHost.size();
+    const TemporalConsts K = temporalSetup(*p, have ? &c->tpCam : nullptr, c->instHost.data(), have ? c->tpInst.data() : nullptr, nInst,
+                                           c->tpMotionHost);
+    float4* const* prev = c->tp + 3 * c->tpCur;
+    float4* const* next = c->tp + 3 * (c->tpCur ^ 1);
+    SvgfPlanes pl{};
+    pl.A = c->acc;
+    pl.P = static_cast<const float4*>(c->aov[SURF_AOV_POSITION]);
+    pl.N = static_cast<const float4*>(c->aov[SURF_AOV_NORMAL]);
+    pl.alb = static_cast<const float4*>(c->aov[SURF_AOV_ALBEDO]);
+    pl.ID = static_cast<const uint4*>(c->aov[SURF_AOV_ID]);
+    if (have) {
+        pl.pH = prev[0];
+        pl.pP = prev[1];
+        pl.pG = reinterpret_cast<const TemporalGuide*>(prev[2]);
+        pl.pM = c->svHave ? c->sv[c->svCur] : nullptr;
+    }
+    pl.blend = c->tp[6];
+    pl.hist = next[0];
+    pl.gP = next[1];
+    pl.gN = reinterpret_cast<TemporalGuide*>(next[2]);
+    pl.outM = c->sv[c->svCur ^ 1];
+    pl.var = reinterpret_cast<float*>(c->sv[2]);
+    const float4* res = nullptr;
+    if ((rc = runSvgf(c, c->width, c->height, pl, K, *sp, &res))) return rc;
+    c->tpCur ^= 1;
+    c->tpHave = true;
+    c->tpCam = c->camUbo;
+    c->tpInst = c->instHost;
+    c->svCur ^= 1;
+    c->svHave = true;
+    SURF_CHECK(c, hipMemcpyAsync(dst, res, (size_t)c->npx * sizeof(float4), kind, c->stream));
+    SURF_CHECK(c, hipStreamSynchronize(c->stream));
+    return SURF_OK;
+}
+
+/* the two float planes of variances as the (x, y, 0, 0) image the interface returns */
+void interleaveVariance(const std::vector<float>& var, size_t npx, float* out) {
+    for (size_t q = 0; q < npx; ++q) {
+        out[4 * q] = var[q];
+        out[4 * q + 1] = var[npx + q];
+        out[4 * q + 2] = out[4 * q + 3] = 0.0f;
+    }
+}
+
+/* what surf_svgf_image and its host twin refuse, beside the parameters */
+const char* svgfFrameError(uint32_t w, uint32_t h, const surf_svgf_frame* cur, const surf_svgf_prev* prev, const float* out,
+                           const float* outHist, const float* outMom, const float* outVar) {
+    if (!cur || !outMom || !outVar) return "NULL argument";
+    if (!cur->albedo) return "NULL plane in the current frame";
+    const surf_temporal_frame tc{cur->acc, cur->position, cur->normal, cur->id, cur->instances, cur->instance_count, 0};
+    surf_temporal_prev tq{};
+    if (prev) {
+        tq.history = prev->history; tq.position = prev->position; tq.normal = prev->normal; tq.id = prev->id;
+        tq.instances = prev->instances; tq.instance_count = prev->instance_count;
+    }
+    return temporalFrameError(w, h, &tc, prev ? &tq : nullptr, out, outHist);
+}
+
+}  // namespace
+
+void surfhost::freeSvgf(surf_ctx* c) {
+    for (float4*& p : c->sv) { if (p) (void)hipFree(p); p = nullptr; }
+    for (float4*& p : c->svIn) { if (p) (void)hipFree(p); p = nullptr; }
+    for (auto& e : c->svEv) { if (e) (void)hipEventDestroy(e); e = nullptr; }
+    c->svCap = c->svInCap = 0;
+    c->svHave = false;
+}
+
+extern "C" {
+
+int surf_svgf_default_params(surf_svgf_params* p) {
+    if (!p) return SURF_ERR_INVALID;
+    std::memset(p, 0, sizeof *p);
+    p->iterations = 5;
+    p->sigma_lum = 4.0f;
+    p->sigma_normal = 0.3f;
+    p->sigma_plane = 0.1f;
+    p->demodulate = 1;
+    p->spatial_below = 4;
+    p->variance_eps = 1e-10f;
+    return SURF_OK;
+}
+
+int surf_svgf_accumulate(surf_ctx* c, const surf_temporal_params* p, const surf_svgf_params* sp, float* out) {
+    return svgfContext(c, p, sp, out, hipMemcpyDeviceToHost);
+}
+
+int surf_svgf_copy_device(surf_ctx* c, const surf_temporal_params* p, const surf_svgf_params* sp, void* dst) {
+    return svgfContext(c, p, sp, dst, hipMemcpyDeviceToDevice);
+}
+
+int surf_svgf_moments(surf_ctx* c, float* out) {
+    if (!c || !out) return SURF_ERR_INVALID;
+    if (!(c->tpHave && c->svHave)) return fail(c, SURF_ERR_INVALID, "surf_svgf_moments: no moments stored (call surf_svgf_accumulate first)");
+    SURF_CHECK(c, hipSetDevice(c->device));
+    SURF_CHECK(c, hipMemcpyAsync(out, c->sv[c->svCur], (size_t)c->npx * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
+    SURF_CHECK(c, hipStreamSynchronize(c->stream));
+    return SURF_OK;
+}
+
+int surf_svgf_variance(surf_ctx* c, float* out) {
+    if (!c || !out) return SURF_ERR_INVALID;
+    if (!(c->tpHave && c->svHave)) return fail(c, SURF_ERR_INVALID, "surf_svgf_variance: no variance stored (call surf_svgf_accumulate first)");
+    SURF_CHECK(c, hipSetDevice(c->device));
+    std::vector<float> var(2 * (size_t)c->npx);
+    SURF_CHECK(c, hipMemcpyAsync(var.data(), c->sv[2], var.size() * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    SURF_CHECK(c, hipStreamSynchronize(c->stream));
+    interleaveVariance(var, c->npx, out);
+    return SURF_OK;
+}
+
+int surf_svgf_image(surf_ctx* c, uint32_t w, uint32_t h, const surf_svgf_frame* cur, const surf_svgf_prev* prev, const surf_temporal_params* p,
+                    const surf_svgf_params* sp, float* out, float* outHist, float* outMom, float* outVar) {
+    if (!c) return SURF_ERR_INVALID;
+    if (const char* why = svgfFrameError(w, h, cur, prev, out, outHist, outMom, outVar)) return fail(c, SURF_ERR_INVALID, std::string("surf_svgf_image: ") + why);
+    if (const char* why = temporalParamError(p)) return fail(c, SURF_ERR_INVALID, std::string("surf_svgf_image: ") + why);
+    if (const char* why = svgfParamError(sp)) return fail(c, SURF_ERR_INVALID, std::string("surf_svgf_image: ") + why);
+    SURF_CHECK(c, hipSetDevice(c->device));
+    const size_t npx = (size_t)w * h, bytes = npx * sizeof(float4);
+    int rc = growImages(c, c->tpIn, 9, c->tpInCap, npx);
+    if (rc) return rc;
+    if ((rc = growImages(c, c->svIn, 4, c->svInCap, npx))) return rc;
+    const void* curSrc[4] = {cur->acc, cur->position, cur->normal, cur->id};
+    for (int k = 0; k < 4; ++k) SURF_CHECK(c, hipMemcpyAsync(c->tpIn[k], curSrc[k], bytes, hipMemcpyHostToDevice, c->stream));
+    SURF_CHECK(c, hipMemcpyAsync(c->svIn[0], cur->albedo, bytes, hipMemcpyHostToDevice, c->stream));
+    std::vector<TemporalGuide> guides;
+    if (prev) {
+        packGuides(prev->normal, prev->id, npx, guides);
+        const void* prevSrc[3] = {prev->history, prev->position, guides.data()};
+        for (int k = 0; k < 3; ++k) SURF_CHECK(c, hipMemcpyAsync(c->tpIn[4 + k], prevSrc[k], bytes, hipMemcpyHostToDevice, c->stream));
+        if (prev->moments) SURF_CHECK(c, hipMemcpyAsync(c->svIn[1], prev->moments, bytes, hipMemcpyHostToDevice, c->stream));
+    }
+    const TemporalConsts K = temporalSetup(*p, prev ? &prev->camera : nullptr, cur->instances, prev ? prev->instances : nullptr,
+                                           cur->instance_count, c->tpMotionHost);
+    SvgfPlanes pl{};
+    pl.A = c->tpIn[0];
+    pl.P = c->tpIn[1];
+    pl.N = c->tpIn[2];
+    pl.ID = reinterpret_cast<const uint4*>(c->tpIn[3]);
+    pl.alb = c->svIn[0];
+    if (prev) {
+        pl.pH = c->tpIn[4];
+        pl.pP = c->tpIn[5];
+        pl.pG = reinterpret_cast<const TemporalGuide*>(c->tpIn[6]);
+        pl.pM = prev->moments ? c->svIn[1] : nullptr;
+    }
+    pl.blend = c->tpIn[7];
+    pl.hist = c->tpIn[8];
+    pl.outM = c->svIn[2];
+    pl.var = reinterpret_cast<float*>(c->svIn[3]);
+    const float4* res = nullptr;
+    if ((rc = runSvgf(c, w, h, pl, K, *sp, &res))) return rc;
+    std::vector<float> var(2 * npx);
+    SURF_CHECK(c, hipMemcpyAsync(out, res, bytes, hipMemcpyDeviceToHost, c->stream));
+    SURF_CHECK(c, hipMemcpyAsync(outHist, c->tpIn[8], bytes, hipMemcpyDeviceToHost, c->stream));
+    SURF_CHECK(c, hipMemcpyAsync(outMom, c->svIn[2], bytes, hipMemcpyDeviceToHost, c->stream));
+    SURF_CHECK(c, hipMemcpyAsync(var.data(), c->svIn[3], var.size() * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    SURF_CHECK(c, hipStreamSynchronize(c->stream));
+    interleaveVariance(var, npx, outVar);
+    return SURF_OK;
+}
+
+/* The CPU twin: temporalPixel<true>, svgfVariancePixel, denoisePixelVar and
+ * their companions compiled for the host, on host arrays. */
+int surf_svgf_image_host(uint32_t w, uint32_t h, const surf_svgf_frame* cur, const surf_svgf_prev* prev, const surf_temporal_params* p,
+                         const surf_svgf_params* sp, float* out, float* outHist, float* outMom, float* outVar) {
+    if (const char* why = svgfFrameError(w, h, cur, prev, out, outHist, outMom, outVar)) return fail(nullptr, SURF_ERR_INVALID, std::string("surf_svgf_image_host: ") + why);
+    if (const char* why = temporalParamError(p)) return fail(nullptr, SURF_ERR_INVALID, std::string("surf_svgf_image_host: ") + why);
+    if (const char* why = svgfParamError(sp)) return fail(nullptr, SURF_ERR_INVALID, std::string("surf_svgf_image_host: ") + why);
+    const size_t npx = (size_t)w * h;
+    std::vector<float> motion;
+    const TemporalConsts K = temporalSetup(*p, prev ? &prev->camera : nullptr, cur->instances, prev ? prev->instances : nullptr,
+                                           cur->instance_count, motion);
+    const SvgfConsts S = svgfConsts(*sp);
+    const uint32_t demod = sp->demodulate ? 1u : 0u;
+    std::vector<TemporalGuide> guides;
+    if (prev) packGuides(prev->normal, prev->id, npx, guides);
+    /* the caller's planes need not be 16-byte aligned */
+    auto plane = [npx](const float* src) {
+        std::vector<float4> v(src ? npx : 0);
+        if (src) std::memcpy(v.data(), src, npx * sizeof(float4));
+        return v;
+    };
+    const std::vector<float4> A = plane(cur->acc), Ps = plane(cur->position), Ns = plane(cur->normal), Al = plane(cur->albedo);
+    const std::vector<float4> prevH = plane(prev ? prev->history : nullptr), prevP = plane(prev ? prev->position : nullptr),
+                              prevM = plane(prev ? prev->moments : nullptr);
+    const TemporalFetchPlanes tfetch{prevH.data(), prevP.data(), guides.data(), (int)w, prevM.empty() ? nullptr : prevM.data()};
+    std::vector<float4> R(npx), Hs(npx), M(npx), gN(npx), gP(npx), lvl[2] = {std::vector<float4>(npx), std::vector<float4>(npx)};
+    std::vector<float> var(2 * npx, 0.0f);
+    for (size_t q = 0; q < npx; ++q) {
+        temporalPixel<true>((int)w, (int)h, A[q], Ps[q], Ns[q], cur->id[4 * q], K, motion.data(), tfetch, R[q], Hs[q], denoiseDen(Al[q], demod), M[q]);
+        gN[q] = make_float4(Ns[q].x, Ns[q].y, Ns[q].z, Al[q].w != 0.0f ? 1.0f : 0.0f);
+        gP[q] = make_float4(Ps[q].x, Ps[q].y, Ps[q].z, 0.0f);
+    }
+    const SvgfFetchPlanes vfetch{gN.data(), gP.data(), M.data(), (int)w};
+    for (int y = 0; y < (int)h; ++y)
+        for (int x = 0; x < (int)w; ++x) {
+            const size_t q = (size_t)y * w + x;
+            const float v = gN[q].w != 0.0f ? svgfVariancePixel(x, y, (int)w, (int)h, S, M[q], gN[q], gP[q], vfetch) : 0.0f;
+            lvl[0][q] = svgfLevel0(R[q], Al[q], demod, v);
+            var[q] = lvl[0][q].w;
+        }
+    for (uint32_t i = 0; i < sp->iterations; ++i) {
+        const int s = 1 << i;
+        const bool last = i + 1 == sp->iterations;
+        const std::vector<float4>& I = lvl[i & 1];
+        std::vector<float4>& O = lvl[(i & 1) ^ 1];
+        const DenoiseFetchPlanes fetch{I.data(), gN.data(), gP.data(), (int)w};
+        for (int y = 0; y < (int)h; ++y)
+            for (int x = 0; x < (int)w; ++x) {
+                const size_t q = (size_t)y * w + x;
+                const bool valid = gN[q].w != 0.0f;
+                float4 f = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+                if (valid) f = denoisePixelVar(x, y, (int)w, (int)h, s, S, I[q], gN[q], gP[q], fetch);
+                float v1;
+                O[q] = svgfStore(valid, I[q], f, last, Al[q], demod, v1);
+                if (last) var[npx + q] = v1;
+            }
+    }
+    std::memcpy(out, lvl[sp->iterations & 1].data(), npx * sizeof(float4));
+    std::memcpy(outHist, Hs.data(), npx * sizeof(float4));
+    std::memcpy(outMom, M.data(), npx * sizeof(float4));
+    interleaveVariance(var, npx, outVar);
+    return SURF_OK;
+}
+
+int surf_debug_svgf_time(surf_ctx* c, float* kernel_ms, uint32_t count) {
+    if (!c || !kernel_ms) return SURF_ERR_INVALID;
+    for (uint32_t k = 0; k < count; ++k) kernel_ms[k] = k < (uint32_t)kDenoiseMaxIterations + 2 ? c->svMs[k] : 0.0f;
+    return SURF_OK;
+}
+
+}  // extern "C"

@@ -10,11 +10,9 @@
 #include <cmath>
 #include <cstring>
 
-#include "device/temporal_kernels.h"
+#include "host/temporal_host.h"
 
-namespace {
-
-const char* temporalParamError(const surf_temporal_params* p) {
+const char* surfhost::temporalParamError(const surf_temporal_params* p) {
     if (!p) return "params is NULL";
     if (!(p->alpha_min >= 0.0f && p->alpha_min <= 1.0f)) return "alpha_min outside [0, 1]";
     if (p->max_history == 0) return "max_history is 0";
@@ -28,8 +26,8 @@ const char* temporalParamError(const surf_temporal_params* p) {
 /* The constants of a frame, in f32 on the host as the header states, and the
  * motion table (kTemporalMotionWords floats per instance).  cam, prevInst
  * NULL: no previous frame. */
-TemporalConsts temporalSetup(const surf_temporal_params& p, const surf_camera_ubo* cam, const surf_gpu_instance* curInst,
-                             const surf_gpu_instance* prevInst, uint32_t nInst, std::vector<float>& motion) {
+TemporalConsts surfhost::temporalSetup(const surf_temporal_params& p, const surf_camera_ubo* cam, const surf_gpu_instance* curInst,
+                                       const surf_gpu_instance* prevInst, uint32_t nInst, std::vector<float>& motion) {
     TemporalConsts K{};
     K.alphaMin = p.alpha_min;
     K.maxHistory = (float)p.max_history;
@@ -66,13 +64,8 @@ TemporalConsts temporalSetup(const surf_temporal_params& p, const surf_camera_ub
     return K;
 }
 
-/* One launch on the context's stream over device planes of a full w x h
- * frame; pH, pP, pG NULL with K.havePrev 0.  Waits for the result. */
-int runTemporal(surf_ctx* c, uint32_t w, uint32_t h, const float4* A, const float4* P, const float4* N, const uint4* ID,
-                const float4* pH, const float4* pP, const TemporalGuide* pG, const TemporalConsts& K, float4* out, float4* hist,
-                float4* gP, TemporalGuide* gN) {
-    for (auto& e : c->tpEv)
-        if (!e) SURF_CHECK(c, hipEventCreate(&e));
+/* the motion table of c->tpMotionHost on the device (c->tpMotion), queued on the context's stream */
+int surfhost::temporalMotionUpload(surf_ctx* c, const TemporalConsts& K) {
     if (K.nInst > c->tpMotionCap) {
         if (c->tpMotion) (void)hipFree(c->tpMotion);
         c->tpMotion = nullptr;
@@ -88,10 +81,23 @@ int runTemporal(surf_ctx* c, uint32_t w, uint32_t h, const float4* A, const floa
     if (K.nInst)
         SURF_CHECK(c, hipMemcpyAsync(c->tpMotion, c->tpMotionHost.data(), c->tpMotionHost.size() * sizeof(float), hipMemcpyHostToDevice,
                                      c->stream));
+    return SURF_OK;
+}
+
+namespace {
+
+/* One launch on the context's stream over device planes of a full w x h
+ * frame; pH, pP, pG NULL with K.havePrev 0.  Waits for the result. */
+int runTemporal(surf_ctx* c, uint32_t w, uint32_t h, const float4* A, const float4* P, const float4* N, const uint4* ID,
+                const float4* pH, const float4* pP, const TemporalGuide* pG, const TemporalConsts& K, float4* out, float4* hist,
+                float4* gP, TemporalGuide* gN) {
+    for (auto& e : c->tpEv)
+        if (!e) SURF_CHECK(c, hipEventCreate(&e));
+    if (int rc = temporalMotionUpload(c, K)) return rc;
     const dim3 grid((w + kTemporalTileW - 1) / kTemporalTileW, (h + kTemporalTileH - 1) / kTemporalTileH);
     SURF_CHECK(c, hipEventRecord(c->tpEv[0], c->stream));
-    hipLaunchKernelGGL(k_temporal, grid, dim3(256), 0, c->stream, A, P, N, ID, pH, pP, pG, (const float*)c->tpMotion, K, (int)w, (int)h, out,
-                       hist, gP, gN);
+    hipLaunchKernelGGL(k_temporal<false>, grid, dim3(256), 0, c->stream, A, P, N, ID, pH, pP, pG, (const float*)c->tpMotion, K, (int)w, (int)h,
+                       out, hist, gP, gN, TemporalMomentPlanes{});
     SURF_CHECK(c, hipGetLastError());
     SURF_CHECK(c, hipEventRecord(c->tpEv[1], c->stream));
     SURF_CHECK(c, hipEventSynchronize(c->tpEv[1]));
@@ -131,6 +137,7 @@ int temporalContext(surf_ctx* c, const surf_temporal_params* p, const surf_denoi
     c->tpHave = true;
     c->tpCam = c->camUbo;
     c->tpInst = c->instHost;
+    c->svHave = false;                /* this history carries no moments: the next surf_svgf_accumulate estimates spatially */
     const float4* res = c->tp[6];
     if (spatial) {
         rc = denoisePlanes(c, c->width, c->height, c->tp[6], pos, nrm, static_cast<const float4*>(c->aov[SURF_AOV_ALBEDO]), *spatial, &res);
@@ -141,8 +148,10 @@ int temporalContext(surf_ctx* c, const surf_temporal_params* p, const surf_denoi
     return SURF_OK;
 }
 
+}  // namespace
+
 /* what surf_temporal_image and its host twin refuse, beside the parameters */
-const char* temporalFrameError(uint32_t w, uint32_t h, const surf_temporal_frame* cur, const surf_temporal_prev* prev, const float* out,
+const char* surfhost::temporalFrameError(uint32_t w, uint32_t h, const surf_temporal_frame* cur, const surf_temporal_prev* prev, const float* out,
                                const float* outHist) {
     if (!cur || !out || !outHist) return "NULL argument";
     if (!cur->acc || !cur->position || !cur->normal || !cur->id || (cur->instance_count && !cur->instances)) return "NULL plane in the current frame";
@@ -154,7 +163,7 @@ const char* temporalFrameError(uint32_t w, uint32_t h, const surf_temporal_frame
 }
 
 /* the previous frame's normal and id planes as the guide a tap reads */
-void packGuides(const float* normal, const uint32_t* id, size_t npx, std::vector<TemporalGuide>& g) {
+void surfhost::packGuides(const float* normal, const uint32_t* id, size_t npx, std::vector<TemporalGuide>& g) {
     g.resize(npx);
     for (size_t q = 0; q < npx; ++q) {
         g[q].x = normal[4 * q];
@@ -163,8 +172,6 @@ void packGuides(const float* normal, const uint32_t* id, size_t npx, std::vector
         g[q].id = id[4 * q];
     }
 }
-
-}  // namespace
 
 void surfhost::freeTemporal(surf_ctx* c) {
     for (float4*& p : c->tp) { if (p) (void)hipFree(p); p = nullptr; }
@@ -175,6 +182,7 @@ void surfhost::freeTemporal(surf_ctx* c) {
     c->tpCap = c->tpInCap = 0;
     c->tpMotionCap = 0;
     c->tpHave = false;
+    freeSvgf(c);
 }
 
 extern "C" {
@@ -202,6 +210,7 @@ int surf_temporal_copy_device(surf_ctx* c, const surf_temporal_params* p, const 
 int surf_temporal_reset(surf_ctx* c) {
     if (!c) return SURF_ERR_INVALID;
     c->tpHave = false;
+    c->svHave = false;
     return SURF_OK;
 }
 
@@ -262,7 +271,7 @@ int surf_temporal_image_host(uint32_t w, uint32_t h, const surf_temporal_frame* 
         std::memcpy(prevH.data(), prev->history, npx * sizeof(float4));
         std::memcpy(prevP.data(), prev->position, npx * sizeof(float4));
     }
-    const TemporalFetchPlanes fetch{prevH.data(), prevP.data(), guides.data(), (int)w};
+    const TemporalFetchPlanes fetch{prevH.data(), prevP.data(), guides.data(), (int)w, nullptr};
     float4* O = reinterpret_cast<float4*>(out);
     float4* Hs = reinterpret_cast<float4*>(outHist);
     for (size_t q = 0; q < npx; ++q) {
@@ -270,7 +279,8 @@ int surf_temporal_image_host(uint32_t w, uint32_t h, const surf_temporal_frame* 
         std::memcpy(&a, A + q, sizeof a);
         std::memcpy(&ps, P + q, sizeof ps);
         std::memcpy(&nr, N + q, sizeof nr);
-        temporalPixel((int)w, (int)h, a, ps, nr, cur->id[4 * q], K, motion.data(), fetch, o, hi);
+        float4 unused;
+        temporalPixel<false>((int)w, (int)h, a, ps, nr, cur->id[4 * q], K, motion.data(), fetch, o, hi, mk3(1.0f, 1.0f, 1.0f), unused);
         std::memcpy(O + q, &o, sizeof o);
         std::memcpy(Hs + q, &hi, sizeof hi);
     }

@@ -1130,6 +1130,7 @@ int createCtx(int dev, uint32_t w, uint32_t h, std::vector<uint32_t> rows, surf_
     if (const char* e = std::getenv("SURF_REGEN_FIRST")) c->regenFirst = e[0] == '1';
     if (const char* e = std::getenv("SURF_PIPELINE")) c->pipeline = e[0] != '0';
     if (const char* e = std::getenv("SURF_DENOISE_LDS")) c->dnLdsMax = (uint32_t)std::max(0, std::atoi(e));
+    if (const char* e = std::getenv("SURF_SVGF_LDS")) c->svVarStaged = std::atoi(e) != 0;
     c->width = w;
     c->height = h;
     c->rows = std::move(rows);

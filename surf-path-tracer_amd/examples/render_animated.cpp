@@ -11,7 +11,10 @@
  * over sample count), PREFIX_temporal.pfm (the blend),
  * PREFIX_temporal_denoised.pfm (the blend through the spatial filter) and
  * PREFIX_temporal_denoised.png, that image as the application would present
- * it (surf_pack_rgba8 with the display gamma).
+ * it (surf_pack_rgba8 with the display gamma); and PREFIX_svgf.pfm, the last
+ * frame once more through the variance-guided filter (surf_svgf_accumulate)
+ * on the state the loop left: the blend's history, no moments yet, so the
+ * variance is the spatial estimate.
  */
 #include "surf/surf_host.hpp"
 #include "indoor_scene.hpp"
@@ -67,6 +70,7 @@ int main(int argc, char** argv) {
             std::fprintf(stderr, "render_animated: %s\n", surf_last_error(renderer.handle()));
             return 1;
         }
+        const std::vector<F32> guided = renderer.svgf();  /* after the history was read: the call stores its own */
         std::vector<U32> rgba8((size_t)W * H);
         if (surf_pack_rgba8(clean.data(), W * H, 1.0f, 1, rgba8.data()) != SURF_OK) {
             std::fprintf(stderr, "render_animated: surf_pack_rgba8 failed\n");
@@ -76,6 +80,10 @@ int main(int argc, char** argv) {
                                       prefix + "_temporal_denoised.png"};
         const int rc[4] = {surf_write_pfm(paths[0].c_str(), W, H, noisy.data()), surf_write_pfm(paths[1].c_str(), W, H, blend.data()),
                            surf_write_pfm(paths[2].c_str(), W, H, clean.data()), surf_write_png(paths[3].c_str(), W, H, rgba8.data())};
+        if (surf_write_pfm((prefix + "_svgf.pfm").c_str(), W, H, guided.data()) != SURF_OK) {
+            std::fprintf(stderr, "cannot write %s_svgf.pfm\n", prefix.c_str());
+            return 1;
+        }
         for (int k = 0; k < 4; ++k)
             if (rc[k] != SURF_OK) { std::fprintf(stderr, "cannot write %s\n", paths[k].c_str()); return 1; }
         std::printf("{\"width\": %u, \"height\": %u, \"spp\": %d, \"frames\": %d}\n", W, H, spp, frames);

@@ -15,6 +15,7 @@ Mirrors the reference interface for the hot path:
     .aov()                     first-hit feature buffers (no reference counterpart)
     .denoise()                 edge-avoiding a-trous filter on them (no reference counterpart)
     .temporal()                temporal accumulation with reprojection across cleared frames (no reference counterpart)
+    .svgf()                    the same with luminance moments, their variance guiding the a-trous filter (no reference counterpart)
 """
 from __future__ import annotations
 
@@ -101,6 +102,23 @@ class TemporalPrev(C.Structure):
     _fields_ = [("history", C.c_void_p), ("position", C.c_void_p), ("normal", C.c_void_p), ("id", C.c_void_p),
                 ("instances", C.c_void_p), ("instance_count", C.c_uint32), ("_pad", C.c_uint32), ("camera", CameraUBO)]
 
+
+class SvgfParams(C.Structure):
+    """surf_svgf_params (include/surf_hip.h gives the arithmetic)."""
+    _fields_ = [("iterations", C.c_uint32), ("sigma_lum", C.c_float), ("sigma_normal", C.c_float), ("sigma_plane", C.c_float),
+                ("demodulate", C.c_uint32), ("spatial_below", C.c_uint32), ("variance_eps", C.c_float), ("_pad", C.c_uint32)]
+
+
+class SvgfFrame(C.Structure):
+    """surf_svgf_frame: surf_temporal_frame plus the albedo plane."""
+    _fields_ = TemporalFrame._fields_ + [("albedo", C.c_void_p)]
+
+
+class SvgfPrev(C.Structure):
+    """surf_svgf_prev: surf_temporal_prev plus the moments plane (None: no moments stored)."""
+    _fields_ = TemporalPrev._fields_ + [("moments", C.c_void_p)]
+
+
 _lib = None
 
 # Byte sizes of the reference records (include/surf_hip.h static_asserts).
@@ -167,6 +185,15 @@ def load() -> C.CDLL:
         "surf_temporal_image": ([P, U32, U32, C.POINTER(TemporalFrame), C.POINTER(TemporalPrev), C.POINTER(TemporalParams), P, P], I32),
         "surf_temporal_image_host": ([U32, U32, C.POINTER(TemporalFrame), C.POINTER(TemporalPrev), C.POINTER(TemporalParams), P, P], I32),
         "surf_debug_temporal_time": ([P, C.POINTER(F)], I32),
+        "surf_svgf_default_params": ([C.POINTER(SvgfParams)], I32),
+        "surf_svgf_accumulate": ([P, C.POINTER(TemporalParams), C.POINTER(SvgfParams), P], I32),
+        "surf_svgf_copy_device": ([P, C.POINTER(TemporalParams), C.POINTER(SvgfParams), P], I32),
+        "surf_svgf_moments": ([P, P], I32), "surf_svgf_variance": ([P, P], I32),
+        "surf_svgf_image": ([P, U32, U32, C.POINTER(SvgfFrame), C.POINTER(SvgfPrev), C.POINTER(TemporalParams), C.POINTER(SvgfParams),
+                             P, P, P, P], I32),
+        "surf_svgf_image_host": ([U32, U32, C.POINTER(SvgfFrame), C.POINTER(SvgfPrev), C.POINTER(TemporalParams), C.POINTER(SvgfParams),
+                                  P, P, P, P], I32),
+        "surf_debug_svgf_time": ([P, C.POINTER(F), U32], I32),
         "surf_mesh_data": ([P, C.POINTER(P), C.POINTER(P), C.POINTER(U32)], I32),
         "surf_mesh_destroy": ([P], None),
         "surf_ref_sinf": ([F], F), "surf_ref_cosf": ([F], F), "surf_ref_expf": ([F], F),
@@ -445,6 +472,65 @@ def temporal_image_host(cur, prev, **params):
     _check(load().surf_temporal_image_host(w, h, C.byref(f), C.byref(q) if q is not None else None, C.byref(p), _ptr(out), _ptr(hist)),
            "surf_temporal_image_host")
     return out, hist
+
+
+_TEMPORAL_FIELDS = ("alpha_min", "max_history", "normal_min", "plane_tol", "snap", "min_weight")
+_SVGF_FIELDS = ("iterations", "sigma_lum", "sigma_normal", "sigma_plane", "demodulate", "spatial_below", "variance_eps")
+
+
+def svgf_params(**params) -> SvgfParams:
+    """surf_svgf_default_params (5 iterations, sigma_lum 4.0, sigma_normal 0.3,
+    sigma_plane 0.1, demodulate 1, spatial_below 4, variance_eps 1e-10) with the
+    given fields replaced."""
+    p = SvgfParams()
+    _check(load().surf_svgf_default_params(C.byref(p)), "surf_svgf_default_params")
+    for k, v in params.items():
+        if k not in _SVGF_FIELDS:
+            raise TypeError(f"unknown svgf parameter {k!r}")
+        setattr(p, k, int(v) if k in ("iterations", "demodulate", "spatial_below") else float(v))
+    return p
+
+
+def _svgf_split(params):
+    """One keyword set -> (TemporalParams, SvgfParams): the temporal accumulation's names and the filter's do not overlap."""
+    unknown = [k for k in params if k not in _TEMPORAL_FIELDS + _SVGF_FIELDS]
+    if unknown:
+        raise TypeError(f"unknown svgf parameter {unknown[0]!r}")
+    return (temporal_params(**{k: v for k, v in params.items() if k in _TEMPORAL_FIELDS}),
+            svgf_params(**{k: v for k, v in params.items() if k in _SVGF_FIELDS}))
+
+
+def _svgf_frames(cur, prev):
+    """(w, h, SvgfFrame, SvgfPrev or None, the arrays they point into): _temporal_frames' dicts,
+    cur with 'albedo' ((H, W, 4) float32) and prev with 'moments' (None or absent: no moments stored)."""
+    w, h, f, q, keep = _temporal_frames(cur, prev)
+    alb = np.ascontiguousarray(cur["albedo"], dtype=np.float32)
+    if alb.shape != (h, w, 4):
+        raise ValueError(f"albedo plane {alb.shape} is not ({h}, {w}, 4)")
+    sf = SvgfFrame(*[getattr(f, k) for k, _ in TemporalFrame._fields_], _ptr(alb))
+    keep.append(alb)
+    sq = None
+    if q is not None:
+        mom = prev.get("moments")
+        if mom is not None:
+            mom = np.ascontiguousarray(mom, dtype=np.float32)
+            if mom.shape != (h, w, 4):
+                raise ValueError(f"moments plane {mom.shape} is not ({h}, {w}, 4)")
+            keep.append(mom)
+        sq = SvgfPrev(*[getattr(q, k) for k, _ in TemporalPrev._fields_], _ptr(mom) if mom is not None else None)
+    return w, h, sf, sq, keep
+
+
+def svgf_image_host(cur, prev, **params):
+    """The CPU twin of Renderer.svgf_image (surf_svgf_image_host): the same per-pixel
+    functions compiled for the host, bit-identical; no device.  Returns (out,
+    history, moments, variance), each (H, W, 4) float32."""
+    p, sp = _svgf_split(params)
+    w, h, f, q, _keep = _svgf_frames(cur, prev)
+    res = [np.zeros((h, w, 4), np.float32) for _ in range(4)]
+    _check(load().surf_svgf_image_host(w, h, C.byref(f), C.byref(q) if q is not None else None, C.byref(p), C.byref(sp),
+                                       *[_ptr(a) for a in res]), "surf_svgf_image_host")
+    return tuple(res)
 
 
 def obj_load(path: str, threads: int = 0) -> tuple[np.ndarray, np.ndarray]:
@@ -732,6 +818,51 @@ class Renderer:
         ms = C.c_float()
         _check(load().surf_debug_temporal_time(self._h, C.byref(ms)), "surf_debug_temporal_time", self._h)
         return float(ms.value)
+
+    def svgf(self, **params) -> np.ndarray:
+        """One frame through the variance-guided filter (surf_svgf_accumulate): the
+        loop and the stored state are temporal()'s -- the two may be mixed -- with
+        the luminance moments carried along, their variance setting the a-trous
+        filter's colour width per pixel.  params: temporal_params' and
+        svgf_params' names together.  (H, W, 4) float32 with w = 1.  Raises
+        SURF_ERR_INVALID on a row shard (see svgf_image)."""
+        p, sp = _svgf_split(params)
+        out = np.zeros((self.height, self.width, 4), dtype=np.float32)
+        _check(load().surf_svgf_accumulate(self._h, C.byref(p), C.byref(sp), _ptr(out)), "surf_svgf_accumulate", self._h)
+        return out
+
+    def svgf_moments(self) -> np.ndarray:
+        """(mu1, mu2, m, 0) of the stored moments (surf_svgf_moments); raises when none are stored."""
+        out = np.zeros((self.height, self.width, 4), dtype=np.float32)
+        _check(load().surf_svgf_moments(self._h, _ptr(out)), "surf_svgf_moments", self._h)
+        return out
+
+    def svgf_variance(self) -> np.ndarray:
+        """Of the last svgf(): x the variance entering the filter, y leaving it (surf_svgf_variance)."""
+        out = np.zeros((self.height, self.width, 4), dtype=np.float32)
+        _check(load().surf_svgf_variance(self._h, _ptr(out)), "surf_svgf_variance", self._h)
+        return out
+
+    def svgf_image(self, cur, prev, **params):
+        """The same on host planes of any two full frames (surf_svgf_image; cur and
+        prev as _svgf_frames describes them).  Returns (out, history, moments, variance)."""
+        p, sp = _svgf_split(params)
+        w, h, f, q, _keep = _svgf_frames(cur, prev)
+        res = [np.zeros((h, w, 4), np.float32) for _ in range(4)]
+        _check(load().surf_svgf_image(self._h, w, h, C.byref(f), C.byref(q) if q is not None else None, C.byref(p), C.byref(sp),
+                                      *[_ptr(a) for a in res]), "surf_svgf_image", self._h)
+        return tuple(res)
+
+    def copy_svgf_to(self, device_ptr: int, **params):
+        p, sp = _svgf_split(params)
+        _check(load().surf_svgf_copy_device(self._h, C.byref(p), C.byref(sp), C.c_void_p(device_ptr)), "surf_svgf_copy_device", self._h)
+
+    def debug_svgf_time(self) -> list:
+        """Device milliseconds of the last svgf run's kernels (surf_debug_svgf_time):
+        k_temporal, the guides and the variance estimate, then each iteration."""
+        ms = (C.c_float * 8)()
+        _check(load().surf_debug_svgf_time(self._h, ms, 8), "surf_debug_svgf_time", self._h)
+        return [float(v) for v in ms]
 
     def copy_accumulator_to(self, device_ptr: int):
         _check(load().surf_copy_accumulator_device(self._h, C.c_void_p(device_ptr)), "surf_copy_accumulator_device", self._h)
