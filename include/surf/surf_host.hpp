@@ -360,6 +360,8 @@ public:
     /* the same loop through the variance-guided filter (surf_svgf_accumulate): it shares temporal()'s
      * stored state, the two may be mixed.  The form without arguments takes both sets of default parameters. */
     std::vector<F32> svgf(const surf_temporal_params& params, const surf_svgf_params& filter);
+    /* ... with the firefly clamp and / or the filtered-history feedback (surf_svgf_accumulate_ex; all zero: the form above) */
+    std::vector<F32> svgf(const surf_temporal_params& params, const surf_svgf_params& filter, const surf_svgf_ext& ext);
     std::vector<F32> svgf();
     /* clearAccumulator() for that loop: the next render() goes on with the sample indices after
      * those already rendered instead of repeating the cleared frame's sample stream (a plain

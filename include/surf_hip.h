@@ -390,7 +390,8 @@ int surf_debug_aov_time(surf_ctx* ctx, float* kernel_ms);
  *
  * Known limit: the guides are the first hit of the sharp centre ray.  What is
  * seen THROUGH the lens blur or in a mirror has no guide edges, only the
- * colour term protects it; fireflies survive as well.
+ * colour term protects it; fireflies survive as well (surf_firefly_image
+ * below clamps them in the accumulator beforehand).
  *
  * One launch per iteration (the last fuses the remodulation) on a 32 x 8
  * pixel tile per 256-thread block, in two variants with identical bits: taps
@@ -519,8 +520,8 @@ typedef struct {
 int surf_temporal_default_params(surf_temporal_params* params);
 /* One frame of the loop above: the context's accumulator and (cached) feature
  * planes blended with the state the previous call stored, to a host buffer of
- * width*height*4 floats; then this frame's history (always the unfiltered
- * blend), copies of its guides, its camera and its instance records are
+ * width*height*4 floats; then this frame's history (the unfiltered blend,
+ * whatever `spatial` is), copies of its guides, its camera and its instance records are
  * stored on the context for the next call.  With `spatial` non-NULL the
  * returned image is surf_denoise's filter applied to the blend as the
  * accumulator (w = 1) with this frame's planes; NULL: the blend itself.
@@ -645,10 +646,12 @@ int surf_debug_temporal_time(surf_ctx* ctx, float* kernel_ms);
  *    and I_{i+1}(p) = (sum / sumW, sumV / (sumW*sumW)).
  *    Output: (I_n.rgb * den, 1) for a valid pixel, (I_n.rgb, 1) otherwise.
  *
- * Not done: the paper feeds the first filtered iteration back into the
- * history; here the history stays the unfiltered blend.  No firefly clamp:
- * one very bright sample in a short history means a large variance and a
- * wide filter around it.  The guides' limits are the denoiser's.
+ * Off by default, see "extensions" below: the paper feeds the first filtered
+ * iteration back into the history -- here the history stays the unfiltered
+ * blend unless surf_svgf_ext.feedback asks for it; and without the firefly
+ * clamp (surf_svgf_ext.firefly_scale) one very bright sample in a short
+ * history means a large variance and a wide filter around it.  The guides'
+ * limits are the denoiser's.
  *
  * Launches per frame, 256 threads on a 32 x 8 pixel tile each: k_temporal's
  * moments instantiation (a fourth 16-byte load per used tap), the packed
@@ -673,8 +676,8 @@ int surf_svgf_default_params(surf_svgf_params* params);
 /* One frame of the loop, as surf_temporal_accumulate: the context's
  * accumulator and (cached) feature planes against the stored state, the
  * filtered image to a host buffer of width*height*4 floats.  It shares the
- * stored temporal state with surf_temporal_accumulate -- history (always the
- * unfiltered blend), guide copies, camera, instance records, with the same
+ * stored temporal state with surf_temporal_accumulate -- history (the
+ * unfiltered blend; surf_svgf_accumulate_ex can store the filtered one), guide copies, camera, instance records, with the same
  * lifetime -- and adds the moments.  The two calls may be mixed:
  * surf_temporal_accumulate leaves the stored moments marked absent, so the
  * next surf_svgf_accumulate sees m = 0 everywhere and estimates spatially
@@ -733,6 +736,82 @@ int surf_svgf_image_host(uint32_t w, uint32_t h, const surf_svgf_frame* cur, con
  * this context: [0] k_temporal, [1] the guides and the variance estimate,
  * [2 + i] iteration i; entries past the run's iterations (and past 8) are 0. */
 int surf_debug_svgf_time(surf_ctx* ctx, float* kernel_ms, uint32_t count);
+
+/* ---- variance-guided filter, extensions: firefly clamp and filtered-history feedback ----
+ * Two optional stages of the filter above, both off by default: with ext NULL
+ * or all zero every _ex call below IS its namesake without _ex, bit for bit --
+ * the image, the history, the moments, the variances and the stored state.
+ * The arithmetic is part of the interface, as above (f32, uncontracted, IEEE
+ * /, in exactly this order).
+ *
+ * Stage 0, the firefly clamp, runs when firefly_scale > 0, before step A.  At
+ * 1 sample per pixel a few pixels per thousand carry a sample tens to
+ * thousands of times their converged value; one sets a huge variance, so a
+ * wide filter around it, and stays in the history for max_history frames.
+ * For every pixel p of the full frame, with valid, inv, c and den the
+ * denoiser's Prepare with this call's demodulate:
+ *   l = lum(c / den), the quotients first.
+ *   From mx = 0, cnt = 0 the 8 neighbours q = (x + dx, y + dy), dy = -1..1 the
+ *   outer loop, dx = -1..1 the inner, the centre skipped; a q that is inside
+ *   the frame, valid and has A(q).w > 0 is used:
+ *     cnt = cnt + 1     mx = l_q > mx ? l_q : mx
+ *   lim = firefly_scale * mx
+ *   p valid, A.w > 0, cnt > 0 and l > lim:  f = lim / l,  c'_k = c_k * f
+ *   otherwise:                              c' = c      (a NaN l fails the comparison and stays)
+ *   A'(p) = A.w > 0 ? (c', 1) : (0, 0, 0, 0)
+ * Steps A - C then read A' wherever they read A (c' * (1.0f / 1.0f) is exact).
+ * Known bias: the clamp removes energy -- MEASUREMENTS "Firefly clamp and
+ * feedback" gives the fraction -- and a lone lit pixel among black usable
+ * neighbours (mx = 0) is clamped to black.
+ *
+ * Feedback, when feedback == 1: after iteration 0 of step C the stored and
+ * returned history of a valid pixel becomes (I_1.rgb * den, n'), n' unchanged;
+ * an invalid pixel keeps (r, n').  Moments, variances and the returned image
+ * are defined exactly as above; their values change from the second frame on
+ * only because the history did.  surf_temporal_history returns the fed-back
+ * history.
+ *
+ * Launches: k_firefly, one launch of 256 threads per 32 x 8 tile before
+ * k_temporal -- every thread loads its pixel's accumulator and albedo and
+ * puts l (or a sentinel for "not usable") in a 34 x 10 tile of floats in LDS,
+ * 1 360 bytes, the first 84 threads also one texel each of the halo of 1,
+ * and the 8 taps come from there; 48 bytes of memory traffic per pixel, one
+ * variant, no knob.  Feedback launches nothing more: iteration 0 runs an
+ * instantiation of its kernel that also stores the history. */
+typedef struct {
+    float    firefly_scale;   /* 0: off; else finite and >= 1 */
+    uint32_t feedback;        /* 0 / 1 */
+    uint32_t _pad[2];
+} surf_svgf_ext;
+/* all zero: the filter as it is without extensions */
+int surf_svgf_default_ext(surf_svgf_ext* ext);
+/* surf_svgf_accumulate, _copy_device, _image and _image_host with the
+ * extensions; ext may be NULL.  Status codes as theirs; SURF_ERR_INVALID also
+ * for a firefly_scale that is neither 0 nor finite and >= 1, and for feedback
+ * > 1.  The stored temporal state is the one surf_temporal_accumulate and
+ * surf_svgf_accumulate share, and the three calls may be mixed: whichever
+ * runs next reads the history the last one stored, filtered or not. */
+int surf_svgf_accumulate_ex(surf_ctx* ctx, const surf_temporal_params* params, const surf_svgf_params* svgf, const surf_svgf_ext* ext,
+                            float* out_rgba);
+int surf_svgf_copy_device_ex(surf_ctx* ctx, const surf_temporal_params* params, const surf_svgf_params* svgf, const surf_svgf_ext* ext,
+                             void* dst_device);
+int surf_svgf_image_ex(surf_ctx* ctx, uint32_t w, uint32_t h, const surf_svgf_frame* cur, const surf_svgf_prev* prev,
+                       const surf_temporal_params* params, const surf_svgf_params* svgf, const surf_svgf_ext* ext, float* out_rgba,
+                       float* out_history, float* out_moments, float* out_variance);
+int surf_svgf_image_host_ex(uint32_t w, uint32_t h, const surf_svgf_frame* cur, const surf_svgf_prev* prev,
+                            const surf_temporal_params* params, const surf_svgf_params* svgf, const surf_svgf_ext* ext, float* out_rgba,
+                            float* out_history, float* out_moments, float* out_variance);
+/* The clamp alone on host planes of a full frame (w*h*4 floats each): out_acc
+ * = A' as stage 0 defines it, e.g. to put in front of surf_denoise_image,
+ * whose fixed-sigma filter has the same hole.  Needs no scene on the context.
+ * SURF_ERR_INVALID for a NULL argument, w or h of 0, and a scale that is not
+ * finite and >= 1 (0 included: there is nothing to switch off here). */
+int surf_firefly_image(surf_ctx* ctx, uint32_t w, uint32_t h, const float* acc, const float* albedo, uint32_t demodulate, float scale,
+                       float* out_acc);
+/* The CPU twin: the same per-pixel function compiled for the host.  Bit-identical to surf_firefly_image. */
+int surf_firefly_image_host(uint32_t w, uint32_t h, const float* acc, const float* albedo, uint32_t demodulate, float scale, float* out_acc);
+/* Diagnostics: device time (HIP events) of the last k_firefly launch on this context, 0 before the first. */
+int surf_debug_firefly_time(surf_ctx* ctx, float* kernel_ms);
 
 /* ---- traversal entry points (kernel-level parity tests) ----
  * n world-space rays, o/d 3 floats each.  closest: depth starts at 1e30;

@@ -4,7 +4,10 @@
  * temporal accumulation to the a-trous filter.  The luminance moments ride
  * k_temporal<true> (temporal_kernels.h); here are the per-pixel variance
  * estimate and the a-trous level whose colour edge-stopping width is that
- * variance.  No reference counterpart.
+ * variance; and the filter's two optional stages (surf_svgf_ext): the firefly
+ * clamp in front of the accumulation (k_firefly) and the feedback of the
+ * first filtered iteration into the history (a switch on k_atrous_var).  No
+ * reference counterpart.
  *
  * The arithmetic is part of the interface: f32, no contraction, in the order
  * the header states.  svgfVariancePixel and denoisePixelVar below are the only
@@ -155,6 +158,74 @@ SURF_HD float4 svgfStore(bool valid, float4 Ip, float4 filtered, bool last, floa
     return make_float4(v.x * den.x, v.y * den.y, v.z * den.z, 1.0f);
 }
 
+/* Filtered-history feedback: the history record of a VALID pixel after
+ * iteration 0 -- the level that iteration wrote, remodulated, with the history
+ * length n1 the temporal accumulation gave the pixel. */
+SURF_HD float4 svgfFeedback(float4 filtered, float4 alb, uint32_t demodulate, float n1) {
+    const V3 den = denoiseDen(alb, demodulate);
+    return make_float4(filtered.x * den.x, filtered.y * den.y, filtered.z * den.z, n1);
+}
+
+/* ---- stage 0, the firefly clamp (surf_svgf_ext.firefly_scale, surf_firefly_image) ----
+ * A pixel's luminance of c / den is clamped to firefly_scale times the largest
+ * among its usable 3 x 3 neighbours; the accumulator the later stages read
+ * becomes A' = (c', 1).  fireflyLum and fireflyPixel are the only place this
+ * arithmetic is written; k_firefly and the host twin differ in the Fetch. */
+constexpr int kFireflyTileW = kDenoiseTileW + 2, kFireflyTileH = kDenoiseTileH + 2;      /* 34 x 10: the tile and its halo of 1 */
+constexpr int kFireflyHalo = kFireflyTileW * kFireflyTileH - kDenoiseTileW * kDenoiseTileH;   /* 84 texels */
+/* k_firefly's LDS: one float per texel, 1 360 B, static */
+constexpr size_t kFireflyLdsBytes = sizeof(float) * kFireflyTileW * kFireflyTileH;
+/* what a tap reads of a pixel that is not usable (invalid, or without a sample) */
+constexpr float kFireflyNoTap = -1.0f;
+
+/* c and l = lum(c / den) of a pixel, and, returned, what a neighbour's tap
+ * reads of it: kFireflyNoTap where it is not usable, else l with everything
+ * that cannot raise a maximum that starts at 0 -- l <= 0, a NaN -- stored as
+ * 0: the tap counts and leaves mx alone, exactly as the comparison would. */
+SURF_HD float fireflyLum(float4 A, float4 alb, uint32_t demodulate, V3& c, float& l) {
+    const float inv = A.w > 0.0f ? 1.0f / A.w : 0.0f;
+    c = mk3(A.x * inv, A.y * inv, A.z * inv);
+    const V3 den = denoiseDen(alb, demodulate);
+    l = svgfLum(c.x / den.x, c.y / den.y, c.z / den.z);
+    if (!(alb.w != 0.0f && A.w > 0.0f)) return kFireflyNoTap;
+    return l > 0.0f ? l : 0.0f;
+}
+
+/* A' of pixel (x, y): c, l and tap are fireflyLum's of this pixel; fetch.l
+ * (qx, qy) returns fireflyLum's value of an in-frame neighbour. */
+template <class Fetch>
+SURF_HD float4 fireflyPixel(int x, int y, int W, int H, float scale, float4 A, V3 c, float l, float tap, const Fetch& fetch) {
+    if (!(A.w > 0.0f)) return make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    float mx = 0.0f;
+    int cnt = 0;
+#pragma unroll
+    for (int dy = -1; dy <= 1; ++dy) {
+        const int qy = y + dy;
+#pragma unroll
+        for (int dx = -1; dx <= 1; ++dx) {
+            const int qx = x + dx;
+            if ((dx == 0 && dy == 0) || qx < 0 || qx >= W || qy < 0 || qy >= H) continue;
+            const float lq = fetch.l(qx, qy);
+            if (lq < 0.0f) continue;
+            cnt = cnt + 1;
+            mx = lq > mx ? lq : mx;
+        }
+    }
+    const float lim = scale * mx;
+    if (tap >= 0.0f && cnt > 0 && l > lim) {                 /* a NaN l fails and stays */
+        const float f = lim / l;
+        c = mk3(c.x * f, c.y * f, c.z * f);
+    }
+    return make_float4(c.x, c.y, c.z, 1.0f);
+}
+
+/* taps of the clamp from a full-frame plane of fireflyLum's values (the host twin) */
+struct FireflyFetchPlane {
+    const float* L;
+    int W;
+    SURF_HD float l(int qx, int qy) const { return L[(size_t)qy * W + qx]; }
+};
+
 /* taps of the variance estimate from full-frame planes in memory */
 struct SvgfFetchPlanes {
     const float4* N;
@@ -179,6 +250,68 @@ struct SvgfFetchTile {
     __device__ __forceinline__ float4 p(int qx, int qy) const { return P[(qy - y0) * kSvgfVarTileW + (qx - x0)]; }
     __device__ __forceinline__ float4 m(int qx, int qy) const { return M[(qy - y0) * kSvgfVarTileW + (qx - x0)]; }
 };
+
+/* ... and of the clamp from the staged tile of kFireflyTileW x kFireflyTileH
+ * floats whose texel (0, 0) is frame pixel (x0, y0) */
+struct FireflyFetchTile {
+    const float* L;
+    int x0, y0;
+    __device__ __forceinline__ float l(int qx, int qy) const { return L[(qy - y0) * kFireflyTileW + (qx - x0)]; }
+};
+
+/* The firefly clamp: 256 threads on a 32 x 8 pixel tile, the grid covering
+ * partial tiles.  Every thread loads its pixel's accumulator and albedo (two
+ * 16-byte loads, consecutive lanes consecutive records) and stores
+ * fireflyLum's tap value in a 34 x 10 tile of floats in static LDS
+ * (kFireflyLdsBytes); the first 84 threads also fill one texel each of the
+ * halo of 1 -- top row, bottom row, left and right column.  Every texel
+ * outside the frame holds kFireflyNoTap and is never loaded from memory.
+ * After the one barrier the 8 taps come from LDS: a row of 32 lanes reads 32
+ * consecutive floats, conflict-free.  48 B of memory traffic per pixel.  One
+ * variant: at 1.4 KB there is no LDS to trade against. */
+__global__ __launch_bounds__(256) void k_firefly(const float4* __restrict__ A, const float4* __restrict__ alb,
+                                                 float4* __restrict__ out, int W, int H, float scale, uint32_t demodulate) {
+    __shared__ float ffTile[kFireflyTileW * kFireflyTileH];
+    const int tx = (int)(threadIdx.x & (kDenoiseTileW - 1)), ty = (int)(threadIdx.x / kDenoiseTileW);
+    const int bx = (int)blockIdx.x * kDenoiseTileW, by = (int)blockIdx.y * kDenoiseTileH;
+    const int x = bx + tx, y = by + ty;
+    const int x0 = bx - 1, y0 = by - 1;
+    const bool inside = x < W && y < H;
+    const size_t p = (size_t)y * W + x;
+    float4 a = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    V3 c = mk3(0.0f, 0.0f, 0.0f);
+    float l = 0.0f, tap = kFireflyNoTap;
+    if (inside) {
+        a = A[p];
+        tap = fireflyLum(a, alb[p], demodulate, c, l);
+    }
+    ffTile[(ty + 1) * kFireflyTileW + (tx + 1)] = tap;
+    if (threadIdx.x < (unsigned)kFireflyHalo) {
+        const int t = (int)threadIdx.x;
+        int lx, ly;
+        if (t < 2 * kFireflyTileW) {                          /* the top row, then the bottom row */
+            ly = t < kFireflyTileW ? 0 : kFireflyTileH - 1;
+            lx = t < kFireflyTileW ? t : t - kFireflyTileW;
+        } else {                                              /* the left column, then the right one */
+            const int u = t - 2 * kFireflyTileW;
+            lx = u < kDenoiseTileH ? 0 : kFireflyTileW - 1;
+            ly = 1 + (u < kDenoiseTileH ? u : u - kDenoiseTileH);
+        }
+        const int gx = x0 + lx, gy = y0 + ly;
+        float ht = kFireflyNoTap;
+        if (gx >= 0 && gx < W && gy >= 0 && gy < H) {
+            const size_t g = (size_t)gy * W + gx;
+            V3 hc;
+            float hl;
+            ht = fireflyLum(A[g], alb[g], demodulate, hc, hl);
+        }
+        ffTile[ly * kFireflyTileW + lx] = ht;
+    }
+    __syncthreads();
+    if (!inside) return;
+    const FireflyFetchTile fetch{ffTile, x0, y0};
+    out[p] = fireflyPixel(x, y, W, H, scale, a, c, l, tap, fetch);
+}
 
 /* Elementwise: the packed guides of n pixels, as denoisePrepare packs them. */
 __global__ __launch_bounds__(256) void k_svgf_guides(const float4* __restrict__ pos, const float4* __restrict__ nrm,
@@ -249,12 +382,18 @@ __global__ __launch_bounds__(256) void k_svgf_variance(const float4* __restrict_
  * denoisePixelVar -- the same tile, the same staged layout (the image's w
  * now carries the variance; the 3 x 3 prefilter's taps lie inside the 2*s >= 2
  * halo), the same bits staged or not.  `last` fuses the remodulation and
- * writes the variance leaving the filter to var1. */
-template <bool STAGED>
+ * writes the variance leaving the filter to var1.
+ * FEEDBACK (surf_svgf_ext.feedback, iteration 0 only): the level this launch
+ * writes, remodulated, replaces the colour of a valid pixel's history --
+ * hist(p) = (I_1.rgb * den, n'), n' as k_temporal left it; an invalid pixel's
+ * record is not touched.  One more 16-byte load (alb, unless `last` reads it
+ * anyway), a 4-byte load and a 16-byte store per valid pixel; the other
+ * instantiations never touch hist. */
+template <bool STAGED, bool FEEDBACK>
 __global__ __launch_bounds__(256) void k_atrous_var(const float4* __restrict__ I, const float4* __restrict__ gN,
                                                     const float4* __restrict__ gP, const float4* __restrict__ alb,
                                                     float4* __restrict__ out, float* __restrict__ var1, int W, int H, int s,
-                                                    SvgfConsts K, uint32_t demodulate, int last) {
+                                                    SvgfConsts K, uint32_t demodulate, int last, float4* __restrict__ hist) {
     extern __shared__ float4 dnTile[];
     const int tx = (int)(threadIdx.x & (kDenoiseTileW - 1)), ty = (int)(threadIdx.x / kDenoiseTileW);
     const int bx = (int)blockIdx.x * kDenoiseTileW, by = (int)blockIdx.y * kDenoiseTileH;
@@ -297,6 +436,7 @@ __global__ __launch_bounds__(256) void k_atrous_var(const float4* __restrict__ I
     float var;
     out[p] = svgfStore(Np.w != 0.0f, Ip, f, last != 0, a, demodulate, var);
     if (last) var1[p] = var;
+    if (FEEDBACK && Np.w != 0.0f) hist[p] = svgfFeedback(f, last ? a : alb[p], demodulate, hist[p].w);
 }
 
 #endif  /* HIP */

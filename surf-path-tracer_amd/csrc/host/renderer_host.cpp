@@ -157,6 +157,13 @@ std::vector<F32> WaveFrontRenderer::svgf(const surf_temporal_params& params, con
     return out;
 }
 
+std::vector<F32> WaveFrontRenderer::svgf(const surf_temporal_params& params, const surf_svgf_params& filter, const surf_svgf_ext& ext) {
+    if (m_totalSamples == 0) throw std::runtime_error("svgf: nothing rendered since the last clear");
+    std::vector<F32> out((size_t)m_resolution.width * m_resolution.height * 4);
+    check(surf_svgf_accumulate_ex(m_ctx, &params, &filter, &ext, out.data()), m_ctx, "surf_svgf_accumulate_ex");
+    return out;
+}
+
 std::vector<F32> WaveFrontRenderer::svgf() {
     surf_temporal_params params;
     surf_svgf_params filter;

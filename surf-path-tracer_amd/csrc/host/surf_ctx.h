@@ -114,6 +114,16 @@ struct surf_ctx {
     /* the variance kernel takes its 7 x 7 taps from an LDS copy of the tile
      * (SURF_SVGF_LDS=0: from global memory; MEASUREMENTS "Variance-guided filter") */
     bool svVarStaged = true;
+    /* the firefly clamp (surf_svgf_ext.firefly_scale, surf_firefly_image): ff
+     * the clamped accumulator A' the frame's other kernels read, ffIn the two
+     * planes surf_firefly_image uploads.  Allocated on first use, kept, freed
+     * with the filter's state. */
+    float4* ff[1] = {};
+    size_t ffCap = 0;
+    float4* ffIn[2] = {};
+    size_t ffInCap = 0;
+    hipEvent_t ffEv[2] = {};
+    float ffMs = 0.0f;             /* device time of the last k_firefly launch (surf_debug_firefly_time) */
     /* the instance records as last uploaded (surf_upload_scene, surf_update_instances): their transforms move the history */
     std::vector<surf_gpu_instance> instHost;
     /* one-frame render calls may leave up to a pool of their stream unissued

@@ -1,9 +1,10 @@
 /*
  * svgf.hip -- the variance-guided filter (surf_svgf*, include/surf_hip.h):
- * parameter checks, the launches of one frame -- k_temporal with the moments
- * switched on, the guides and the variance estimate, the variance-guided
- * a-trous iterations -- the moments a frame leaves on the context beside the
- * temporal state, and the CPU twin.  The arithmetic lives in
+ * parameter checks, the launches of one frame -- the firefly clamp where it
+ * is asked for, k_temporal with the moments switched on, the guides and the
+ * variance estimate, the variance-guided a-trous iterations (the first of
+ * them storing the history where feedback is on) -- the moments a frame
+ * leaves on the context beside the temporal state, and the CPU twins.  The arithmetic lives in
  * device/temporal_kernels.h and device/svgf_kernels.h.
  */
 #include "host/temporal_host.h"
@@ -26,6 +27,15 @@ const char* svgfParamError(const surf_svgf_params* p) {
     return nullptr;
 }
 
+/* the extensions: NULL is all zero */
+const char* svgfExtError(const surf_svgf_ext* x) {
+    if (!x) return nullptr;
+    if (!(x->firefly_scale == 0.0f || (std::isfinite(x->firefly_scale) && x->firefly_scale >= 1.0f))) return "firefly_scale is neither 0 nor finite and >= 1";
+    if (x->feedback > 1u) return "feedback is neither 0 nor 1";
+    return nullptr;
+}
+surf_svgf_ext svgfExt(const surf_svgf_ext* x) { return x ? *x : surf_svgf_ext{}; }
+
 /* the constants of a call, computed in f32 on the host as the header states */
 SvgfConsts svgfConsts(const surf_svgf_params& p) {
     SvgfConsts k;
@@ -37,14 +47,19 @@ SvgfConsts svgfConsts(const surf_svgf_params& p) {
     return k;
 }
 
-/* k_svgf_variance<STAGED> and k_atrous_var<STAGED> at step s with their dynamic LDS */
+/* Kernel selection: k_svgf_variance<STAGED> and k_atrous_var<STAGED, FEEDBACK>
+ * at step s with their dynamic LDS.  FEEDBACK is picked for iteration 0 of a
+ * run with surf_svgf_ext.feedback and for no other launch.  k_firefly has one
+ * instantiation and static LDS (kFireflyLdsBytes, device/svgf_kernels.h). */
 template <class F>
 struct Launch { F fn; size_t lds; };
 auto varianceKernel(bool staged) {
     return Launch<decltype(&k_svgf_variance<true>)>{staged ? k_svgf_variance<true> : k_svgf_variance<false>, staged ? kSvgfVarLdsBytes : 0};
 }
-auto atrousVarKernel(bool staged, int s) {
-    return Launch<decltype(&k_atrous_var<true>)>{staged ? k_atrous_var<true> : k_atrous_var<false>,
+auto atrousVarKernel(bool staged, bool feedback, int s) {
+    const auto fn = feedback ? (staged ? k_atrous_var<true, true> : k_atrous_var<false, true>)
+                             : (staged ? k_atrous_var<true, false> : k_atrous_var<false, false>);
+    return Launch<decltype(&k_atrous_var<true, false>)>{fn,
                                                  staged ? (size_t)3 * sizeof(float4) * (kDenoiseTileW + 4 * s) * (kDenoiseTileH + 4 * s) : 0};
 }
 
@@ -60,13 +75,32 @@ struct SvgfPlanes {
     TemporalGuide* gN;
     float4* outM;
     float* var;                  /* 2 * npx floats: the variance entering the filter, then leaving it */
+    float4* clamped;             /* A' of the firefly clamp; read in A's place when the clamp is on */
 };
+
+/* k_firefly over device planes of a full w x h frame, timed (c->ffEv) */
+int launchFirefly(surf_ctx* c, uint32_t w, uint32_t h, const float4* A, const float4* alb, float scale, uint32_t demod, float4* out) {
+    for (auto& e : c->ffEv)
+        if (!e) SURF_CHECK(c, hipEventCreate(&e));
+    const dim3 grid((w + kDenoiseTileW - 1) / kDenoiseTileW, (h + kDenoiseTileH - 1) / kDenoiseTileH);
+    SURF_CHECK(c, hipEventRecord(c->ffEv[0], c->stream));
+    hipLaunchKernelGGL(k_firefly, grid, dim3(256), 0, c->stream, A, alb, out, (int)w, (int)h, scale, demod);
+    SURF_CHECK(c, hipGetLastError());
+    SURF_CHECK(c, hipEventRecord(c->ffEv[1], c->stream));
+    return SURF_OK;
+}
+int fireflyTime(surf_ctx* c) {
+    SURF_CHECK(c, hipEventSynchronize(c->ffEv[1]));
+    c->ffMs = 0.0f;
+    (void)hipEventElapsedTime(&c->ffMs, c->ffEv[0], c->ffEv[1]);
+    return SURF_OK;
+}
 
 /* All launches of a frame on the context's stream over device planes of a
  * full w x h frame; *result is the scratch image that holds the output.
  * Waits for the result. */
 int runSvgf(surf_ctx* c, uint32_t w, uint32_t h, const SvgfPlanes& pl, const TemporalConsts& K, const surf_svgf_params& P,
-            const float4** result) {
+            const surf_svgf_ext& X, const float4** result) {
     const size_t npx = (size_t)w * h;
     int rc = growImages(c, c->dn, 4, c->dnCap, npx);
     if (rc) return rc;
@@ -80,8 +114,11 @@ int runSvgf(surf_ctx* c, uint32_t w, uint32_t h, const SvgfPlanes& pl, const Tem
     float4* gP = c->dn[3];
     const dim3 grid((w + kDenoiseTileW - 1) / kDenoiseTileW, (h + kDenoiseTileH - 1) / kDenoiseTileH);
     static_assert(kDenoiseTileW == kTemporalTileW && kDenoiseTileH == kTemporalTileH, "one grid for every kernel of the frame");
+    const bool clamp = X.firefly_scale > 0.0f;
+    if (clamp && (rc = launchFirefly(c, w, h, pl.A, pl.alb, X.firefly_scale, demod, pl.clamped))) return rc;
+    const float4* A = clamp ? pl.clamped : pl.A;
     SURF_CHECK(c, hipEventRecord(c->svEv[0], c->stream));
-    hipLaunchKernelGGL(k_temporal<true>, grid, dim3(256), 0, c->stream, pl.A, pl.P, pl.N, pl.ID, pl.pH, pl.pP, pl.pG, (const float*)c->tpMotion, K,
+    hipLaunchKernelGGL(k_temporal<true>, grid, dim3(256), 0, c->stream, A, pl.P, pl.N, pl.ID, pl.pH, pl.pP, pl.pG, (const float*)c->tpMotion, K,
                        (int)w, (int)h, pl.blend, pl.hist, pl.gP, pl.gN, TemporalMomentPlanes{pl.alb, pl.pM, pl.outM, demod});
     SURF_CHECK(c, hipGetLastError());
     SURF_CHECK(c, hipEventRecord(c->svEv[1], c->stream));
@@ -96,9 +133,10 @@ int runSvgf(surf_ctx* c, uint32_t w, uint32_t h, const SvgfPlanes& pl, const Tem
     for (uint32_t i = 0; i < P.iterations; ++i) {
         const int s = 1 << i;
         const int last = i + 1 == P.iterations;
-        const auto atrous = atrousVarKernel((uint32_t)s <= stagedMax, s);
+        const bool feedback = X.feedback != 0u && i == 0;
+        const auto atrous = atrousVarKernel((uint32_t)s <= stagedMax, feedback, s);
         hipLaunchKernelGGL(atrous.fn, grid, dim3(256), atrous.lds, c->stream, (const float4*)lvl[i & 1], (const float4*)gN, (const float4*)gP, pl.alb,
-                           lvl[(i & 1) ^ 1], pl.var + npx, (int)w, (int)h, s, S, demod, last);
+                           lvl[(i & 1) ^ 1], pl.var + npx, (int)w, (int)h, s, S, demod, last, feedback ? pl.hist : nullptr);
         SURF_CHECK(c, hipGetLastError());
         SURF_CHECK(c, hipEventRecord(c->svEv[i + 3], c->stream));
     }
@@ -107,16 +145,20 @@ int runSvgf(surf_ctx* c, uint32_t w, uint32_t h, const SvgfPlanes& pl, const Tem
         c->svMs[k] = 0.0f;
         if (k < P.iterations + 2) (void)hipEventElapsedTime(&c->svMs[k], c->svEv[k], c->svEv[k + 1]);
     }
+    if (clamp && (rc = fireflyTime(c))) return rc;
     *result = lvl[P.iterations & 1];
     return SURF_OK;
 }
 
 /* surf_svgf_accumulate / _copy_device: the context's own accumulator and
  * cached feature planes against the stored state, which this frame's replaces */
-int svgfContext(surf_ctx* c, const surf_temporal_params* p, const surf_svgf_params* sp, void* dst, hipMemcpyKind kind) {
+int svgfContext(surf_ctx* c, const surf_temporal_params* p, const surf_svgf_params* sp, const surf_svgf_ext* ext, void* dst,
+                hipMemcpyKind kind) {
     if (!c || !dst) return SURF_ERR_INVALID;
     if (const char* why = temporalParamError(p)) return fail(c, SURF_ERR_INVALID, std::string("surf_svgf_accumulate: ") + why);
     if (const char* why = svgfParamError(sp)) return fail(c, SURF_ERR_INVALID, std::string("surf_svgf_accumulate: ") + why);
+    if (const char* why = svgfExtError(ext)) return fail(c, SURF_ERR_INVALID, std::string("surf_svgf_accumulate: ") + why);
+    const surf_svgf_ext X = svgfExt(ext);
     if (c->rows.size() != c->height)
         return fail(c, SURF_ERR_INVALID, "surf_svgf_accumulate needs a context that owns every row of the frame: a reprojected pixel and "
                                          "a spatial filter read other rows; assemble the shards' accumulators and feature planes and call "
@@ -126,6 +168,7 @@ int svgfContext(surf_ctx* c, const surf_temporal_params* p, const surf_svgf_para
     if ((rc = drainStream(c))) return rc;
     if ((rc = growImages(c, c->tp, 7, c->tpCap, c->npx))) { c->tpHave = false; return rc; }
     if ((rc = growImages(c, c->sv, 3, c->svCap, c->npx))) { c->svHave = false; return rc; }
+    if (X.firefly_scale > 0.0f && (rc = growImages(c, c->ff, 1, c->ffCap, c->npx))) return rc;
     const bool have = c->tpHave && c->tpInst.size() == c->instHost.size();
     const uint32_t nInst = (uint32_t)c->instHost.size();
     const TemporalConsts K = temporalSetup(*p, have ? &c->tpCam : nullptr, c->instHost.data(), have ? c->tpInst.data() : nullptr, nInst,
@@ -150,8 +193,9 @@ int svgfContext(surf_ctx* c, const surf_temporal_params* p, const surf_svgf_para
     pl.gN = reinterpret_cast<TemporalGuide*>(next[2]);
     pl.outM = c->sv[c->svCur ^ 1];
     pl.var = reinterpret_cast<float*>(c->sv[2]);
+    pl.clamped = c->ff[0];
     const float4* res = nullptr;
-    if ((rc = runSvgf(c, c->width, c->height, pl, K, *sp, &res))) return rc;
+    if ((rc = runSvgf(c, c->width, c->height, pl, K, *sp, X, &res))) return rc;
     c->tpCur ^= 1;
     c->tpHave = true;
     c->tpCam = c->camUbo;
@@ -161,6 +205,30 @@ int svgfContext(surf_ctx* c, const surf_temporal_params* p, const surf_svgf_para
     SURF_CHECK(c, hipMemcpyAsync(dst, res, (size_t)c->npx * sizeof(float4), kind, c->stream));
     SURF_CHECK(c, hipStreamSynchronize(c->stream));
     return SURF_OK;
+}
+
+/* stage 0 on host planes: fireflyLum's tap value of every pixel, then A' of every pixel */
+std::vector<float4> fireflyHost(uint32_t w, uint32_t h, const std::vector<float4>& A, const std::vector<float4>& alb, uint32_t demod, float scale) {
+    const size_t npx = (size_t)w * h;
+    std::vector<float> tap(npx), l(npx);
+    std::vector<V3> c(npx);
+    for (size_t q = 0; q < npx; ++q) tap[q] = fireflyLum(A[q], alb[q], demod, c[q], l[q]);
+    const FireflyFetchPlane fetch{tap.data(), (int)w};
+    std::vector<float4> out(npx);
+    for (int y = 0; y < (int)h; ++y)
+        for (int x = 0; x < (int)w; ++x) {
+            const size_t q = (size_t)y * w + x;
+            out[q] = fireflyPixel(x, y, (int)w, (int)h, scale, A[q], c[q], l[q], tap[q], fetch);
+        }
+    return out;
+}
+
+/* what surf_firefly_image and its host twin refuse */
+const char* fireflyError(uint32_t w, uint32_t h, const float* acc, const float* albedo, float scale, const float* out) {
+    if (!acc || !albedo || !out) return "NULL argument";
+    if (w == 0 || h == 0) return "w or h is 0";
+    if (!(std::isfinite(scale) && scale >= 1.0f)) return "scale is not finite and >= 1";
+    return nullptr;
 }
 
 /* the two float planes of variances as the (x, y, 0, 0) image the interface returns */
@@ -191,8 +259,11 @@ const char* svgfFrameError(uint32_t w, uint32_t h, const surf_svgf_frame* cur, c
 void surfhost::freeSvgf(surf_ctx* c) {
     for (float4*& p : c->sv) { if (p) (void)hipFree(p); p = nullptr; }
     for (float4*& p : c->svIn) { if (p) (void)hipFree(p); p = nullptr; }
+    for (float4*& p : c->ff) { if (p) (void)hipFree(p); p = nullptr; }
+    for (float4*& p : c->ffIn) { if (p) (void)hipFree(p); p = nullptr; }
     for (auto& e : c->svEv) { if (e) (void)hipEventDestroy(e); e = nullptr; }
-    c->svCap = c->svInCap = 0;
+    for (auto& e : c->ffEv) { if (e) (void)hipEventDestroy(e); e = nullptr; }
+    c->svCap = c->svInCap = c->ffCap = c->ffInCap = 0;
     c->svHave = false;
 }
 
@@ -211,12 +282,26 @@ int surf_svgf_default_params(surf_svgf_params* p) {
     return SURF_OK;
 }
 
+int surf_svgf_default_ext(surf_svgf_ext* x) {
+    if (!x) return SURF_ERR_INVALID;
+    std::memset(x, 0, sizeof *x);
+    return SURF_OK;
+}
+
 int surf_svgf_accumulate(surf_ctx* c, const surf_temporal_params* p, const surf_svgf_params* sp, float* out) {
-    return svgfContext(c, p, sp, out, hipMemcpyDeviceToHost);
+    return svgfContext(c, p, sp, nullptr, out, hipMemcpyDeviceToHost);
 }
 
 int surf_svgf_copy_device(surf_ctx* c, const surf_temporal_params* p, const surf_svgf_params* sp, void* dst) {
-    return svgfContext(c, p, sp, dst, hipMemcpyDeviceToDevice);
+    return svgfContext(c, p, sp, nullptr, dst, hipMemcpyDeviceToDevice);
+}
+
+int surf_svgf_accumulate_ex(surf_ctx* c, const surf_temporal_params* p, const surf_svgf_params* sp, const surf_svgf_ext* ext, float* out) {
+    return svgfContext(c, p, sp, ext, out, hipMemcpyDeviceToHost);
+}
+
+int surf_svgf_copy_device_ex(surf_ctx* c, const surf_temporal_params* p, const surf_svgf_params* sp, const surf_svgf_ext* ext, void* dst) {
+    return svgfContext(c, p, sp, ext, dst, hipMemcpyDeviceToDevice);
 }
 
 int surf_svgf_moments(surf_ctx* c, float* out) {
@@ -241,15 +326,23 @@ int surf_svgf_variance(surf_ctx* c, float* out) {
 
 int surf_svgf_image(surf_ctx* c, uint32_t w, uint32_t h, const surf_svgf_frame* cur, const surf_svgf_prev* prev, const surf_temporal_params* p,
                     const surf_svgf_params* sp, float* out, float* outHist, float* outMom, float* outVar) {
+    return surf_svgf_image_ex(c, w, h, cur, prev, p, sp, nullptr, out, outHist, outMom, outVar);
+}
+
+int surf_svgf_image_ex(surf_ctx* c, uint32_t w, uint32_t h, const surf_svgf_frame* cur, const surf_svgf_prev* prev, const surf_temporal_params* p,
+                       const surf_svgf_params* sp, const surf_svgf_ext* ext, float* out, float* outHist, float* outMom, float* outVar) {
     if (!c) return SURF_ERR_INVALID;
     if (const char* why = svgfFrameError(w, h, cur, prev, out, outHist, outMom, outVar)) return fail(c, SURF_ERR_INVALID, std::string("surf_svgf_image: ") + why);
     if (const char* why = temporalParamError(p)) return fail(c, SURF_ERR_INVALID, std::string("surf_svgf_image: ") + why);
     if (const char* why = svgfParamError(sp)) return fail(c, SURF_ERR_INVALID, std::string("surf_svgf_image: ") + why);
+    if (const char* why = svgfExtError(ext)) return fail(c, SURF_ERR_INVALID, std::string("surf_svgf_image: ") + why);
+    const surf_svgf_ext X = svgfExt(ext);
     SURF_CHECK(c, hipSetDevice(c->device));
     const size_t npx = (size_t)w * h, bytes = npx * sizeof(float4);
     int rc = growImages(c, c->tpIn, 9, c->tpInCap, npx);
     if (rc) return rc;
     if ((rc = growImages(c, c->svIn, 4, c->svInCap, npx))) return rc;
+    if (X.firefly_scale > 0.0f && (rc = growImages(c, c->ff, 1, c->ffCap, npx))) return rc;
     const void* curSrc[4] = {cur->acc, cur->position, cur->normal, cur->id};
     for (int k = 0; k < 4; ++k) SURF_CHECK(c, hipMemcpyAsync(c->tpIn[k], curSrc[k], bytes, hipMemcpyHostToDevice, c->stream));
     SURF_CHECK(c, hipMemcpyAsync(c->svIn[0], cur->albedo, bytes, hipMemcpyHostToDevice, c->stream));
@@ -278,8 +371,9 @@ int surf_svgf_image(surf_ctx* c, uint32_t w, uint32_t h, const surf_svgf_frame* 
     pl.hist = c->tpIn[8];
     pl.outM = c->svIn[2];
     pl.var = reinterpret_cast<float*>(c->svIn[3]);
+    pl.clamped = c->ff[0];
     const float4* res = nullptr;
-    if ((rc = runSvgf(c, w, h, pl, K, *sp, &res))) return rc;
+    if ((rc = runSvgf(c, w, h, pl, K, *sp, X, &res))) return rc;
     std::vector<float> var(2 * npx);
     SURF_CHECK(c, hipMemcpyAsync(out, res, bytes, hipMemcpyDeviceToHost, c->stream));
     SURF_CHECK(c, hipMemcpyAsync(outHist, c->tpIn[8], bytes, hipMemcpyDeviceToHost, c->stream));
@@ -294,9 +388,16 @@ int surf_svgf_image(surf_ctx* c, uint32_t w, uint32_t h, const surf_svgf_frame* 
  * their companions compiled for the host, on host arrays. */
 int surf_svgf_image_host(uint32_t w, uint32_t h, const surf_svgf_frame* cur, const surf_svgf_prev* prev, const surf_temporal_params* p,
                          const surf_svgf_params* sp, float* out, float* outHist, float* outMom, float* outVar) {
+    return surf_svgf_image_host_ex(w, h, cur, prev, p, sp, nullptr, out, outHist, outMom, outVar);
+}
+
+int surf_svgf_image_host_ex(uint32_t w, uint32_t h, const surf_svgf_frame* cur, const surf_svgf_prev* prev, const surf_temporal_params* p,
+                            const surf_svgf_params* sp, const surf_svgf_ext* ext, float* out, float* outHist, float* outMom, float* outVar) {
     if (const char* why = svgfFrameError(w, h, cur, prev, out, outHist, outMom, outVar)) return fail(nullptr, SURF_ERR_INVALID, std::string("surf_svgf_image_host: ") + why);
     if (const char* why = temporalParamError(p)) return fail(nullptr, SURF_ERR_INVALID, std::string("surf_svgf_image_host: ") + why);
     if (const char* why = svgfParamError(sp)) return fail(nullptr, SURF_ERR_INVALID, std::string("surf_svgf_image_host: ") + why);
+    if (const char* why = svgfExtError(ext)) return fail(nullptr, SURF_ERR_INVALID, std::string("surf_svgf_image_host: ") + why);
+    const surf_svgf_ext X = svgfExt(ext);
     const size_t npx = (size_t)w * h;
     std::vector<float> motion;
     const TemporalConsts K = temporalSetup(*p, prev ? &prev->camera : nullptr, cur->instances, prev ? prev->instances : nullptr,
@@ -311,7 +412,9 @@ int surf_svgf_image_host(uint32_t w, uint32_t h, const surf_svgf_frame* cur, con
         if (src) std::memcpy(v.data(), src, npx * sizeof(float4));
         return v;
     };
-    const std::vector<float4> A = plane(cur->acc), Ps = plane(cur->position), Ns = plane(cur->normal), Al = plane(cur->albedo);
+    const std::vector<float4> Ps = plane(cur->position), Ns = plane(cur->normal), Al = plane(cur->albedo);
+    std::vector<float4> A = plane(cur->acc);
+    if (X.firefly_scale > 0.0f) A = fireflyHost(w, h, A, Al, demod, X.firefly_scale);
     const std::vector<float4> prevH = plane(prev ? prev->history : nullptr), prevP = plane(prev ? prev->position : nullptr),
                               prevM = plane(prev ? prev->moments : nullptr);
     const TemporalFetchPlanes tfetch{prevH.data(), prevP.data(), guides.data(), (int)w, prevM.empty() ? nullptr : prevM.data()};
@@ -345,12 +448,47 @@ int surf_svgf_image_host(uint32_t w, uint32_t h, const surf_svgf_frame* cur, con
                 float v1;
                 O[q] = svgfStore(valid, I[q], f, last, Al[q], demod, v1);
                 if (last) var[npx + q] = v1;
+                if (X.feedback != 0u && i == 0 && valid) Hs[q] = svgfFeedback(f, Al[q], demod, Hs[q].w);
             }
     }
     std::memcpy(out, lvl[sp->iterations & 1].data(), npx * sizeof(float4));
     std::memcpy(outHist, Hs.data(), npx * sizeof(float4));
     std::memcpy(outMom, M.data(), npx * sizeof(float4));
     interleaveVariance(var, npx, outVar);
+    return SURF_OK;
+}
+
+int surf_firefly_image(surf_ctx* c, uint32_t w, uint32_t h, const float* acc, const float* albedo, uint32_t demodulate, float scale, float* out) {
+    if (!c) return SURF_ERR_INVALID;
+    if (const char* why = fireflyError(w, h, acc, albedo, scale, out)) return fail(c, SURF_ERR_INVALID, std::string("surf_firefly_image: ") + why);
+    SURF_CHECK(c, hipSetDevice(c->device));
+    const size_t npx = (size_t)w * h, bytes = npx * sizeof(float4);
+    int rc = growImages(c, c->ffIn, 2, c->ffInCap, npx);
+    if (rc) return rc;
+    if ((rc = growImages(c, c->ff, 1, c->ffCap, npx))) return rc;
+    SURF_CHECK(c, hipMemcpyAsync(c->ffIn[0], acc, bytes, hipMemcpyHostToDevice, c->stream));
+    SURF_CHECK(c, hipMemcpyAsync(c->ffIn[1], albedo, bytes, hipMemcpyHostToDevice, c->stream));
+    if ((rc = launchFirefly(c, w, h, c->ffIn[0], c->ffIn[1], scale, demodulate ? 1u : 0u, c->ff[0]))) return rc;
+    SURF_CHECK(c, hipMemcpyAsync(out, c->ff[0], bytes, hipMemcpyDeviceToHost, c->stream));
+    SURF_CHECK(c, hipStreamSynchronize(c->stream));
+    return fireflyTime(c);
+}
+
+/* The CPU twin: fireflyLum and fireflyPixel compiled for the host, on host arrays. */
+int surf_firefly_image_host(uint32_t w, uint32_t h, const float* acc, const float* albedo, uint32_t demodulate, float scale, float* out) {
+    if (const char* why = fireflyError(w, h, acc, albedo, scale, out)) return fail(nullptr, SURF_ERR_INVALID, std::string("surf_firefly_image_host: ") + why);
+    const size_t npx = (size_t)w * h;
+    std::vector<float4> A(npx), Al(npx);                    /* the caller's planes need not be 16-byte aligned */
+    std::memcpy(A.data(), acc, npx * sizeof(float4));
+    std::memcpy(Al.data(), albedo, npx * sizeof(float4));
+    const std::vector<float4> res = fireflyHost(w, h, A, Al, demodulate ? 1u : 0u, scale);
+    std::memcpy(out, res.data(), npx * sizeof(float4));
+    return SURF_OK;
+}
+
+int surf_debug_firefly_time(surf_ctx* c, float* kernel_ms) {
+    if (!c || !kernel_ms) return SURF_ERR_INVALID;
+    *kernel_ms = c->ffMs;
     return SURF_OK;
 }
 

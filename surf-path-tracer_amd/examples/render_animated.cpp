@@ -14,7 +14,9 @@
  * it (surf_pack_rgba8 with the display gamma); and PREFIX_svgf.pfm, the last
  * frame once more through the variance-guided filter (surf_svgf_accumulate)
  * on the state the loop left: the blend's history, no moments yet, so the
- * variance is the spatial estimate.
+ * variance is the spatial estimate; and PREFIX_svgf_ex.pfm, that frame a
+ * third time with the firefly clamp at scale 4 and the filtered-history
+ * feedback (surf_svgf_accumulate_ex), on the state the call before left.
  */
 #include "surf/surf_host.hpp"
 #include "indoor_scene.hpp"
@@ -71,6 +73,15 @@ int main(int argc, char** argv) {
             return 1;
         }
         const std::vector<F32> guided = renderer.svgf();  /* after the history was read: the call stores its own */
+        surf_svgf_params filter;
+        surf_svgf_ext ext;
+        if (surf_svgf_default_params(&filter) != SURF_OK || surf_svgf_default_ext(&ext) != SURF_OK) {
+            std::fprintf(stderr, "render_animated: default parameters failed\n");
+            return 1;
+        }
+        ext.firefly_scale = 4.0f;
+        ext.feedback = 1;
+        const std::vector<F32> guidedEx = renderer.svgf(temporal, filter, ext);
         std::vector<U32> rgba8((size_t)W * H);
         if (surf_pack_rgba8(clean.data(), W * H, 1.0f, 1, rgba8.data()) != SURF_OK) {
             std::fprintf(stderr, "render_animated: surf_pack_rgba8 failed\n");
@@ -82,6 +93,10 @@ int main(int argc, char** argv) {
                            surf_write_pfm(paths[2].c_str(), W, H, clean.data()), surf_write_png(paths[3].c_str(), W, H, rgba8.data())};
         if (surf_write_pfm((prefix + "_svgf.pfm").c_str(), W, H, guided.data()) != SURF_OK) {
             std::fprintf(stderr, "cannot write %s_svgf.pfm\n", prefix.c_str());
+            return 1;
+        }
+        if (surf_write_pfm((prefix + "_svgf_ex.pfm").c_str(), W, H, guidedEx.data()) != SURF_OK) {
+            std::fprintf(stderr, "cannot write %s_svgf_ex.pfm\n", prefix.c_str());
             return 1;
         }
         for (int k = 0; k < 4; ++k)

@@ -15,7 +15,8 @@ Mirrors the reference interface for the hot path:
     .aov()                     first-hit feature buffers (no reference counterpart)
     .denoise()                 edge-avoiding a-trous filter on them (no reference counterpart)
     .temporal()                temporal accumulation with reprojection across cleared frames (no reference counterpart)
-    .svgf()                    the same with luminance moments, their variance guiding the a-trous filter (no reference counterpart)
+    .svgf()                    the same with luminance moments, their variance guiding the a-trous filter (no reference counterpart);
+                               firefly_scale= and feedback= switch on the firefly clamp and the filtered-history feedback
 """
 from __future__ import annotations
 
@@ -109,6 +110,11 @@ class SvgfParams(C.Structure):
                 ("demodulate", C.c_uint32), ("spatial_below", C.c_uint32), ("variance_eps", C.c_float), ("_pad", C.c_uint32)]
 
 
+class SvgfExt(C.Structure):
+    """surf_svgf_ext: the firefly clamp (firefly_scale 0 = off, else >= 1) and the filtered-history feedback (0 / 1)."""
+    _fields_ = [("firefly_scale", C.c_float), ("feedback", C.c_uint32), ("_pad", C.c_uint32 * 2)]
+
+
 class SvgfFrame(C.Structure):
     """surf_svgf_frame: surf_temporal_frame plus the albedo plane."""
     _fields_ = TemporalFrame._fields_ + [("albedo", C.c_void_p)]
@@ -194,6 +200,16 @@ def load() -> C.CDLL:
         "surf_svgf_image_host": ([U32, U32, C.POINTER(SvgfFrame), C.POINTER(SvgfPrev), C.POINTER(TemporalParams), C.POINTER(SvgfParams),
                                   P, P, P, P], I32),
         "surf_debug_svgf_time": ([P, C.POINTER(F), U32], I32),
+        "surf_svgf_default_ext": ([C.POINTER(SvgfExt)], I32),
+        "surf_svgf_accumulate_ex": ([P, C.POINTER(TemporalParams), C.POINTER(SvgfParams), C.POINTER(SvgfExt), P], I32),
+        "surf_svgf_copy_device_ex": ([P, C.POINTER(TemporalParams), C.POINTER(SvgfParams), C.POINTER(SvgfExt), P], I32),
+        "surf_svgf_image_ex": ([P, U32, U32, C.POINTER(SvgfFrame), C.POINTER(SvgfPrev), C.POINTER(TemporalParams), C.POINTER(SvgfParams),
+                                C.POINTER(SvgfExt), P, P, P, P], I32),
+        "surf_svgf_image_host_ex": ([U32, U32, C.POINTER(SvgfFrame), C.POINTER(SvgfPrev), C.POINTER(TemporalParams), C.POINTER(SvgfParams),
+                                     C.POINTER(SvgfExt), P, P, P, P], I32),
+        "surf_firefly_image": ([P, U32, U32, P, P, U32, F, P], I32),
+        "surf_firefly_image_host": ([U32, U32, P, P, U32, F, P], I32),
+        "surf_debug_firefly_time": ([P, C.POINTER(F)], I32),
         "surf_mesh_data": ([P, C.POINTER(P), C.POINTER(P), C.POINTER(U32)], I32),
         "surf_mesh_destroy": ([P], None),
         "surf_ref_sinf": ([F], F), "surf_ref_cosf": ([F], F), "surf_ref_expf": ([F], F),
@@ -500,6 +516,46 @@ def _svgf_split(params):
             svgf_params(**{k: v for k, v in params.items() if k in _SVGF_FIELDS}))
 
 
+def svgf_ext(firefly_scale=0.0, feedback=False) -> SvgfExt:
+    """surf_svgf_default_ext (everything off) with the given fields replaced."""
+    x = SvgfExt()
+    _check(load().surf_svgf_default_ext(C.byref(x)), "surf_svgf_default_ext")
+    x.firefly_scale, x.feedback = float(firefly_scale), int(feedback)
+    return x
+
+
+def _svgf_ext(params):
+    """Takes 'ext' (a SvgfExt, or None for a NULL ext) or 'firefly_scale' / 'feedback' out of a
+    keyword set: (the rest, whether any was given, the ext argument for C).  With none of the
+    three given the caller takes the entry point without _ex."""
+    rest = {k: v for k, v in params.items() if k not in ("ext", "firefly_scale", "feedback")}
+    if len(rest) == len(params):
+        return rest, False, None
+    if "ext" in params:
+        if len(params) - len(rest) > 1:
+            raise TypeError("give either ext or firefly_scale / feedback")
+        if params["ext"] is not None and not isinstance(params["ext"], SvgfExt):
+            raise TypeError("ext is not a SvgfExt")
+        return rest, True, C.byref(params["ext"]) if params["ext"] is not None else None
+    return rest, True, C.byref(svgf_ext(params.get("firefly_scale", 0.0), params.get("feedback", False)))
+
+
+def _firefly_planes(acc, albedo):
+    a, alb = (np.ascontiguousarray(v, dtype=np.float32) for v in (acc, albedo))
+    if a.ndim != 3 or a.shape[2] != 4 or alb.shape != a.shape:
+        raise ValueError(f"firefly planes {a.shape}, {alb.shape} are not two (H, W, 4) images of one size")
+    return a, alb, np.zeros_like(a)
+
+
+def firefly_image_host(acc, albedo, scale, demodulate=True) -> np.ndarray:
+    """The CPU twin of Renderer.firefly_image (surf_firefly_image_host): the clamped
+    accumulator A' = (c', 1), (H, W, 4) float32; bit-identical, no device."""
+    a, alb, out = _firefly_planes(acc, albedo)
+    _check(load().surf_firefly_image_host(a.shape[1], a.shape[0], _ptr(a), _ptr(alb), int(bool(demodulate)), float(scale), _ptr(out)),
+           "surf_firefly_image_host")
+    return out
+
+
 def _svgf_frames(cur, prev):
     """(w, h, SvgfFrame, SvgfPrev or None, the arrays they point into): _temporal_frames' dicts,
     cur with 'albedo' ((H, W, 4) float32) and prev with 'moments' (None or absent: no moments stored)."""
@@ -524,12 +580,17 @@ def _svgf_frames(cur, prev):
 def svgf_image_host(cur, prev, **params):
     """The CPU twin of Renderer.svgf_image (surf_svgf_image_host): the same per-pixel
     functions compiled for the host, bit-identical; no device.  Returns (out,
-    history, moments, variance), each (H, W, 4) float32."""
+    history, moments, variance), each (H, W, 4) float32.  firefly_scale=, feedback=
+    or ext= (a SvgfExt or None) go through surf_svgf_image_host_ex."""
+    params, ex, x = _svgf_ext(params)
     p, sp = _svgf_split(params)
     w, h, f, q, _keep = _svgf_frames(cur, prev)
     res = [np.zeros((h, w, 4), np.float32) for _ in range(4)]
-    _check(load().surf_svgf_image_host(w, h, C.byref(f), C.byref(q) if q is not None else None, C.byref(p), C.byref(sp),
-                                       *[_ptr(a) for a in res]), "surf_svgf_image_host")
+    args = (w, h, C.byref(f), C.byref(q) if q is not None else None, C.byref(p), C.byref(sp))
+    if ex:
+        _check(load().surf_svgf_image_host_ex(*args, x, *[_ptr(a) for a in res]), "surf_svgf_image_host_ex")
+    else:
+        _check(load().surf_svgf_image_host(*args, *[_ptr(a) for a in res]), "surf_svgf_image_host")
     return tuple(res)
 
 
@@ -825,10 +886,17 @@ class Renderer:
         the luminance moments carried along, their variance setting the a-trous
         filter's colour width per pixel.  params: temporal_params' and
         svgf_params' names together.  (H, W, 4) float32 with w = 1.  Raises
-        SURF_ERR_INVALID on a row shard (see svgf_image)."""
+        SURF_ERR_INVALID on a row shard (see svgf_image).  firefly_scale= (0 = off,
+        else >= 1: the firefly clamp in front), feedback= (the first filtered
+        iteration becomes the stored history) or ext= (a SvgfExt or None) go
+        through surf_svgf_accumulate_ex; all off is the call without them."""
+        params, ex, x = _svgf_ext(params)
         p, sp = _svgf_split(params)
         out = np.zeros((self.height, self.width, 4), dtype=np.float32)
-        _check(load().surf_svgf_accumulate(self._h, C.byref(p), C.byref(sp), _ptr(out)), "surf_svgf_accumulate", self._h)
+        if ex:
+            _check(load().surf_svgf_accumulate_ex(self._h, C.byref(p), C.byref(sp), x, _ptr(out)), "surf_svgf_accumulate_ex", self._h)
+        else:
+            _check(load().surf_svgf_accumulate(self._h, C.byref(p), C.byref(sp), _ptr(out)), "surf_svgf_accumulate", self._h)
         return out
 
     def svgf_moments(self) -> np.ndarray:
@@ -845,17 +913,41 @@ class Renderer:
 
     def svgf_image(self, cur, prev, **params):
         """The same on host planes of any two full frames (surf_svgf_image; cur and
-        prev as _svgf_frames describes them).  Returns (out, history, moments, variance)."""
+        prev as _svgf_frames describes them).  Returns (out, history, moments, variance).
+        firefly_scale=, feedback= or ext= as svgf() (surf_svgf_image_ex)."""
+        params, ex, x = _svgf_ext(params)
         p, sp = _svgf_split(params)
         w, h, f, q, _keep = _svgf_frames(cur, prev)
         res = [np.zeros((h, w, 4), np.float32) for _ in range(4)]
-        _check(load().surf_svgf_image(self._h, w, h, C.byref(f), C.byref(q) if q is not None else None, C.byref(p), C.byref(sp),
-                                      *[_ptr(a) for a in res]), "surf_svgf_image", self._h)
+        args = (self._h, w, h, C.byref(f), C.byref(q) if q is not None else None, C.byref(p), C.byref(sp))
+        if ex:
+            _check(load().surf_svgf_image_ex(*args, x, *[_ptr(a) for a in res]), "surf_svgf_image_ex", self._h)
+        else:
+            _check(load().surf_svgf_image(*args, *[_ptr(a) for a in res]), "surf_svgf_image", self._h)
         return tuple(res)
 
     def copy_svgf_to(self, device_ptr: int, **params):
+        params, ex, x = _svgf_ext(params)
         p, sp = _svgf_split(params)
-        _check(load().surf_svgf_copy_device(self._h, C.byref(p), C.byref(sp), C.c_void_p(device_ptr)), "surf_svgf_copy_device", self._h)
+        if ex:
+            _check(load().surf_svgf_copy_device_ex(self._h, C.byref(p), C.byref(sp), x, C.c_void_p(device_ptr)), "surf_svgf_copy_device_ex",
+                   self._h)
+        else:
+            _check(load().surf_svgf_copy_device(self._h, C.byref(p), C.byref(sp), C.c_void_p(device_ptr)), "surf_svgf_copy_device", self._h)
+
+    def firefly_image(self, acc, albedo, scale, demodulate=True) -> np.ndarray:
+        """The firefly clamp alone on host planes of any full frame (surf_firefly_image):
+        the clamped accumulator A' = (c', 1), (H, W, 4) float32."""
+        a, alb, out = _firefly_planes(acc, albedo)
+        _check(load().surf_firefly_image(self._h, a.shape[1], a.shape[0], _ptr(a), _ptr(alb), int(bool(demodulate)), float(scale), _ptr(out)),
+               "surf_firefly_image", self._h)
+        return out
+
+    def debug_firefly_time(self) -> float:
+        """Device milliseconds of the last k_firefly launch (surf_debug_firefly_time)."""
+        ms = C.c_float()
+        _check(load().surf_debug_firefly_time(self._h, C.byref(ms)), "surf_debug_firefly_time", self._h)
+        return float(ms.value)
 
     def debug_svgf_time(self) -> list:
         """Device milliseconds of the last svgf run's kernels (surf_debug_svgf_time):
