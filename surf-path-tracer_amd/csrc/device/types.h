@@ -75,7 +75,16 @@ struct DevScene {
      * most 3) instances with the largest BLASes; keyMode 1: pool key by them */
     uint32_t nHeavy, keyMode;
     float4 hvLo[3], hvHi[3];
+    /* leaf runs of a single-leaf TLAS (traceScene, leafRun), one bit per TLAS
+     * position: runMember = the position belongs to a run, runHead = it is the
+     * run's first.  A run is kLeafRunMin..kLeafRunMax consecutive positions
+     * whose instances are affine root leaves of at most kLeafRunTris triangles
+     * over one triangle range (the room's planes).  0: no runs */
+    unsigned long long runHead, runMember;
 };
+/* kLeafRunMax: the lanes' 32-bit mask; kLeafRunPositions: runs lie in the first 63
+ * TLAS positions, so the walk's look at the bit behind a run never shifts by 64 */
+constexpr uint32_t kLeafRunTris = 2, kLeafRunMin = 2, kLeafRunMax = 32, kLeafRunPositions = 63;
 
 struct DevCamera {
     float pos[3], firstPixel[3], uVec[3], vVec[3], diskU[3], diskV[3];

@@ -488,6 +488,63 @@ __device__ __forceinline__ TraceTables traceTables(const DevScene& S, uint32_t* 
     return TraceTables{S.tinst, S.tlasIdx};
 }
 
+/* A leaf run of a single-leaf TLAS (DevScene::runHead): positions k0, k0 + 1,
+ * ... hold affine root-leaf instances over one triangle range -- the room's
+ * planes.  The wave-uniform loop would take every one of them in turn for all
+ * lanes as soon as one lane passes its cull, while a ray meets one or two.
+ * Here one uniform pass takes every lane's culls (the arithmetic of
+ * traceScene's, at the depth the run starts with) into a per-lane bit mask,
+ * and each lane then takes only its own instances, lowest bit = TLAS order
+ * first, reading their rows at a per-lane LDS address; the triangles are the
+ * run's one range, at a uniform address (loaded per turn: held across the
+ * loop they cost k_extend registers it does not have).  The caller marks its
+ * branch into a run unlikely so that the register allocator weighs the BVH
+ * loops as it did without this code.  A lane performs the instance turns the loop
+ * would, in the same order with the same operations: the earlier depth only
+ * admits instances the loop would have culled, the cull is conservative
+ * (traceScene) and triHit tests an admitted instance at the current depth. */
+template <bool ANY>
+__device__ __forceinline__ bool leafRun(const DevScene& S, const TraceTables& Tt, uint32_t k0, unsigned long long more, V3 o, V3 d,
+                                        V3 rdw, bool cullOk, float& depth, float& hu, float& hv, uint32_t& hinst, uint32_t& hprim) {
+    uint32_t m = 0u, n = 0u;
+    do {
+        const TraceInst& I = Tt.inst[Tt.order[k0 + n]];
+        bool take = true;
+        if (cullOk && I.wlo.w != 0.0f) {
+            const float tx0 = (I.wlo.x - o.x) * rdw.x, tx1 = (I.whi.x - o.x) * rdw.x;
+            const float ty0 = (I.wlo.y - o.y) * rdw.y, ty1 = (I.whi.y - o.y) * rdw.y;
+            const float tz0 = (I.wlo.z - o.z) * rdw.z, tz1 = (I.whi.z - o.z) * rdw.z;
+            const float t0 = fmaxf(fmaxf(fminf(tx0, tx1), fminf(ty0, ty1)), fminf(tz0, tz1));
+            const float t1 = fminf(fminf(fmaxf(tx0, tx1), fmaxf(ty0, ty1)), fmaxf(tz0, tz1));
+            take = !(t1 < t0 || t1 < 0.0f || t0 >= depth);
+        }
+        m |= take ? 1u << n : 0u;
+        ++n;
+    } while ((more >> (k0 + n)) & 1ull);
+    /* the run's triangles (wave-uniform: the first instance's range is every instance's) */
+    const TraceInst& H = Tt.inst[Tt.order[k0]];
+    const float4* tri = S.tris + 3u * (H.meta.y + f2u(H.r0.w));
+    const uint32_t cnt = f2u(H.r1.w);
+    bool any = false;
+    while (m) {
+        const uint32_t ii = Tt.order[k0 + (uint32_t)__ffs((int)m) - 1u];
+        m &= m - 1u;
+        const TraceInst& I = Tt.inst[ii];
+        const V3 oo = mk3(rowDot(I.m0, o.x, o.y, o.z, 1.0f), rowDot(I.m1, o.x, o.y, o.z, 1.0f), rowDot(I.m2, o.x, o.y, o.z, 1.0f));
+        const V3 dd = mk3(rowDot(I.m0, d.x, d.y, d.z, 0.0f), rowDot(I.m1, d.x, d.y, d.z, 0.0f), rowDot(I.m2, d.x, d.y, d.z, 0.0f));
+        for (uint32_t t = 0; t < cnt; ++t) {
+            const float4 a = tri[3u * t], b = tri[3u * t + 1u], c = tri[3u * t + 2u];
+            float u, v;
+            if (triHit(xyz(a), xyz(b), xyz(c), oo, dd, depth, u, v)) {
+                if (ANY) return true;
+                any = true;
+                hu = u; hv = v; hprim = f2u(a.w); hinst = ii;
+            }
+        }
+    }
+    return any;
+}
+
 /* BvhTLAS::intersect / intersectAny (bvh.cpp:654-778). */
 template <bool ANY, bool LW = false, bool STG = false, typename SK = uint32_t>
 __device__ __forceinline__ bool traceScene(const DevScene& S, const TraceTables& Tt, V3 o, V3 d, float& depth, float& hu, float& hv,
@@ -504,7 +561,17 @@ __device__ __forceinline__ bool traceScene(const DevScene& S, const TraceTables&
          * shadow queue is ordered by light and origin cell). */
         const V3 rdw = mk3(1.0f / d.x, 1.0f / d.y, 1.0f / d.z);
         const bool cullOk = finite3(o) && finite3(rdw);
+        const unsigned long long runMore = S.runMember & ~S.runHead;
         for (uint32_t k = 0; k < S.tlasLeafCount; ++k) {
+            if (__builtin_expect((S.runMember >> k) & 1ull, 0)) {
+                /* a leaf run is taken per lane at its first position (leafRun) */
+                if ((runMore >> k) & 1ull) continue;
+                if (leafRun<ANY>(S, Tt, k, runMore, o, d, rdw, cullOk, depth, hu, hv, hinst, hprim)) {
+                    if (ANY) return true;
+                    any = true;
+                }
+                continue;
+            }
             const uint32_t ii = Tt.order[k];
             const TraceInst& I = Tt.inst[ii];
             if (cullOk && I.wlo.w != 0.0f) {

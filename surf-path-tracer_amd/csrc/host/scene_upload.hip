@@ -77,6 +77,7 @@ struct InstanceTables {
     uint32_t nHeavy = 0;
     float4 hvLo[3], hvHi[3];
     uint32_t hvInst[3] = {0, 0, 0};
+    unsigned long long runHead = 0, runMember = 0;
 };
 
 /* The heavy-instance boxes of the ray-order keys (kernel arguments). */
@@ -90,6 +91,8 @@ void setKeys(surf_ctx* c, DevScene& S, const InstanceTables& T) {
         S.hvHi[h] = h < T.nHeavy ? T.hvHi[h] : make_float4(0, 0, 0, 0);
     }
     S.keyMode = T.nHeavy ? c->keyMode : 0u;
+    S.runHead = c->leafRun ? T.runHead : 0ull;
+    S.runMember = c->leafRun ? T.runMember : 0ull;
     /* the emitters' BLAS, when every light instance uses one BLAS and its
      * node records fit kLdsLightBlas bytes: k_connect stages them */
     S.sbNode0 = S.sbRecN = S.sbTri0 = S.sbTriN = 0u;
@@ -211,6 +214,31 @@ int buildInstanceTables(surf_ctx* c, const surf_gpu_instance* instances, uint32_
             T.hvHi[h] = T.tinst[big[h].second].whi;
             T.hvInst[h] = big[h].second;
             T.nHeavy = (uint32_t)h + 1;
+        }
+    }
+    /* leaf runs (DevScene::runHead): maximal sequences of consecutive TLAS
+     * positions whose instances are affine root leaves of at most kLeafRunTris
+     * triangles over one triangle range; a sequence longer than kLeafRunMax
+     * (the lanes' bit mask) continues as another run, a lone position is none */
+    if (T.tlasLeafCount && T.tlasLeafCount <= 64u) {
+        auto runLeaf = [&](uint32_t k) {
+            const TraceInst& R = T.tinst[T.tidx[k]];
+            return R.meta.z != 0u && f2u(R.r1.w) >= 1u && f2u(R.r1.w) <= kLeafRunTris;
+        };
+        auto sameRange = [&](uint32_t k, uint32_t j) {
+            const TraceInst &A = T.tinst[T.tidx[k]], &B = T.tinst[T.tidx[j]];
+            return A.meta.y == B.meta.y && f2u(A.r0.w) == f2u(B.r0.w) && f2u(A.r1.w) == f2u(B.r1.w);
+        };
+        const uint32_t end = std::min(T.tlasLeafCount, kLeafRunPositions);
+        for (uint32_t k = 0; k < end;) {
+            uint32_t len = 0;
+            if (runLeaf(k))
+                for (len = 1; k + len < end && len < kLeafRunMax && runLeaf(k + len) && sameRange(k, k + len);) ++len;
+            if (len >= kLeafRunMin) {
+                T.runHead |= 1ull << k;
+                for (uint32_t j = 0; j < len; ++j) T.runMember |= 1ull << (k + j);
+            }
+            k += std::max(len, 1u);
         }
     }
     T.lights.resize(nLights);

@@ -145,6 +145,10 @@ struct surf_ctx {
      * first-dispatched workgroups, DESIGN 4 "Pool sizing"), 1 the same key
      * ascending, 0 start instance x quadrant */
     uint32_t keyMode = 2;
+    /* the lane walk takes a single-leaf TLAS's leaf runs (the room's planes) per
+     * lane (DevScene::runHead, leafRun; SURF_LEAF_RUN=0: the wave-uniform loop
+     * takes every instance) */
+    bool leafRun = true;
     /* camera */
     bool hasCamera = false;
     DevCamera cam{};

@@ -1119,6 +1119,7 @@ int createCtx(int dev, uint32_t w, uint32_t h, std::vector<uint32_t> rows, surf_
     if (const char* e = std::getenv("SURF_EXT_STACK16")) c->extStack16 = e[0] != '0';
     if (const char* e = std::getenv("SURF_REGEN_COUNT")) c->regenCount = e[0] != '0';
     if (const char* e = std::getenv("SURF_KEY")) c->keyMode = e[0] == '0' ? 0u : (e[0] == '1' ? 1u : 2u);
+    if (const char* e = std::getenv("SURF_LEAF_RUN")) c->leafRun = e[0] != '0';
     if (const char* e = std::getenv("SURF_OVERLAP")) c->overlap = e[0] != '0';
     if (const char* e = std::getenv("SURF_LOOP_LAG")) c->loopLag = e[0] != '0';
     if (const char* e = std::getenv("SURF_EXT_LDS_PAD")) c->extLdsPad = (size_t)std::max(0, std::atoi(e));
