@@ -363,6 +363,21 @@ public:
     /* ... with the firefly clamp and / or the filtered-history feedback (surf_svgf_accumulate_ex; all zero: the form above) */
     std::vector<F32> svgf(const surf_temporal_params& params, const surf_svgf_params& filter, const surf_svgf_ext& ext);
     std::vector<F32> svgf();
+    /* the per-sample second moments beside the accumulator (surf_set_sample_squares): switch them on
+     * before the first render() or right after a clearAccumulator(); readSampleSquares() is the plane,
+     * width*height*4 floats */
+    void setSampleSquares(bool enabled);
+    std::vector<F32> readSampleSquares();
+    /* the rendered radiance through the sample-variance-guided filter (surf_denoise_sampled;
+     * width*height*4 floats, w = 1), for stills from about 16 samples per pixel; needs
+     * setSampleSquares(true).  The form without arguments takes surf_svgf_default_params. */
+    std::vector<F32> denoiseSampled(const surf_svgf_params& params);
+    std::vector<F32> denoiseSampled();
+    /* per pixel the relative standard error of its mean luminance and their summary
+     * (surf_noise_estimate); error non-NULL: it receives the image, width*height floats.  The form
+     * without arguments takes surf_noise_default_params and writes no image. */
+    surf_noise_summary noiseEstimate(const surf_noise_params& params, std::vector<F32>* error = nullptr);
+    surf_noise_summary noiseEstimate();
     /* clearAccumulator() for that loop: the next render() goes on with the sample indices after
      * those already rendered instead of repeating the cleared frame's sample stream (a plain
      * clearAccumulator() starts again from sample 0, as the reference does) */

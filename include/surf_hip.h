@@ -813,6 +813,123 @@ int surf_firefly_image_host(uint32_t w, uint32_t h, const float* acc, const floa
 /* Diagnostics: device time (HIP events) of the last k_firefly launch on this context, 0 before the first. */
 int surf_debug_firefly_time(surf_ctx* ctx, float* kernel_ms);
 
+/* ---- per-sample second moments, the sample-variance-guided filter, the noise estimate ----
+ * For stills of many samples per pixel (from about 16; below that the
+ * filters above are the better ones, INTEGRATION 9 has the measured table).
+ * Everything here is opt-in: until surf_set_sample_squares switches it on,
+ * no kernel, no result bit and no allocation differs.  The arithmetic is part
+ * of the interface, as above (f32, uncontracted, / and sqrtf IEEE, in exactly
+ * this order); lum is the variance-guided filter's.  No reference counterpart.
+ *
+ * The squares plane: rows*width float4 records in shard order, like the
+ * accumulator.  With the plane on, the kernel that adds each pass's radiance
+ * r -- one sample per pixel, whatever samples_per_frame is, so the moments
+ * are per sample for multi-sample frames too -- to the accumulator also adds,
+ * in pass order:
+ *   Q.x = Q.x + r.x*r.x    Q.y = Q.y + r.y*r.y    Q.z = Q.z + r.z*r.z
+ *   l   = (0.2126f*r.x + 0.7152f*r.y) + 0.0722f*r.z
+ *   Q.w = Q.w + l*l
+ * The accumulator, the sample stream and the event counters are bit for bit
+ * what they are with the plane off.  surf_clear_accumulator zeroes the plane
+ * with the accumulator; surf_destroy frees it.  Pointwise, so row shards work
+ * as they are and assemble like accumulators; gathering the plane through
+ * libsurf_mgpu.so is not provided.
+ *
+ * The sample-variance-guided filter.  Inputs: full-frame planes A (the
+ * accumulator, n = A.w), Q (the squares), position, normal and albedo as
+ * surf_read_aov defines them.  Parameters: surf_svgf_params, checked as for
+ * surf_svgf_accumulate except that spatial_below is ignored.  Level 0, per
+ * pixel, with valid, inv, c and den the denoiser's Prepare with this call's
+ * demodulate:
+ *   !valid or !(n >= 2.0f):   v = 0
+ *   else, k = x, y, z:  m_k = Q_k * inv;  t_k = m_k - c_k*c_k;  t_k = t_k > 0 ? t_k : 0   (a NaN becomes 0)
+ *                       s_k = sqrtf(t_k) / den_k
+ *         sd = (0.2126f*s_x + 0.7152f*s_y) + 0.0722f*s_z
+ *         v  = (sd*sd) / (n - 1.0f)
+ *   I0 = (c / den, v)
+ * -- the unbiased sample variance of the pixel mean, the channels' deviations
+ * taken as fully correlated.  Then step C of the variance-guided filter runs
+ * unchanged, with its output rule and its variance image (x = I0.w, y = I_n.w,
+ * 0 for an invalid pixel, z = w = 0).  The variance falls as 1/n, so the
+ * filter narrows as the render converges.  A frame with n < 2 everywhere is
+ * valid: v = 0 everywhere, the colour term then rejects every tap whose
+ * luminance differs (kl = 1 / variance_eps) and the filter all but returns
+ * its input.
+ * Launches: the packed guides, one level-0 kernel (256 threads per 32 x 8
+ * tile; three 16-byte loads, a 16-byte and a 4-byte store per pixel), then the
+ * variance-guided filter's own iteration kernels under SURF_DENOISE_LDS.
+ *
+ * The noise estimate: the relative standard error of a pixel's mean
+ * luminance, from A and Q alone.  Parameters threshold and floor, both finite
+ * and > 0.  Per pixel:
+ *   n = A.w;  !(n >= 2.0f):  e = 1e30f
+ *   else inv = 1.0f/n;  lb = lum(A.rgb*inv);  t = Q.w*inv - lb*lb;  t = t > 0 ? t : 0
+ *        e = sqrtf(t / (n - 1.0f)) / (lb + floor)
+ * The summary: pixels, the pixels looked at; above, those with !(e <=
+ * threshold) (a NaN counts); max_error, the largest e, starting from 0 -- a NaN
+ * or a negative e (a negative mean luminance) leaves it alone.  One kernel
+ * writes the image where one is asked for and reduces the summary: per wave a
+ * ballot and popcount and six lane shuffles, then one integer add and one
+ * unsigned max on the float's bits -- exact, whatever order the waves arrive in. */
+/* Switches the squares plane on (enabled != 0) or off.  Drains the stream.
+ * SURF_ERR_INVALID unless the accumulator is empty -- no sample since
+ * surf_create* or the last surf_clear_accumulator: the moments of samples
+ * already absorbed cannot be recovered; SURF_ERR_OOM when the plane cannot be
+ * allocated.  Switching off keeps the allocation. */
+int surf_set_sample_squares(surf_ctx* ctx, int enabled);
+/* The plane, to a host buffer of rows*width*4 floats / a buffer on the
+ * context's device (rows*width*16 bytes).  Drain the stream, as every read
+ * does; SURF_ERR_INVALID while the plane is off. */
+int surf_read_sample_squares(surf_ctx* ctx, float* out);
+int surf_copy_sample_squares_device(surf_ctx* ctx, void* dst_device);
+/* The context's accumulator and squares filtered with its own (cached)
+ * feature planes, as surf_denoise; status codes as surf_denoise's (on a row
+ * shard surf_last_error points to surf_denoise_sampled_image), and
+ * SURF_ERR_INVALID while the plane is off. */
+int surf_denoise_sampled(surf_ctx* ctx, const surf_svgf_params* params, float* out_rgba);
+int surf_denoise_sampled_copy_device(surf_ctx* ctx, const surf_svgf_params* params, void* dst_device);
+/* Host planes of any full frame (w*h*4 floats each), e.g. one assembled from
+ * row shards; two outputs of w*h*4 floats: the image and the variances.
+ * Needs no scene on the context and no squares plane. */
+int surf_denoise_sampled_image(surf_ctx* ctx, uint32_t w, uint32_t h, const float* acc, const float* squares, const float* position,
+                               const float* normal, const float* albedo, const surf_svgf_params* params, float* out_rgba,
+                               float* out_variance);
+/* The CPU twin: the same per-pixel functions compiled for the host; needs no
+ * device.  Bit-identical to surf_denoise_sampled_image. */
+int surf_denoise_sampled_image_host(uint32_t w, uint32_t h, const float* acc, const float* squares, const float* position,
+                                    const float* normal, const float* albedo, const surf_svgf_params* params, float* out_rgba,
+                                    float* out_variance);
+/* Diagnostics: device time (HIP events) of the last sampled run on this
+ * context: kernel_ms[0] the level-0 kernel (the guide packing in front of it is
+ * not counted), kernel_ms[1 + i] iteration i; entries past the run's iterations
+ * (and past 7) are 0. */
+int surf_debug_sampled_time(surf_ctx* ctx, float* kernel_ms, uint32_t count);
+typedef struct {
+    float threshold;
+    float floor;
+} surf_noise_params;
+typedef struct {
+    uint64_t pixels, above;
+    float max_error;
+    uint32_t _pad;
+} surf_noise_summary;
+/* threshold 0.05, floor 0.01 */
+int surf_noise_default_params(surf_noise_params* params);
+/* The estimate of the context's own rows: out_error (rows*width floats) may be
+ * NULL.  Works per shard: counts add across shards, the frame's max_error is
+ * the largest of the shards'.  Drains the stream; SURF_ERR_INVALID for a NULL
+ * context, params or summary, a threshold or floor that is not finite and > 0,
+ * and while the plane is off; SURF_ERR_OOM when a scratch image cannot be
+ * allocated. */
+int surf_noise_estimate(surf_ctx* ctx, const surf_noise_params* params, float* out_error, surf_noise_summary* summary);
+/* Host planes of npx pixels (npx*4 floats each), npx in 1..2^31; out_error
+ * (npx floats) may be NULL.  Needs no scene and no squares plane. */
+int surf_noise_image(surf_ctx* ctx, uint32_t npx, const float* acc, const float* squares, const surf_noise_params* params,
+                     float* out_error, surf_noise_summary* summary);
+/* The CPU twin; needs no device.  Bit-identical to surf_noise_image. */
+int surf_noise_image_host(uint32_t npx, const float* acc, const float* squares, const surf_noise_params* params, float* out_error,
+                          surf_noise_summary* summary);
+
 /* ---- traversal entry points (kernel-level parity tests) ----
  * n world-space rays, o/d 3 floats each.  closest: depth starts at 1e30;
  * writes t,u,v (floats) and inst,prim (u32, ~0 on miss).  any: tmax per ray,

@@ -2954,10 +2954,15 @@ __global__ __launch_bounds__(128, SURF_COOP_WAVES) void k_tail_pair(DevScene S, 
 }
 
 /* acc[p] += (radiance, 1) for frames [f0, f0+count) of the stream, in frame
- * order (renderer.cpp:180); frame f's radiance lives in slot f % window. */
+ * order (renderer.cpp:180); frame f's radiance lives in slot f % window.
+ * SQUARES (surf_set_sample_squares): the same loop also carries the pixel's
+ * record of the squares plane, sq[p] += (r.x^2, r.y^2, r.z^2, lum(r)^2) per
+ * pass -- one more 16-byte load and store per pixel, nothing more per pass;
+ * the other instantiation never touches sq. */
+template <bool SQUARES>
 __global__ __launch_bounds__(kBlock) void k_accumulate(const float4* __restrict__ rad, float4* __restrict__ acc,
                                                        uint32_t npx, unsigned long long f0, uint32_t count, uint32_t window,
-                                                       uint32_t* __restrict__ frameDone) {
+                                                       uint32_t* __restrict__ frameDone, float4* __restrict__ sq) {
     const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
     /* the accumulated frames' slots are free again: reset their completion
      * stripes here, on the render stream (the escape worker may be updating
@@ -2965,12 +2970,20 @@ __global__ __launch_bounds__(kBlock) void k_accumulate(const float4* __restrict_
     if (p < count * kStripes) frameDone[(p % kStripes) * window + (uint32_t)((f0 + p / kStripes) % window)] = 0u;
     if (p >= npx) return;
     float4 a = acc[p];
+    float4 q = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    if (SQUARES) q = sq[p];
     for (uint32_t k = 0; k < count; ++k) {
         const uint32_t slot = (uint32_t)((f0 + k) % window);
         const float4 r = rad[(size_t)slot * npx + p];
         a.x = a.x + r.x; a.y = a.y + r.y; a.z = a.z + r.z; a.w = a.w + 1.0f;
+        if (SQUARES) {
+            q.x = q.x + r.x * r.x; q.y = q.y + r.y * r.y; q.z = q.z + r.z * r.z;
+            const float l = (0.2126f * r.x + 0.7152f * r.y) + 0.0722f * r.z;
+            q.w = q.w + l * l;
+        }
     }
     acc[p] = a;
+    if (SQUARES) sq[p] = q;
 }
 
 /* wavefront_finalize.comp + RgbaToU32 (cvtps2dq round-to-even, packus saturation) */

@@ -172,6 +172,43 @@ std::vector<F32> WaveFrontRenderer::svgf() {
     return svgf(params, filter);
 }
 
+void WaveFrontRenderer::setSampleSquares(bool enabled) {
+    check(surf_set_sample_squares(m_ctx, enabled ? 1 : 0), m_ctx, "surf_set_sample_squares");
+}
+
+std::vector<F32> WaveFrontRenderer::readSampleSquares() {
+    std::vector<F32> out((size_t)m_resolution.width * m_resolution.height * 4);
+    check(surf_read_sample_squares(m_ctx, out.data()), m_ctx, "surf_read_sample_squares");
+    return out;
+}
+
+/* Like denoise(), the filter keeps the camera and the scene of the last render() call. */
+std::vector<F32> WaveFrontRenderer::denoiseSampled(const surf_svgf_params& params) {
+    if (m_totalSamples == 0) throw std::runtime_error("denoiseSampled: nothing rendered since the last clear");
+    std::vector<F32> out((size_t)m_resolution.width * m_resolution.height * 4);
+    check(surf_denoise_sampled(m_ctx, &params, out.data()), m_ctx, "surf_denoise_sampled");
+    return out;
+}
+
+std::vector<F32> WaveFrontRenderer::denoiseSampled() {
+    surf_svgf_params params;
+    check(surf_svgf_default_params(&params), m_ctx, "surf_svgf_default_params");
+    return denoiseSampled(params);
+}
+
+surf_noise_summary WaveFrontRenderer::noiseEstimate(const surf_noise_params& params, std::vector<F32>* error) {
+    if (error) error->assign((size_t)m_resolution.width * m_resolution.height, 0.0f);
+    surf_noise_summary summary{};
+    check(surf_noise_estimate(m_ctx, &params, error ? error->data() : nullptr, &summary), m_ctx, "surf_noise_estimate");
+    return summary;
+}
+
+surf_noise_summary WaveFrontRenderer::noiseEstimate() {
+    surf_noise_params params;
+    check(surf_noise_default_params(&params), m_ctx, "surf_noise_default_params");
+    return noiseEstimate(params, nullptr);
+}
+
 void WaveFrontRenderer::resetTemporal() { check(surf_temporal_reset(m_ctx), m_ctx, "surf_temporal_reset"); }
 
 std::vector<U32> WaveFrontRenderer::displayRGBA8() {

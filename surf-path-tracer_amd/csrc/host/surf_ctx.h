@@ -124,6 +124,25 @@ struct surf_ctx {
     size_t ffInCap = 0;
     hipEvent_t ffEv[2] = {};
     float ffMs = 0.0f;             /* device time of the last k_firefly launch (surf_debug_firefly_time) */
+    /* the sample-variance-guided filter and the noise estimate (surf_denoise_sampled*,
+     * surf_noise_*, host/svgf.hip) share the denoiser's scratch (dn) and add,
+     * each sized to what it stores (the capacities count 16-byte records):
+     * sdVar, two float planes (the variance entering and leaving the filter,
+     * 8 B per pixel); sdErr, the noise estimate's sums in its first record and
+     * behind them the error image (4 B per pixel); sdAQ, the accumulator and
+     * squares planes the two image forms upload, and sdIn, the three feature
+     * planes surf_denoise_sampled_image uploads.  Allocated on first use,
+     * kept, freed with the filter's state. */
+    float4* sdVar[1] = {};
+    size_t sdVarCap = 0;
+    float4* sdErr[1] = {};
+    size_t sdErrCap = 0;
+    float4* sdAQ[2] = {};
+    size_t sdAQCap = 0;
+    float4* sdIn[3] = {};
+    size_t sdInCap = 0;
+    hipEvent_t sdEv[kDenoiseMaxIterations + 2] = {};
+    float sdMs[kDenoiseMaxIterations + 1] = {};   /* the level-0 kernel, then the iterations of the last run (surf_debug_sampled_time) */
     /* the instance records as last uploaded (surf_upload_scene, surf_update_instances): their transforms move the history */
     std::vector<surf_gpu_instance> instHost;
     /* one-frame render calls may leave up to a pool of their stream unissued
@@ -162,6 +181,12 @@ struct surf_ctx {
     ShadowQ Q{};
     float4* rad = nullptr;
     float4* acc = nullptr;
+    /* the per-sample second moments beside the accumulator (surf_set_sample_squares):
+     * npx records (sum r.x^2, sum r.y^2, sum r.z^2, sum lum(r)^2), allocated when
+     * first switched on, kept when switched off, freed in surf_destroy */
+    float4* sq = nullptr;
+    bool sqOn = false;
+    hipEvent_t accEv[2] = {};      /* profiling: around each k_accumulate launch (surf_stats.ms_accum), created on first use */
     uint32_t* dRows = nullptr;
     Counters* ctr = nullptr;
     Counters* hctr = nullptr;      /* pinned: the counters as of the last consumed snapshot */

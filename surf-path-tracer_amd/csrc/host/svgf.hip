@@ -6,6 +6,10 @@
  * them storing the history where feedback is on) -- the moments a frame
  * leaves on the context beside the temporal state, and the CPU twins.  The arithmetic lives in
  * device/temporal_kernels.h and device/svgf_kernels.h.
+ * Also the two readers of the per-sample squares plane, which run the same
+ * a-trous iterations or none: the sample-variance-guided filter
+ * (surf_denoise_sampled*) and the noise estimate (surf_noise_*), their
+ * arithmetic in device/sampled_kernels.h.
  */
 #include "host/temporal_host.h"
 
@@ -14,15 +18,17 @@
 #include <cstring>
 
 #include "device/svgf_kernels.h"
+#include "device/sampled_kernels.h"
 
 namespace {
 
-const char* svgfParamError(const surf_svgf_params* p) {
+/* needSpatial: spatial_below is checked (surf_denoise_sampled* ignores the field) */
+const char* svgfParamError(const surf_svgf_params* p, bool needSpatial = true) {
     if (!p) return "svgf params is NULL";
     if (p->iterations < 1 || p->iterations > (uint32_t)kDenoiseMaxIterations) return "iterations outside 1..6";
     for (float s : {p->sigma_lum, p->sigma_normal, p->sigma_plane})
         if (!(std::isfinite(s) && s > 0.0f)) return "a sigma is not finite and > 0";
-    if (p->spatial_below == 0) return "spatial_below is 0";
+    if (needSpatial && p->spatial_below == 0) return "spatial_below is 0";
     if (!(std::isfinite(p->variance_eps) && p->variance_eps > 0.0f)) return "variance_eps is not finite and > 0";
     return nullptr;
 }
@@ -50,7 +56,11 @@ SvgfConsts svgfConsts(const surf_svgf_params& p) {
 /* Kernel selection: k_svgf_variance<STAGED> and k_atrous_var<STAGED, FEEDBACK>
  * at step s with their dynamic LDS.  FEEDBACK is picked for iteration 0 of a
  * run with surf_svgf_ext.feedback and for no other launch.  k_firefly has one
- * instantiation and static LDS (kFireflyLdsBytes, device/svgf_kernels.h). */
+ * instantiation and static LDS (kFireflyLdsBytes, device/svgf_kernels.h).
+ * The sample-variance-guided filter (surf_denoise_sampled*) takes
+ * k_atrous_var<STAGED, false> through the same selector; its level-0 kernel
+ * k_sampled_level0 and the noise estimate's k_noise (device/sampled_kernels.h)
+ * have one instantiation each and no LDS. */
 template <class F>
 struct Launch { F fn; size_t lds; };
 auto varianceKernel(bool staged) {
@@ -254,9 +264,122 @@ const char* svgfFrameError(uint32_t w, uint32_t h, const surf_svgf_frame* cur, c
     return temporalFrameError(w, h, &tc, prev ? &tq : nullptr, out, outHist);
 }
 
+/* ---- the sample-variance-guided filter (surf_denoise_sampled*) ---- */
+
+/* The launches of a run on the context's stream over device planes of a full
+ * w x h frame: the guides, level 0, the iterations.  *result is the scratch
+ * image that holds the output; the two variance planes are left in c->sdVar
+ * (2 * npx floats, i.e. (npx + 1) / 2 records).  Waits for the result. */
+int runSampled(surf_ctx* c, uint32_t w, uint32_t h, const float4* A, const float4* Q, const float4* P, const float4* N, const float4* alb,
+               const surf_svgf_params& sp, const float4** result) {
+    const size_t npx = (size_t)w * h;
+    int rc = growImages(c, c->dn, 4, c->dnCap, npx);
+    if (rc) return rc;
+    if ((rc = growImages(c, c->sdVar, 1, c->sdVarCap, (npx + 1) / 2))) return rc;
+    float* var = reinterpret_cast<float*>(c->sdVar[0]);
+    for (auto& e : c->sdEv)
+        if (!e) SURF_CHECK(c, hipEventCreate(&e));
+    const uint32_t demod = sp.demodulate ? 1u : 0u;
+    const SvgfConsts S = svgfConsts(sp);
+    float4* lvl[2] = {c->dn[0], c->dn[1]};
+    float4* gN = c->dn[2];
+    float4* gP = c->dn[3];
+    const dim3 grid((w + kDenoiseTileW - 1) / kDenoiseTileW, (h + kDenoiseTileH - 1) / kDenoiseTileH);
+    hipLaunchKernelGGL(k_svgf_guides, dim3((uint32_t)((npx + 255) / 256)), dim3(256), 0, c->stream, P, N, alb, (uint32_t)npx, gN, gP);
+    SURF_CHECK(c, hipGetLastError());
+    SURF_CHECK(c, hipEventRecord(c->sdEv[0], c->stream));
+    hipLaunchKernelGGL(k_sampled_level0, grid, dim3(256), 0, c->stream, A, Q, alb, lvl[0], var, (int)w, (int)h, demod);
+    SURF_CHECK(c, hipGetLastError());
+    SURF_CHECK(c, hipEventRecord(c->sdEv[1], c->stream));
+    const uint32_t stagedMax = std::min<uint32_t>(c->dnLdsMax, (uint32_t)kDenoiseMaxStagedStep);
+    for (uint32_t i = 0; i < sp.iterations; ++i) {
+        const int s = 1 << i;
+        const int last = i + 1 == sp.iterations;
+        const auto atrous = atrousVarKernel((uint32_t)s <= stagedMax, false, s);
+        hipLaunchKernelGGL(atrous.fn, grid, dim3(256), atrous.lds, c->stream, (const float4*)lvl[i & 1], (const float4*)gN, (const float4*)gP, alb,
+                           lvl[(i & 1) ^ 1], var + npx, (int)w, (int)h, s, S, demod, last, (float4*)nullptr);
+        SURF_CHECK(c, hipGetLastError());
+        SURF_CHECK(c, hipEventRecord(c->sdEv[i + 2], c->stream));
+    }
+    SURF_CHECK(c, hipEventSynchronize(c->sdEv[sp.iterations + 1]));
+    for (uint32_t k = 0; k <= (uint32_t)kDenoiseMaxIterations; ++k) {
+        c->sdMs[k] = 0.0f;
+        if (k <= sp.iterations) (void)hipEventElapsedTime(&c->sdMs[k], c->sdEv[k], c->sdEv[k + 1]);
+    }
+    *result = lvl[sp.iterations & 1];
+    return SURF_OK;
+}
+
+/* surf_denoise_sampled / _copy_device: the context's own accumulator, squares and cached feature planes */
+int sampledContext(surf_ctx* c, const surf_svgf_params* sp, void* dst, hipMemcpyKind kind) {
+    if (!c || !dst) return SURF_ERR_INVALID;
+    if (const char* why = svgfParamError(sp, false)) return fail(c, SURF_ERR_INVALID, std::string("surf_denoise_sampled: ") + why);
+    if (c->rows.size() != c->height)
+        return fail(c, SURF_ERR_INVALID, "surf_denoise_sampled needs a context that owns every row of the frame: a spatial filter reads its "
+                                         "neighbours' rows; assemble the shards' accumulators, squares and feature planes and call "
+                                         "surf_denoise_sampled_image");
+    if (!c->sqOn) return fail(c, SURF_ERR_INVALID, "surf_denoise_sampled: sample squares are off (surf_set_sample_squares)");
+    int rc = featurePlanes(c);
+    if (rc) return rc;
+    if ((rc = drainStream(c))) return rc;
+    const float4* res = nullptr;
+    rc = runSampled(c, c->width, c->height, c->acc, c->sq, static_cast<const float4*>(c->aov[SURF_AOV_POSITION]),
+                    static_cast<const float4*>(c->aov[SURF_AOV_NORMAL]), static_cast<const float4*>(c->aov[SURF_AOV_ALBEDO]), *sp,
+                    &res);
+    if (rc) return rc;
+    SURF_CHECK(c, hipMemcpyAsync(dst, res, (size_t)c->npx * sizeof(float4), kind, c->stream));
+    SURF_CHECK(c, hipStreamSynchronize(c->stream));
+    return SURF_OK;
+}
+
+/* what surf_denoise_sampled_image and its host twin refuse, beside the parameters */
+const char* sampledFrameError(uint32_t w, uint32_t h, const float* acc, const float* squares, const float* position, const float* normal,
+                              const float* albedo, const float* out, const float* outVar) {
+    if (!acc || !squares || !position || !normal || !albedo || !out || !outVar) return "NULL argument";
+    if (w == 0 || h == 0 || (uint64_t)w * h > (1ull << 31)) return "empty or too large a frame";
+    return nullptr;
+}
+
+/* ---- the noise estimate (surf_noise_*) ---- */
+const char* noiseParamError(const surf_noise_params* p) {
+    if (!p) return "noise params is NULL";
+    if (!(std::isfinite(p->threshold) && p->threshold > 0.0f)) return "threshold is not finite and > 0";
+    if (!(std::isfinite(p->floor) && p->floor > 0.0f)) return "floor is not finite and > 0";
+    return nullptr;
+}
+
+/* k_noise over device planes of npx pixels; the error image (outErr not NULL)
+ * and the summary go to the host.  c->sdErr holds the sums in its first
+ * record, then the image: 1 + (npx + 3) / 4 records. */
+int runNoise(surf_ctx* c, uint32_t npx, const float4* A, const float4* Q, const surf_noise_params& P, float* outErr, surf_noise_summary* sum) {
+    const int rc = growImages(c, c->sdErr, 1, c->sdErrCap, 1 + ((size_t)npx + 3) / 4);
+    if (rc) return rc;
+    NoiseSums* dSums = reinterpret_cast<NoiseSums*>(c->sdErr[0]);
+    float* dErr = outErr ? reinterpret_cast<float*>(c->sdErr[0] + 1) : nullptr;
+    static_assert(sizeof(NoiseSums) <= sizeof(float4), "the sums fit the first record of their image");
+    SURF_CHECK(c, hipMemsetAsync(dSums, 0, sizeof(NoiseSums), c->stream));
+    hipLaunchKernelGGL(k_noise, dim3((npx + 255) / 256), dim3(256), 0, c->stream, A, Q, npx, P.threshold, P.floor, dErr, dSums);
+    SURF_CHECK(c, hipGetLastError());
+    NoiseSums hs{};
+    SURF_CHECK(c, hipMemcpyAsync(&hs, dSums, sizeof hs, hipMemcpyDeviceToHost, c->stream));
+    if (outErr) SURF_CHECK(c, hipMemcpyAsync(outErr, dErr, (size_t)npx * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    SURF_CHECK(c, hipStreamSynchronize(c->stream));
+    sum->pixels = npx;
+    sum->above = hs.above;
+    std::memcpy(&sum->max_error, &hs.maxBits, sizeof(float));
+    sum->_pad = 0;
+    return SURF_OK;
+}
+
 }  // namespace
 
 void surfhost::freeSvgf(surf_ctx* c) {
+    for (float4** planes : {c->sdVar, c->sdErr})
+        if (planes[0]) { (void)hipFree(planes[0]); planes[0] = nullptr; }
+    for (float4*& p : c->sdAQ) { if (p) (void)hipFree(p); p = nullptr; }
+    for (float4*& p : c->sdIn) { if (p) (void)hipFree(p); p = nullptr; }
+    for (auto& e : c->sdEv) { if (e) (void)hipEventDestroy(e); e = nullptr; }
+    c->sdVarCap = c->sdErrCap = c->sdAQCap = c->sdInCap = 0;
     for (float4*& p : c->sv) { if (p) (void)hipFree(p); p = nullptr; }
     for (float4*& p : c->svIn) { if (p) (void)hipFree(p); p = nullptr; }
     for (float4*& p : c->ff) { if (p) (void)hipFree(p); p = nullptr; }
@@ -489,6 +612,138 @@ int surf_firefly_image_host(uint32_t w, uint32_t h, const float* acc, const floa
 int surf_debug_firefly_time(surf_ctx* c, float* kernel_ms) {
     if (!c || !kernel_ms) return SURF_ERR_INVALID;
     *kernel_ms = c->ffMs;
+    return SURF_OK;
+}
+
+int surf_denoise_sampled(surf_ctx* c, const surf_svgf_params* sp, float* out) { return sampledContext(c, sp, out, hipMemcpyDeviceToHost); }
+
+int surf_denoise_sampled_copy_device(surf_ctx* c, const surf_svgf_params* sp, void* dst) {
+    return sampledContext(c, sp, dst, hipMemcpyDeviceToDevice);
+}
+
+int surf_denoise_sampled_image(surf_ctx* c, uint32_t w, uint32_t h, const float* acc, const float* squares, const float* position,
+                               const float* normal, const float* albedo, const surf_svgf_params* sp, float* out, float* outVar) {
+    if (!c) return SURF_ERR_INVALID;
+    if (const char* why = sampledFrameError(w, h, acc, squares, position, normal, albedo, out, outVar))
+        return fail(c, SURF_ERR_INVALID, std::string("surf_denoise_sampled_image: ") + why);
+    if (const char* why = svgfParamError(sp, false)) return fail(c, SURF_ERR_INVALID, std::string("surf_denoise_sampled_image: ") + why);
+    SURF_CHECK(c, hipSetDevice(c->device));
+    const size_t npx = (size_t)w * h, bytes = npx * sizeof(float4);
+    int rc = growImages(c, c->sdAQ, 2, c->sdAQCap, npx);
+    if (rc) return rc;
+    if ((rc = growImages(c, c->sdIn, 3, c->sdInCap, npx))) return rc;
+    float4* const dst[5] = {c->sdAQ[0], c->sdAQ[1], c->sdIn[0], c->sdIn[1], c->sdIn[2]};
+    const float* src[5] = {acc, squares, position, normal, albedo};
+    for (int k = 0; k < 5; ++k) SURF_CHECK(c, hipMemcpyAsync(dst[k], src[k], bytes, hipMemcpyHostToDevice, c->stream));
+    const float4* res = nullptr;
+    if ((rc = runSampled(c, w, h, dst[0], dst[1], dst[2], dst[3], dst[4], *sp, &res))) return rc;
+    std::vector<float> var(2 * npx);
+    SURF_CHECK(c, hipMemcpyAsync(out, res, bytes, hipMemcpyDeviceToHost, c->stream));
+    SURF_CHECK(c, hipMemcpyAsync(var.data(), c->sdVar[0], var.size() * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    SURF_CHECK(c, hipStreamSynchronize(c->stream));
+    interleaveVariance(var, npx, outVar);
+    return SURF_OK;
+}
+
+/* The CPU twin: sampledLevel0, denoisePixelVar and svgfStore compiled for the host, on host arrays. */
+int surf_denoise_sampled_image_host(uint32_t w, uint32_t h, const float* acc, const float* squares, const float* position, const float* normal,
+                                    const float* albedo, const surf_svgf_params* sp, float* out, float* outVar) {
+    if (const char* why = sampledFrameError(w, h, acc, squares, position, normal, albedo, out, outVar))
+        return fail(nullptr, SURF_ERR_INVALID, std::string("surf_denoise_sampled_image_host: ") + why);
+    if (const char* why = svgfParamError(sp, false)) return fail(nullptr, SURF_ERR_INVALID, std::string("surf_denoise_sampled_image_host: ") + why);
+    const size_t npx = (size_t)w * h;
+    const SvgfConsts S = svgfConsts(*sp);
+    const uint32_t demod = sp->demodulate ? 1u : 0u;
+    auto plane = [npx](const float* src) {                       /* the caller's planes need not be 16-byte aligned */
+        std::vector<float4> v(npx);
+        std::memcpy(v.data(), src, npx * sizeof(float4));
+        return v;
+    };
+    const std::vector<float4> A = plane(acc), Q = plane(squares), Ps = plane(position), Ns = plane(normal), Al = plane(albedo);
+    std::vector<float4> gN(npx), gP(npx), lvl[2] = {std::vector<float4>(npx), std::vector<float4>(npx)};
+    std::vector<float> var(2 * npx, 0.0f);
+    for (size_t q = 0; q < npx; ++q) {
+        gN[q] = make_float4(Ns[q].x, Ns[q].y, Ns[q].z, Al[q].w != 0.0f ? 1.0f : 0.0f);
+        gP[q] = make_float4(Ps[q].x, Ps[q].y, Ps[q].z, 0.0f);
+        lvl[0][q] = sampledLevel0(A[q], Q[q], Al[q], demod);
+        var[q] = lvl[0][q].w;
+    }
+    for (uint32_t i = 0; i < sp->iterations; ++i) {
+        const int s = 1 << i;
+        const bool last = i + 1 == sp->iterations;
+        const std::vector<float4>& I = lvl[i & 1];
+        std::vector<float4>& O = lvl[(i & 1) ^ 1];
+        const DenoiseFetchPlanes fetch{I.data(), gN.data(), gP.data(), (int)w};
+        for (int y = 0; y < (int)h; ++y)
+            for (int x = 0; x < (int)w; ++x) {
+                const size_t q = (size_t)y * w + x;
+                const bool valid = gN[q].w != 0.0f;
+                float4 f = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+                if (valid) f = denoisePixelVar(x, y, (int)w, (int)h, s, S, I[q], gN[q], gP[q], fetch);
+                float v1;
+                O[q] = svgfStore(valid, I[q], f, last, Al[q], demod, v1);
+                if (last) var[npx + q] = v1;
+            }
+    }
+    std::memcpy(out, lvl[sp->iterations & 1].data(), npx * sizeof(float4));
+    interleaveVariance(var, npx, outVar);
+    return SURF_OK;
+}
+
+int surf_debug_sampled_time(surf_ctx* c, float* kernel_ms, uint32_t count) {
+    if (!c || !kernel_ms) return SURF_ERR_INVALID;
+    for (uint32_t k = 0; k < count; ++k) kernel_ms[k] = k <= (uint32_t)kDenoiseMaxIterations ? c->sdMs[k] : 0.0f;
+    return SURF_OK;
+}
+
+int surf_noise_default_params(surf_noise_params* p) {
+    if (!p) return SURF_ERR_INVALID;
+    std::memset(p, 0, sizeof *p);
+    p->threshold = 0.05f;
+    p->floor = 0.01f;
+    return SURF_OK;
+}
+
+int surf_noise_estimate(surf_ctx* c, const surf_noise_params* p, float* outErr, surf_noise_summary* sum) {
+    if (!c || !sum) return SURF_ERR_INVALID;
+    if (const char* why = noiseParamError(p)) return fail(c, SURF_ERR_INVALID, std::string("surf_noise_estimate: ") + why);
+    if (!c->sqOn) return fail(c, SURF_ERR_INVALID, "surf_noise_estimate: sample squares are off (surf_set_sample_squares)");
+    SURF_CHECK(c, hipSetDevice(c->device));
+    int rc = drainStream(c);
+    if (rc) return rc;
+    return runNoise(c, c->npx, c->acc, c->sq, *p, outErr, sum);
+}
+
+int surf_noise_image(surf_ctx* c, uint32_t npx, const float* acc, const float* squares, const surf_noise_params* p, float* outErr,
+                     surf_noise_summary* sum) {
+    if (!c || !acc || !squares || !sum) return SURF_ERR_INVALID;
+    if (npx == 0 || npx > (1u << 31)) return fail(c, SURF_ERR_INVALID, "surf_noise_image: no pixels or too many");
+    if (const char* why = noiseParamError(p)) return fail(c, SURF_ERR_INVALID, std::string("surf_noise_image: ") + why);
+    SURF_CHECK(c, hipSetDevice(c->device));
+    int rc = growImages(c, c->sdAQ, 2, c->sdAQCap, npx);
+    if (rc) return rc;
+    SURF_CHECK(c, hipMemcpyAsync(c->sdAQ[0], acc, (size_t)npx * sizeof(float4), hipMemcpyHostToDevice, c->stream));
+    SURF_CHECK(c, hipMemcpyAsync(c->sdAQ[1], squares, (size_t)npx * sizeof(float4), hipMemcpyHostToDevice, c->stream));
+    return runNoise(c, npx, c->sdAQ[0], c->sdAQ[1], *p, outErr, sum);
+}
+
+/* The CPU twin: noiseError, noiseAbove and noiseMax compiled for the host. */
+int surf_noise_image_host(uint32_t npx, const float* acc, const float* squares, const surf_noise_params* p, float* outErr,
+                          surf_noise_summary* sum) {
+    if (!acc || !squares || !sum) return fail(nullptr, SURF_ERR_INVALID, "surf_noise_image_host: NULL argument");
+    if (npx == 0 || npx > (1u << 31)) return fail(nullptr, SURF_ERR_INVALID, "surf_noise_image_host: no pixels or too many");
+    if (const char* why = noiseParamError(p)) return fail(nullptr, SURF_ERR_INVALID, std::string("surf_noise_image_host: ") + why);
+    std::memset(sum, 0, sizeof *sum);
+    sum->pixels = npx;
+    for (size_t q = 0; q < npx; ++q) {
+        float4 A, Q;                                             /* the caller's planes need not be 16-byte aligned */
+        std::memcpy(&A, acc + 4 * q, sizeof A);
+        std::memcpy(&Q, squares + 4 * q, sizeof Q);
+        const float e = noiseError(A, Q, p->floor);
+        if (outErr) outErr[q] = e;
+        if (noiseAbove(e, p->threshold)) ++sum->above;
+        sum->max_error = noiseMax(sum->max_error, e);
+    }
     return SURF_OK;
 }
 

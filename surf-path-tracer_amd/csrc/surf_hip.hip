@@ -160,6 +160,9 @@ auto atrousKernel(bool staged, int s) {
                   staged ? (size_t)3 * sizeof(float4) * (kDenoiseTileW + 4 * s) * (kDenoiseTileH + 4 * s) : 0);
 }
 
+/* k_accumulate<SQUARES>: the squares plane rides the sum where surf_set_sample_squares switched it on */
+auto accumulateKernel(const surf_ctx* c) { return c->sqOn ? k_accumulate<true> : k_accumulate<false>; }
+
 int allocWavefront(surf_ctx* c) {
     if (c->allocated) return SURF_OK;
     if (c->capacity == 0) {
@@ -746,9 +749,21 @@ int consumeSnap(surf_ctx* c) {
     if (f == c->accPasses) return SURF_OK;
     const uint32_t count = (uint32_t)(f - c->accPasses);
     const uint32_t threads = std::max<uint32_t>(c->npx, count * kStripes);
-    hipLaunchKernelGGL(k_accumulate, dim3((threads + kBlock - 1) / kBlock), dim3(kBlock), 0, c->stream, (const float4*)c->rad,
-                       c->acc, c->npx, (unsigned long long)c->accPasses, count, c->window, c->frameDone);
+    if (c->profiling) {                                /* events of its own: ev0 / ev1 bracket the drain this launch runs inside */
+        for (auto& e : c->accEv)
+            if (!e) SURF_CHECK(c, hipEventCreate(&e));
+        SURF_CHECK(c, hipEventRecord(c->accEv[0], c->stream));
+    }
+    hipLaunchKernelGGL(accumulateKernel(c), dim3((threads + kBlock - 1) / kBlock), dim3(kBlock), 0, c->stream, (const float4*)c->rad,
+                       c->acc, c->npx, (unsigned long long)c->accPasses, count, c->window, c->frameDone, c->sqOn ? c->sq : nullptr);
     SURF_CHECK(c, hipGetLastError());
+    if (c->profiling) {                                /* surf_stats.ms_accum; profiling waits for every launch anyway */
+        SURF_CHECK(c, hipEventRecord(c->accEv[1], c->stream));
+        SURF_CHECK(c, hipEventSynchronize(c->accEv[1]));
+        float ms = 0;
+        (void)hipEventElapsedTime(&ms, c->accEv[0], c->accEv[1]);
+        c->stats.ms_accum += ms;
+    }
     c->accPasses = f;
     return pushLimit(c);
 }
@@ -1205,6 +1220,8 @@ void surf_destroy(surf_ctx* c) {
     if (c->hPhaseN) (void)hipHostFree(c->hPhaseN);
     if (c->phaseLog) std::fclose(c->phaseLog);
     if (c->acc) (void)hipFree(c->acc);
+    if (c->sq) (void)hipFree(c->sq);
+    for (auto& e : c->accEv) if (e) (void)hipEventDestroy(e);
     for (void*& p : c->aov) { if (p) (void)hipFree(p); p = nullptr; }
     for (float4*& p : c->dn) { if (p) (void)hipFree(p); p = nullptr; }
     for (float4*& p : c->dnIn) { if (p) (void)hipFree(p); p = nullptr; }
@@ -1430,6 +1447,7 @@ int surf_clear_accumulator(surf_ctx* c) {
     int rc = endStream(c);
     if (rc) return rc;
     SURF_CHECK(c, hipMemsetAsync(c->acc, 0, (size_t)c->npx * sizeof(float4), c->stream));
+    if (c->sq) SURF_CHECK(c, hipMemsetAsync(c->sq, 0, (size_t)c->npx * sizeof(float4), c->stream));
     SURF_CHECK(c, hipStreamSynchronize(c->stream));
     c->totalSamples = 0;
     std::memset(&c->stats, 0, sizeof c->stats);
@@ -1458,6 +1476,43 @@ int surf_copy_accumulator_device(surf_ctx* c, void* dst) {
     SURF_CHECK(c, hipStreamSynchronize(c->stream));
     return SURF_OK;
 }
+
+int surf_set_sample_squares(surf_ctx* c, int enabled) {
+    if (!c) return SURF_ERR_INVALID;
+    SURF_CHECK(c, hipSetDevice(c->device));
+    int rc = ensureDrained(c);
+    if (rc) return rc;
+    if (c->totalSamples != 0)
+        return fail(c, SURF_ERR_INVALID, "surf_set_sample_squares: the accumulator holds samples whose squares are lost; call "
+                                         "surf_clear_accumulator first");
+    if (enabled && !c->sq) {
+        if (hipMalloc(&c->sq, (size_t)c->npx * sizeof(float4)) != hipSuccess || !c->sq) {
+            c->sq = nullptr;
+            (void)hipGetLastError();
+            return fail(c, SURF_ERR_OOM, "hipMalloc of the squares plane (" + std::to_string((size_t)c->npx * sizeof(float4)) + " bytes) failed");
+        }
+        SURF_CHECK(c, hipMemsetAsync(c->sq, 0, (size_t)c->npx * sizeof(float4), c->stream));
+        SURF_CHECK(c, hipStreamSynchronize(c->stream));
+    }
+    c->sqOn = enabled != 0;
+    return SURF_OK;
+}
+
+/* surf_read_sample_squares / surf_copy_sample_squares_device */
+static int copySquares(surf_ctx* c, void* dst, hipMemcpyKind kind) {
+    if (!c || !dst) return SURF_ERR_INVALID;
+    SURF_CHECK(c, hipSetDevice(c->device));
+    int rc = ensureDrained(c);
+    if (rc) return rc;
+    if (!c->sqOn) return fail(c, SURF_ERR_INVALID, "sample squares are off (surf_set_sample_squares)");
+    SURF_CHECK(c, hipMemcpyAsync(dst, c->sq, (size_t)c->npx * sizeof(float4), kind, c->stream));
+    SURF_CHECK(c, hipStreamSynchronize(c->stream));
+    return SURF_OK;
+}
+
+int surf_read_sample_squares(surf_ctx* c, float* out) { return copySquares(c, out, hipMemcpyDeviceToHost); }
+
+int surf_copy_sample_squares_device(surf_ctx* c, void* dst) { return copySquares(c, dst, hipMemcpyDeviceToDevice); }
 
 int surf_read_aov(surf_ctx* c, int plane, void* out) {
     if (!c || !out || plane < 0 || plane >= SURF_AOV_COUNT) return SURF_ERR_INVALID;

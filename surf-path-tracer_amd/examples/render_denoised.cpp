@@ -10,7 +10,11 @@
  * Writes PREFIX_noisy.pfm (radiance sum over sample count) and
  * PREFIX_denoised.pfm (colour PFM, surf_write_pfm), and PREFIX_denoised.png:
  * the denoised image as the application would present it (surf_pack_rgba8
- * with the display gamma).
+ * with the display gamma).  With SPP >= 2 also PREFIX_sampled.pfm: the same
+ * accumulator through the sample-variance-guided filter
+ * (WaveFrontRenderer::denoiseSampled, surf_denoise_sampled), for which the
+ * render keeps the per-sample second moments (setSampleSquares); the other
+ * outputs are what they are without it.
  */
 #include "surf/surf_host.hpp"
 #include "indoor_scene.hpp"
@@ -38,6 +42,8 @@ int main(int argc, char** argv) {
         RendererConfig config;
         config.samplesPerFrame = (U32)spp;
         WaveFrontRenderer renderer(&context, nullptr, config, FramebufferSize{W, H}, worldCam, *indoor.scene);
+        const bool sampled = spp >= 2;    /* one sample has no variance */
+        if (sampled) renderer.setSampleSquares(true);
         renderer.render(0.0f);
 
         std::vector<F32> noisy = renderer.readAccumulator();
@@ -57,6 +63,11 @@ int main(int argc, char** argv) {
                            surf_write_png(paths[2].c_str(), W, H, rgba8.data())};
         for (int k = 0; k < 3; ++k)
             if (rc[k] != SURF_OK) { std::fprintf(stderr, "cannot write %s\n", paths[k].c_str()); return 1; }
+        if (sampled) {
+            const std::string path = prefix + "_sampled.pfm";
+            const std::vector<F32> guided = renderer.denoiseSampled();
+            if (surf_write_pfm(path.c_str(), W, H, guided.data()) != SURF_OK) { std::fprintf(stderr, "cannot write %s\n", path.c_str()); return 1; }
+        }
         std::printf("{\"width\": %u, \"height\": %u, \"spp\": %d}\n", W, H, spp);
     } catch (const std::exception& e) {
         std::fprintf(stderr, "render_denoised: %s\n", e.what());

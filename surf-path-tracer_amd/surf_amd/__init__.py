@@ -17,6 +17,9 @@ Mirrors the reference interface for the hot path:
     .temporal()                temporal accumulation with reprojection across cleared frames (no reference counterpart)
     .svgf()                    the same with luminance moments, their variance guiding the a-trous filter (no reference counterpart);
                                firefly_scale= and feedback= switch on the firefly clamp and the filtered-history feedback
+    .set_sample_squares(on)    per-sample second moments beside the accumulator, .sample_squares() reads them (no reference counterpart)
+    .denoise_sampled()         the a-trous filter guided by each pixel's own sample variance, for stills from about 16 spp
+    .noise_estimate()          per-pixel relative standard error of the mean luminance and its summary
 """
 from __future__ import annotations
 
@@ -125,6 +128,19 @@ class SvgfPrev(C.Structure):
     _fields_ = TemporalPrev._fields_ + [("moments", C.c_void_p)]
 
 
+class NoiseParams(C.Structure):
+    """surf_noise_params: the threshold a pixel's relative standard error is counted against and the floor under its mean luminance."""
+    _fields_ = [("threshold", C.c_float), ("floor", C.c_float)]
+
+
+class NoiseSummary(C.Structure):
+    """surf_noise_summary: pixels looked at, pixels above the threshold, the largest error."""
+    _fields_ = [("pixels", C.c_uint64), ("above", C.c_uint64), ("max_error", C.c_float), ("_pad", C.c_uint32)]
+
+    def as_dict(self) -> dict:
+        return {"pixels": int(self.pixels), "above": int(self.above), "max_error": float(self.max_error)}
+
+
 _lib = None
 
 # Byte sizes of the reference records (include/surf_hip.h static_asserts).
@@ -210,6 +226,17 @@ def load() -> C.CDLL:
         "surf_firefly_image": ([P, U32, U32, P, P, U32, F, P], I32),
         "surf_firefly_image_host": ([U32, U32, P, P, U32, F, P], I32),
         "surf_debug_firefly_time": ([P, C.POINTER(F)], I32),
+        "surf_set_sample_squares": ([P, I32], I32), "surf_read_sample_squares": ([P, P], I32),
+        "surf_copy_sample_squares_device": ([P, P], I32),
+        "surf_denoise_sampled": ([P, C.POINTER(SvgfParams), P], I32),
+        "surf_denoise_sampled_copy_device": ([P, C.POINTER(SvgfParams), P], I32),
+        "surf_denoise_sampled_image": ([P, U32, U32, P, P, P, P, P, C.POINTER(SvgfParams), P, P], I32),
+        "surf_denoise_sampled_image_host": ([U32, U32, P, P, P, P, P, C.POINTER(SvgfParams), P, P], I32),
+        "surf_debug_sampled_time": ([P, C.POINTER(F), U32], I32),
+        "surf_noise_default_params": ([C.POINTER(NoiseParams)], I32),
+        "surf_noise_estimate": ([P, C.POINTER(NoiseParams), P, C.POINTER(NoiseSummary)], I32),
+        "surf_noise_image": ([P, U32, P, P, C.POINTER(NoiseParams), P, C.POINTER(NoiseSummary)], I32),
+        "surf_noise_image_host": ([U32, P, P, C.POINTER(NoiseParams), P, C.POINTER(NoiseSummary)], I32),
         "surf_mesh_data": ([P, C.POINTER(P), C.POINTER(P), C.POINTER(U32)], I32),
         "surf_mesh_destroy": ([P], None),
         "surf_ref_sinf": ([F], F), "surf_ref_cosf": ([F], F), "surf_ref_expf": ([F], F),
@@ -594,6 +621,60 @@ def svgf_image_host(cur, prev, **params):
     return tuple(res)
 
 
+def _sampled_params(params) -> SvgfParams:
+    """svgf_params for the sample-variance-guided filter: spatial_below is ignored there and not accepted."""
+    if "spatial_below" in params:
+        raise TypeError("the sample-variance-guided filter has no spatial_below")
+    return svgf_params(**params)
+
+
+def _sampled_planes(acc, squares, planes):
+    """(w, h, [acc, squares, position, normal, albedo]) as contiguous (H, W, 4) float32; planes as _denoise_planes takes them."""
+    w, h, a = _denoise_planes(acc, planes)
+    q = np.ascontiguousarray(squares, dtype=np.float32)
+    if q.shape != a[0].shape:
+        raise ValueError(f"squares plane {q.shape} is not {a[0].shape}")
+    return w, h, [a[0], q, a[1], a[2], a[3]]
+
+
+def denoise_sampled_image_host(acc, squares, planes, **params):
+    """The CPU twin of Renderer.denoise_sampled_image (surf_denoise_sampled_image_host):
+    bit-identical, no device.  Returns (out, variance), each (H, W, 4) float32."""
+    w, h, a = _sampled_planes(acc, squares, planes)
+    p = _sampled_params(params)
+    out, var = np.zeros((h, w, 4), np.float32), np.zeros((h, w, 4), np.float32)
+    _check(load().surf_denoise_sampled_image_host(w, h, *[_ptr(x) for x in a], C.byref(p), _ptr(out), _ptr(var)),
+           "surf_denoise_sampled_image_host")
+    return out, var
+
+
+def noise_params(threshold=None, floor=None) -> NoiseParams:
+    """surf_noise_default_params (threshold 0.05, floor 0.01) with the given fields replaced."""
+    p = NoiseParams()
+    _check(load().surf_noise_default_params(C.byref(p)), "surf_noise_default_params")
+    if threshold is not None:
+        p.threshold = float(threshold)
+    if floor is not None:
+        p.floor = float(floor)
+    return p
+
+
+def _noise_planes(acc, squares):
+    a, q = (np.ascontiguousarray(v, dtype=np.float32) for v in (acc, squares))
+    if a.ndim < 2 or a.shape[-1] != 4 or q.shape != a.shape:
+        raise ValueError(f"noise planes {a.shape}, {q.shape} are not two (..., 4) images of one size")
+    return a, q, np.zeros(a.shape[:-1], np.float32)
+
+
+def noise_image_host(acc, squares, threshold=None, floor=None):
+    """The CPU twin of Renderer.noise_image (surf_noise_image_host): (error image,
+    summary dict) of planes of any shape (..., 4); bit-identical, no device."""
+    a, q, err = _noise_planes(acc, squares)
+    p, s = noise_params(threshold, floor), NoiseSummary()
+    _check(load().surf_noise_image_host(err.size, _ptr(a), _ptr(q), C.byref(p), _ptr(err), C.byref(s)), "surf_noise_image_host")
+    return err, s.as_dict()
+
+
 def obj_load(path: str, threads: int = 0) -> tuple[np.ndarray, np.ndarray]:
     """Mesh(path) (mesh.cpp:69-154): parallel tinyobj-compatible OBJ/OBJ.GZ parse.
     Returns ((n, 16) float32 Triangle records, (n, 20) float32 TriExtension
@@ -955,6 +1036,71 @@ class Renderer:
         ms = (C.c_float * 8)()
         _check(load().surf_debug_svgf_time(self._h, ms, 8), "surf_debug_svgf_time", self._h)
         return [float(v) for v in ms]
+
+    def set_sample_squares(self, on: bool):
+        """Switches the per-sample second moments on or off (surf_set_sample_squares): with
+        them on every sample's squares are summed beside the accumulator.  Raises
+        SURF_ERR_INVALID unless the accumulator is empty (new, or just cleared)."""
+        _check(load().surf_set_sample_squares(self._h, 1 if on else 0), "surf_set_sample_squares", self._h)
+
+    def sample_squares(self) -> np.ndarray:
+        """The squares plane of this shard's rows (surf_read_sample_squares): (rows, width, 4)
+        float32, (sum r^2, sum g^2, sum b^2, sum lum^2) over the samples."""
+        out = np.zeros((len(self.rows), self.width, 4), dtype=np.float32)
+        _check(load().surf_read_sample_squares(self._h, _ptr(out)), "surf_read_sample_squares", self._h)
+        return out
+
+    def copy_sample_squares_to(self, device_ptr: int):
+        _check(load().surf_copy_sample_squares_device(self._h, C.c_void_p(device_ptr)), "surf_copy_sample_squares_device", self._h)
+
+    def denoise_sampled(self, **params) -> np.ndarray:
+        """The accumulated radiance through the sample-variance-guided filter
+        (surf_denoise_sampled; svgf_params' names without spatial_below): the a-trous
+        filter whose colour width is each pixel's own sample variance of the mean,
+        for stills from about 16 samples per pixel.  (H, W, 4) float32 with w = 1.
+        Needs set_sample_squares(True) before the samples; raises SURF_ERR_INVALID
+        on a row shard (see denoise_sampled_image)."""
+        p = _sampled_params(params)
+        out = np.zeros((self.height, self.width, 4), dtype=np.float32)
+        _check(load().surf_denoise_sampled(self._h, C.byref(p), _ptr(out)), "surf_denoise_sampled", self._h)
+        return out
+
+    def denoise_sampled_image(self, acc, squares, planes, **params):
+        """The same filter on host planes of any full frame (surf_denoise_sampled_image).
+        Returns (out, variance): variance x entering the filter, y leaving it."""
+        w, h, a = _sampled_planes(acc, squares, planes)
+        p = _sampled_params(params)
+        out, var = np.zeros((h, w, 4), np.float32), np.zeros((h, w, 4), np.float32)
+        _check(load().surf_denoise_sampled_image(self._h, w, h, *[_ptr(x) for x in a], C.byref(p), _ptr(out), _ptr(var)),
+               "surf_denoise_sampled_image", self._h)
+        return out, var
+
+    def copy_denoise_sampled_to(self, device_ptr: int, **params):
+        p = _sampled_params(params)
+        _check(load().surf_denoise_sampled_copy_device(self._h, C.byref(p), C.c_void_p(device_ptr)), "surf_denoise_sampled_copy_device",
+               self._h)
+
+    def debug_sampled_time(self) -> list:
+        """Device milliseconds of the last sampled run's kernels (surf_debug_sampled_time): level 0, then each iteration."""
+        ms = (C.c_float * 7)()
+        _check(load().surf_debug_sampled_time(self._h, ms, 7), "surf_debug_sampled_time", self._h)
+        return [float(v) for v in ms]
+
+    def noise_estimate(self, threshold=None, floor=None, image: bool = True):
+        """(error image, summary dict) of this shard's rows (surf_noise_estimate): per pixel the
+        relative standard error of its mean luminance (1e30 below two samples), and
+        {'pixels', 'above', 'max_error'}.  image=False: no image is written, None returned in its place."""
+        p, s = noise_params(threshold, floor), NoiseSummary()
+        err = np.zeros((len(self.rows), self.width), np.float32) if image else None
+        _check(load().surf_noise_estimate(self._h, C.byref(p), _ptr(err) if image else None, C.byref(s)), "surf_noise_estimate", self._h)
+        return err, s.as_dict()
+
+    def noise_image(self, acc, squares, threshold=None, floor=None):
+        """The same on host planes of any shape (..., 4) (surf_noise_image)."""
+        a, q, err = _noise_planes(acc, squares)
+        p, s = noise_params(threshold, floor), NoiseSummary()
+        _check(load().surf_noise_image(self._h, err.size, _ptr(a), _ptr(q), C.byref(p), _ptr(err), C.byref(s)), "surf_noise_image", self._h)
+        return err, s.as_dict()
 
     def copy_accumulator_to(self, device_ptr: int):
         _check(load().surf_copy_accumulator_device(self._h, C.c_void_p(device_ptr)), "surf_copy_accumulator_device", self._h)
