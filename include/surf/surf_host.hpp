@@ -378,6 +378,24 @@ public:
      * without arguments takes surf_noise_default_params and writes no image. */
     surf_noise_summary noiseEstimate(const surf_noise_params& params, std::vector<F32>* error = nullptr);
     surf_noise_summary noiseEstimate();
+    /* the active-pixel mask (surf_set_pixel_mask): width*height bytes, nonzero = active, render()
+     * then traces those pixels only; an empty vector = every pixel.  pixelMask: the mask as set and,
+     * where asked for, its active count. */
+    void setPixelMask(const std::vector<uint8_t>& mask);
+    std::vector<uint8_t> pixelMask(U32* activeCount = nullptr);
+    /* builds the mask from the noise estimate and sets it (surf_mask_from_noise); returns the active
+     * count.  Needs setSampleSquares(true). */
+    U32 maskFromNoise(const surf_adaptive_mask_params& params);
+    /* renders until converged (surf_render_adaptive, whose header comment defines the loop): 1-sample
+     * frames from the renderer's next sample index on an empty accumulator, with
+     * setSampleSquares(true); the camera and the scene are pushed first, as render() pushes them.
+     * roundActive non-NULL: the active count of each round.  params' first_sample_index and
+     * max_segments are replaced by the renderer's.  The form without arguments takes
+     * surf_adaptive_default_params. */
+    surf_adaptive_summary renderAdaptive(const surf_adaptive_params& params, std::vector<U32>* roundActive = nullptr);
+    surf_adaptive_summary renderAdaptive();
+    /* RGBA8 with each pixel divided by its own sample count (surf_finalize_rgba8_weighted) */
+    std::vector<U32> finalizeWeighted(bool display = false);
     /* clearAccumulator() for that loop: the next render() goes on with the sample indices after
      * those already rendered instead of repeating the cleared frame's sample stream (a plain
      * clearAccumulator() starts again from sample 0, as the reference does) */

@@ -930,6 +930,122 @@ int surf_noise_image(surf_ctx* ctx, uint32_t npx, const float* acc, const float*
 int surf_noise_image_host(uint32_t npx, const float* acc, const float* squares, const surf_noise_params* params, float* out_error,
                           surf_noise_summary* summary);
 
+/* ---- per-pixel sample masks and the adaptive loop (no reference counterpart) ----
+ * A context carries an active-pixel mask: one byte per pixel of the shard in
+ * shard order (rows*width), nonzero = active.  After surf_create* and after
+ * surf_clear_accumulator every pixel is active.  With a mask set,
+ * surf_render(frames, first_sample_index, max_segments, spp) issues only the
+ * active pixels' chains; frame k is still seeded initSeed(p + 1799 *
+ * (first_sample_index + k*spp)), so an active pixel receives exactly the
+ * samples it would receive without a mask, bit for bit, and an inactive
+ * pixel's accumulator and squares records stay untouched: its w does not
+ * advance.  surf_stats.samples and the event counters count what was traced.
+ * An all-ones mask is no mask (the same kernels, counters and issue order); an
+ * all-zero mask makes surf_render return SURF_OK and change nothing.  Setting
+ * a mask drains and ends the open stream, as a change of spp does.  Camera,
+ * scene and instance updates keep the mask.
+ * surf_finalize_rgba8, surf_display_rgba8 and surf_stats.energy keep dividing
+ * by the context's frame count -- the frames requested of surf_render since the
+ * last clear, whatever the mask was: under a mask that is no pixel's mean but a
+ * stale pixel's.  surf_finalize_rgba8_weighted divides each pixel by its own w.
+ * Device side: the mask is compacted to the ascending list of active local
+ * pixels (4 B per pixel, allocated on first use beside the 1 B per pixel of
+ * the mask); a masked stream issues frame-major over the list and accumulates
+ * through it, sample ids and the radiance ring are those of the full shard.
+ *
+ * The mask from the noise estimate.  Parameters: threshold and floor finite
+ * and > 0, min_samples >= 2, max_samples >= min_samples, dilate in 0..2.  With
+ * e(p) the noise estimate's error of pixel p (above) at `floor`:
+ *   raw(p)    = !(A.w >= (float)min_samples) || !(e(p) <= threshold)
+ *               (a NaN counts as noisy; n < 2 gives e = 1e30)
+ *   active(p) = (some q with |dx| <= dilate, |dy| <= dilate inside the frame has raw(q))
+ *               && A(p).w < (float)max_samples
+ *   mask byte = active ? 1 : 0;  list = the active pixels' indices y*w + x, ascending
+ * The dilation exists because the estimate is itself noisy: a lone pixel that
+ * stops early shows as a speckle.
+ * Launches: the flags kernel, 256 threads per 32 x 8 tile -- the raw flags of
+ * the tile and its halo of `dilate` go to LDS (up to 36 x 12 bytes; 32 B read
+ * per texel), then one byte is written per pixel -- and an order-preserving
+ * compaction of the byte mask: per 256-pixel block a count (ballot and
+ * popcount per wave), one block that scans the block counts, and a scatter
+ * that repeats the ballots and writes each active index at block offset + wave
+ * offset + its rank in the wave.  No atomic: the list does not depend on the
+ * order the blocks arrive in.  1 B in twice and 4 B out per active pixel. */
+typedef struct {
+    float threshold, floor;
+    uint32_t min_samples, max_samples, dilate, _pad[3];
+} surf_adaptive_mask_params;
+/* mask: rows*width bytes, NULL = every pixel.  Drains and ends the stream.
+ * SURF_ERR_INVALID for a NULL context, SURF_ERR_OOM when the mask's buffers
+ * cannot be allocated. */
+int surf_set_pixel_mask(surf_ctx* ctx, const uint8_t* mask);
+/* out_mask (rows*width bytes of 0 / 1, may be NULL) and the active count
+ * (rows*width without a mask).  Reads what is set; drains nothing. */
+int surf_get_pixel_mask(surf_ctx* ctx, uint8_t* out_mask, uint32_t* active_count);
+/* threshold 0.05, floor 0.01, min_samples 16, max_samples 1024, dilate 1 */
+int surf_adaptive_default_mask_params(surf_adaptive_mask_params* params);
+/* Builds the mask from the context's accumulator and squares and sets it; the
+ * planes, the mask and the list stay on the device, the count comes back.
+ * Drains and ends the stream.  SURF_ERR_INVALID for bad parameters, while the
+ * squares plane is off, and on a row shard when dilate > 0 -- a dilation needs
+ * its neighbours' rows (surf_last_error points to surf_adaptive_mask_image);
+ * with dilate == 0 it works per shard. */
+int surf_mask_from_noise(surf_ctx* ctx, const surf_adaptive_mask_params* params, uint32_t* active_count);
+/* Host planes of any w x h frame (w*h*4 floats each), e.g. one assembled from
+ * row shards.  mask_out: w*h bytes; list_out (w*h words, the first *count
+ * written) may be NULL.  Needs no scene and no squares plane; leaves the
+ * context's mask alone. */
+int surf_adaptive_mask_image(surf_ctx* ctx, uint32_t w, uint32_t h, const float* acc, const float* squares,
+                             const surf_adaptive_mask_params* params, uint8_t* mask_out, uint32_t* list_out, uint32_t* count);
+/* The CPU twin; needs no device.  Bit-identical to surf_adaptive_mask_image. */
+int surf_adaptive_mask_image_host(uint32_t w, uint32_t h, const float* acc, const float* squares,
+                                  const surf_adaptive_mask_params* params, uint8_t* mask_out, uint32_t* list_out, uint32_t* count);
+
+/* "Render until converged".  Needs the squares plane on and an empty
+ * accumulator (SURF_ERR_INVALID otherwise, as surf_set_sample_squares); renders
+ * 1-sample frames.  The definition, part of the interface:
+ *   1. mask = every pixel
+ *   2. render mask.min_samples frames from first_sample_index; f = min_samples
+ *   3. repeat: build the mask from the estimate (surf_mask_from_noise);
+ *              stop when no pixel is active or f == mask.max_samples;
+ *              nb = min(batch, max_samples - f);
+ *              render nb frames at first_sample_index + f under the mask; f += nb
+ *   4. the final mask stays set
+ * round_active[r] (the first min(rounds, round_cap) entries; may be NULL) is
+ * the active count round r of step 3 rendered with.  Summary: rounds (renders
+ * of step 3), frames = f, active_last (the final mask's count), samples (camera
+ * samples traced, step 2 included), noise (surf_noise_estimate's summary of the
+ * final state at mask.threshold and mask.floor).  batch >= 1 (default 64,
+ * the fastest of 8, 16, 32 and 64 at 1280 x 720: a round's drain costs about
+ * what 16 full frames do, MEASUREMENTS "Adaptive sampling").
+ * Known limits: stopping on an estimate made from the same samples biases the
+ * result slightly towards dark (pixels whose early samples happen to agree
+ * stop early); min_samples and dilate are the mitigation.  Each round drains
+ * the stream -- the drain is the long Russian-roulette tail -- so small batches
+ * cost throughput. */
+typedef struct {
+    surf_adaptive_mask_params mask;
+    uint32_t batch, max_segments, first_sample_index, _pad;
+} surf_adaptive_params;
+typedef struct {
+    uint32_t rounds, frames, active_last, _pad;
+    uint64_t samples;
+    surf_noise_summary noise;
+} surf_adaptive_summary;
+/* the mask defaults, batch 64, max_segments 0, first_sample_index 0 */
+int surf_adaptive_default_params(surf_adaptive_params* params);
+int surf_render_adaptive(surf_ctx* ctx, const surf_adaptive_params* params, uint32_t* round_active, uint32_t round_cap,
+                         surf_adaptive_summary* summary);
+
+/* RGBA8 of the accumulator with each pixel divided by its own sample count:
+ *   inv = A.w > 0 ? 1.0f/A.w : 0.0f;  channel k = packChannel((a_k*inv)*255.0f), alpha included
+ * (packChannel: surf_finalize_rgba8's rounding and saturation), and with
+ * display != 0 surf_display_rgba8's displayChannel on top of each.  Drains the
+ * stream.  One pointwise kernel, 16 B in and 4 B out per pixel. */
+int surf_finalize_rgba8_weighted(surf_ctx* ctx, int display, uint32_t* out_rgba8);
+/* The CPU twin on n records of a host plane; needs no device.  Bit-identical. */
+int surf_pack_rgba8_weighted(const float* acc, uint32_t n, int display, uint32_t* out_rgba8);
+
 /* ---- traversal entry points (kernel-level parity tests) ----
  * n world-space rays, o/d 3 floats each.  closest: depth starts at 1e30;
  * writes t,u,v (floats) and inst,prim (u32, ~0 on miss).  any: tmax per ray,

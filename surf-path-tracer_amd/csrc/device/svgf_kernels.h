@@ -269,7 +269,7 @@ struct FireflyFetchTile {
  * After the one barrier the 8 taps come from LDS: a row of 32 lanes reads 32
  * consecutive floats, conflict-free.  48 B of memory traffic per pixel.  One
  * variant: at 1.4 KB there is no LDS to trade against. */
-__global__ __launch_bounds__(256) void k_firefly(const float4* __restrict__ A, const float4* __restrict__ alb,
+static __global__ __launch_bounds__(256) void k_firefly(const float4* __restrict__ A, const float4* __restrict__ alb,
                                                  float4* __restrict__ out, int W, int H, float scale, uint32_t demodulate) {
     __shared__ float ffTile[kFireflyTileW * kFireflyTileH];
     const int tx = (int)(threadIdx.x & (kDenoiseTileW - 1)), ty = (int)(threadIdx.x / kDenoiseTileW);
@@ -314,7 +314,7 @@ __global__ __launch_bounds__(256) void k_firefly(const float4* __restrict__ A, c
 }
 
 /* Elementwise: the packed guides of n pixels, as denoisePrepare packs them. */
-__global__ __launch_bounds__(256) void k_svgf_guides(const float4* __restrict__ pos, const float4* __restrict__ nrm,
+static __global__ __launch_bounds__(256) void k_svgf_guides(const float4* __restrict__ pos, const float4* __restrict__ nrm,
                                                      const float4* __restrict__ alb, uint32_t n, float4* __restrict__ gN,
                                                      float4* __restrict__ gP) {
     const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;

@@ -6,6 +6,7 @@
  */
 #pragma once
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
 #include "lds_layout.h"
 
@@ -146,6 +147,10 @@ struct Counters {
      * sample k's path left -- so k_regen issues only the first sample of each
      * (frame, pixel) and the kernel that ends a sample's path starts the next */
     uint32_t spp;
+    /* masked streams (surf_set_pixel_mask): the length of the active-pixel list
+     * StreamGeom::perm then points to; k_regen<true> issues frame-major over it.
+     * Takes the word the 64-bit members' alignment left free: no other offset moves. */
+    uint32_t nActive;
     unsigned long long issued[2];    /* stream chains issued (first samples of (frame, pixel)), per parity */
     unsigned long long limit;        /* host-written issue limit (frame window) */
     unsigned long long baseFrame;    /* absolute frame index of stream frame 0 */
@@ -157,6 +162,7 @@ struct Counters {
     unsigned long long evS[32][16];
     unsigned long long dbg[8];       /* SURF_SEG_TIMING builds: k_tail_coop cycles (extend, shade, connect, segments) */
 };
+static_assert(offsetof(Counters, issued) == 56, "nActive fills the alignment gap in front of issued");
 constexpr uint32_t kStripes = 32;    /* frameDone and event-count stripes */
 constexpr int kEvents = 9;           /* event kinds counted (ev / evS index) */
 
@@ -167,7 +173,8 @@ constexpr int kEvents = 9;           /* event kinds counted (ev / evS index) */
 struct StreamGeom {
     const uint32_t* rows;            /* shard rows */
     uint32_t width, npx, window;
-    const uint32_t* perm;            /* local pixels, class A (Counters::permA of them) first */
+    const uint32_t* perm;            /* local pixels, class A (Counters::permA of them) first; a masked stream's
+                                        graph: the ascending active-pixel list (Counters::nActive of them) */
 };
 
 /* Record encodings the upload writes and the walks read */

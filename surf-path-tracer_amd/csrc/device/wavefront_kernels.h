@@ -2467,6 +2467,11 @@ struct RegenPlan {
     unsigned long long iss, base, f0, endA, endP;
     uint32_t spp;
 };
+/* MASKED (a stream under surf_set_pixel_mask): frame-major over the active
+ * list -- G.perm holds its Counters::nActive ascending local pixels -- so nA is
+ * the list's length, a frame counts nA chains and there is no permuted head.
+ * The other instantiation is the code it was before the mask existed. */
+template <bool MASKED = false>
 __device__ __forceinline__ RegenPlan regenPlan(const Counters* C, int par, uint32_t capacity, const StreamGeom& G) {
     RegenPlan R;
     R.cont = C->app[par];
@@ -2477,6 +2482,15 @@ __device__ __forceinline__ RegenPlan regenPlan(const Counters* C, int par, uint3
     const uint32_t room = capacity - R.cont;
     const unsigned long long left = lim > R.iss ? lim - R.iss : 0ull;
     R.nnew = (unsigned long long)room < left ? room : (uint32_t)left;
+    if (MASKED) {
+        /* frame / list index of the first new chain (nnew > 0 only where the list is not empty) */
+        R.nA = C->nActive; R.nB = 0u;
+        const uint32_t nA = R.nA ? R.nA : 1u;
+        R.f0 = R.iss / nA;
+        R.lp0 = (uint32_t)(R.iss - R.f0 * nA);
+        R.endA = R.endP = 0ull;
+        return R;
+    }
     /* frame / pixel of the first new chain, then step without 64-bit divisions */
     R.f0 = R.iss / G.npx;
     R.lp0 = (uint32_t)(R.iss - R.f0 * G.npx);
@@ -2486,11 +2500,18 @@ __device__ __forceinline__ RegenPlan regenPlan(const Counters* C, int par, uint3
     return R;
 }
 /* The k-th new chain's first sample into pool slot cont + k. */
+template <bool MASKED = false>
 __device__ __forceinline__ void regenSample(const DevCamera& cam, const Pool& nxt, float4* __restrict__ rad, const StreamGeom& G,
                                             const RegenPlan& R, uint32_t k) {
     uint32_t lp;
     unsigned long long f;
-    if (R.iss + k < R.endP) {
+    if (MASKED) {
+        /* 64-bit: lp0 + k stays below nA + capacity, which may pass 2^32 only in theory */
+        const unsigned long long i = (unsigned long long)R.lp0 + k;
+        const unsigned long long df = i / R.nA;
+        lp = G.perm[(uint32_t)(i - df * R.nA)];
+        f = R.f0 + df;
+    } else if (R.iss + k < R.endP) {
         const unsigned long long s = R.iss + k;
         if (s < R.endA) { f = s / R.nA; lp = G.perm[(uint32_t)(s - f * R.nA)]; }
         else { const unsigned long long j = s - R.endA; f = j / R.nB; lp = G.perm[R.nA + (uint32_t)(j - f * R.nB)]; }
@@ -2529,12 +2550,13 @@ __device__ __forceinline__ void regenCounters(Counters* C, int par, const RegenP
  * order: frame f's first sample is stream pass f * spp, seeded
  * initSeed(p + 1799 * (baseFrame + f * spp)) (renderer.cpp:169; baseFrame =
  * the sample count before the stream). */
+template <bool MASKED>
 __global__ __launch_bounds__(kBlock) void k_regen(DevCamera cam, Pool nxt, float4* __restrict__ rad, Counters* C, int par,
                                                   uint32_t capacity, StreamGeom G, ShadowQ Q) {
-    const RegenPlan R = regenPlan(C, par, capacity, G);
+    const RegenPlan R = regenPlan<MASKED>(C, par, capacity, G);
     const uint32_t gid = blockIdx.x * blockDim.x + threadIdx.x;
     if (gid < kShSegs) *shCursor(Q, par ^ 1, gid) = 0u;      /* the next phase's shadow-queue cursors */
-    for (uint32_t k = gid; k < R.nnew; k += gridDim.x * blockDim.x) regenSample(cam, nxt, rad, G, R, k);
+    for (uint32_t k = gid; k < R.nnew; k += gridDim.x * blockDim.x) regenSample<MASKED>(cam, nxt, rad, G, R, k);
     if (gid == 0) regenCounters(C, par, R);
 }
 
@@ -2545,11 +2567,12 @@ __global__ __launch_bounds__(kBlock) void k_regen(DevCamera cam, Pool nxt, float
  * samples (key kBins - 1), then writes the chunk's bin counts where k_bincount
  * would -- so the next phase's sort is k_binscatter alone, and one kernel
  * instead of two waits for CU slots beside k_connect. */
+template <bool MASKED>
 __global__ __launch_bounds__(kSortThreads) void k_regen_count(DevCamera cam, Pool nxt, float4* __restrict__ rad, Counters* C, int par,
                                                              uint32_t capacity, StreamGeom G, ShadowQ Q, uint32_t* __restrict__ hist) {
     __shared__ uint32_t h[kBins];
     if (threadIdx.x < kBins) h[threadIdx.x] = 0u;
-    const RegenPlan R = regenPlan(C, par, capacity, G);
+    const RegenPlan R = regenPlan<MASKED>(C, par, capacity, G);
     const uint32_t gid = blockIdx.x * blockDim.x + threadIdx.x;
     if (gid < kShSegs) *shCursor(Q, par ^ 1, gid) = 0u;      /* the next phase's shadow-queue cursors */
     __syncthreads();
@@ -2558,7 +2581,7 @@ __global__ __launch_bounds__(kSortThreads) void k_regen_count(DevCamera cam, Poo
     uint32_t cam0 = 0u;
     for (uint32_t i = a + threadIdx.x; i < b; i += blockDim.x) {
         if (i < R.cont) atomicAdd(&h[nxt.key[i]], 1u);
-        else { regenSample(cam, nxt, rad, G, R, i - R.cont); ++cam0; }
+        else { regenSample<MASKED>(cam, nxt, rad, G, R, i - R.cont); ++cam0; }
     }
     if (cam0) atomicAdd(&h[kBins - 1u], cam0);
     __syncthreads();
@@ -2986,6 +3009,37 @@ __global__ __launch_bounds__(kBlock) void k_accumulate(const float4* __restrict_
     if (SQUARES) sq[p] = q;
 }
 
+/* k_accumulate over the active list of a masked stream (surf_set_pixel_mask):
+ * thread i takes pixel list[i] of the n listed, every other pixel's records
+ * stay untouched -- w does not advance there.  The same sums in the same
+ * order, the same completion-stripe reset.  A kernel of its own beside
+ * k_accumulate, whose text and arguments stay what they were (DESIGN 4 "Masked streams"). */
+template <bool SQUARES>
+__global__ __launch_bounds__(kBlock) void k_accumulate_list(const float4* __restrict__ rad, float4* __restrict__ acc,
+                                                            uint32_t npx, unsigned long long f0, uint32_t count, uint32_t window,
+                                                            uint32_t* __restrict__ frameDone, float4* __restrict__ sq,
+                                                            const uint32_t* __restrict__ list, uint32_t n) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < count * kStripes) frameDone[(i % kStripes) * window + (uint32_t)((f0 + i / kStripes) % window)] = 0u;
+    if (i >= n) return;
+    const uint32_t p = list[i];
+    float4 a = acc[p];
+    float4 q = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    if (SQUARES) q = sq[p];
+    for (uint32_t k = 0; k < count; ++k) {
+        const uint32_t slot = (uint32_t)((f0 + k) % window);
+        const float4 r = rad[(size_t)slot * npx + p];
+        a.x = a.x + r.x; a.y = a.y + r.y; a.z = a.z + r.z; a.w = a.w + 1.0f;
+        if (SQUARES) {
+            q.x = q.x + r.x * r.x; q.y = q.y + r.y * r.y; q.z = q.z + r.z * r.z;
+            const float l = (0.2126f * r.x + 0.7152f * r.y) + 0.0722f * r.z;
+            q.w = q.w + l * l;
+        }
+    }
+    acc[p] = a;
+    if (SQUARES) sq[p] = q;
+}
+
 /* wavefront_finalize.comp + RgbaToU32 (cvtps2dq round-to-even, packus saturation) */
 SURF_HD uint32_t packChannel(float v) {
     if (!(v >= -2147483648.0f && v < 2147483648.0f)) return 0u;
@@ -3015,6 +3069,23 @@ __global__ __launch_bounds__(kBlock) void k_display(const float4* __restrict__ a
     const float4 a = acc[p];
     out[p] = displayChannel(packChannel((a.x * inv) * 255.0f)) | (displayChannel(packChannel((a.y * inv) * 255.0f)) << 8) |
              (displayChannel(packChannel((a.z * inv) * 255.0f)) << 16) | (displayChannel(packChannel((a.w * inv) * 255.0f)) << 24);
+}
+
+/* The packing by each pixel's own sample count (surf_finalize_rgba8_weighted,
+ * surf_pack_rgba8_weighted): inv = 1 / A.w, 0 where the pixel holds no sample;
+ * the alpha channel too.  The only place this arithmetic is written. */
+SURF_HD uint32_t packWeighted(float4 a, bool display) {
+    const float inv = a.w > 0.0f ? 1.0f / a.w : 0.0f;
+    uint32_t c0 = packChannel((a.x * inv) * 255.0f), c1 = packChannel((a.y * inv) * 255.0f);
+    uint32_t c2 = packChannel((a.z * inv) * 255.0f), c3 = packChannel((a.w * inv) * 255.0f);
+    if (display) { c0 = displayChannel(c0); c1 = displayChannel(c1); c2 = displayChannel(c2); c3 = displayChannel(c3); }
+    return c0 | (c1 << 8) | (c2 << 16) | (c3 << 24);
+}
+__global__ __launch_bounds__(kBlock) void k_pack_weighted(const float4* __restrict__ acc, uint32_t* __restrict__ out,
+                                                          uint32_t npx, uint32_t display) {
+    const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= npx) return;
+    out[p] = packWeighted(acc[p], display != 0u);
 }
 
 /* Per-pixel term of the Lumen energy (renderer.cpp:191-201): (r/N + g/N) + b/N.

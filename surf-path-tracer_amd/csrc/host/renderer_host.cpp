@@ -12,6 +12,7 @@
  */
 #include "surf/surf_host.hpp"
 
+#include <algorithm>
 #include <stdexcept>
 #include <string>
 
@@ -207,6 +208,55 @@ surf_noise_summary WaveFrontRenderer::noiseEstimate() {
     surf_noise_params params;
     check(surf_noise_default_params(&params), m_ctx, "surf_noise_default_params");
     return noiseEstimate(params, nullptr);
+}
+
+void WaveFrontRenderer::setPixelMask(const std::vector<uint8_t>& mask) {
+    if (!mask.empty() && mask.size() != (size_t)m_resolution.width * m_resolution.height)
+        throw std::runtime_error("setPixelMask: the mask is not width*height bytes");
+    check(surf_set_pixel_mask(m_ctx, mask.empty() ? nullptr : mask.data()), m_ctx, "surf_set_pixel_mask");
+}
+
+std::vector<uint8_t> WaveFrontRenderer::pixelMask(U32* activeCount) {
+    std::vector<uint8_t> out((size_t)m_resolution.width * m_resolution.height);
+    uint32_t n = 0;
+    check(surf_get_pixel_mask(m_ctx, out.data(), &n), m_ctx, "surf_get_pixel_mask");
+    if (activeCount) *activeCount = n;
+    return out;
+}
+
+U32 WaveFrontRenderer::maskFromNoise(const surf_adaptive_mask_params& params) {
+    uint32_t n = 0;
+    check(surf_mask_from_noise(m_ctx, &params, &n), m_ctx, "surf_mask_from_noise");
+    return n;
+}
+
+surf_adaptive_summary WaveFrontRenderer::renderAdaptive(const surf_adaptive_params& params, std::vector<U32>* roundActive) {
+    pushSceneAndCamera();
+    surf_adaptive_params p = params;
+    p.first_sample_index = m_firstSample + m_totalSamples;
+    p.max_segments = m_config.maxSegments;
+    const U32 cap = p.batch ? (p.mask.max_samples - std::min(p.mask.min_samples, p.mask.max_samples)) / p.batch + 1u : 0u;
+    if (roundActive) roundActive->assign(cap, 0u);
+    surf_adaptive_summary summary{};
+    check(surf_render_adaptive(m_ctx, &p, roundActive ? roundActive->data() : nullptr, roundActive ? cap : 0u, &summary), m_ctx,
+          "surf_render_adaptive");
+    if (roundActive) roundActive->resize(summary.rounds);
+    m_totalSamples += summary.frames;
+    m_frameInfo.totalSamples = m_totalSamples;
+    m_energyStale = true;
+    return summary;
+}
+
+surf_adaptive_summary WaveFrontRenderer::renderAdaptive() {
+    surf_adaptive_params params;
+    check(surf_adaptive_default_params(&params), m_ctx, "surf_adaptive_default_params");
+    return renderAdaptive(params, nullptr);
+}
+
+std::vector<U32> WaveFrontRenderer::finalizeWeighted(bool display) {
+    std::vector<U32> out((size_t)m_resolution.width * m_resolution.height);
+    check(surf_finalize_rgba8_weighted(m_ctx, display ? 1 : 0, out.data()), m_ctx, "surf_finalize_rgba8_weighted");
+    return out;
 }
 
 void WaveFrontRenderer::resetTemporal() { check(surf_temporal_reset(m_ctx), m_ctx, "surf_temporal_reset"); }

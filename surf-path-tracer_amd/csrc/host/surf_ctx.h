@@ -186,6 +186,22 @@ struct surf_ctx {
      * first switched on, kept when switched off, freed in surf_destroy */
     float4* sq = nullptr;
     bool sqOn = false;
+    /* the active-pixel mask (surf_set_pixel_mask, surf_mask_from_noise; host/adaptive.hip):
+     * pmOn: a mask that leaves some pixel out is set (an all-ones mask is "no
+     * mask"); then pmMask holds its npx bytes, pmList the pmActive ascending
+     * local pixels a masked stream issues and accumulates, pmBlk the
+     * compaction's per-block counts.  Allocated on first use, kept, freed in
+     * surf_destroy.  adImg*: the same three buffers for surf_adaptive_mask_image's
+     * frame, grown when a larger one arrives. */
+    bool pmOn = false;
+    uint32_t pmActive = 0;
+    uint8_t* pmMask = nullptr;
+    uint32_t* pmList = nullptr;
+    uint32_t* pmBlk = nullptr;
+    uint8_t* adImgMask = nullptr;
+    uint32_t* adImgList = nullptr;
+    uint32_t* adImgBlk = nullptr;
+    size_t adImgCap = 0;
     hipEvent_t accEv[2] = {};      /* profiling: around each k_accumulate launch (surf_stats.ms_accum), created on first use */
     uint32_t* dRows = nullptr;
     Counters* ctr = nullptr;
@@ -224,6 +240,11 @@ struct surf_ctx {
     uint64_t targetFrames = 0;     /* frames requested (chains per pixel) */
     uint64_t accPasses = 0;        /* passes accumulated (in order) */
     uint32_t spp = 1;              /* samples per frame of the stream (a frame's samples chain their RNG state) */
+    /* the stream's chains per frame: npx, or the active list's length for a
+     * stream opened under a mask (streamMasked: its graphs issue through
+     * k_regen<true>, its frames are accumulated by k_accumulate_list) */
+    uint32_t streamPx = 0;
+    bool streamMasked = false;
     uint32_t streamMaxSeg = 0;
     int zeroCutoff = -1;           /* early end of paths with throughput < FLT_MIN: 1 on, 0 off, -1 automatic (on for 1-sample frames) */
     uint64_t pushedLimit = 0;
@@ -259,6 +280,9 @@ struct surf_ctx {
     /* graph */
     hipGraphExec_t graphExec = nullptr, graphExecShort = nullptr;
     hipGraph_t graph = nullptr, graphShort = nullptr;
+    /* the same two graphs captured for masked streams (k_regen<true> over pmList; built when first needed) */
+    hipGraphExec_t graphExecM = nullptr, graphExecShortM = nullptr;
+    hipGraph_t graphM = nullptr, graphShortM = nullptr;
     uint32_t gridWork = 0, gridRegen = 0, gridExtend = 0, gridConnect = 0;
 
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
@@ -295,6 +319,8 @@ const char* denoiseParamsError(const surf_denoise_params* p);
 void freeTemporal(surf_ctx* c);
 /* defined in host/svgf.hip: freeTemporal's part for the variance-guided filter's state */
 void freeSvgf(surf_ctx* c);
+/* defined in host/adaptive.hip: surf_destroy's part for the mask's buffers */
+void freeAdaptive(surf_ctx* c);
 
 #define SURF_CHECK(ctx, call)                                                             \
     do {                                                                                  \

@@ -58,6 +58,12 @@ void surfhost::destroyGraph(surf_ctx* c) {
     if (c->graphShort) (void)hipGraphDestroy(c->graphShort);
     c->graphExec = c->graphExecShort = nullptr;
     c->graph = c->graphShort = nullptr;
+    if (c->graphExecM) (void)hipGraphExecDestroy(c->graphExecM);
+    if (c->graphM) (void)hipGraphDestroy(c->graphM);
+    if (c->graphExecShortM) (void)hipGraphExecDestroy(c->graphExecShortM);
+    if (c->graphShortM) (void)hipGraphDestroy(c->graphShortM);
+    c->graphExecM = c->graphExecShortM = nullptr;
+    c->graphM = c->graphShortM = nullptr;
 }
 
 namespace {
@@ -162,6 +168,11 @@ auto atrousKernel(bool staged, int s) {
 
 /* k_accumulate<SQUARES>: the squares plane rides the sum where surf_set_sample_squares switched it on */
 auto accumulateKernel(const surf_ctx* c) { return c->sqOn ? k_accumulate<true> : k_accumulate<false>; }
+/* ... and a masked stream's frames go through the active list */
+auto accumulateListKernel(const surf_ctx* c) { return c->sqOn ? k_accumulate_list<true> : k_accumulate_list<false>; }
+/* k_regen<MASKED> / k_regen_count<MASKED>: a masked stream issues frame-major over the active list */
+auto regenKernel(const surf_ctx* c) { return c->streamMasked ? k_regen<true> : k_regen<false>; }
+auto regenCountKernel(const surf_ctx* c) { return c->streamMasked ? k_regen_count<true> : k_regen_count<false>; }
 
 int allocWavefront(surf_ctx* c) {
     if (c->allocated) return SURF_OK;
@@ -310,7 +321,10 @@ int ensureWindow(surf_ctx* c, uint64_t frames, uint32_t spp) {
     return SURF_OK;
 }
 
-StreamGeom geom(const surf_ctx* c) { return StreamGeom{c->dRows, c->width, c->npx, c->window, c->dPerm}; }
+/* (a masked stream's issue list takes the place of the class order it never uses) */
+StreamGeom geom(const surf_ctx* c) {
+    return StreamGeom{c->dRows, c->width, c->npx, c->window, c->streamMasked ? (const uint32_t*)c->pmList : (const uint32_t*)c->dPerm};
+}
 
 /* Counting sort of the pool (which 0) or shadow queue (which 1) of phase par
  * by its 4-bit key into c->order. */
@@ -351,10 +365,10 @@ void launchPhase(surf_ctx* c, int ph, hipEvent_t* ev) {
     }
     auto regen = [&]() {
         if (fused)
-            hipLaunchKernelGGL(k_regen_count, dim3(kSortBlocks), dim3(kSortThreads), 0, s0, c->cam, c->pool[par ^ 1], c->rad, c->ctr,
+            hipLaunchKernelGGL(regenCountKernel(c), dim3(kSortBlocks), dim3(kSortThreads), 0, s0, c->cam, c->pool[par ^ 1], c->rad, c->ctr,
                                par, c->capacity, geom(c), c->Q, c->binHist);
         else
-            hipLaunchKernelGGL(k_regen, dim3(c->gridRegen), dim3(kBlock), 0, s0, c->cam, c->pool[par ^ 1], c->rad, c->ctr, par,
+            hipLaunchKernelGGL(regenKernel(c), dim3(c->gridRegen), dim3(kBlock), 0, s0, c->cam, c->pool[par ^ 1], c->rad, c->ctr, par,
                                c->capacity, geom(c), c->Q);
     };
     if (ev) (void)hipEventRecord(ev[1], s0);
@@ -391,16 +405,18 @@ void launchPhase(surf_ctx* c, int ph, hipEvent_t* ev) {
 }
 
 int buildGraph(surf_ctx* c) {
-    if (c->graphExec) return SURF_OK;
+    const bool m = c->streamMasked;            /* the graphs of the open stream's kind */
+    if (m ? c->graphExecM : c->graphExec) return SURF_OK;
     for (int shortG = 0; shortG < 2; ++shortG) {
         SURF_CHECK(c, hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
         const int nph = shortG ? kPhasesShort : kPhasesPerGraph;
         for (int ph = 0; ph < nph; ++ph) launchPhase(c, ph, nullptr);
         if (c->overlap) (void)hipStreamWaitEvent(c->stream, c->capEv[2 * (nph - 1) + 1], 0);   /* join the last connect */
-        hipGraph_t& g = shortG ? c->graphShort : c->graph;
+        hipGraph_t& g = m ? (shortG ? c->graphShortM : c->graphM) : (shortG ? c->graphShort : c->graph);
         hipError_t e = hipStreamEndCapture(c->stream, &g);
         if (e != hipSuccess) return fail(c, SURF_ERR_HIP, std::string("graph capture: ") + hipGetErrorString(e));
-        SURF_CHECK(c, hipGraphInstantiate(shortG ? &c->graphExecShort : &c->graphExec, g, nullptr, nullptr, 0));
+        hipGraphExec_t* ex = m ? (shortG ? &c->graphExecShortM : &c->graphExecM) : (shortG ? &c->graphExecShort : &c->graphExec);
+        SURF_CHECK(c, hipGraphInstantiate(ex, g, nullptr, nullptr, 0));
     }
     return SURF_OK;
 }
@@ -614,7 +630,10 @@ int startStream(surf_ctx* c, uint64_t baseFrame, uint32_t maxSeg, uint32_t frame
     for (uint32_t& v : h.capped) v = kUnset;
     /* a multi-frame request that fits the window: its pixels in class order */
     c->permFrames = 0;
-    if (c->reorder && frames >= 2 && (uint64_t)frames * spp <= c->window && c->heavyInst.size()) {
+    c->streamMasked = c->pmOn;
+    c->streamPx = c->pmOn ? c->pmActive : c->npx;
+    h.nActive = c->pmOn ? c->pmActive : 0u;
+    if (!c->pmOn && c->reorder && frames >= 2 && (uint64_t)frames * spp <= c->window && c->heavyInst.size()) {
         int rc = classifyPixels(c);
         if (rc) return rc;
         if (c->permA > 0 && c->permA < c->npx) c->permFrames = frames;
@@ -652,7 +671,7 @@ int startStream(surf_ctx* c, uint64_t baseFrame, uint32_t maxSeg, uint32_t frame
 /* Chains (first samples of (frame, pixel)) that may be issued: a frame is
  * issued only when all its passes fit the window past the accumulated ones. */
 uint64_t issueLimit(const surf_ctx* c) {
-    return std::min<uint64_t>(c->targetFrames, (c->accPasses + c->window) / c->spp) * (uint64_t)c->npx;
+    return std::min<uint64_t>(c->targetFrames, (c->accPasses + c->window) / c->spp) * (uint64_t)c->streamPx;
 }
 uint64_t targetPasses(const surf_ctx* c) { return c->targetFrames * c->spp; }
 
@@ -670,7 +689,7 @@ int pushLimit(surf_ctx* c) {
  * the permuted head of permFrames frames, then frame-major). */
 uint64_t fullyIssuedFrames(const surf_ctx* c, uint64_t iss) {
     const uint64_t P = c->permFrames;
-    if (!P || iss >= (uint64_t)c->npx * P) return iss / c->npx;
+    if (!P || iss >= (uint64_t)c->npx * P) return iss / c->streamPx;      /* (masked streams have no permuted head) */
     const uint64_t endA = (uint64_t)c->permA * P;
     return iss <= endA ? 0 : (iss - endA) / (c->npx - c->permA);
 }
@@ -745,17 +764,22 @@ int consumeSnap(surf_ctx* c) {
     const uint64_t issuedPasses = fullyIssuedFrames(c, c->hctr->issued[0]) * c->spp;
     const uint64_t hi = sn.acc + sn.open;
     uint64_t f = c->accPasses;
-    while (f < tp && f < issuedPasses && f < hi && framePaths(c, sn.fd, (uint32_t)(f % c->window)) == c->npx) ++f;
+    while (f < tp && f < issuedPasses && f < hi && framePaths(c, sn.fd, (uint32_t)(f % c->window)) == c->streamPx) ++f;
     if (f == c->accPasses) return SURF_OK;
     const uint32_t count = (uint32_t)(f - c->accPasses);
-    const uint32_t threads = std::max<uint32_t>(c->npx, count * kStripes);
+    const uint32_t threads = std::max<uint32_t>(c->streamPx, count * kStripes);
     if (c->profiling) {                                /* events of its own: ev0 / ev1 bracket the drain this launch runs inside */
         for (auto& e : c->accEv)
             if (!e) SURF_CHECK(c, hipEventCreate(&e));
         SURF_CHECK(c, hipEventRecord(c->accEv[0], c->stream));
     }
-    hipLaunchKernelGGL(accumulateKernel(c), dim3((threads + kBlock - 1) / kBlock), dim3(kBlock), 0, c->stream, (const float4*)c->rad,
-                       c->acc, c->npx, (unsigned long long)c->accPasses, count, c->window, c->frameDone, c->sqOn ? c->sq : nullptr);
+    if (c->streamMasked)
+        hipLaunchKernelGGL(accumulateListKernel(c), dim3((threads + kBlock - 1) / kBlock), dim3(kBlock), 0, c->stream, (const float4*)c->rad,
+                           c->acc, c->npx, (unsigned long long)c->accPasses, count, c->window, c->frameDone, c->sqOn ? c->sq : nullptr,
+                           (const uint32_t*)c->pmList, c->pmActive);
+    else
+        hipLaunchKernelGGL(accumulateKernel(c), dim3((threads + kBlock - 1) / kBlock), dim3(kBlock), 0, c->stream, (const float4*)c->rad,
+                           c->acc, c->npx, (unsigned long long)c->accPasses, count, c->window, c->frameDone, c->sqOn ? c->sq : nullptr);
     SURF_CHECK(c, hipGetLastError());
     if (c->profiling) {                                /* surf_stats.ms_accum; profiling waits for every launch anyway */
         SURF_CHECK(c, hipEventRecord(c->accEv[1], c->stream));
@@ -805,7 +829,10 @@ int advance(surf_ctx* c, bool shortRun = false) {
         }
         if (c->phaseLog) std::fflush(c->phaseLog);
     } else {
-        SURF_CHECK(c, hipGraphLaunch(shortRun ? c->graphExecShort : c->graphExec, c->stream));
+        if (c->streamMasked)
+            SURF_CHECK(c, hipGraphLaunch(shortRun ? c->graphExecShortM : c->graphExecM, c->stream));
+        else
+            SURF_CHECK(c, hipGraphLaunch(shortRun ? c->graphExecShort : c->graphExec, c->stream));
     }
     c->stats.iterations += phases;
     if (c->stats.iterations > kMaxIterations)
@@ -969,7 +996,7 @@ int pump(surf_ctx* c, bool drain, uint64_t lag) {
     const bool pipe = c->pipeline && !drain;
     if (!pipe && (rc = consumeAll(c))) return rc;
     if ((rc = pushLimit(c))) return rc;
-    const uint64_t target = c->targetFrames * (uint64_t)c->npx;
+    const uint64_t target = c->targetFrames * (uint64_t)c->streamPx;
     for (;;) {
         if (pipe)       /* the snapshots that have landed, and the oldest when both are in flight */
             while (c->snapCount && (c->snapCount == surf_ctx::kSnaps || hipEventQuery(c->snap[c->snapHead].ev) == hipSuccess))
@@ -1010,7 +1037,7 @@ int pump(surf_ctx* c, bool drain, uint64_t lag) {
              * issue): short replays (SURF_DRAIN_SHORT=1: also once nothing is
              * left to issue, so the drain takes over within kPhasesShort phases instead
              * of up to kPhasesPerGraph (16) -- measured slower) */
-            const bool shortRun = (!drain && (lag > 0 || target - issued <= c->npx)) || (starved && c->drainShort);
+            const bool shortRun = (!drain && (lag > 0 || target - issued <= c->streamPx)) || (starved && c->drainShort);
             for (int k = 0; k < reps; ++k)
                 if ((rc = advance(c, shortRun))) return rc;
             phases = reps * (shortRun ? kPhasesShort : kPhasesPerGraph);
@@ -1227,6 +1254,7 @@ void surf_destroy(surf_ctx* c) {
     for (float4*& p : c->dnIn) { if (p) (void)hipFree(p); p = nullptr; }
     for (auto& e : c->dnEv) if (e) (void)hipEventDestroy(e);
     freeTemporal(c);
+    freeAdaptive(c);
     if (c->dRows) (void)hipFree(c->dRows);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
@@ -1394,6 +1422,7 @@ int surf_render(surf_ctx* c, uint32_t frames, uint32_t firstSample, uint32_t max
     if (!c->hasScene) return fail(c, SURF_ERR_NO_SCENE, "no scene uploaded");
     if (!c->hasCamera) return fail(c, SURF_ERR_NO_SCENE, "no camera set");
     if (frames == 0) return SURF_OK;
+    if (c->pmOn && c->pmActive == 0) return SURF_OK;      /* an all-zero mask: nothing to trace, nothing changes */
     SURF_CHECK(c, hipSetDevice(c->device));
     int rc = allocWavefront(c);
     if (rc) return rc;
@@ -1437,7 +1466,7 @@ int surf_render(surf_ctx* c, uint32_t frames, uint32_t firstSample, uint32_t max
         c->stats.ms_total += ms;
     }
     c->totalSamples += (uint64_t)frames * spp;
-    c->stats.samples += (uint64_t)frames * spp * c->npx;
+    c->stats.samples += (uint64_t)frames * spp * c->streamPx;
     return SURF_OK;
 }
 
@@ -1454,6 +1483,8 @@ int surf_clear_accumulator(surf_ctx* c) {
     std::memset(c->evBase, 0, sizeof c->evBase);
     c->segMaxBase = 0;
     c->tailFirstRays = 0;
+    c->pmOn = false;               /* the mask is back to "every pixel" */
+    c->pmActive = 0;
     return SURF_OK;
 }
 
@@ -1648,6 +1679,31 @@ int surf_display_rgba8(surf_ctx* c, uint32_t* out) {
     SURF_CHECK(c, hipGetLastError());
     SURF_CHECK(c, hipMemcpyAsync(out, c->dOutRGBA, (size_t)c->npx * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
     SURF_CHECK(c, hipStreamSynchronize(c->stream));
+    return SURF_OK;
+}
+
+int surf_finalize_rgba8_weighted(surf_ctx* c, int display, uint32_t* out) {
+    if (!c || !out) return SURF_ERR_INVALID;
+    SURF_CHECK(c, hipSetDevice(c->device));
+    int rc = allocWavefront(c);
+    if (rc) return rc;
+    if ((rc = ensureDrained(c))) return rc;
+    hipLaunchKernelGGL(k_pack_weighted, dim3((c->npx + kBlock - 1) / kBlock), dim3(kBlock), 0, c->stream, (const float4*)c->acc,
+                       c->dOutRGBA, c->npx, display ? 1u : 0u);
+    SURF_CHECK(c, hipGetLastError());
+    SURF_CHECK(c, hipMemcpyAsync(out, c->dOutRGBA, (size_t)c->npx * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    SURF_CHECK(c, hipStreamSynchronize(c->stream));
+    return SURF_OK;
+}
+
+/* The CPU twin: packWeighted compiled for the host. */
+int surf_pack_rgba8_weighted(const float* acc, uint32_t n, int display, uint32_t* out) {
+    if (!acc || !out) return fail(nullptr, SURF_ERR_INVALID, "surf_pack_rgba8_weighted: NULL argument");
+    for (size_t p = 0; p < n; ++p) {
+        float4 a;                                                /* the caller's plane need not be 16-byte aligned */
+        std::memcpy(&a, acc + 4 * p, sizeof a);
+        out[p] = packWeighted(a, display != 0);
+    }
     return SURF_OK;
 }
 

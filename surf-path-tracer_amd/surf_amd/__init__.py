@@ -20,6 +20,9 @@ Mirrors the reference interface for the hot path:
     .set_sample_squares(on)    per-sample second moments beside the accumulator, .sample_squares() reads them (no reference counterpart)
     .denoise_sampled()         the a-trous filter guided by each pixel's own sample variance, for stills from about 16 spp
     .noise_estimate()          per-pixel relative standard error of the mean luminance and its summary
+    .set_pixel_mask(mask)      per-pixel sample mask: render() then traces the active pixels only (no reference counterpart)
+    .mask_from_noise()         the mask from the noise estimate; .render_adaptive() the "render until converged" loop around it
+    .finalize_weighted()       RGBA8 with each pixel divided by its own sample count
 """
 from __future__ import annotations
 
@@ -141,6 +144,25 @@ class NoiseSummary(C.Structure):
         return {"pixels": int(self.pixels), "above": int(self.above), "max_error": float(self.max_error)}
 
 
+class AdaptiveMaskParams(C.Structure):
+    """surf_adaptive_mask_params: the noise estimate's threshold and floor, the sample counts a pixel stays active
+    below / stops at, and the dilation of the noisy pixels."""
+    _fields_ = [("threshold", C.c_float), ("floor", C.c_float), ("min_samples", C.c_uint32), ("max_samples", C.c_uint32),
+                ("dilate", C.c_uint32), ("_pad", C.c_uint32 * 3)]
+
+
+class AdaptiveParams(C.Structure):
+    """surf_adaptive_params: the mask's parameters and the loop's."""
+    _fields_ = [("mask", AdaptiveMaskParams), ("batch", C.c_uint32), ("max_segments", C.c_uint32),
+                ("first_sample_index", C.c_uint32), ("_pad", C.c_uint32)]
+
+
+class AdaptiveSummary(C.Structure):
+    """surf_adaptive_summary."""
+    _fields_ = [("rounds", C.c_uint32), ("frames", C.c_uint32), ("active_last", C.c_uint32), ("_pad", C.c_uint32),
+                ("samples", C.c_uint64), ("noise", NoiseSummary)]
+
+
 _lib = None
 
 # Byte sizes of the reference records (include/surf_hip.h static_asserts).
@@ -237,6 +259,14 @@ def load() -> C.CDLL:
         "surf_noise_estimate": ([P, C.POINTER(NoiseParams), P, C.POINTER(NoiseSummary)], I32),
         "surf_noise_image": ([P, U32, P, P, C.POINTER(NoiseParams), P, C.POINTER(NoiseSummary)], I32),
         "surf_noise_image_host": ([U32, P, P, C.POINTER(NoiseParams), P, C.POINTER(NoiseSummary)], I32),
+        "surf_set_pixel_mask": ([P, P], I32), "surf_get_pixel_mask": ([P, P, C.POINTER(U32)], I32),
+        "surf_adaptive_default_mask_params": ([C.POINTER(AdaptiveMaskParams)], I32),
+        "surf_adaptive_default_params": ([C.POINTER(AdaptiveParams)], I32),
+        "surf_mask_from_noise": ([P, C.POINTER(AdaptiveMaskParams), C.POINTER(U32)], I32),
+        "surf_adaptive_mask_image": ([P, U32, U32, P, P, C.POINTER(AdaptiveMaskParams), P, P, C.POINTER(U32)], I32),
+        "surf_adaptive_mask_image_host": ([U32, U32, P, P, C.POINTER(AdaptiveMaskParams), P, P, C.POINTER(U32)], I32),
+        "surf_render_adaptive": ([P, C.POINTER(AdaptiveParams), P, U32, C.POINTER(AdaptiveSummary)], I32),
+        "surf_finalize_rgba8_weighted": ([P, I32, P], I32), "surf_pack_rgba8_weighted": ([P, U32, I32, P], I32),
         "surf_mesh_data": ([P, C.POINTER(P), C.POINTER(P), C.POINTER(U32)], I32),
         "surf_mesh_destroy": ([P], None),
         "surf_ref_sinf": ([F], F), "surf_ref_cosf": ([F], F), "surf_ref_expf": ([F], F),
@@ -317,6 +347,14 @@ def pack_rgba8(acc: np.ndarray, samples: int, display: bool = False) -> np.ndarr
     out = np.zeros(len(a), np.uint32)
     _check(load().surf_pack_rgba8(a.ctypes.data, len(a), np.float32(1.0) / np.float32(samples), 1 if display else 0,
                                   out.ctypes.data), "surf_pack_rgba8")
+    return out
+
+
+def pack_rgba8_weighted(acc: np.ndarray, display: bool = False) -> np.ndarray:
+    """surf_finalize_rgba8_weighted of a host accumulator (surf_pack_rgba8_weighted): each pixel divided by its own w."""
+    a = np.ascontiguousarray(acc, dtype=np.float32).reshape(-1, 4)
+    out = np.zeros(len(a), np.uint32)
+    _check(load().surf_pack_rgba8_weighted(a.ctypes.data, len(a), 1 if display else 0, out.ctypes.data), "surf_pack_rgba8_weighted")
     return out
 
 
@@ -673,6 +711,54 @@ def noise_image_host(acc, squares, threshold=None, floor=None):
     p, s = noise_params(threshold, floor), NoiseSummary()
     _check(load().surf_noise_image_host(err.size, _ptr(a), _ptr(q), C.byref(p), _ptr(err), C.byref(s)), "surf_noise_image_host")
     return err, s.as_dict()
+
+
+_MASK_FIELDS = ("threshold", "floor", "min_samples", "max_samples", "dilate")
+
+
+def adaptive_mask_params(**params) -> AdaptiveMaskParams:
+    """surf_adaptive_default_mask_params (threshold 0.05, floor 0.01, min_samples 16, max_samples 1024, dilate 1)
+    with the given fields replaced."""
+    p = AdaptiveMaskParams()
+    _check(load().surf_adaptive_default_mask_params(C.byref(p)), "surf_adaptive_default_mask_params")
+    for k, v in params.items():
+        if k not in _MASK_FIELDS:
+            raise TypeError(f"unknown mask parameter {k!r}")
+        setattr(p, k, float(v) if k in ("threshold", "floor") else int(v))
+    return p
+
+
+def adaptive_params(**params) -> AdaptiveParams:
+    """surf_adaptive_default_params (the mask defaults, batch 64, max_segments 0, first_sample_index 0) with the given
+    fields replaced; the mask's fields are given by their own names."""
+    p = AdaptiveParams()
+    _check(load().surf_adaptive_default_params(C.byref(p)), "surf_adaptive_default_params")
+    p.mask = adaptive_mask_params(**{k: v for k, v in params.items() if k in _MASK_FIELDS})
+    for k, v in params.items():
+        if k in _MASK_FIELDS:
+            continue
+        if k not in ("batch", "max_segments", "first_sample_index"):
+            raise TypeError(f"unknown adaptive parameter {k!r}")
+        setattr(p, k, int(v))
+    return p
+
+
+def _mask_planes(acc, squares):
+    a, q = (np.ascontiguousarray(v, dtype=np.float32) for v in (acc, squares))
+    if a.ndim != 3 or a.shape[2] != 4 or q.shape != a.shape:
+        raise ValueError(f"mask planes {a.shape}, {q.shape} are not two (H, W, 4) images of one size")
+    h, w = a.shape[:2]
+    return w, h, a, q, np.zeros((h, w), np.uint8), np.zeros(h * w, np.uint32)
+
+
+def adaptive_mask_image_host(acc, squares, **params):
+    """The CPU twin of Renderer.adaptive_mask_image (surf_adaptive_mask_image_host): (mask (H, W) uint8, the
+    ascending list of active pixel indices) of two (H, W, 4) planes; bit-identical, no device."""
+    w, h, a, q, mask, lst = _mask_planes(acc, squares)
+    p, n = adaptive_mask_params(**params), C.c_uint32()
+    _check(load().surf_adaptive_mask_image_host(w, h, _ptr(a), _ptr(q), C.byref(p), _ptr(mask), _ptr(lst), C.byref(n)),
+           "surf_adaptive_mask_image_host")
+    return mask, lst[:n.value].copy()
 
 
 def obj_load(path: str, threads: int = 0) -> tuple[np.ndarray, np.ndarray]:
@@ -1101,6 +1187,53 @@ class Renderer:
         p, s = noise_params(threshold, floor), NoiseSummary()
         _check(load().surf_noise_image(self._h, err.size, _ptr(a), _ptr(q), C.byref(p), _ptr(err), C.byref(s)), "surf_noise_image", self._h)
         return err, s.as_dict()
+
+    def set_pixel_mask(self, mask):
+        """The active-pixel mask of this shard (surf_set_pixel_mask): (rows, W) or flat, nonzero = active; None = every
+        pixel.  render() then traces the active pixels only; the others' records stay untouched."""
+        if mask is None:
+            _check(load().surf_set_pixel_mask(self._h, None), "surf_set_pixel_mask", self._h)
+            return
+        m = np.ascontiguousarray(np.asarray(mask) != 0, dtype=np.uint8)
+        if m.size != len(self.rows) * self.width:
+            raise ValueError(f"mask of {m.size} pixels for a shard of {len(self.rows) * self.width}")
+        _check(load().surf_set_pixel_mask(self._h, _ptr(m)), "surf_set_pixel_mask", self._h)
+
+    def pixel_mask(self):
+        """(mask (rows, W) uint8, active count) as set (surf_get_pixel_mask)."""
+        m, n = np.zeros((len(self.rows), self.width), np.uint8), C.c_uint32()
+        _check(load().surf_get_pixel_mask(self._h, _ptr(m), C.byref(n)), "surf_get_pixel_mask", self._h)
+        return m, int(n.value)
+
+    def mask_from_noise(self, **params) -> int:
+        """Builds the mask from this context's accumulator and squares and sets it (surf_mask_from_noise; parameters as
+        adaptive_mask_params); returns the active count.  Refused on a row shard unless dilate=0."""
+        p, n = adaptive_mask_params(**params), C.c_uint32()
+        _check(load().surf_mask_from_noise(self._h, C.byref(p), C.byref(n)), "surf_mask_from_noise", self._h)
+        return int(n.value)
+
+    def adaptive_mask_image(self, acc, squares, **params):
+        """The same rule on host planes of any (H, W, 4) frame (surf_adaptive_mask_image): (mask, ascending list)."""
+        w, h, a, q, mask, lst = _mask_planes(acc, squares)
+        p, n = adaptive_mask_params(**params), C.c_uint32()
+        _check(load().surf_adaptive_mask_image(self._h, w, h, _ptr(a), _ptr(q), C.byref(p), _ptr(mask), _ptr(lst), C.byref(n)),
+               "surf_adaptive_mask_image", self._h)
+        return mask, lst[:n.value].copy()
+
+    def render_adaptive(self, round_cap: int = 4096, **params) -> dict:
+        """Renders until converged (surf_render_adaptive; parameters as adaptive_params): needs sample squares on and an
+        empty accumulator.  Returns {'rounds', 'frames', 'active_last', 'samples', 'noise', 'round_active'}."""
+        p, s = adaptive_params(**params), AdaptiveSummary()
+        ra = np.zeros(max(1, round_cap), np.uint32)
+        _check(load().surf_render_adaptive(self._h, C.byref(p), _ptr(ra), round_cap, C.byref(s)), "surf_render_adaptive", self._h)
+        return {"rounds": int(s.rounds), "frames": int(s.frames), "active_last": int(s.active_last), "samples": int(s.samples),
+                "noise": s.noise.as_dict(), "round_active": [int(v) for v in ra[:min(int(s.rounds), round_cap)]]}
+
+    def finalize_weighted(self, display: bool = False) -> np.ndarray:
+        """RGBA8 with each pixel divided by its own sample count (surf_finalize_rgba8_weighted)."""
+        out = np.zeros((len(self.rows), self.width), dtype=np.uint32)
+        _check(load().surf_finalize_rgba8_weighted(self._h, 1 if display else 0, _ptr(out)), "surf_finalize_rgba8_weighted", self._h)
+        return out
 
     def copy_accumulator_to(self, device_ptr: int):
         _check(load().surf_copy_accumulator_device(self._h, C.c_void_p(device_ptr)), "surf_copy_accumulator_device", self._h)
