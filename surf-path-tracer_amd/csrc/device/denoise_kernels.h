@@ -123,6 +123,47 @@ struct DenoiseFetchTile {
     __device__ __forceinline__ float4 p(int qx, int qy) const { return P[(qy - y0) * tw + (qx - x0)]; }
 };
 
+/* the pixel a thread of a 256-thread block on a 32 x 8 tile stands for: its
+ * place in the tile, the tile's origin (bx, by), the frame pixel (x, y),
+ * whether the frame holds it and its index p there */
+struct TilePixel {
+    int tx, ty, bx, by, x, y;
+    bool inside;
+    size_t p;
+};
+__device__ __forceinline__ TilePixel tilePixel(int W, int H) {
+    TilePixel t;
+    t.tx = (int)(threadIdx.x & (kDenoiseTileW - 1));
+    t.ty = (int)(threadIdx.x / kDenoiseTileW);
+    t.bx = (int)blockIdx.x * kDenoiseTileW;
+    t.by = (int)blockIdx.y * kDenoiseTileH;
+    t.x = t.bx + t.tx;
+    t.y = t.by + t.ty;
+    t.inside = t.x < W && t.y < H;
+    t.p = (size_t)t.y * W + t.x;
+    return t;
+}
+
+/* The block copies the in-frame part of a tw x th tile of three planes, whose
+ * texel (0, 0) is frame pixel (x0, y0), from g0..g2 into t0..t2 in LDS, then
+ * meets at a barrier: every thread of the block calls it.  Out-of-frame texels
+ * are left unwritten. */
+__device__ __forceinline__ void stageTile3(float4* t0, float4* t1, float4* t2, const float4* __restrict__ g0,
+                                           const float4* __restrict__ g1, const float4* __restrict__ g2, int x0, int y0, int tw,
+                                           int th, int W, int H) {
+    for (int t = (int)threadIdx.x; t < tw * th; t += 256) {
+        const int ly = t / tw, lx = t - ly * tw;
+        const int gx = x0 + lx, gy = y0 + ly;
+        if (gx >= 0 && gx < W && gy >= 0 && gy < H) {
+            const size_t g = (size_t)gy * W + gx;
+            t0[t] = g0[g];
+            t1[t] = g1[g];
+            t2[t] = g2[g];
+        }
+    }
+    __syncthreads();
+}
+
 /* Elementwise: level 0 and the packed guides of n pixels.  (static: the
  * header is included by more than one translation unit; the one that
  * launches it owns it.) */
@@ -158,37 +199,25 @@ __global__ __launch_bounds__(256) void k_atrous(const float4* __restrict__ I, co
                                                 float4* __restrict__ out, int W, int H, int s, float kc, float kn, float kp,
                                                 uint32_t demodulate, int last) {
     extern __shared__ float4 dnTile[];
-    const int tx = (int)(threadIdx.x & (kDenoiseTileW - 1)), ty = (int)(threadIdx.x / kDenoiseTileW);
-    const int bx = (int)blockIdx.x * kDenoiseTileW, by = (int)blockIdx.y * kDenoiseTileH;
-    const int x = bx + tx, y = by + ty;
-    const bool inside = x < W && y < H;
-    const size_t p = (size_t)y * W + x;
+    const TilePixel px = tilePixel(W, H);
+    const int x = px.x, y = px.y;
+    const size_t p = px.p;
     float4 Ip, Np, Pp;
     V3 f = mk3(0.0f, 0.0f, 0.0f);
     if (STAGED) {
-        const int tw = kDenoiseTileW + 4 * s, th = kDenoiseTileH + 4 * s, x0 = bx - 2 * s, y0 = by - 2 * s;
+        const int tw = kDenoiseTileW + 4 * s, th = kDenoiseTileH + 4 * s, x0 = px.bx - 2 * s, y0 = px.by - 2 * s;
         float4* tN = dnTile;
         float4* tI = dnTile + tw * th;
         float4* tP = dnTile + 2 * tw * th;
-        for (int t = (int)threadIdx.x; t < tw * th; t += 256) {
-            const int ly = t / tw, lx = t - ly * tw;
-            const int gx = x0 + lx, gy = y0 + ly;
-            if (gx >= 0 && gx < W && gy >= 0 && gy < H) {
-                const size_t g = (size_t)gy * W + gx;
-                tN[t] = gN[g];
-                tI[t] = I[g];
-                tP[t] = gP[g];
-            }
-        }
-        __syncthreads();
-        if (!inside) return;
+        stageTile3(tN, tI, tP, gN, I, gP, x0, y0, tw, th, W, H);
+        if (!px.inside) return;
         const DenoiseFetchTile fetch{tN, tI, tP, x0, y0, tw};
         Np = fetch.n(x, y);
         Ip = fetch.i(x, y);
         Pp = fetch.p(x, y);
         if (Np.w != 0.0f) f = denoisePixel(x, y, W, H, s, kc, kn, kp, Ip, Np, Pp, fetch);
     } else {
-        if (!inside) return;
+        if (!px.inside) return;
         const DenoiseFetchPlanes fetch{I, gN, gP, W};
         Np = gN[p];
         Ip = I[p];

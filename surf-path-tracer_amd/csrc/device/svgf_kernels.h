@@ -333,7 +333,10 @@ static __global__ __launch_bounds__(256) void k_svgf_guides(const float4* __rest
  * k_atrous's tile: conflict-free.  Not STAGED: from global memory.  Both call
  * svgfVariancePixel on the same values: identical bits.  A tile whose pixels
  * all have a long history takes no tap at all; the staged copy is made
- * before that is known. */
+ * before that is known.  (The prologue and the staging loop are tilePixel's
+ * and stageTile3's of denoise_kernels.h written out: through the helpers the
+ * kernel compiled to five instructions fewer and one of its ten timed figures
+ * came out over the parent's margin, MEASUREMENTS "Filters' home".) */
 template <bool STAGED>
 __global__ __launch_bounds__(256) void k_svgf_variance(const float4* __restrict__ R, const float4* __restrict__ alb,
                                                        const float4* __restrict__ gN, const float4* __restrict__ gP,
@@ -395,37 +398,25 @@ __global__ __launch_bounds__(256) void k_atrous_var(const float4* __restrict__ I
                                                     float4* __restrict__ out, float* __restrict__ var1, int W, int H, int s,
                                                     SvgfConsts K, uint32_t demodulate, int last, float4* __restrict__ hist) {
     extern __shared__ float4 dnTile[];
-    const int tx = (int)(threadIdx.x & (kDenoiseTileW - 1)), ty = (int)(threadIdx.x / kDenoiseTileW);
-    const int bx = (int)blockIdx.x * kDenoiseTileW, by = (int)blockIdx.y * kDenoiseTileH;
-    const int x = bx + tx, y = by + ty;
-    const bool inside = x < W && y < H;
-    const size_t p = (size_t)y * W + x;
+    const TilePixel px = tilePixel(W, H);
+    const int x = px.x, y = px.y;
+    const size_t p = px.p;
     float4 Ip, Np, Pp;
     float4 f = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
     if (STAGED) {
-        const int tw = kDenoiseTileW + 4 * s, th = kDenoiseTileH + 4 * s, x0 = bx - 2 * s, y0 = by - 2 * s;
+        const int tw = kDenoiseTileW + 4 * s, th = kDenoiseTileH + 4 * s, x0 = px.bx - 2 * s, y0 = px.by - 2 * s;
         float4* tN = dnTile;
         float4* tI = dnTile + tw * th;
         float4* tP = dnTile + 2 * tw * th;
-        for (int t = (int)threadIdx.x; t < tw * th; t += 256) {
-            const int ly = t / tw, lx = t - ly * tw;
-            const int gx = x0 + lx, gy = y0 + ly;
-            if (gx >= 0 && gx < W && gy >= 0 && gy < H) {
-                const size_t g = (size_t)gy * W + gx;
-                tN[t] = gN[g];
-                tI[t] = I[g];
-                tP[t] = gP[g];
-            }
-        }
-        __syncthreads();
-        if (!inside) return;
+        stageTile3(tN, tI, tP, gN, I, gP, x0, y0, tw, th, W, H);
+        if (!px.inside) return;
         const DenoiseFetchTile fetch{tN, tI, tP, x0, y0, tw};
         Np = fetch.n(x, y);
         Ip = fetch.i(x, y);
         Pp = fetch.p(x, y);
         if (Np.w != 0.0f) f = denoisePixelVar(x, y, W, H, s, K, Ip, Np, Pp, fetch);
     } else {
-        if (!inside) return;
+        if (!px.inside) return;
         const DenoiseFetchPlanes fetch{I, gN, gP, W};
         Np = gN[p];
         Ip = I[p];

@@ -160,7 +160,7 @@ int surf_adaptive_mask_image(surf_ctx* c, uint32_t w, uint32_t h, const float* a
     if (const char* why = maskParamError(p)) return fail(c, SURF_ERR_INVALID, std::string("surf_adaptive_mask_image: ") + why);
     SURF_CHECK(c, hipSetDevice(c->device));
     const size_t npx = (size_t)w * h;
-    int rc = growImages(c, c->sdAQ, 2, c->sdAQCap, npx);
+    int rc = c->sdAQ.grow(c, npx);
     if (rc) return rc;
     if (npx > c->adImgCap) {
         SURF_CHECK(c, hipStreamSynchronize(c->stream));

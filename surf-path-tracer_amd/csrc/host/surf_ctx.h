@@ -1,5 +1,6 @@
 /*
- * surf_ctx.h -- internal: the device context behind include/surf_hip.h and the
+ * surf_ctx.h -- internal: the device context behind include/surf_hip.h, the two
+ * records the image-space filters keep on it (PlaneGroup, StageTimer) and the
  * helpers every host translation unit of the library uses (error reporting,
  * device allocation lists, scene-table upload).  Includes no kernel.
  */
@@ -19,6 +20,52 @@
 using namespace surfdev;                     /* internal header: the host code names the shared records unqualified */
 
 constexpr uint32_t kMaxStack = 120;         /* LDS stack entries per ray (block 256 -> 120 KiB max) */
+
+/* N device images of `cap` 16-byte records each that a filter keeps on the
+ * context: allocated on first use, grown (contents dropped) only when a larger
+ * frame arrives, freed with the context.  `what` names the group in an
+ * out-of-memory message. */
+template <int N>
+struct PlaneGroup {
+    const char* what;
+    float4* p[N] = {};
+    size_t cap = 0;
+    float4* operator[](int k) const { return p[k]; }
+    int grow(surf_ctx* c, size_t npx);
+    void free() {
+        for (float4*& q : p) { if (q) (void)hipFree(q); q = nullptr; }
+        cap = 0;
+    }
+};
+
+/* The device times of a filter's last run: N stages between N + 1 events on
+ * the context's stream, created on first use.  mark(i) records event i, the
+ * start of stage i and the end of stage i - 1; collect(n) waits for event n and
+ * fills ms[0..n), zeroing the rest; read() is the body of a surf_debug_*_time. */
+template <int N>
+struct StageTimer {
+    hipEvent_t ev[N + 1] = {};
+    float ms[N] = {};
+    hipError_t mark(int i, hipStream_t stream) {
+        if (!ev[i])
+            if (const hipError_t e = hipEventCreate(&ev[i]); e != hipSuccess) return e;
+        return hipEventRecord(ev[i], stream);
+    }
+    hipError_t collect(int n) {
+        if (const hipError_t e = hipEventSynchronize(ev[n]); e != hipSuccess) return e;
+        for (int k = 0; k < N; ++k) {
+            ms[k] = 0.0f;
+            if (k < n) (void)hipEventElapsedTime(&ms[k], ev[k], ev[k + 1]);
+        }
+        return hipSuccess;
+    }
+    void read(float* out, uint32_t count) const {
+        for (uint32_t k = 0; k < count; ++k) out[k] = k < (uint32_t)N ? ms[k] : 0.0f;
+    }
+    void destroy() {
+        for (hipEvent_t& e : ev) { if (e) (void)hipEventDestroy(e); e = nullptr; }
+    }
+};
 
 struct surf_ctx {
     int device = 0;
@@ -60,16 +107,13 @@ struct surf_ctx {
     void* aov[SURF_AOV_COUNT] = {};
     bool aovValid = false;
     float aovKernelMs = 0.0f;      /* device time of the last k_aov launch (surf_debug_aov_time) */
-    /* the a-trous denoiser (surf_denoise*): scratch images of dnCap pixels --
-     * the two ping-pong levels, the packed normal and position guides -- and,
-     * for surf_denoise_image, the four uploaded planes; allocated on first use,
-     * grown only when a larger frame arrives, freed in surf_destroy */
-    float4* dn[4] = {};
-    size_t dnCap = 0;
-    float4* dnIn[4] = {};
-    size_t dnInCap = 0;
-    hipEvent_t dnEv[kDenoiseMaxIterations + 2] = {};
-    float dnMs[kDenoiseMaxIterations + 1] = {};   /* prepare, then the iterations of the last run (surf_debug_denoise_time) */
+    /* the a-trous denoiser (surf_denoise*, host/denoise.hip): dn, the scratch
+     * every a-trous filter runs in -- the two ping-pong levels, the packed
+     * normal and position guides -- and, for surf_denoise_image, the four
+     * uploaded planes */
+    PlaneGroup<4> dn{"the a-trous scratch"};
+    PlaneGroup<4> dnIn{"surf_denoise_image's planes"};
+    StageTimer<kDenoiseMaxIterations + 1> dnTime;   /* prepare, then the iterations of the last run (surf_debug_denoise_time) */
     /* largest a-trous step whose tile is staged in LDS (SURF_DENOISE_LDS; 0 =
      * every step reads its taps from global memory).  2: staging takes a third
      * off the launches at steps 1 and 2 and adds 10 % at step 4 (MEASUREMENTS
@@ -81,49 +125,38 @@ struct surf_ctx {
      * (tp[3 * tpCur ..] is the stored one), tp[6] the blended output -- then
      * the camera and the instance records that frame saw.  surf_temporal_image
      * has images of its own (four current planes, three previous, two
-     * outputs).  Allocated on first use, kept, freed in surf_destroy. */
-    float4* tp[7] = {};
-    size_t tpCap = 0;
+     * outputs). */
+    PlaneGroup<7> tp{"the temporal state"};
     int tpCur = 0;
     bool tpHave = false;           /* a previous frame is stored (dropped by surf_upload_scene and surf_temporal_reset) */
     surf_camera_ubo tpCam{};
     std::vector<surf_gpu_instance> tpInst;
-    float4* tpIn[9] = {};
-    size_t tpInCap = 0;
+    PlaneGroup<9> tpIn{"surf_temporal_image's planes"};
     float* tpMotion = nullptr;     /* the motion table on the device, tpMotionCap records */
     uint32_t tpMotionCap = 0;
     std::vector<float> tpMotionHost;
-    hipEvent_t tpEv[2] = {};
-    float tpMs = 0.0f;             /* device time of the last k_temporal launch (surf_debug_temporal_time) */
+    StageTimer<1> tpTime;          /* the last k_temporal launch (surf_debug_temporal_time) */
     /* the variance-guided filter (surf_svgf*, host/svgf.hip) shares the
      * temporal state above and the denoiser's scratch (dn) and adds: the
      * luminance moments as a plane pair used in turn (sv[svCur] the stored
      * one; svHave: it belongs to the stored history -- surf_temporal_accumulate
      * clears it) and sv[2], two float planes: the variance entering and leaving
      * the filter.  surf_svgf_image has images of its own beside tpIn: albedo,
-     * previous moments, moments out, the two variances.  Allocated on first
-     * use, kept, freed in surf_destroy. */
-    float4* sv[3] = {};
-    size_t svCap = 0;
+     * previous moments, moments out, the two variances. */
+    PlaneGroup<3> sv{"the variance-guided filter's moments"};
     int svCur = 0;
     bool svHave = false;
-    float4* svIn[4] = {};
-    size_t svInCap = 0;
-    hipEvent_t svEv[kDenoiseMaxIterations + 3] = {};
-    float svMs[kDenoiseMaxIterations + 2] = {};   /* k_temporal, guides + variance, then the iterations of the last run (surf_debug_svgf_time) */
+    PlaneGroup<4> svIn{"surf_svgf_image's planes"};
+    StageTimer<kDenoiseMaxIterations + 2> svTime;   /* k_temporal, guides + variance, then the iterations of the last run (surf_debug_svgf_time) */
     /* the variance kernel takes its 7 x 7 taps from an LDS copy of the tile
      * (SURF_SVGF_LDS=0: from global memory; MEASUREMENTS "Variance-guided filter") */
     bool svVarStaged = true;
     /* the firefly clamp (surf_svgf_ext.firefly_scale, surf_firefly_image): ff
      * the clamped accumulator A' the frame's other kernels read, ffIn the two
-     * planes surf_firefly_image uploads.  Allocated on first use, kept, freed
-     * with the filter's state. */
-    float4* ff[1] = {};
-    size_t ffCap = 0;
-    float4* ffIn[2] = {};
-    size_t ffInCap = 0;
-    hipEvent_t ffEv[2] = {};
-    float ffMs = 0.0f;             /* device time of the last k_firefly launch (surf_debug_firefly_time) */
+     * planes surf_firefly_image uploads. */
+    PlaneGroup<1> ff{"the firefly clamp's image"};
+    PlaneGroup<2> ffIn{"surf_firefly_image's planes"};
+    StageTimer<1> ffTime;          /* the last k_firefly launch (surf_debug_firefly_time) */
     /* the sample-variance-guided filter and the noise estimate (surf_denoise_sampled*,
      * surf_noise_*, host/svgf.hip) share the denoiser's scratch (dn) and add,
      * each sized to what it stores (the capacities count 16-byte records):
@@ -131,18 +164,12 @@ struct surf_ctx {
      * 8 B per pixel); sdErr, the noise estimate's sums in its first record and
      * behind them the error image (4 B per pixel); sdAQ, the accumulator and
      * squares planes the two image forms upload, and sdIn, the three feature
-     * planes surf_denoise_sampled_image uploads.  Allocated on first use,
-     * kept, freed with the filter's state. */
-    float4* sdVar[1] = {};
-    size_t sdVarCap = 0;
-    float4* sdErr[1] = {};
-    size_t sdErrCap = 0;
-    float4* sdAQ[2] = {};
-    size_t sdAQCap = 0;
-    float4* sdIn[3] = {};
-    size_t sdInCap = 0;
-    hipEvent_t sdEv[kDenoiseMaxIterations + 2] = {};
-    float sdMs[kDenoiseMaxIterations + 1] = {};   /* the level-0 kernel, then the iterations of the last run (surf_debug_sampled_time) */
+     * planes surf_denoise_sampled_image uploads. */
+    PlaneGroup<1> sdVar{"the sample variances"};
+    PlaneGroup<1> sdErr{"the noise estimate's image"};
+    PlaneGroup<2> sdAQ{"the accumulator and squares planes of an image call"};
+    PlaneGroup<3> sdIn{"surf_denoise_sampled_image's planes"};
+    StageTimer<kDenoiseMaxIterations + 1> sdTime;   /* the level-0 kernel, then the iterations of the last run (surf_debug_sampled_time) */
     /* the instance records as last uploaded (surf_upload_scene, surf_update_instances): their transforms move the history */
     std::vector<surf_gpu_instance> instHost;
     /* one-frame render calls may leave up to a pool of their stream unissued
@@ -304,20 +331,19 @@ void setGlobalError(const std::string& e);
  * whose kernel arguments carry the scene descriptor */
 int endStream(surf_ctx* c);
 void destroyGraph(surf_ctx* c);
-/* ... and for the temporal filter (host/temporal.hip) what a read of the
- * context needs: the sample stream drained, the cached feature planes
- * computed (c->aov), images of `count` x npx pixels grown, and the a-trous
- * filter on device planes (*result: its scratch image holding the output) */
+/* ... and for the image-space filters (the .hip files of host/) what a read of the context
+ * needs: the sample stream drained, the cached feature planes computed (c->aov) */
 int drainStream(surf_ctx* c);
 int featurePlanes(surf_ctx* c);
-int growImages(surf_ctx* c, float4** planes, int count, size_t& cap, size_t npx);
-int denoisePlanes(surf_ctx* c, uint32_t w, uint32_t h, const float4* acc, const float4* pos, const float4* nrm, const float4* alb,
-                  const surf_denoise_params& P, const float4** result);
-/* NULL when the parameters are valid, else what is wrong with them */
-const char* denoiseParamsError(const surf_denoise_params* p);
+/* defined in host/denoise.hip: PlaneGroup::grow's body -- `count` images of at
+ * least npx records each (OOM message: "... of <what> ...") */
+int growImages(surf_ctx* c, float4** planes, int count, size_t& cap, size_t npx, const char* what);
+/* defined in host/denoise.hip: surf_destroy's part for the denoiser's state */
+void freeDenoise(surf_ctx* c);
 /* defined in host/temporal.hip: surf_destroy's part for the temporal state */
 void freeTemporal(surf_ctx* c);
-/* defined in host/svgf.hip: freeTemporal's part for the variance-guided filter's state */
+/* defined in host/svgf.hip: freeTemporal's part for the state of the variance-guided
+ * filter, the firefly clamp, the sample-variance-guided filter and the noise estimate */
 void freeSvgf(surf_ctx* c);
 /* defined in host/adaptive.hip: surf_destroy's part for the mask's buffers */
 void freeAdaptive(surf_ctx* c);
@@ -368,3 +394,6 @@ int upload(surf_ctx* c, const std::vector<T>& host, const T** devOut) {
 
 }  // namespace surfhost
 using namespace surfhost;
+
+template <int N>
+int PlaneGroup<N>::grow(surf_ctx* c, size_t npx) { return growImages(c, p, N, cap, npx, what); }

@@ -4,18 +4,19 @@
  * is asked for, k_temporal with the moments switched on, the guides and the
  * variance estimate, the variance-guided a-trous iterations (the first of
  * them storing the history where feedback is on) -- the moments a frame
- * leaves on the context beside the temporal state, and the CPU twins.  The arithmetic lives in
- * device/temporal_kernels.h and device/svgf_kernels.h.
- * Also the two readers of the per-sample squares plane, which run the same
- * a-trous iterations or none: the sample-variance-guided filter
- * (surf_denoise_sampled*) and the noise estimate (surf_noise_*), their
- * arithmetic in device/sampled_kernels.h.
+ * leaves on the context beside the temporal state, and the CPU twins.  The
+ * arithmetic lives in device/temporal_kernels.h and device/svgf_kernels.h.
+ *
+ * The file is the one home of k_atrous_var, so it also holds the two readers
+ * of the per-sample squares plane, which run the same iterations or none: the
+ * sample-variance-guided filter (surf_denoise_sampled*) and the noise estimate
+ * (surf_noise_*), their arithmetic in device/sampled_kernels.h.  A file of
+ * their own would instantiate k_atrous_var a second time.
  */
+#include "host/filter_host.h"
 #include "host/temporal_host.h"
 
-#include <algorithm>
 #include <cmath>
-#include <cstring>
 
 #include "device/svgf_kernels.h"
 #include "device/sampled_kernels.h"
@@ -53,24 +54,37 @@ SvgfConsts svgfConsts(const surf_svgf_params& p) {
     return k;
 }
 
-/* Kernel selection: k_svgf_variance<STAGED> and k_atrous_var<STAGED, FEEDBACK>
- * at step s with their dynamic LDS.  FEEDBACK is picked for iteration 0 of a
- * run with surf_svgf_ext.feedback and for no other launch.  k_firefly has one
- * instantiation and static LDS (kFireflyLdsBytes, device/svgf_kernels.h).
- * The sample-variance-guided filter (surf_denoise_sampled*) takes
- * k_atrous_var<STAGED, false> through the same selector; its level-0 kernel
- * k_sampled_level0 and the noise estimate's k_noise (device/sampled_kernels.h)
- * have one instantiation each and no LDS. */
+/* Kernel selection: k_svgf_variance<STAGED> with its dynamic LDS, and
+ * k_atrous_var<STAGED, FEEDBACK> for a step of the a-trous driver
+ * (host/filter_host.h), which decides STAGED and the LDS.  FEEDBACK is picked
+ * for iteration 0 of a run with surf_svgf_ext.feedback and for no other
+ * launch.  k_firefly has one instantiation and static LDS (kFireflyLdsBytes,
+ * device/svgf_kernels.h); k_sampled_level0 and the noise estimate's k_noise
+ * (device/sampled_kernels.h) have one each and no LDS. */
 template <class F>
 struct Launch { F fn; size_t lds; };
 auto varianceKernel(bool staged) {
     return Launch<decltype(&k_svgf_variance<true>)>{staged ? k_svgf_variance<true> : k_svgf_variance<false>, staged ? kSvgfVarLdsBytes : 0};
 }
-auto atrousVarKernel(bool staged, bool feedback, int s) {
-    const auto fn = feedback ? (staged ? k_atrous_var<true, true> : k_atrous_var<false, true>)
-                             : (staged ? k_atrous_var<true, false> : k_atrous_var<false, false>);
-    return Launch<decltype(&k_atrous_var<true, false>)>{fn,
-                                                 staged ? (size_t)3 * sizeof(float4) * (kDenoiseTileW + 4 * s) * (kDenoiseTileH + 4 * s) : 0};
+
+/* The variance-guided a-trous iterations of both filters over the scratch
+ * c->dn (level 0 in dn[0], the guides in dn[2] and dn[3]); var1 takes the
+ * variance leaving the filter, hist (not NULL: feedback) the history that
+ * iteration 0 rewrites.  T's events up to firstStage are the caller's. */
+template <int N>
+int runAtrousVar(surf_ctx* c, uint32_t w, uint32_t h, const surf_svgf_params& P, const float4* alb, float* var1, float4* hist,
+                 StageTimer<N>& T, int firstStage, const float4** result) {
+    const SvgfConsts S = svgfConsts(P);
+    const uint32_t demod = P.demodulate ? 1u : 0u;
+    const float4* gN = c->dn[2];
+    const float4* gP = c->dn[3];
+    return runAtrous(c, w, h, P.iterations, T, firstStage, [&](const AtrousStep& st) {
+        const bool feedback = hist && st.i == 0;
+        const auto fn = feedback ? (st.staged ? k_atrous_var<true, true> : k_atrous_var<false, true>)
+                                 : (st.staged ? k_atrous_var<true, false> : k_atrous_var<false, false>);
+        hipLaunchKernelGGL(fn, st.grid, dim3(256), st.lds, c->stream, st.in, gN, gP, alb, st.out, var1, (int)w, (int)h, st.s, S, demod,
+                           st.last, feedback ? hist : (float4*)nullptr);
+    }, result);
 }
 
 /* the device planes of one frame: the current frame's, the previous frame's
@@ -88,21 +102,16 @@ struct SvgfPlanes {
     float4* clamped;             /* A' of the firefly clamp; read in A's place when the clamp is on */
 };
 
-/* k_firefly over device planes of a full w x h frame, timed (c->ffEv) */
+/* k_firefly over device planes of a full w x h frame, timed (c->ffTime; fireflyTime reads it once the launch has ended) */
 int launchFirefly(surf_ctx* c, uint32_t w, uint32_t h, const float4* A, const float4* alb, float scale, uint32_t demod, float4* out) {
-    for (auto& e : c->ffEv)
-        if (!e) SURF_CHECK(c, hipEventCreate(&e));
-    const dim3 grid((w + kDenoiseTileW - 1) / kDenoiseTileW, (h + kDenoiseTileH - 1) / kDenoiseTileH);
-    SURF_CHECK(c, hipEventRecord(c->ffEv[0], c->stream));
-    hipLaunchKernelGGL(k_firefly, grid, dim3(256), 0, c->stream, A, alb, out, (int)w, (int)h, scale, demod);
+    SURF_CHECK(c, c->ffTime.mark(0, c->stream));
+    hipLaunchKernelGGL(k_firefly, tileGrid(w, h), dim3(256), 0, c->stream, A, alb, out, (int)w, (int)h, scale, demod);
     SURF_CHECK(c, hipGetLastError());
-    SURF_CHECK(c, hipEventRecord(c->ffEv[1], c->stream));
+    SURF_CHECK(c, c->ffTime.mark(1, c->stream));
     return SURF_OK;
 }
 int fireflyTime(surf_ctx* c) {
-    SURF_CHECK(c, hipEventSynchronize(c->ffEv[1]));
-    c->ffMs = 0.0f;
-    (void)hipEventElapsedTime(&c->ffMs, c->ffEv[0], c->ffEv[1]);
+    SURF_CHECK(c, c->ffTime.collect(1));
     return SURF_OK;
 }
 
@@ -112,52 +121,31 @@ int fireflyTime(surf_ctx* c) {
 int runSvgf(surf_ctx* c, uint32_t w, uint32_t h, const SvgfPlanes& pl, const TemporalConsts& K, const surf_svgf_params& P,
             const surf_svgf_ext& X, const float4** result) {
     const size_t npx = (size_t)w * h;
-    int rc = growImages(c, c->dn, 4, c->dnCap, npx);
+    int rc = c->dn.grow(c, npx);
     if (rc) return rc;
-    for (auto& e : c->svEv)
-        if (!e) SURF_CHECK(c, hipEventCreate(&e));
     if ((rc = temporalMotionUpload(c, K))) return rc;
     const uint32_t demod = P.demodulate ? 1u : 0u;
-    const SvgfConsts S = svgfConsts(P);
-    float4* lvl[2] = {c->dn[0], c->dn[1]};
     float4* gN = c->dn[2];
     float4* gP = c->dn[3];
-    const dim3 grid((w + kDenoiseTileW - 1) / kDenoiseTileW, (h + kDenoiseTileH - 1) / kDenoiseTileH);
+    const dim3 grid = tileGrid(w, h);
     static_assert(kDenoiseTileW == kTemporalTileW && kDenoiseTileH == kTemporalTileH, "one grid for every kernel of the frame");
     const bool clamp = X.firefly_scale > 0.0f;
     if (clamp && (rc = launchFirefly(c, w, h, pl.A, pl.alb, X.firefly_scale, demod, pl.clamped))) return rc;
     const float4* A = clamp ? pl.clamped : pl.A;
-    SURF_CHECK(c, hipEventRecord(c->svEv[0], c->stream));
+    SURF_CHECK(c, c->svTime.mark(0, c->stream));
     hipLaunchKernelGGL(k_temporal<true>, grid, dim3(256), 0, c->stream, A, pl.P, pl.N, pl.ID, pl.pH, pl.pP, pl.pG, (const float*)c->tpMotion, K,
                        (int)w, (int)h, pl.blend, pl.hist, pl.gP, pl.gN, TemporalMomentPlanes{pl.alb, pl.pM, pl.outM, demod});
     SURF_CHECK(c, hipGetLastError());
-    SURF_CHECK(c, hipEventRecord(c->svEv[1], c->stream));
+    SURF_CHECK(c, c->svTime.mark(1, c->stream));
     hipLaunchKernelGGL(k_svgf_guides, dim3((uint32_t)((npx + 255) / 256)), dim3(256), 0, c->stream, pl.P, pl.N, pl.alb, (uint32_t)npx, gN, gP);
     SURF_CHECK(c, hipGetLastError());
     const auto variance = varianceKernel(c->svVarStaged);
     hipLaunchKernelGGL(variance.fn, grid, dim3(256), variance.lds, c->stream, (const float4*)pl.blend, pl.alb, (const float4*)gN, (const float4*)gP,
-                       (const float4*)pl.outM, lvl[0], pl.var, (int)w, (int)h, S, demod);
+                       (const float4*)pl.outM, c->dn[0], pl.var, (int)w, (int)h, svgfConsts(P), demod);
     SURF_CHECK(c, hipGetLastError());
-    SURF_CHECK(c, hipEventRecord(c->svEv[2], c->stream));
-    const uint32_t stagedMax = std::min<uint32_t>(c->dnLdsMax, (uint32_t)kDenoiseMaxStagedStep);
-    for (uint32_t i = 0; i < P.iterations; ++i) {
-        const int s = 1 << i;
-        const int last = i + 1 == P.iterations;
-        const bool feedback = X.feedback != 0u && i == 0;
-        const auto atrous = atrousVarKernel((uint32_t)s <= stagedMax, feedback, s);
-        hipLaunchKernelGGL(atrous.fn, grid, dim3(256), atrous.lds, c->stream, (const float4*)lvl[i & 1], (const float4*)gN, (const float4*)gP, pl.alb,
-                           lvl[(i & 1) ^ 1], pl.var + npx, (int)w, (int)h, s, S, demod, last, feedback ? pl.hist : nullptr);
-        SURF_CHECK(c, hipGetLastError());
-        SURF_CHECK(c, hipEventRecord(c->svEv[i + 3], c->stream));
-    }
-    SURF_CHECK(c, hipEventSynchronize(c->svEv[P.iterations + 2]));
-    for (uint32_t k = 0; k < (uint32_t)kDenoiseMaxIterations + 2; ++k) {
-        c->svMs[k] = 0.0f;
-        if (k < P.iterations + 2) (void)hipEventElapsedTime(&c->svMs[k], c->svEv[k], c->svEv[k + 1]);
-    }
-    if (clamp && (rc = fireflyTime(c))) return rc;
-    *result = lvl[P.iterations & 1];
-    return SURF_OK;
+    SURF_CHECK(c, c->svTime.mark(2, c->stream));
+    if ((rc = runAtrousVar(c, w, h, P, pl.alb, pl.var + npx, X.feedback != 0u ? pl.hist : nullptr, c->svTime, 2, result))) return rc;
+    return clamp ? fireflyTime(c) : SURF_OK;
 }
 
 /* surf_svgf_accumulate / _copy_device: the context's own accumulator and
@@ -176,15 +164,15 @@ int svgfContext(surf_ctx* c, const surf_temporal_params* p, const surf_svgf_para
     int rc = featurePlanes(c);
     if (rc) return rc;
     if ((rc = drainStream(c))) return rc;
-    if ((rc = growImages(c, c->tp, 7, c->tpCap, c->npx))) { c->tpHave = false; return rc; }
-    if ((rc = growImages(c, c->sv, 3, c->svCap, c->npx))) { c->svHave = false; return rc; }
-    if (X.firefly_scale > 0.0f && (rc = growImages(c, c->ff, 1, c->ffCap, c->npx))) return rc;
+    if ((rc = c->tp.grow(c, c->npx))) { c->tpHave = false; return rc; }
+    if ((rc = c->sv.grow(c, c->npx))) { c->svHave = false; return rc; }
+    if (X.firefly_scale > 0.0f && (rc = c->ff.grow(c, c->npx))) return rc;
     const bool have = c->tpHave && c->tpInst.size() == c->instHost.size();
     const uint32_t nInst = (uint32_t)c->instHost.size();
     const TemporalConsts K = temporalSetup(*p, have ? &c->tpCam : nullptr, c->instHost.data(), have ? c->tpInst.data() : nullptr, nInst,
                                            c->tpMotionHost);
-    float4* const* prev = c->tp + 3 * c->tpCur;
-    float4* const* next = c->tp + 3 * (c->tpCur ^ 1);
+    float4* const* prev = c->tp.p + 3 * c->tpCur;
+    float4* const* next = c->tp.p + 3 * (c->tpCur ^ 1);
     SvgfPlanes pl{};
     pl.A = c->acc;
     pl.P = static_cast<const float4*>(c->aov[SURF_AOV_POSITION]);
@@ -264,6 +252,48 @@ const char* svgfFrameError(uint32_t w, uint32_t h, const surf_svgf_frame* cur, c
     return temporalFrameError(w, h, &tc, prev ? &tq : nullptr, out, outHist);
 }
 
+/* the guides a tap of either variance-guided filter reads, on host planes, as
+ * k_svgf_guides and denoisePrepare pack them */
+void packGuidesHost(const std::vector<float4>& Ps, const std::vector<float4>& Ns, const std::vector<float4>& Al, std::vector<float4>& gN,
+                    std::vector<float4>& gP) {
+    gN.resize(Ps.size());
+    gP.resize(Ps.size());
+    for (size_t q = 0; q < Ps.size(); ++q) {
+        gN[q] = make_float4(Ns[q].x, Ns[q].y, Ns[q].z, Al[q].w != 0.0f ? 1.0f : 0.0f);
+        gP[q] = make_float4(Ps[q].x, Ps[q].y, Ps[q].z, 0.0f);
+    }
+}
+
+/* The variance-guided a-trous iterations on host planes: level 0 in lvl[0],
+ * the levels used in turn; var1 takes the variance leaving the filter, Hs (not
+ * NULL: feedback) the history that iteration 0 rewrites.  Returns the level
+ * that holds the output. */
+const std::vector<float4>& atrousVarHost(uint32_t w, uint32_t h, const surf_svgf_params& sp, const std::vector<float4>& Al,
+                                         const std::vector<float4>& gN, const std::vector<float4>& gP, std::vector<float4> (&lvl)[2],
+                                         float* var1, std::vector<float4>* Hs) {
+    const SvgfConsts S = svgfConsts(sp);
+    const uint32_t demod = sp.demodulate ? 1u : 0u;
+    for (uint32_t i = 0; i < sp.iterations; ++i) {
+        const int s = 1 << i;
+        const bool last = i + 1 == sp.iterations;
+        const std::vector<float4>& I = lvl[i & 1];
+        std::vector<float4>& O = lvl[(i & 1) ^ 1];
+        const DenoiseFetchPlanes fetch{I.data(), gN.data(), gP.data(), (int)w};
+        for (int y = 0; y < (int)h; ++y)
+            for (int x = 0; x < (int)w; ++x) {
+                const size_t q = (size_t)y * w + x;
+                const bool valid = gN[q].w != 0.0f;
+                float4 f = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+                if (valid) f = denoisePixelVar(x, y, (int)w, (int)h, s, S, I[q], gN[q], gP[q], fetch);
+                float v1;
+                O[q] = svgfStore(valid, I[q], f, last, Al[q], demod, v1);
+                if (last) var1[q] = v1;
+                if (Hs && i == 0 && valid) (*Hs)[q] = svgfFeedback(f, Al[q], demod, (*Hs)[q].w);
+            }
+    }
+    return lvl[sp.iterations & 1];
+}
+
 /* ---- the sample-variance-guided filter (surf_denoise_sampled*) ---- */
 
 /* The launches of a run on the context's stream over device planes of a full
@@ -273,41 +303,17 @@ const char* svgfFrameError(uint32_t w, uint32_t h, const surf_svgf_frame* cur, c
 int runSampled(surf_ctx* c, uint32_t w, uint32_t h, const float4* A, const float4* Q, const float4* P, const float4* N, const float4* alb,
                const surf_svgf_params& sp, const float4** result) {
     const size_t npx = (size_t)w * h;
-    int rc = growImages(c, c->dn, 4, c->dnCap, npx);
+    int rc = c->dn.grow(c, npx);
     if (rc) return rc;
-    if ((rc = growImages(c, c->sdVar, 1, c->sdVarCap, (npx + 1) / 2))) return rc;
+    if ((rc = c->sdVar.grow(c, (npx + 1) / 2))) return rc;
     float* var = reinterpret_cast<float*>(c->sdVar[0]);
-    for (auto& e : c->sdEv)
-        if (!e) SURF_CHECK(c, hipEventCreate(&e));
-    const uint32_t demod = sp.demodulate ? 1u : 0u;
-    const SvgfConsts S = svgfConsts(sp);
-    float4* lvl[2] = {c->dn[0], c->dn[1]};
-    float4* gN = c->dn[2];
-    float4* gP = c->dn[3];
-    const dim3 grid((w + kDenoiseTileW - 1) / kDenoiseTileW, (h + kDenoiseTileH - 1) / kDenoiseTileH);
-    hipLaunchKernelGGL(k_svgf_guides, dim3((uint32_t)((npx + 255) / 256)), dim3(256), 0, c->stream, P, N, alb, (uint32_t)npx, gN, gP);
+    hipLaunchKernelGGL(k_svgf_guides, dim3((uint32_t)((npx + 255) / 256)), dim3(256), 0, c->stream, P, N, alb, (uint32_t)npx, c->dn[2], c->dn[3]);
     SURF_CHECK(c, hipGetLastError());
-    SURF_CHECK(c, hipEventRecord(c->sdEv[0], c->stream));
-    hipLaunchKernelGGL(k_sampled_level0, grid, dim3(256), 0, c->stream, A, Q, alb, lvl[0], var, (int)w, (int)h, demod);
+    SURF_CHECK(c, c->sdTime.mark(0, c->stream));
+    hipLaunchKernelGGL(k_sampled_level0, tileGrid(w, h), dim3(256), 0, c->stream, A, Q, alb, c->dn[0], var, (int)w, (int)h, sp.demodulate ? 1u : 0u);
     SURF_CHECK(c, hipGetLastError());
-    SURF_CHECK(c, hipEventRecord(c->sdEv[1], c->stream));
-    const uint32_t stagedMax = std::min<uint32_t>(c->dnLdsMax, (uint32_t)kDenoiseMaxStagedStep);
-    for (uint32_t i = 0; i < sp.iterations; ++i) {
-        const int s = 1 << i;
-        const int last = i + 1 == sp.iterations;
-        const auto atrous = atrousVarKernel((uint32_t)s <= stagedMax, false, s);
-        hipLaunchKernelGGL(atrous.fn, grid, dim3(256), atrous.lds, c->stream, (const float4*)lvl[i & 1], (const float4*)gN, (const float4*)gP, alb,
-                           lvl[(i & 1) ^ 1], var + npx, (int)w, (int)h, s, S, demod, last, (float4*)nullptr);
-        SURF_CHECK(c, hipGetLastError());
-        SURF_CHECK(c, hipEventRecord(c->sdEv[i + 2], c->stream));
-    }
-    SURF_CHECK(c, hipEventSynchronize(c->sdEv[sp.iterations + 1]));
-    for (uint32_t k = 0; k <= (uint32_t)kDenoiseMaxIterations; ++k) {
-        c->sdMs[k] = 0.0f;
-        if (k <= sp.iterations) (void)hipEventElapsedTime(&c->sdMs[k], c->sdEv[k], c->sdEv[k + 1]);
-    }
-    *result = lvl[sp.iterations & 1];
-    return SURF_OK;
+    SURF_CHECK(c, c->sdTime.mark(1, c->stream));
+    return runAtrousVar(c, w, h, sp, alb, var + npx, nullptr, c->sdTime, 1, result);
 }
 
 /* surf_denoise_sampled / _copy_device: the context's own accumulator, squares and cached feature planes */
@@ -352,7 +358,7 @@ const char* noiseParamError(const surf_noise_params* p) {
  * and the summary go to the host.  c->sdErr holds the sums in its first
  * record, then the image: 1 + (npx + 3) / 4 records. */
 int runNoise(surf_ctx* c, uint32_t npx, const float4* A, const float4* Q, const surf_noise_params& P, float* outErr, surf_noise_summary* sum) {
-    const int rc = growImages(c, c->sdErr, 1, c->sdErrCap, 1 + ((size_t)npx + 3) / 4);
+    const int rc = c->sdErr.grow(c, 1 + ((size_t)npx + 3) / 4);
     if (rc) return rc;
     NoiseSums* dSums = reinterpret_cast<NoiseSums*>(c->sdErr[0]);
     float* dErr = outErr ? reinterpret_cast<float*>(c->sdErr[0] + 1) : nullptr;
@@ -374,19 +380,17 @@ int runNoise(surf_ctx* c, uint32_t npx, const float4* A, const float4* Q, const 
 }  // namespace
 
 void surfhost::freeSvgf(surf_ctx* c) {
-    for (float4** planes : {c->sdVar, c->sdErr})
-        if (planes[0]) { (void)hipFree(planes[0]); planes[0] = nullptr; }
-    for (float4*& p : c->sdAQ) { if (p) (void)hipFree(p); p = nullptr; }
-    for (float4*& p : c->sdIn) { if (p) (void)hipFree(p); p = nullptr; }
-    for (auto& e : c->sdEv) { if (e) (void)hipEventDestroy(e); e = nullptr; }
-    c->sdVarCap = c->sdErrCap = c->sdAQCap = c->sdInCap = 0;
-    for (float4*& p : c->sv) { if (p) (void)hipFree(p); p = nullptr; }
-    for (float4*& p : c->svIn) { if (p) (void)hipFree(p); p = nullptr; }
-    for (float4*& p : c->ff) { if (p) (void)hipFree(p); p = nullptr; }
-    for (float4*& p : c->ffIn) { if (p) (void)hipFree(p); p = nullptr; }
-    for (auto& e : c->svEv) { if (e) (void)hipEventDestroy(e); e = nullptr; }
-    for (auto& e : c->ffEv) { if (e) (void)hipEventDestroy(e); e = nullptr; }
-    c->svCap = c->svInCap = c->ffCap = c->ffInCap = 0;
+    c->sdVar.free();
+    c->sdErr.free();
+    c->sdAQ.free();
+    c->sdIn.free();
+    c->sdTime.destroy();
+    c->sv.free();
+    c->svIn.free();
+    c->ff.free();
+    c->ffIn.free();
+    c->svTime.destroy();
+    c->ffTime.destroy();
     c->svHave = false;
 }
 
@@ -462,10 +466,10 @@ int surf_svgf_image_ex(surf_ctx* c, uint32_t w, uint32_t h, const surf_svgf_fram
     const surf_svgf_ext X = svgfExt(ext);
     SURF_CHECK(c, hipSetDevice(c->device));
     const size_t npx = (size_t)w * h, bytes = npx * sizeof(float4);
-    int rc = growImages(c, c->tpIn, 9, c->tpInCap, npx);
+    int rc = c->tpIn.grow(c, npx);
     if (rc) return rc;
-    if ((rc = growImages(c, c->svIn, 4, c->svInCap, npx))) return rc;
-    if (X.firefly_scale > 0.0f && (rc = growImages(c, c->ff, 1, c->ffCap, npx))) return rc;
+    if ((rc = c->svIn.grow(c, npx))) return rc;
+    if (X.firefly_scale > 0.0f && (rc = c->ff.grow(c, npx))) return rc;
     const void* curSrc[4] = {cur->acc, cur->position, cur->normal, cur->id};
     for (int k = 0; k < 4; ++k) SURF_CHECK(c, hipMemcpyAsync(c->tpIn[k], curSrc[k], bytes, hipMemcpyHostToDevice, c->stream));
     SURF_CHECK(c, hipMemcpyAsync(c->svIn[0], cur->albedo, bytes, hipMemcpyHostToDevice, c->stream));
@@ -529,25 +533,17 @@ int surf_svgf_image_host_ex(uint32_t w, uint32_t h, const surf_svgf_frame* cur, 
     const uint32_t demod = sp->demodulate ? 1u : 0u;
     std::vector<TemporalGuide> guides;
     if (prev) packGuides(prev->normal, prev->id, npx, guides);
-    /* the caller's planes need not be 16-byte aligned */
-    auto plane = [npx](const float* src) {
-        std::vector<float4> v(src ? npx : 0);
-        if (src) std::memcpy(v.data(), src, npx * sizeof(float4));
-        return v;
-    };
-    const std::vector<float4> Ps = plane(cur->position), Ns = plane(cur->normal), Al = plane(cur->albedo);
-    std::vector<float4> A = plane(cur->acc);
+    const std::vector<float4> Ps = hostPlane(cur->position, npx), Ns = hostPlane(cur->normal, npx), Al = hostPlane(cur->albedo, npx);
+    std::vector<float4> A = hostPlane(cur->acc, npx);
     if (X.firefly_scale > 0.0f) A = fireflyHost(w, h, A, Al, demod, X.firefly_scale);
-    const std::vector<float4> prevH = plane(prev ? prev->history : nullptr), prevP = plane(prev ? prev->position : nullptr),
-                              prevM = plane(prev ? prev->moments : nullptr);
+    const std::vector<float4> prevH = hostPlane(prev ? prev->history : nullptr, npx), prevP = hostPlane(prev ? prev->position : nullptr, npx),
+                              prevM = hostPlane(prev ? prev->moments : nullptr, npx);
     const TemporalFetchPlanes tfetch{prevH.data(), prevP.data(), guides.data(), (int)w, prevM.empty() ? nullptr : prevM.data()};
-    std::vector<float4> R(npx), Hs(npx), M(npx), gN(npx), gP(npx), lvl[2] = {std::vector<float4>(npx), std::vector<float4>(npx)};
+    std::vector<float4> R(npx), Hs(npx), M(npx), gN, gP, lvl[2] = {std::vector<float4>(npx), std::vector<float4>(npx)};
     std::vector<float> var(2 * npx, 0.0f);
-    for (size_t q = 0; q < npx; ++q) {
+    packGuidesHost(Ps, Ns, Al, gN, gP);
+    for (size_t q = 0; q < npx; ++q)
         temporalPixel<true>((int)w, (int)h, A[q], Ps[q], Ns[q], cur->id[4 * q], K, motion.data(), tfetch, R[q], Hs[q], denoiseDen(Al[q], demod), M[q]);
-        gN[q] = make_float4(Ns[q].x, Ns[q].y, Ns[q].z, Al[q].w != 0.0f ? 1.0f : 0.0f);
-        gP[q] = make_float4(Ps[q].x, Ps[q].y, Ps[q].z, 0.0f);
-    }
     const SvgfFetchPlanes vfetch{gN.data(), gP.data(), M.data(), (int)w};
     for (int y = 0; y < (int)h; ++y)
         for (int x = 0; x < (int)w; ++x) {
@@ -556,25 +552,8 @@ int surf_svgf_image_host_ex(uint32_t w, uint32_t h, const surf_svgf_frame* cur, 
             lvl[0][q] = svgfLevel0(R[q], Al[q], demod, v);
             var[q] = lvl[0][q].w;
         }
-    for (uint32_t i = 0; i < sp->iterations; ++i) {
-        const int s = 1 << i;
-        const bool last = i + 1 == sp->iterations;
-        const std::vector<float4>& I = lvl[i & 1];
-        std::vector<float4>& O = lvl[(i & 1) ^ 1];
-        const DenoiseFetchPlanes fetch{I.data(), gN.data(), gP.data(), (int)w};
-        for (int y = 0; y < (int)h; ++y)
-            for (int x = 0; x < (int)w; ++x) {
-                const size_t q = (size_t)y * w + x;
-                const bool valid = gN[q].w != 0.0f;
-                float4 f = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-                if (valid) f = denoisePixelVar(x, y, (int)w, (int)h, s, S, I[q], gN[q], gP[q], fetch);
-                float v1;
-                O[q] = svgfStore(valid, I[q], f, last, Al[q], demod, v1);
-                if (last) var[npx + q] = v1;
-                if (X.feedback != 0u && i == 0 && valid) Hs[q] = svgfFeedback(f, Al[q], demod, Hs[q].w);
-            }
-    }
-    std::memcpy(out, lvl[sp->iterations & 1].data(), npx * sizeof(float4));
+    const std::vector<float4>& res = atrousVarHost(w, h, *sp, Al, gN, gP, lvl, var.data() + npx, X.feedback != 0u ? &Hs : nullptr);
+    std::memcpy(out, res.data(), npx * sizeof(float4));
     std::memcpy(outHist, Hs.data(), npx * sizeof(float4));
     std::memcpy(outMom, M.data(), npx * sizeof(float4));
     interleaveVariance(var, npx, outVar);
@@ -586,9 +565,9 @@ int surf_firefly_image(surf_ctx* c, uint32_t w, uint32_t h, const float* acc, co
     if (const char* why = fireflyError(w, h, acc, albedo, scale, out)) return fail(c, SURF_ERR_INVALID, std::string("surf_firefly_image: ") + why);
     SURF_CHECK(c, hipSetDevice(c->device));
     const size_t npx = (size_t)w * h, bytes = npx * sizeof(float4);
-    int rc = growImages(c, c->ffIn, 2, c->ffInCap, npx);
+    int rc = c->ffIn.grow(c, npx);
     if (rc) return rc;
-    if ((rc = growImages(c, c->ff, 1, c->ffCap, npx))) return rc;
+    if ((rc = c->ff.grow(c, npx))) return rc;
     SURF_CHECK(c, hipMemcpyAsync(c->ffIn[0], acc, bytes, hipMemcpyHostToDevice, c->stream));
     SURF_CHECK(c, hipMemcpyAsync(c->ffIn[1], albedo, bytes, hipMemcpyHostToDevice, c->stream));
     if ((rc = launchFirefly(c, w, h, c->ffIn[0], c->ffIn[1], scale, demodulate ? 1u : 0u, c->ff[0]))) return rc;
@@ -601,17 +580,14 @@ int surf_firefly_image(surf_ctx* c, uint32_t w, uint32_t h, const float* acc, co
 int surf_firefly_image_host(uint32_t w, uint32_t h, const float* acc, const float* albedo, uint32_t demodulate, float scale, float* out) {
     if (const char* why = fireflyError(w, h, acc, albedo, scale, out)) return fail(nullptr, SURF_ERR_INVALID, std::string("surf_firefly_image_host: ") + why);
     const size_t npx = (size_t)w * h;
-    std::vector<float4> A(npx), Al(npx);                    /* the caller's planes need not be 16-byte aligned */
-    std::memcpy(A.data(), acc, npx * sizeof(float4));
-    std::memcpy(Al.data(), albedo, npx * sizeof(float4));
-    const std::vector<float4> res = fireflyHost(w, h, A, Al, demodulate ? 1u : 0u, scale);
+    const std::vector<float4> res = fireflyHost(w, h, hostPlane(acc, npx), hostPlane(albedo, npx), demodulate ? 1u : 0u, scale);
     std::memcpy(out, res.data(), npx * sizeof(float4));
     return SURF_OK;
 }
 
 int surf_debug_firefly_time(surf_ctx* c, float* kernel_ms) {
     if (!c || !kernel_ms) return SURF_ERR_INVALID;
-    *kernel_ms = c->ffMs;
+    c->ffTime.read(kernel_ms, 1);
     return SURF_OK;
 }
 
@@ -629,9 +605,9 @@ int surf_denoise_sampled_image(surf_ctx* c, uint32_t w, uint32_t h, const float*
     if (const char* why = svgfParamError(sp, false)) return fail(c, SURF_ERR_INVALID, std::string("surf_denoise_sampled_image: ") + why);
     SURF_CHECK(c, hipSetDevice(c->device));
     const size_t npx = (size_t)w * h, bytes = npx * sizeof(float4);
-    int rc = growImages(c, c->sdAQ, 2, c->sdAQCap, npx);
+    int rc = c->sdAQ.grow(c, npx);
     if (rc) return rc;
-    if ((rc = growImages(c, c->sdIn, 3, c->sdInCap, npx))) return rc;
+    if ((rc = c->sdIn.grow(c, npx))) return rc;
     float4* const dst[5] = {c->sdAQ[0], c->sdAQ[1], c->sdIn[0], c->sdIn[1], c->sdIn[2]};
     const float* src[5] = {acc, squares, position, normal, albedo};
     for (int k = 0; k < 5; ++k) SURF_CHECK(c, hipMemcpyAsync(dst[k], src[k], bytes, hipMemcpyHostToDevice, c->stream));
@@ -652,47 +628,25 @@ int surf_denoise_sampled_image_host(uint32_t w, uint32_t h, const float* acc, co
         return fail(nullptr, SURF_ERR_INVALID, std::string("surf_denoise_sampled_image_host: ") + why);
     if (const char* why = svgfParamError(sp, false)) return fail(nullptr, SURF_ERR_INVALID, std::string("surf_denoise_sampled_image_host: ") + why);
     const size_t npx = (size_t)w * h;
-    const SvgfConsts S = svgfConsts(*sp);
     const uint32_t demod = sp->demodulate ? 1u : 0u;
-    auto plane = [npx](const float* src) {                       /* the caller's planes need not be 16-byte aligned */
-        std::vector<float4> v(npx);
-        std::memcpy(v.data(), src, npx * sizeof(float4));
-        return v;
-    };
-    const std::vector<float4> A = plane(acc), Q = plane(squares), Ps = plane(position), Ns = plane(normal), Al = plane(albedo);
-    std::vector<float4> gN(npx), gP(npx), lvl[2] = {std::vector<float4>(npx), std::vector<float4>(npx)};
+    const std::vector<float4> A = hostPlane(acc, npx), Q = hostPlane(squares, npx), Ps = hostPlane(position, npx), Ns = hostPlane(normal, npx),
+                              Al = hostPlane(albedo, npx);
+    std::vector<float4> gN, gP, lvl[2] = {std::vector<float4>(npx), std::vector<float4>(npx)};
     std::vector<float> var(2 * npx, 0.0f);
+    packGuidesHost(Ps, Ns, Al, gN, gP);
     for (size_t q = 0; q < npx; ++q) {
-        gN[q] = make_float4(Ns[q].x, Ns[q].y, Ns[q].z, Al[q].w != 0.0f ? 1.0f : 0.0f);
-        gP[q] = make_float4(Ps[q].x, Ps[q].y, Ps[q].z, 0.0f);
         lvl[0][q] = sampledLevel0(A[q], Q[q], Al[q], demod);
         var[q] = lvl[0][q].w;
     }
-    for (uint32_t i = 0; i < sp->iterations; ++i) {
-        const int s = 1 << i;
-        const bool last = i + 1 == sp->iterations;
-        const std::vector<float4>& I = lvl[i & 1];
-        std::vector<float4>& O = lvl[(i & 1) ^ 1];
-        const DenoiseFetchPlanes fetch{I.data(), gN.data(), gP.data(), (int)w};
-        for (int y = 0; y < (int)h; ++y)
-            for (int x = 0; x < (int)w; ++x) {
-                const size_t q = (size_t)y * w + x;
-                const bool valid = gN[q].w != 0.0f;
-                float4 f = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-                if (valid) f = denoisePixelVar(x, y, (int)w, (int)h, s, S, I[q], gN[q], gP[q], fetch);
-                float v1;
-                O[q] = svgfStore(valid, I[q], f, last, Al[q], demod, v1);
-                if (last) var[npx + q] = v1;
-            }
-    }
-    std::memcpy(out, lvl[sp->iterations & 1].data(), npx * sizeof(float4));
+    const std::vector<float4>& res = atrousVarHost(w, h, *sp, Al, gN, gP, lvl, var.data() + npx, nullptr);
+    std::memcpy(out, res.data(), npx * sizeof(float4));
     interleaveVariance(var, npx, outVar);
     return SURF_OK;
 }
 
 int surf_debug_sampled_time(surf_ctx* c, float* kernel_ms, uint32_t count) {
     if (!c || !kernel_ms) return SURF_ERR_INVALID;
-    for (uint32_t k = 0; k < count; ++k) kernel_ms[k] = k <= (uint32_t)kDenoiseMaxIterations ? c->sdMs[k] : 0.0f;
+    c->sdTime.read(kernel_ms, count);
     return SURF_OK;
 }
 
@@ -720,7 +674,7 @@ int surf_noise_image(surf_ctx* c, uint32_t npx, const float* acc, const float* s
     if (npx == 0 || npx > (1u << 31)) return fail(c, SURF_ERR_INVALID, "surf_noise_image: no pixels or too many");
     if (const char* why = noiseParamError(p)) return fail(c, SURF_ERR_INVALID, std::string("surf_noise_image: ") + why);
     SURF_CHECK(c, hipSetDevice(c->device));
-    int rc = growImages(c, c->sdAQ, 2, c->sdAQCap, npx);
+    int rc = c->sdAQ.grow(c, npx);
     if (rc) return rc;
     SURF_CHECK(c, hipMemcpyAsync(c->sdAQ[0], acc, (size_t)npx * sizeof(float4), hipMemcpyHostToDevice, c->stream));
     SURF_CHECK(c, hipMemcpyAsync(c->sdAQ[1], squares, (size_t)npx * sizeof(float4), hipMemcpyHostToDevice, c->stream));
@@ -749,7 +703,7 @@ int surf_noise_image_host(uint32_t npx, const float* acc, const float* squares, 
 
 int surf_debug_svgf_time(surf_ctx* c, float* kernel_ms, uint32_t count) {
     if (!c || !kernel_ms) return SURF_ERR_INVALID;
-    for (uint32_t k = 0; k < count; ++k) kernel_ms[k] = k < (uint32_t)kDenoiseMaxIterations + 2 ? c->svMs[k] : 0.0f;
+    c->svTime.read(kernel_ms, count);
     return SURF_OK;
 }
 

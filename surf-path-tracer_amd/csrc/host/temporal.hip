@@ -5,10 +5,9 @@
  * the next, and the CPU twin.  The arithmetic lives in
  * device/temporal_kernels.h.
  */
-#include "host/surf_ctx.h"
+#include "host/filter_host.h"
 
 #include <cmath>
-#include <cstring>
 
 #include "host/temporal_host.h"
 
@@ -91,18 +90,14 @@ namespace {
 int runTemporal(surf_ctx* c, uint32_t w, uint32_t h, const float4* A, const float4* P, const float4* N, const uint4* ID,
                 const float4* pH, const float4* pP, const TemporalGuide* pG, const TemporalConsts& K, float4* out, float4* hist,
                 float4* gP, TemporalGuide* gN) {
-    for (auto& e : c->tpEv)
-        if (!e) SURF_CHECK(c, hipEventCreate(&e));
     if (int rc = temporalMotionUpload(c, K)) return rc;
     const dim3 grid((w + kTemporalTileW - 1) / kTemporalTileW, (h + kTemporalTileH - 1) / kTemporalTileH);
-    SURF_CHECK(c, hipEventRecord(c->tpEv[0], c->stream));
+    SURF_CHECK(c, c->tpTime.mark(0, c->stream));
     hipLaunchKernelGGL(k_temporal<false>, grid, dim3(256), 0, c->stream, A, P, N, ID, pH, pP, pG, (const float*)c->tpMotion, K, (int)w, (int)h,
                        out, hist, gP, gN, TemporalMomentPlanes{});
     SURF_CHECK(c, hipGetLastError());
-    SURF_CHECK(c, hipEventRecord(c->tpEv[1], c->stream));
-    SURF_CHECK(c, hipEventSynchronize(c->tpEv[1]));
-    c->tpMs = 0.0f;
-    (void)hipEventElapsedTime(&c->tpMs, c->tpEv[0], c->tpEv[1]);
+    SURF_CHECK(c, c->tpTime.mark(1, c->stream));
+    SURF_CHECK(c, c->tpTime.collect(1));
     return SURF_OK;
 }
 
@@ -120,13 +115,13 @@ int temporalContext(surf_ctx* c, const surf_temporal_params* p, const surf_denoi
     int rc = featurePlanes(c);
     if (rc) return rc;
     if ((rc = drainStream(c))) return rc;
-    if ((rc = growImages(c, c->tp, 7, c->tpCap, c->npx))) { c->tpHave = false; return rc; }
+    if ((rc = c->tp.grow(c, c->npx))) { c->tpHave = false; return rc; }
     const bool have = c->tpHave && c->tpInst.size() == c->instHost.size();
     const uint32_t nInst = (uint32_t)c->instHost.size();
     const TemporalConsts K = temporalSetup(*p, have ? &c->tpCam : nullptr, c->instHost.data(), have ? c->tpInst.data() : nullptr, nInst,
                                            c->tpMotionHost);
-    float4* const* prev = c->tp + 3 * c->tpCur;
-    float4* const* next = c->tp + 3 * (c->tpCur ^ 1);
+    float4* const* prev = c->tp.p + 3 * c->tpCur;
+    float4* const* next = c->tp.p + 3 * (c->tpCur ^ 1);
     const float4* pos = static_cast<const float4*>(c->aov[SURF_AOV_POSITION]);
     const float4* nrm = static_cast<const float4*>(c->aov[SURF_AOV_NORMAL]);
     rc = runTemporal(c, c->width, c->height, c->acc, pos, nrm, static_cast<const uint4*>(c->aov[SURF_AOV_ID]), have ? prev[0] : nullptr,
@@ -174,12 +169,11 @@ void surfhost::packGuides(const float* normal, const uint32_t* id, size_t npx, s
 }
 
 void surfhost::freeTemporal(surf_ctx* c) {
-    for (float4*& p : c->tp) { if (p) (void)hipFree(p); p = nullptr; }
-    for (float4*& p : c->tpIn) { if (p) (void)hipFree(p); p = nullptr; }
+    c->tp.free();
+    c->tpIn.free();
     if (c->tpMotion) (void)hipFree(c->tpMotion);
     c->tpMotion = nullptr;
-    for (auto& e : c->tpEv) { if (e) (void)hipEventDestroy(e); e = nullptr; }
-    c->tpCap = c->tpInCap = 0;
+    c->tpTime.destroy();
     c->tpMotionCap = 0;
     c->tpHave = false;
     freeSvgf(c);
@@ -230,7 +224,7 @@ int surf_temporal_image(surf_ctx* c, uint32_t w, uint32_t h, const surf_temporal
     if (const char* why = temporalParamError(p)) return fail(c, SURF_ERR_INVALID, std::string("surf_temporal_image: ") + why);
     SURF_CHECK(c, hipSetDevice(c->device));
     const size_t npx = (size_t)w * h, bytes = npx * sizeof(float4);
-    int rc = growImages(c, c->tpIn, 9, c->tpInCap, npx);
+    int rc = c->tpIn.grow(c, npx);
     if (rc) return rc;
     const void* curSrc[4] = {cur->acc, cur->position, cur->normal, cur->id};
     for (int k = 0; k < 4; ++k) SURF_CHECK(c, hipMemcpyAsync(c->tpIn[k], curSrc[k], bytes, hipMemcpyHostToDevice, c->stream));
@@ -263,33 +257,22 @@ int surf_temporal_image_host(uint32_t w, uint32_t h, const surf_temporal_frame* 
                                            cur->instance_count, motion);
     std::vector<TemporalGuide> guides;
     if (prev) packGuides(prev->normal, prev->id, npx, guides);
-    const float4* A = reinterpret_cast<const float4*>(cur->acc);
-    const float4* P = reinterpret_cast<const float4*>(cur->position);
-    const float4* N = reinterpret_cast<const float4*>(cur->normal);
-    std::vector<float4> prevH(prev ? npx : 0), prevP(prev ? npx : 0);
-    if (prev) {
-        std::memcpy(prevH.data(), prev->history, npx * sizeof(float4));
-        std::memcpy(prevP.data(), prev->position, npx * sizeof(float4));
-    }
+    const std::vector<float4> A = hostPlane(cur->acc, npx), P = hostPlane(cur->position, npx), N = hostPlane(cur->normal, npx);
+    const std::vector<float4> prevH = hostPlane(prev ? prev->history : nullptr, npx), prevP = hostPlane(prev ? prev->position : nullptr, npx);
     const TemporalFetchPlanes fetch{prevH.data(), prevP.data(), guides.data(), (int)w, nullptr};
-    float4* O = reinterpret_cast<float4*>(out);
-    float4* Hs = reinterpret_cast<float4*>(outHist);
+    std::vector<float4> O(npx), Hs(npx);
     for (size_t q = 0; q < npx; ++q) {
-        float4 a, ps, nr, o, hi;                                  /* the caller's planes need not be 16-byte aligned */
-        std::memcpy(&a, A + q, sizeof a);
-        std::memcpy(&ps, P + q, sizeof ps);
-        std::memcpy(&nr, N + q, sizeof nr);
         float4 unused;
-        temporalPixel<false>((int)w, (int)h, a, ps, nr, cur->id[4 * q], K, motion.data(), fetch, o, hi, mk3(1.0f, 1.0f, 1.0f), unused);
-        std::memcpy(O + q, &o, sizeof o);
-        std::memcpy(Hs + q, &hi, sizeof hi);
+        temporalPixel<false>((int)w, (int)h, A[q], P[q], N[q], cur->id[4 * q], K, motion.data(), fetch, O[q], Hs[q], mk3(1.0f, 1.0f, 1.0f), unused);
     }
+    std::memcpy(out, O.data(), npx * sizeof(float4));
+    std::memcpy(outHist, Hs.data(), npx * sizeof(float4));
     return SURF_OK;
 }
 
 int surf_debug_temporal_time(surf_ctx* c, float* kernel_ms) {
     if (!c || !kernel_ms) return SURF_ERR_INVALID;
-    *kernel_ms = c->tpMs;
+    c->tpTime.read(kernel_ms, 1);
     return SURF_OK;
 }
 

@@ -1,12 +1,13 @@
 /*
  * surf_hip.hip -- the kernels' translation unit: kernel selection, the
  * wavefront render loop (hipGraph-captured phases), the sample stream's pump
- * and drain, feature buffers, denoiser and the C ABI (include/surf_hip.h)
- * around them.  Replaces WaveFrontRenderer's Vulkan orchestration
+ * and drain, feature buffers and the C ABI (include/surf_hip.h) around them.
+ * Replaces WaveFrontRenderer's Vulkan orchestration
  * (renderer.cpp:604-1454) -- without its per-bounce host round trip: the
  * host only polls a pinned counter block once per replayed graph of
  * kPhasesPerGraph phases.  Scene validation and re-layout launch no kernel
- * and live in host/scene_upload.hip.
+ * and live in host/scene_upload.hip; the image-space filters, with their
+ * kernels, each in a file of host/.
  */
 #include "host/surf_ctx.h"
 
@@ -18,7 +19,6 @@
 #include <mutex>
 
 #include "device/wavefront_kernels.h"
-#include "device/denoise_kernels.h"
 
 namespace {
 
@@ -159,12 +159,6 @@ auto tailCoopKernel(const surf_ctx* c, const Variant& v) { return kernel(SURF_PI
 auto segmentCyclesKernel(const surf_ctx* c, const Variant& v) { return kernel(SURF_PICK2(k_segment_cycles, v.lds, v.w2), waveTailLds(c, 1u)); }
 auto traceClosestCoopKernel(const surf_ctx* c, const Variant& v) { return kernel(SURF_PICK2(k_trace_closest_coop, v.lds, v.w2), waveTraceLds(c)); }
 auto traceAnyCoopKernel(const surf_ctx* c, const Variant& v) { return kernel(SURF_PICK2(k_trace_any_coop, v.lds, v.w2), waveTraceLds(c)); }
-
-/* k_atrous<STAGED> at step s: the staged one holds the tile and its 2 s halo, three float4 planes */
-auto atrousKernel(bool staged, int s) {
-    return kernel(staged ? k_atrous<true> : k_atrous<false>,
-                  staged ? (size_t)3 * sizeof(float4) * (kDenoiseTileW + 4 * s) * (kDenoiseTileH + 4 * s) : 0);
-}
 
 /* k_accumulate<SQUARES>: the squares plane rides the sum where surf_set_sample_squares switched it on */
 auto accumulateKernel(const surf_ctx* c) { return c->sqOn ? k_accumulate<true> : k_accumulate<false>; }
@@ -523,104 +517,6 @@ int ensureAov(surf_ctx* c) {
     SURF_CHECK(c, hipEventSynchronize(c->ev1));
     (void)hipEventElapsedTime(&c->aovKernelMs, c->ev0, c->ev1);
     c->aovValid = true;
-    return SURF_OK;
-}
-
-/* ---- a-trous denoiser ---------------------------------------------------- */
-const char* denoiseParamError(const surf_denoise_params* p) {
-    if (!p) return "params is NULL";
-    if (p->iterations < 1 || p->iterations > (uint32_t)kDenoiseMaxIterations) return "iterations outside 1..6";
-    for (float s : {p->sigma_color, p->sigma_normal, p->sigma_plane})
-        if (!(std::isfinite(s) && s > 0.0f)) return "a sigma is not finite and > 0";
-    return nullptr;
-}
-
-/* the per-iteration constants, computed in f32 on the host as the header states */
-struct DenoiseConsts { float kc, kn, kp; };
-DenoiseConsts denoiseConsts(const surf_denoise_params& p, uint32_t i) {
-    const float sc = p.sigma_color * ldexpf(1.0f, -(int)i);
-    DenoiseConsts k;
-    k.kc = 1.0f / (sc * sc);
-    k.kn = 1.0f / (p.sigma_normal * p.sigma_normal);
-    k.kp = 1.0f / (p.sigma_plane * p.sigma_plane);
-    return k;
-}
-
-int growPlanes(surf_ctx* c, float4** planes, int count, size_t& cap, size_t npx) {
-    if (npx <= cap) return SURF_OK;
-    for (int k = 0; k < count; ++k) {
-        if (planes[k]) (void)hipFree(planes[k]);
-        planes[k] = nullptr;
-    }
-    cap = 0;
-    for (int k = 0; k < count; ++k)
-        if (hipMalloc(reinterpret_cast<void**>(&planes[k]), npx * sizeof(float4)) != hipSuccess || !planes[k]) {
-            planes[k] = nullptr;
-            (void)hipGetLastError();
-            return fail(c, SURF_ERR_OOM, "hipMalloc of a denoiser image (" + std::to_string(npx * sizeof(float4)) + " bytes) failed");
-        }
-    cap = npx;
-    return SURF_OK;
-}
-
-/* Prepare + n a-trous launches on the context's stream over device planes of
- * a full w x h frame; *result is the scratch image that holds the output
- * (valid until the next denoise call).  Waits for the result. */
-int runDenoise(surf_ctx* c, uint32_t w, uint32_t h, const float4* acc, const float4* pos, const float4* nrm, const float4* alb,
-               const surf_denoise_params& P, const float4** result) {
-    const size_t npx = (size_t)w * h;
-    int rc = growPlanes(c, c->dn, 4, c->dnCap, npx);
-    if (rc) return rc;
-    for (auto& e : c->dnEv)
-        if (!e) SURF_CHECK(c, hipEventCreate(&e));
-    float4* lvl[2] = {c->dn[0], c->dn[1]};
-    float4* gN = c->dn[2];
-    float4* gP = c->dn[3];
-    SURF_CHECK(c, hipEventRecord(c->dnEv[0], c->stream));
-    hipLaunchKernelGGL(k_denoise_prepare, dim3((uint32_t)((npx + 255) / 256)), dim3(256), 0, c->stream, acc, pos, nrm, alb,
-                       P.demodulate ? 1u : 0u, (uint32_t)npx, lvl[0], gN, gP);
-    SURF_CHECK(c, hipGetLastError());
-    SURF_CHECK(c, hipEventRecord(c->dnEv[1], c->stream));
-    const dim3 grid((w + kDenoiseTileW - 1) / kDenoiseTileW, (h + kDenoiseTileH - 1) / kDenoiseTileH);
-    const uint32_t stagedMax = std::min<uint32_t>(c->dnLdsMax, (uint32_t)kDenoiseMaxStagedStep);
-    for (uint32_t i = 0; i < P.iterations; ++i) {
-        const int s = 1 << i;
-        const DenoiseConsts k = denoiseConsts(P, i);
-        const int last = i + 1 == P.iterations;
-        const auto atrous = atrousKernel((uint32_t)s <= stagedMax, s);
-        hipLaunchKernelGGL(atrous.fn, grid, dim3(256), atrous.lds, c->stream, (const float4*)lvl[i & 1], (const float4*)gN,
-                           (const float4*)gP, alb, lvl[(i & 1) ^ 1], (int)w, (int)h, s, k.kc, k.kn, k.kp, P.demodulate ? 1u : 0u, last);
-        SURF_CHECK(c, hipGetLastError());
-        SURF_CHECK(c, hipEventRecord(c->dnEv[i + 2], c->stream));
-    }
-    SURF_CHECK(c, hipEventSynchronize(c->dnEv[P.iterations + 1]));
-    for (uint32_t k = 0; k <= (uint32_t)kDenoiseMaxIterations; ++k) {
-        c->dnMs[k] = 0.0f;
-        if (k <= P.iterations) (void)hipEventElapsedTime(&c->dnMs[k], c->dnEv[k], c->dnEv[k + 1]);
-    }
-    *result = lvl[P.iterations & 1];
-    return SURF_OK;
-}
-
-int ensureDrained(surf_ctx* c);
-
-/* surf_denoise / surf_denoise_copy_device: the context's own accumulator and
- * cached feature planes, the result copied to the host or to a device buffer */
-int denoiseContext(surf_ctx* c, const surf_denoise_params* p, void* dst, hipMemcpyKind kind) {
-    if (!c || !dst) return SURF_ERR_INVALID;
-    if (const char* why = denoiseParamError(p)) return fail(c, SURF_ERR_INVALID, std::string("surf_denoise: ") + why);
-    if (c->rows.size() != c->height)
-        return fail(c, SURF_ERR_INVALID, "surf_denoise needs a context that owns every row of the frame: a spatial filter reads its "
-                                         "neighbours' rows; assemble the shards' accumulators and feature planes and call surf_denoise_image");
-    int rc = ensureAov(c);
-    if (rc) return rc;
-    if ((rc = ensureDrained(c))) return rc;
-    const float4* res = nullptr;
-    rc = runDenoise(c, c->width, c->height, c->acc, static_cast<const float4*>(c->aov[SURF_AOV_POSITION]),
-                    static_cast<const float4*>(c->aov[SURF_AOV_NORMAL]), static_cast<const float4*>(c->aov[SURF_AOV_ALBEDO]), *p, &res);
-    if (rc) return rc;
-    SURF_CHECK(c, hipMemcpyAsync(dst, res, (size_t)c->npx * sizeof(float4), kind, c->stream));
-    SURF_CHECK(c, hipStreamSynchronize(c->stream));
     return SURF_OK;
 }
 
@@ -1093,12 +989,6 @@ int ensureDrained(surf_ctx* c) {
 
 int surfhost::drainStream(surf_ctx* c) { return ensureDrained(c); }
 int surfhost::featurePlanes(surf_ctx* c) { return ensureAov(c); }
-int surfhost::growImages(surf_ctx* c, float4** planes, int count, size_t& cap, size_t npx) { return growPlanes(c, planes, count, cap, npx); }
-int surfhost::denoisePlanes(surf_ctx* c, uint32_t w, uint32_t h, const float4* acc, const float4* pos, const float4* nrm,
-                            const float4* alb, const surf_denoise_params& P, const float4** result) {
-    return runDenoise(c, w, h, acc, pos, nrm, alb, P, result);
-}
-const char* surfhost::denoiseParamsError(const surf_denoise_params* p) { return denoiseParamError(p); }
 
 /* A stream ends when its pool is empty and all its frames are accumulated. */
 int surfhost::endStream(surf_ctx* c) {
@@ -1250,9 +1140,7 @@ void surf_destroy(surf_ctx* c) {
     if (c->sq) (void)hipFree(c->sq);
     for (auto& e : c->accEv) if (e) (void)hipEventDestroy(e);
     for (void*& p : c->aov) { if (p) (void)hipFree(p); p = nullptr; }
-    for (float4*& p : c->dn) { if (p) (void)hipFree(p); p = nullptr; }
-    for (float4*& p : c->dnIn) { if (p) (void)hipFree(p); p = nullptr; }
-    for (auto& e : c->dnEv) if (e) (void)hipEventDestroy(e);
+    freeDenoise(c);
     freeTemporal(c);
     freeAdaptive(c);
     if (c->dRows) (void)hipFree(c->dRows);
@@ -1566,87 +1454,6 @@ int surf_copy_aov_device(surf_ctx* c, int plane, void* dst) {
 int surf_debug_aov_time(surf_ctx* c, float* kernel_ms) {
     if (!c || !kernel_ms) return SURF_ERR_INVALID;
     *kernel_ms = c->aovKernelMs;
-    return SURF_OK;
-}
-
-int surf_denoise_default_params(surf_denoise_params* p) {
-    if (!p) return SURF_ERR_INVALID;
-    std::memset(p, 0, sizeof *p);
-    p->iterations = 5;
-    p->sigma_color = 1.0f;
-    p->sigma_normal = 0.3f;
-    p->sigma_plane = 0.1f;
-    p->demodulate = 1;
-    return SURF_OK;
-}
-
-int surf_denoise(surf_ctx* c, const surf_denoise_params* p, float* out) {
-    return denoiseContext(c, p, out, hipMemcpyDeviceToHost);
-}
-
-int surf_denoise_copy_device(surf_ctx* c, const surf_denoise_params* p, void* dst) {
-    return denoiseContext(c, p, dst, hipMemcpyDeviceToDevice);
-}
-
-int surf_denoise_image(surf_ctx* c, uint32_t w, uint32_t h, const float* acc, const float* position, const float* normal,
-                       const float* albedo, const surf_denoise_params* p, float* out) {
-    if (!c || !acc || !position || !normal || !albedo || !out) return SURF_ERR_INVALID;
-    if (w == 0 || h == 0 || (uint64_t)w * h > (1ull << 31)) return fail(c, SURF_ERR_INVALID, "surf_denoise_image: empty or too large a frame");
-    if (const char* why = denoiseParamError(p)) return fail(c, SURF_ERR_INVALID, std::string("surf_denoise_image: ") + why);
-    SURF_CHECK(c, hipSetDevice(c->device));
-    const size_t npx = (size_t)w * h;
-    int rc = growPlanes(c, c->dnIn, 4, c->dnInCap, npx);
-    if (rc) return rc;
-    const float* src[4] = {acc, position, normal, albedo};
-    for (int k = 0; k < 4; ++k)
-        SURF_CHECK(c, hipMemcpyAsync(c->dnIn[k], src[k], npx * sizeof(float4), hipMemcpyHostToDevice, c->stream));
-    const float4* res = nullptr;
-    if ((rc = runDenoise(c, w, h, c->dnIn[0], c->dnIn[1], c->dnIn[2], c->dnIn[3], *p, &res))) return rc;
-    SURF_CHECK(c, hipMemcpyAsync(out, res, npx * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
-    SURF_CHECK(c, hipStreamSynchronize(c->stream));
-    return SURF_OK;
-}
-
-/* The CPU twin: denoisePrepare / denoisePixel / denoiseStore of
- * device/denoise_kernels.h compiled for the host, on host arrays. */
-int surf_denoise_image_host(uint32_t w, uint32_t h, const float* acc, const float* position, const float* normal,
-                            const float* albedo, const surf_denoise_params* p, float* out) {
-    if (!acc || !position || !normal || !albedo || !out) return fail(nullptr, SURF_ERR_INVALID, "surf_denoise_image_host: NULL argument");
-    if (w == 0 || h == 0 || (uint64_t)w * h > (1ull << 31)) return fail(nullptr, SURF_ERR_INVALID, "surf_denoise_image_host: empty or too large a frame");
-    if (const char* why = denoiseParamError(p)) return fail(nullptr, SURF_ERR_INVALID, std::string("surf_denoise_image_host: ") + why);
-    const size_t npx = (size_t)w * h;
-    const float4* A = reinterpret_cast<const float4*>(acc);
-    const float4* Ps = reinterpret_cast<const float4*>(position);
-    const float4* Ns = reinterpret_cast<const float4*>(normal);
-    const float4* Al = reinterpret_cast<const float4*>(albedo);
-    const uint32_t demod = p->demodulate ? 1u : 0u;
-    std::vector<float4> lvl[2], gN(npx), gP(npx);
-    lvl[0].resize(npx);
-    lvl[1].resize(npx);
-    for (size_t q = 0; q < npx; ++q) denoisePrepare(A[q], Ps[q], Ns[q], Al[q], demod, lvl[0][q], gN[q], gP[q]);
-    for (uint32_t i = 0; i < p->iterations; ++i) {
-        const int s = 1 << i;
-        const DenoiseConsts k = denoiseConsts(*p, i);
-        const bool last = i + 1 == p->iterations;
-        const std::vector<float4>& I = lvl[i & 1];
-        std::vector<float4>& O = lvl[(i & 1) ^ 1];
-        const DenoiseFetchPlanes fetch{I.data(), gN.data(), gP.data(), (int)w};
-        for (int y = 0; y < (int)h; ++y)
-            for (int x = 0; x < (int)w; ++x) {
-                const size_t q = (size_t)y * w + x;
-                const bool valid = gN[q].w != 0.0f;
-                V3 f = mk3(0.0f, 0.0f, 0.0f);
-                if (valid) f = denoisePixel(x, y, (int)w, (int)h, s, k.kc, k.kn, k.kp, I[q], gN[q], gP[q], fetch);
-                O[q] = denoiseStore(valid, I[q], f, last, Al[q], demod);
-            }
-    }
-    std::memcpy(out, lvl[p->iterations & 1].data(), npx * sizeof(float4));
-    return SURF_OK;
-}
-
-int surf_debug_denoise_time(surf_ctx* c, float* kernel_ms, uint32_t count) {
-    if (!c || !kernel_ms) return SURF_ERR_INVALID;
-    for (uint32_t k = 0; k < count; ++k) kernel_ms[k] = k <= (uint32_t)kDenoiseMaxIterations ? c->dnMs[k] : 0.0f;
     return SURF_OK;
 }
 
