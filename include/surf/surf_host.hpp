@@ -343,6 +343,13 @@ public:
      * width*height*4 values each): a float plane (position, normal or albedo), and the id plane */
     std::vector<F32> readAOV(surf_aov plane);
     std::vector<U32> readAOVIds();
+    /* the same planes traced through mirrors and glass to the first surface that is neither, or to
+     * link maxLinks (surf_read_aov_chain, which defines the chain; 0..SURF_AOV_CHAIN_MAX_LINKS) */
+    std::vector<F32> readAOVChain(surf_aov plane, U32 maxLinks = 8);
+    std::vector<U32> readAOVChainIds(U32 maxLinks = 8);
+    /* which planes denoise() and denoiseSampled() read (surf_set_filter_guides): the first-hit
+     * planes (the default) or the chain's at maxLinks; every other filter keeps the first-hit planes */
+    void setFilterGuides(surf_guides guides, U32 maxLinks = 8);
     /* the rendered radiance through the edge-avoiding a-trous filter (surf_denoise; width*height*4
      * floats, w = 1): the accumulator and the feature buffers of the camera and scene of the last
      * render() call; the accumulator is left untouched.  The form without arguments takes

@@ -344,6 +344,68 @@ int surf_copy_aov_device(surf_ctx* ctx, int plane, void* dst_device);
  * launch, 0 before the first.  No reference counterpart. */
 int surf_debug_aov_time(surf_ctx* ctx, float* kernel_ms);
 
+/* ---- feature buffers through mirrors and glass (the chain) ----
+ * On a mirror or a glass pixel the first-hit planes describe the smooth
+ * surface, not what is seen in it.  These planes follow the same unjittered
+ * ray through the delta interactions -- a material with
+ * reflectivity + refractivity >= 0.5 -- to the first surface that is not one,
+ * or to the max_links-th link (0..SURF_AOV_CHAIN_MAX_LINKS).  No RNG anywhere;
+ * all arithmetic f32 and uncontracted, in the path tracer's operand order, so
+ * a host restatement reproduces every plane bit for bit.  No reference
+ * counterpart.  State: tint = (1,1,1), L = 0.0f, inMedium = false, k = 0; then
+ *   1. closest hit of (o, d) from depth 1e30; a miss is a terminal miss
+ *   2. an emitter (emission_strength > 0 and a positive emission channel) is a
+ *      terminal surface with a = emission_strength * emission_color and
+ *      medium = (1,1,1) even inside a medium (the path tracer absorbs nothing
+ *      on the segment that reaches an emitter); L, P, N as in 3
+ *   3. L = L + t; medium_c = inMedium ? expf(absorption_c * (-t)) : 1;
+ *      P = o + t*d; N = the shading normal of SURF_AOV_NORMAL, turned against d
+ *   4. delta = (reflectivity + refractivity) >= 0.5f; if !delta or
+ *      k == max_links: a terminal surface with a = albedo
+ *   5. tint = tint * (albedo * medium).  reflectivity >= refractivity:
+ *      R = d - (2*dot(N,d))*N.  Otherwise n1 = inMedium ? ior : 1,
+ *      n2 = inMedium ? 1 : ior, ratio = n1 / n2, cosI = -dot(d,N),
+ *      cos2 = 1 - (ratio*ratio) * (1 - cosI*cosI); cos2 > 0:
+ *      R = ratio*d + (ratio*cosI - sqrtf(fabsf(cos2)))*N and inMedium toggles;
+ *      else the mirror R and inMedium stays (total internal reflection).  There
+ *      is no Fresnel draw: a dielectric transmits whenever it can
+ *   6. o = P + 1e-5f*R, d = R, k = k + 1
+ * The planes, laid out as surf_read_aov's:
+ *   SURF_AOV_POSITION  surface (P, L): the terminal point ITSELF in world
+ *                      space -- not a virtual point unfolded behind the mirror --
+ *                      and the path length summed along the chain;
+ *                      miss (0, 0, 0, 1e30)
+ *   SURF_AOV_NORMAL    surface (N, 0), turned against the last d; miss 0
+ *   SURF_AOV_ALBEDO    surface ((tint * medium) * a, 1);
+ *                      miss (tint * background along the last d, 0)
+ *   SURF_AOV_ID        surface (instance, primitive, material index, k);
+ *                      miss (~0, ~0, ~0, k) -- k = the links followed
+ * With max_links = 0 every plane equals surf_read_aov's bit for bit, and at
+ * any max_links so does a pixel whose first hit is not delta.  The real
+ * position keeps the a-trous filter's plane term dot(Pq - Pp, Np) consistent
+ * inside a reflection; it makes the planes UNSUITABLE FOR REPROJECTION (a
+ * reflected point does not move with the instance it lies on as the camera
+ * sees it), so the temporal and the variance-guided filters keep the first-hit
+ * planes.  Device planes of their own, computed by one kernel on the first
+ * read and cached until what drops surf_read_aov's planes or a read with
+ * another max_links; status codes as surf_read_aov, and SURF_ERR_INVALID for
+ * max_links > SURF_AOV_CHAIN_MAX_LINKS.  A read never changes the sample
+ * stream. */
+#define SURF_AOV_CHAIN_MAX_LINKS 16
+int surf_read_aov_chain(surf_ctx* ctx, int plane, uint32_t max_links, void* out);
+int surf_copy_aov_chain_device(surf_ctx* ctx, int plane, uint32_t max_links, void* dst_device);
+/* Diagnostics: device time (HIP events) of the last chain kernel launch, 0 before the first. */
+int surf_debug_aov_chain_time(surf_ctx* ctx, float* kernel_ms);
+/* Which planes the two purely spatial context filters read -- surf_denoise and
+ * surf_denoise_sampled with their _copy_device forms: the first-hit planes (the
+ * default) or the chain's at max_links.  No other filter is affected: the
+ * temporal and variance-guided filters, surf_mask_from_noise and the adaptive
+ * loop need reprojectable planes.  SURF_ERR_INVALID for an unknown mode or
+ * max_links > SURF_AOV_CHAIN_MAX_LINKS (checked in either mode). */
+typedef enum { SURF_GUIDES_FIRST_HIT = 0, SURF_GUIDES_CHAIN = 1 } surf_guides;
+int surf_set_filter_guides(surf_ctx* ctx, int guides, uint32_t max_links);
+int surf_get_filter_guides(const surf_ctx* ctx, int* guides, uint32_t* max_links);
+
 /* ---- denoiser: edge-avoiding a-trous wavelet filter on the feature buffers ----
  * A pure post-process of the radiance (Dammertz et al. 2010, with albedo
  * demodulation): it reads the accumulator and the first-hit feature planes

@@ -79,12 +79,13 @@ int denoiseContext(surf_ctx* c, const surf_denoise_params* p, void* dst, hipMemc
     if (c->rows.size() != c->height)
         return fail(c, SURF_ERR_INVALID, "surf_denoise needs a context that owns every row of the frame: a spatial filter reads its "
                                          "neighbours' rows; assemble the shards' accumulators and feature planes and call surf_denoise_image");
-    int rc = featurePlanes(c);
+    void* const* g = nullptr;     /* the first-hit planes, or the chain's (surf_set_filter_guides) */
+    int rc = guidePlanes(c, &g);
     if (rc) return rc;
     if ((rc = drainStream(c))) return rc;
     const float4* res = nullptr;
-    rc = denoisePlanes(c, c->width, c->height, c->acc, static_cast<const float4*>(c->aov[SURF_AOV_POSITION]),
-                       static_cast<const float4*>(c->aov[SURF_AOV_NORMAL]), static_cast<const float4*>(c->aov[SURF_AOV_ALBEDO]), *p, &res);
+    rc = denoisePlanes(c, c->width, c->height, c->acc, static_cast<const float4*>(g[SURF_AOV_POSITION]),
+                       static_cast<const float4*>(g[SURF_AOV_NORMAL]), static_cast<const float4*>(g[SURF_AOV_ALBEDO]), *p, &res);
     if (rc) return rc;
     SURF_CHECK(c, hipMemcpyAsync(dst, res, (size_t)c->npx * sizeof(float4), kind, c->stream));
     SURF_CHECK(c, hipStreamSynchronize(c->stream));

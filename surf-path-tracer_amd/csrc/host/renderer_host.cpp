@@ -121,6 +121,26 @@ std::vector<U32> WaveFrontRenderer::readAOVIds() {
     return out;
 }
 
+std::vector<F32> WaveFrontRenderer::readAOVChain(surf_aov plane, U32 maxLinks) {
+    if (plane != SURF_AOV_POSITION && plane != SURF_AOV_NORMAL && plane != SURF_AOV_ALBEDO)
+        throw std::runtime_error("readAOVChain: not a float plane (the id plane is readAOVChainIds)");
+    pushSceneAndCamera();
+    std::vector<F32> out((size_t)m_resolution.width * m_resolution.height * 4);
+    check(surf_read_aov_chain(m_ctx, plane, maxLinks, out.data()), m_ctx, "surf_read_aov_chain");
+    return out;
+}
+
+std::vector<U32> WaveFrontRenderer::readAOVChainIds(U32 maxLinks) {
+    pushSceneAndCamera();
+    std::vector<U32> out((size_t)m_resolution.width * m_resolution.height * 4);
+    check(surf_read_aov_chain(m_ctx, SURF_AOV_ID, maxLinks, out.data()), m_ctx, "surf_read_aov_chain");
+    return out;
+}
+
+void WaveFrontRenderer::setFilterGuides(surf_guides guides, U32 maxLinks) {
+    check(surf_set_filter_guides(m_ctx, guides, maxLinks), m_ctx, "surf_set_filter_guides");
+}
+
 /* The filter reads the accumulator beside the feature buffers, so it keeps
  * the camera and the scene of the last render() call: those the accumulated
  * samples saw. */

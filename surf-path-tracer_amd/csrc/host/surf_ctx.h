@@ -107,6 +107,15 @@ struct surf_ctx {
     void* aov[SURF_AOV_COUNT] = {};
     bool aovValid = false;
     float aovKernelMs = 0.0f;      /* device time of the last k_aov launch (surf_debug_aov_time) */
+    /* the same four planes traced through mirrors and glass (surf_read_aov_chain):
+     * planes of their own, valid until what clears aovValid or another max_links */
+    void* aovChain[SURF_AOV_COUNT] = {};
+    bool aovChainValid = false;
+    uint32_t aovChainLinks = 0;    /* the max_links the cached planes were traced with */
+    float aovChainKernelMs = 0.0f; /* device time of the last k_aov_chain launch (surf_debug_aov_chain_time) */
+    /* which planes surf_denoise and surf_denoise_sampled read (surf_set_filter_guides) */
+    int guides = SURF_GUIDES_FIRST_HIT;
+    uint32_t guideLinks = 8;
     /* the a-trous denoiser (surf_denoise*, host/denoise.hip): dn, the scratch
      * every a-trous filter runs in -- the two ping-pong levels, the packed
      * normal and position guides -- and, for surf_denoise_image, the four
@@ -335,6 +344,9 @@ void destroyGraph(surf_ctx* c);
  * needs: the sample stream drained, the cached feature planes computed (c->aov) */
 int drainStream(surf_ctx* c);
 int featurePlanes(surf_ctx* c);
+/* ... and for the two purely spatial context filters the planes surf_set_filter_guides chose,
+ * computed: *planes is c->aov or c->aovChain */
+int guidePlanes(surf_ctx* c, void* const** planes);
 /* defined in host/denoise.hip: PlaneGroup::grow's body -- `count` images of at
  * least npx records each (OOM message: "... of <what> ...") */
 int growImages(surf_ctx* c, float4** planes, int count, size_t& cap, size_t npx, const char* what);

@@ -325,12 +325,13 @@ int sampledContext(surf_ctx* c, const surf_svgf_params* sp, void* dst, hipMemcpy
                                          "neighbours' rows; assemble the shards' accumulators, squares and feature planes and call "
                                          "surf_denoise_sampled_image");
     if (!c->sqOn) return fail(c, SURF_ERR_INVALID, "surf_denoise_sampled: sample squares are off (surf_set_sample_squares)");
-    int rc = featurePlanes(c);
+    void* const* g = nullptr;     /* the first-hit planes, or the chain's (surf_set_filter_guides) */
+    int rc = guidePlanes(c, &g);
     if (rc) return rc;
     if ((rc = drainStream(c))) return rc;
     const float4* res = nullptr;
-    rc = runSampled(c, c->width, c->height, c->acc, c->sq, static_cast<const float4*>(c->aov[SURF_AOV_POSITION]),
-                    static_cast<const float4*>(c->aov[SURF_AOV_NORMAL]), static_cast<const float4*>(c->aov[SURF_AOV_ALBEDO]), *sp,
+    rc = runSampled(c, c->width, c->height, c->acc, c->sq, static_cast<const float4*>(g[SURF_AOV_POSITION]),
+                    static_cast<const float4*>(g[SURF_AOV_NORMAL]), static_cast<const float4*>(g[SURF_AOV_ALBEDO]), *sp,
                     &res);
     if (rc) return rc;
     SURF_CHECK(c, hipMemcpyAsync(dst, res, (size_t)c->npx * sizeof(float4), kind, c->stream));

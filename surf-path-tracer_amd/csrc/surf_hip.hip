@@ -151,6 +151,7 @@ auto connectKernel(const surf_ctx* c, const Variant& v) {
 auto traceClosestKernel(const surf_ctx* c, const Variant& v) { return kernel(SURF_PICK2(k_trace_closest, v.lds, v.laneW), laneLds(c, kBlock, false, v.lds)); }
 auto traceAnyKernel(const surf_ctx* c, const Variant& v) { return kernel(SURF_PICK2(k_trace_any, v.lds, v.laneW), laneLds(c, kBlock, false, v.lds)); }
 auto aovKernel(const surf_ctx* c, const Variant& v) { return kernel(SURF_PICK2(k_aov, v.lds, v.laneW), laneLds(c, kBlock, false, v.lds)); }
+auto aovChainKernel(const surf_ctx* c, const Variant& v) { return kernel(SURF_PICK2(k_aov_chain, v.lds, v.laneW), laneLds(c, kBlock, false, v.lds)); }
 auto tailKernel(const surf_ctx* c, const Variant& v) { return kernel(v.lds ? k_tail<true> : k_tail<false>, laneLds(c, 64, false, v.lds)); }
 
 /* the one-ray-per-wave kernels over <LDS, W2> */
@@ -517,6 +518,37 @@ int ensureAov(surf_ctx* c) {
     SURF_CHECK(c, hipEventSynchronize(c->ev1));
     (void)hipEventElapsedTime(&c->aovKernelMs, c->ev0, c->ev1);
     c->aovValid = true;
+    return SURF_OK;
+}
+
+/* The same planes traced through mirrors and glass (k_aov_chain), in device
+ * planes of their own: kept until what drops the first-hit planes, or a read
+ * with another max_links.  One launch on the render stream, as ensureAov. */
+int ensureAovChain(surf_ctx* c, uint32_t maxLinks) {
+    if (maxLinks > SURF_AOV_CHAIN_MAX_LINKS)
+        return fail(c, SURF_ERR_INVALID, "max_links is above SURF_AOV_CHAIN_MAX_LINKS (" + std::to_string(SURF_AOV_CHAIN_MAX_LINKS) + ")");
+    if (!c->hasScene) return fail(c, SURF_ERR_NO_SCENE, "no scene uploaded");
+    if (!c->hasCamera) return fail(c, SURF_ERR_NO_SCENE, "no camera set");
+    SURF_CHECK(c, hipSetDevice(c->device));
+    if (c->aovChainValid && c->aovChainLinks == maxLinks) return SURF_OK;
+    c->aovChainValid = false;
+    for (void*& p : c->aovChain)
+        if (!p && (hipMalloc(&p, (size_t)c->npx * 16) != hipSuccess || !p)) {
+            p = nullptr;
+            (void)hipGetLastError();
+            return fail(c, SURF_ERR_OOM, "hipMalloc of a feature plane (" + std::to_string((size_t)c->npx * 16) + " bytes) failed");
+        }
+    SURF_CHECK(c, hipEventRecord(c->ev0, c->stream));
+    const auto aov = aovChainKernel(c, variantOf(c));
+    hipLaunchKernelGGL(aov.fn, dim3((c->npx + kBlock - 1) / kBlock), dim3(kBlock), aov.lds, c->stream, c->S, c->cam, (const uint32_t*)c->dRows, c->width, c->npx, static_cast<float4*>(c->aovChain[SURF_AOV_POSITION]),
+                       static_cast<float4*>(c->aovChain[SURF_AOV_NORMAL]), static_cast<float4*>(c->aovChain[SURF_AOV_ALBEDO]),
+                       static_cast<uint4*>(c->aovChain[SURF_AOV_ID]), stackWords(c, kBlock), maxLinks);
+    SURF_CHECK(c, hipGetLastError());
+    SURF_CHECK(c, hipEventRecord(c->ev1, c->stream));
+    SURF_CHECK(c, hipEventSynchronize(c->ev1));
+    (void)hipEventElapsedTime(&c->aovChainKernelMs, c->ev0, c->ev1);
+    c->aovChainLinks = maxLinks;
+    c->aovChainValid = true;
     return SURF_OK;
 }
 
@@ -989,6 +1021,11 @@ int ensureDrained(surf_ctx* c) {
 
 int surfhost::drainStream(surf_ctx* c) { return ensureDrained(c); }
 int surfhost::featurePlanes(surf_ctx* c) { return ensureAov(c); }
+int surfhost::guidePlanes(surf_ctx* c, void* const** planes) {
+    const bool chain = c->guides == SURF_GUIDES_CHAIN;
+    *planes = chain ? c->aovChain : c->aov;
+    return chain ? ensureAovChain(c, c->guideLinks) : ensureAov(c);
+}
 
 /* A stream ends when its pool is empty and all its frames are accumulated. */
 int surfhost::endStream(surf_ctx* c) {
@@ -1140,6 +1177,7 @@ void surf_destroy(surf_ctx* c) {
     if (c->sq) (void)hipFree(c->sq);
     for (auto& e : c->accEv) if (e) (void)hipEventDestroy(e);
     for (void*& p : c->aov) { if (p) (void)hipFree(p); p = nullptr; }
+    for (void*& p : c->aovChain) { if (p) (void)hipFree(p); p = nullptr; }
     freeDenoise(c);
     freeTemporal(c);
     freeAdaptive(c);
@@ -1298,6 +1336,7 @@ int surf_set_camera(surf_ctx* c, const surf_camera_ubo* u) {
     c->cam = k;
     c->permValid = false;
     c->aovValid = false;
+    c->aovChainValid = false;
     c->camUbo = *u;
     c->hasCamera = true;
     destroyGraph(c);     /* camera is a kernel argument of the captured graph */
@@ -1454,6 +1493,47 @@ int surf_copy_aov_device(surf_ctx* c, int plane, void* dst) {
 int surf_debug_aov_time(surf_ctx* c, float* kernel_ms) {
     if (!c || !kernel_ms) return SURF_ERR_INVALID;
     *kernel_ms = c->aovKernelMs;
+    return SURF_OK;
+}
+
+/* surf_read_aov_chain / surf_copy_aov_chain_device */
+static int copyAovChain(surf_ctx* c, int plane, uint32_t maxLinks, void* dst, hipMemcpyKind kind) {
+    if (!c || !dst || plane < 0 || plane >= SURF_AOV_COUNT) return SURF_ERR_INVALID;
+    int rc = ensureAovChain(c, maxLinks);
+    if (rc) return rc;
+    SURF_CHECK(c, hipMemcpyAsync(dst, c->aovChain[plane], (size_t)c->npx * 16, kind, c->stream));
+    SURF_CHECK(c, hipStreamSynchronize(c->stream));
+    return SURF_OK;
+}
+
+int surf_read_aov_chain(surf_ctx* c, int plane, uint32_t max_links, void* out) {
+    return copyAovChain(c, plane, max_links, out, hipMemcpyDeviceToHost);
+}
+
+int surf_copy_aov_chain_device(surf_ctx* c, int plane, uint32_t max_links, void* dst) {
+    return copyAovChain(c, plane, max_links, dst, hipMemcpyDeviceToDevice);
+}
+
+int surf_debug_aov_chain_time(surf_ctx* c, float* kernel_ms) {
+    if (!c || !kernel_ms) return SURF_ERR_INVALID;
+    *kernel_ms = c->aovChainKernelMs;
+    return SURF_OK;
+}
+
+int surf_set_filter_guides(surf_ctx* c, int guides, uint32_t max_links) {
+    if (!c) return SURF_ERR_INVALID;
+    if (guides != SURF_GUIDES_FIRST_HIT && guides != SURF_GUIDES_CHAIN) return fail(c, SURF_ERR_INVALID, "surf_set_filter_guides: unknown guides mode");
+    if (max_links > SURF_AOV_CHAIN_MAX_LINKS)
+        return fail(c, SURF_ERR_INVALID, "surf_set_filter_guides: max_links is above SURF_AOV_CHAIN_MAX_LINKS (" + std::to_string(SURF_AOV_CHAIN_MAX_LINKS) + ")");
+    c->guides = guides;
+    c->guideLinks = max_links;
+    return SURF_OK;
+}
+
+int surf_get_filter_guides(const surf_ctx* c, int* guides, uint32_t* max_links) {
+    if (!c || !guides || !max_links) return SURF_ERR_INVALID;
+    *guides = c->guides;
+    *max_links = c->guideLinks;
     return SURF_OK;
 }
 

@@ -4,11 +4,14 @@
  * built as render_indoor.cpp builds them, then WaveFrontRenderer::readAOV /
  * readAOVIds instead of a render loop (no sample is rendered).
  *
- * usage: render_aov ASSETS_DIR WIDTH HEIGHT PREFIX
+ * usage: render_aov ASSETS_DIR WIDTH HEIGHT PREFIX [MAX_LINKS]
  * Writes PREFIX_position.pfm, PREFIX_normal.pfm and PREFIX_albedo.pfm (colour
  * PFM, surf_write_pfm: the planes' RGB, alpha dropped) and PREFIX_planes.bin:
  * the four raw planes in surf_aov order (position, normal, albedo, id), each
- * WIDTH*HEIGHT records of 16 bytes, rows top to bottom.
+ * WIDTH*HEIGHT records of 16 bytes, rows top to bottom.  With MAX_LINKS
+ * (0..16) also the planes traced through mirrors and glass (readAOVChain /
+ * readAOVChainIds), as PREFIX_chain_{position,normal,albedo}.pfm and
+ * PREFIX_chain_planes.bin in the same layout.
  */
 #include "surf/surf_host.hpp"
 #include "indoor_scene.hpp"
@@ -21,42 +24,62 @@
 using namespace surf;
 
 int main(int argc, char** argv) {
-    if (argc != 5) {
-        std::fprintf(stderr, "usage: %s ASSETS_DIR WIDTH HEIGHT PREFIX\n", argv[0]);
+    if (argc != 5 && argc != 6) {
+        std::fprintf(stderr, "usage: %s ASSETS_DIR WIDTH HEIGHT PREFIX [MAX_LINKS]\n", argv[0]);
         return 2;
     }
     const std::string dir = argv[1], prefix = argv[4];
     const int w = std::atoi(argv[2]), h = std::atoi(argv[3]);
     if (w <= 0 || h <= 0) { std::fprintf(stderr, "render_aov: WIDTH and HEIGHT must be positive\n"); return 2; }
     const U32 W = (U32)w, H = (U32)h;
+    const bool withChain = argc == 6;
+    const int links = withChain ? std::atoi(argv[5]) : 0;
+    if (links < 0 || links > SURF_AOV_CHAIN_MAX_LINKS) {
+        std::fprintf(stderr, "render_aov: MAX_LINKS must be 0..%d\n", SURF_AOV_CHAIN_MAX_LINKS);
+        return 2;
+    }
+    const U32 maxLinks = (U32)links;
     try {
         RenderContext context;            /* HIP device 0 */
         Camera worldCam = indoorCamera(W, H);
         IndoorScene indoor(&context, dir);
         WaveFrontRenderer renderer(&context, nullptr, RendererConfig{}, FramebufferSize{W, H}, worldCam, *indoor.scene);
 
-        const char* names[3] = {"position", "normal", "albedo"};
-        const surf_aov planes[3] = {SURF_AOV_POSITION, SURF_AOV_NORMAL, SURF_AOV_ALBEDO};
-        const std::string binPath = prefix + "_planes.bin";
-        FILE* bin = std::fopen(binPath.c_str(), "wb");
-        if (!bin) { std::fprintf(stderr, "cannot write %s\n", binPath.c_str()); return 1; }
-        bool ok = true;
-        for (int k = 0; k < 3; ++k) {
-            const std::vector<F32> plane = renderer.readAOV(planes[k]);
-            const std::string path = prefix + "_" + names[k] + ".pfm";
-            if (surf_write_pfm(path.c_str(), W, H, plane.data()) != SURF_OK) {
-                std::fprintf(stderr, "cannot write %s\n", path.c_str());
-                std::fclose(bin);
-                return 1;
+        /* one set of planes: three PFM images and the four raw planes behind each other */
+        const auto writePlanes = [&](const std::string& stem, bool chain, std::vector<U32>& ids) {
+            const char* names[3] = {"position", "normal", "albedo"};
+            const surf_aov planes[3] = {SURF_AOV_POSITION, SURF_AOV_NORMAL, SURF_AOV_ALBEDO};
+            const std::string binPath = stem + "_planes.bin";
+            FILE* bin = std::fopen(binPath.c_str(), "wb");
+            if (!bin) { std::fprintf(stderr, "cannot write %s\n", binPath.c_str()); return false; }
+            bool ok = true;
+            for (int k = 0; k < 3; ++k) {
+                const std::vector<F32> plane = chain ? renderer.readAOVChain(planes[k], maxLinks) : renderer.readAOV(planes[k]);
+                const std::string path = stem + "_" + names[k] + ".pfm";
+                if (surf_write_pfm(path.c_str(), W, H, plane.data()) != SURF_OK) {
+                    std::fprintf(stderr, "cannot write %s\n", path.c_str());
+                    std::fclose(bin);
+                    return false;
+                }
+                ok = ok && std::fwrite(plane.data(), sizeof(F32), plane.size(), bin) == plane.size();
             }
-            ok = ok && std::fwrite(plane.data(), sizeof(F32), plane.size(), bin) == plane.size();
-        }
-        const std::vector<U32> ids = renderer.readAOVIds();
-        ok = ok && std::fwrite(ids.data(), sizeof(U32), ids.size(), bin) == ids.size();
-        if (std::fclose(bin) != 0 || !ok) { std::fprintf(stderr, "cannot write %s\n", binPath.c_str()); return 1; }
+            ids = chain ? renderer.readAOVChainIds(maxLinks) : renderer.readAOVIds();
+            ok = ok && std::fwrite(ids.data(), sizeof(U32), ids.size(), bin) == ids.size();
+            if (std::fclose(bin) != 0 || !ok) { std::fprintf(stderr, "cannot write %s\n", binPath.c_str()); return false; }
+            return true;
+        };
+        std::vector<U32> ids, chainIds;
+        if (!writePlanes(prefix, false, ids)) return 1;
+        if (withChain && !writePlanes(prefix + "_chain", true, chainIds)) return 1;
         size_t hits = 0;
         for (size_t p = 0; p < (size_t)W * H; ++p) hits += ids[4 * p] != 0xffffffffu;
-        std::printf("{\"width\": %u, \"height\": %u, \"hit_pixels\": %zu}\n", W, H, hits);
+        if (withChain) {
+            size_t linked = 0;
+            for (size_t p = 0; p < (size_t)W * H; ++p) linked += chainIds[4 * p + 3] != 0u;
+            std::printf("{\"width\": %u, \"height\": %u, \"hit_pixels\": %zu, \"max_links\": %u, \"chain_pixels\": %zu}\n", W, H, hits,
+                        maxLinks, linked);
+        } else
+            std::printf("{\"width\": %u, \"height\": %u, \"hit_pixels\": %zu}\n", W, H, hits);
     } catch (const std::exception& e) {
         std::fprintf(stderr, "render_aov: %s\n", e.what());
         return 1;

@@ -13,6 +13,8 @@ Mirrors the reference interface for the hot path:
     .finalize_rgba8()          wavefront_finalize.comp + RgbaToU32
     .trace_closest/.trace_any  ray_extend / ray_connect traversal (tests)
     .aov()                     first-hit feature buffers (no reference counterpart)
+    .aov_chain(max_links)      the same planes traced through mirrors and glass; .set_filter_guides("chain") guides
+                               denoise() and denoise_sampled() with them (no reference counterpart)
     .denoise()                 edge-avoiding a-trous filter on them (no reference counterpart)
     .temporal()                temporal accumulation with reprojection across cleared frames (no reference counterpart)
     .svgf()                    the same with luminance moments, their variance guiding the a-trous filter (no reference counterpart);
@@ -215,6 +217,9 @@ def load() -> C.CDLL:
         "surf_display_rgba8": ([P, P], I32),
         "surf_read_aov": ([P, I32, P], I32), "surf_copy_aov_device": ([P, I32, P], I32),
         "surf_debug_aov_time": ([P, C.POINTER(F)], I32),
+        "surf_read_aov_chain": ([P, I32, U32, P], I32), "surf_copy_aov_chain_device": ([P, I32, U32, P], I32),
+        "surf_debug_aov_chain_time": ([P, C.POINTER(F)], I32),
+        "surf_set_filter_guides": ([P, I32, U32], I32), "surf_get_filter_guides": ([P, C.POINTER(I32), C.POINTER(U32)], I32),
         "surf_write_pfm": ([C.c_char_p, U32, U32, P], I32),
         "surf_denoise_default_params": ([C.POINTER(DenoiseParams)], I32),
         "surf_denoise": ([P, C.POINTER(DenoiseParams), P], I32),
@@ -455,6 +460,16 @@ def write_pfm(path: str, rgba: np.ndarray) -> None:
 
 
 AOV_PLANES = ("position", "normal", "albedo", "id")      # surf_aov order
+AOV_CHAIN_MAX_LINKS = 16                                 # SURF_AOV_CHAIN_MAX_LINKS
+FILTER_GUIDES = ("first_hit", "chain")                   # surf_guides order
+
+
+def _chain_links(max_links) -> int:
+    """max_links of the chain planes, checked before the library sees it."""
+    n = int(max_links)
+    if n != max_links or not 0 <= n <= AOV_CHAIN_MAX_LINKS:
+        raise ValueError(f"max_links {max_links!r}: an integer in 0..{AOV_CHAIN_MAX_LINKS}")
+    return n
 
 
 def denoise_params(**params) -> DenoiseParams:
@@ -965,6 +980,46 @@ class Renderer:
         ms = C.c_float()
         _check(load().surf_debug_aov_time(self._h, C.byref(ms)), "surf_debug_aov_time", self._h)
         return float(ms.value)
+
+    def aov_chain(self, max_links: int = 8) -> dict:
+        """The feature buffers traced through mirrors and glass (surf_read_aov_chain,
+        which defines the chain): aov()'s keys, shapes and dtypes, each pixel's
+        record taken at the first surface that is neither mirror nor glass along
+        the pixel's unjittered ray, or at link max_links (0..AOV_CHAIN_MAX_LINKS);
+        id.w is the number of links followed.  Cached like aov(), per max_links.
+        Not for reprojection: the position is the real terminal point."""
+        max_links = _chain_links(max_links)
+        out = {}
+        for k, name in enumerate(AOV_PLANES):
+            a = np.zeros((len(self.rows), self.width, 4), dtype=np.uint32 if name == "id" else np.float32)
+            _check(load().surf_read_aov_chain(self._h, k, max_links, _ptr(a)), "surf_read_aov_chain", self._h)
+            out[name] = a
+        return out
+
+    def copy_aov_chain_to(self, plane: int, device_ptr: int, max_links: int = 8):
+        max_links = _chain_links(max_links)
+        _check(load().surf_copy_aov_chain_device(self._h, plane, max_links, C.c_void_p(device_ptr)), "surf_copy_aov_chain_device", self._h)
+
+    def debug_aov_chain_time(self) -> float:
+        """Device milliseconds of the last chain kernel launch (surf_debug_aov_chain_time)."""
+        ms = C.c_float()
+        _check(load().surf_debug_aov_chain_time(self._h, C.byref(ms)), "surf_debug_aov_chain_time", self._h)
+        return float(ms.value)
+
+    def set_filter_guides(self, guides: str = "first_hit", max_links: int = 8):
+        """Which planes denoise() and denoise_sampled() read (surf_set_filter_guides):
+        "first_hit" (the default) or "chain", aov_chain(max_links)'s.  temporal(),
+        svgf(), mask_from_noise() and render_adaptive() keep the first-hit planes."""
+        if guides not in FILTER_GUIDES:
+            raise ValueError(f"filter guides {guides!r}: one of {FILTER_GUIDES}")
+        max_links = _chain_links(max_links)
+        _check(load().surf_set_filter_guides(self._h, FILTER_GUIDES.index(guides), max_links), "surf_set_filter_guides", self._h)
+
+    def filter_guides(self) -> tuple:
+        """(guides, max_links) as set_filter_guides took them (surf_get_filter_guides)."""
+        g, n = C.c_int(), C.c_uint32()
+        _check(load().surf_get_filter_guides(self._h, C.byref(g), C.byref(n)), "surf_get_filter_guides", self._h)
+        return FILTER_GUIDES[g.value], int(n.value)
 
     def denoise(self, **params) -> np.ndarray:
         """The accumulated radiance through the edge-avoiding a-trous filter
