@@ -385,6 +385,17 @@ public:
      * without arguments takes surf_noise_default_params and writes no image. */
     surf_noise_summary noiseEstimate(const surf_noise_params& params, std::vector<F32>* error = nullptr);
     surf_noise_summary noiseEstimate();
+    /* M partial accumulators per pixel beside the accumulator (surf_set_sample_buckets; M = 2, 4, 8 or
+     * 16, 0 = off): switch them on before the first render() or right after a clearAccumulator();
+     * readSampleBuckets() is the M planes, bucket-major, M*width*height*4 floats */
+    void setSampleBuckets(U32 M);
+    std::vector<F32> readSampleBuckets();
+    /* the median-of-means estimate of the accumulator from the buckets (surf_robust_accumulator): an
+     * accumulator plane, width*height*4 floats, the mean is rgb / w; trim non-NULL: it receives per
+     * pixel the bucket means dropped at either end, width*height bytes; summary non-NULL: the counts.
+     * The form without arguments takes surf_robust_default_params. */
+    std::vector<F32> robust(const surf_robust_params& params, std::vector<uint8_t>* trim = nullptr, surf_robust_summary* summary = nullptr);
+    std::vector<F32> robust();
     /* the active-pixel mask (surf_set_pixel_mask): width*height bytes, nonzero = active, render()
      * then traces those pixels only; an empty vector = every pixel.  pixelMask: the mask as set and,
      * where asked for, its active count. */

@@ -992,6 +992,118 @@ int surf_noise_image(surf_ctx* ctx, uint32_t npx, const float* acc, const float*
 int surf_noise_image_host(uint32_t npx, const float* acc, const float* squares, const surf_noise_params* params, float* out_error,
                           surf_noise_summary* summary);
 
+/* ---- sample buckets and the robust (median-of-means) estimate (no reference counterpart) ----
+ * For stills whose pixels have heavy-tailed sample distributions (caustics,
+ * paths that survive Russian roulette with probability 1): there the plain
+ * mean stops converging, and every filter and estimate above works from it.
+ * Everything here is opt-in: until surf_set_sample_buckets switches it on, no
+ * kernel, no launch, no allocation and no result bit differs.  The arithmetic
+ * is part of the interface (f32, uncontracted, / IEEE, in exactly this order);
+ * lum is the variance-guided filter's.
+ *
+ * The bucket planes: M planes (M = 2, 4, 8 or 16), bucket-major, each
+ * rows*width float4 records in shard order like the accumulator: 16 M bytes
+ * per pixel.  With the planes on, the kernel that adds a pass's radiance r --
+ * one sample per pixel, whatever samples_per_frame is -- to pixel p's
+ * accumulator record A takes, before that add,
+ *   s = (uint32_t)A.w;   j = s & (M - 1)
+ * and adds, plain f32 adds in pass order, to p's record of plane j:
+ *   B_j.x = B_j.x + r.x    B_j.y = B_j.y + r.y    B_j.z = B_j.z + r.z    B_j.w = B_j.w + 1.0f
+ * The bucket follows the pixel's own sample count, not the stream's pass
+ * number: the buckets stay balanced (counts differ by at most one) under a
+ * pixel mask, under the adaptive loop and across surf_render calls.  A.w is
+ * exact up to 2^24 samples.  The buckets with B_j.w > 0 partition the pixel's
+ * samples.  The accumulator, the squares plane, the sample stream, surf_stats
+ * and the event counters are bit for bit what they are with buckets off.
+ * surf_clear_accumulator zeroes the planes; surf_destroy frees them; a masked
+ * stream leaves an inactive pixel's bucket records untouched.  Pointwise, so
+ * row shards work as they are and the planes assemble like accumulators, plane
+ * by plane; gathering them through libsurf_mgpu.so is not provided.
+ * The sums of the even and of the odd planes are two half images of
+ * independent samples: what a dual-buffer error estimate of a filtered picture
+ * needs.
+ * Cost: while a pixel's passes arrive one at a time each is a read-modify-write
+ * of one bucket record (32 B beside the pass's 16 B of radiance); from a
+ * sample count that is a multiple of M, with M or more passes at hand, the M
+ * records are kept in registers for as many whole groups of M passes as there
+ * are and written once (32 M bytes a launch).  MEASUREMENTS "Sample buckets".
+ *
+ * The robust estimate.  Inputs: A, the M bucket records B_0 .. B_{M-1} of the
+ * pixel, trim_scale (finite and >= 0, default 1).  Per pixel; every sum starts
+ * from 0.0f and adds in the order given:
+ *   1. n_j = B_j.w; some n_j not > 0:                          out = A
+ *   2. m_j = (B_j.x / n_j, B_j.y / n_j, B_j.z / n_j);  l_j = lum(m_j)
+ *      some l_j not finite:                                    out = A
+ *   3. order the buckets ascending by (l_j, j): a precedes b iff
+ *      l_a < l_b || (l_a == l_b && a < b); call them (1) .. (M)
+ *   4. T  = sum over i = 1 .. M of l_(i)
+ *      Gn = sum over i = 1 .. M of (float)(2i - M - 1) * l_(i)
+ *      !(T > 0):                                               out = A
+ *   5. G = Gn / ((float)M * T)            -- the Gini coefficient of the bucket luminances
+ *      f = floorf((G * trim_scale) * ((float)M * 0.5f))
+ *      c = !(f >= 1) ? 0 : f >= (M-1)/2 ? (M-1)/2 : (uint32_t)f   (a NaN gives 0)
+ *   6. c == 0:                                                 out = A, bit for bit
+ *   7. e_k = (sum over i = c+1 .. M-c of m_(i).k) / (float)(M - 2c),  k = x, y, z
+ *      out = (e.x * A.w, e.y * A.w, e.z * A.w, A.w)
+ *   8. trim image byte = c (0 wherever out = A); summary: pixels, the pixels
+ *      looked at; trimmed, those with c > 0
+ * The output is an accumulator plane -- the mean is out.rgb / out.w -- so it
+ * goes straight into surf_denoise_image, surf_denoise_sampled_image,
+ * surf_firefly_image and surf_pack_rgba8_weighted.  With M = 2 the cap is 0
+ * and the estimate is the accumulator: two buckets only give the half images.
+ * The estimate is biased low by design: it removes energy.  On the bundled
+ * scene at 256 samples per pixel, M = 8, the image mean falls by about 0.0025
+ * (radiance units) against the plain mean; MEASUREMENTS "Robust estimate" has
+ * the errors.  It wants about 32 samples per bucket: at 64 samples and M = 8
+ * three quarters of the pixels are trimmed by plain noise and nothing is
+ * gained, at 256 samples one pixel in nine is.
+ * One kernel, one thread per pixel in blocks of 256: M + 1 16-byte loads, one
+ * 16-byte store and one byte per pixel; the buckets are ordered by counting
+ * ranks (M^2 compares) and taken by rank, nothing is indexed at run time; the
+ * trimmed pixels are counted by a ballot and popcount per wave and one integer
+ * add -- exact, whatever order the waves arrive in. */
+/* M planes on (M = 2, 4, 8, 16) or off (M = 0).  Drains the stream.
+ * SURF_ERR_INVALID for any other M, and unless the accumulator is empty -- no
+ * sample since surf_create* or the last surf_clear_accumulator: the buckets of
+ * samples already absorbed cannot be recovered; SURF_ERR_OOM when the planes
+ * cannot be allocated.  Switching off or to a smaller M keeps the allocation. */
+int surf_set_sample_buckets(surf_ctx* ctx, uint32_t M);
+int surf_get_sample_buckets(const surf_ctx* ctx, uint32_t* M);
+/* The M planes, bucket-major, to a host buffer of M*rows*width*4 floats / a
+ * buffer on the context's device (M*rows*width*16 bytes).  Drain the stream,
+ * as every read does; SURF_ERR_INVALID while the buckets are off. */
+int surf_read_sample_buckets(surf_ctx* ctx, float* out);
+int surf_copy_sample_buckets_device(surf_ctx* ctx, void* dst_device);
+typedef struct {
+    float trim_scale;
+    uint32_t _pad;
+} surf_robust_params;
+typedef struct {
+    uint64_t pixels, trimmed;
+} surf_robust_summary;
+/* trim_scale 1.0 */
+int surf_robust_default_params(surf_robust_params* params);
+/* The estimate of the context's own rows from its accumulator and buckets:
+ * out_acc rows*width*4 floats; out_trim (rows*width bytes) and summary may be
+ * NULL.  Works per shard: the counts add across shards.  Drains the stream;
+ * SURF_ERR_INVALID for a NULL context, params or out_acc, a trim_scale that is
+ * not finite and >= 0, and while the buckets are off; SURF_ERR_OOM when a
+ * scratch image cannot be allocated. */
+int surf_robust_accumulator(surf_ctx* ctx, const surf_robust_params* params, float* out_acc, uint8_t* out_trim,
+                            surf_robust_summary* summary);
+/* ... the output plane to a buffer on the context's device (rows*width*16 bytes) */
+int surf_robust_copy_device(surf_ctx* ctx, const surf_robust_params* params, void* dst_acc_device);
+/* Host planes of npx pixels, npx in 1..2^27: acc npx*4 floats, buckets
+ * M*npx*4 floats bucket-major, e.g. assembled from row shards; M = 2, 4, 8 or
+ * 16.  Needs no scene and no buckets on the context. */
+int surf_robust_image(surf_ctx* ctx, uint32_t npx, uint32_t M, const float* acc, const float* buckets,
+                      const surf_robust_params* params, float* out_acc, uint8_t* out_trim, surf_robust_summary* summary);
+/* The CPU twin; needs no device.  Bit-identical to surf_robust_image. */
+int surf_robust_image_host(uint32_t npx, uint32_t M, const float* acc, const float* buckets,
+                           const surf_robust_params* params, float* out_acc, uint8_t* out_trim, surf_robust_summary* summary);
+/* Diagnostics: device time (HIP events) of the last k_robust launch on this context. */
+int surf_debug_robust_time(surf_ctx* ctx, float* kernel_ms);
+
 /* ---- per-pixel sample masks and the adaptive loop (no reference counterpart) ----
  * A context carries an active-pixel mask: one byte per pixel of the shard in
  * shard order (rows*width), nonzero = active.  After surf_create* and after

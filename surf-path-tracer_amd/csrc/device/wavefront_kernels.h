@@ -3040,6 +3040,91 @@ __global__ __launch_bounds__(kBlock) void k_accumulate_list(const float4* __rest
     if (SQUARES) sq[p] = q;
 }
 
+/* The sum of k_accumulate for pixel p with the sample buckets on
+ * (surf_set_sample_buckets): M planes of npx records, bucket-major; the pass
+ * that finds the pixel with a.w = s samples also adds (r, 1) to the pixel's
+ * record of plane s & (M - 1).  acc and sq receive the same adds in the same
+ * order as without buckets.
+ * A pass on its own is a read-modify-write of its bucket's record (32 B).
+ * Once the pixel's count is a multiple of M and M passes or more are left,
+ * the M records go to registers, every following group of M passes adds pass
+ * i to record i -- a compile-time index, so nothing spills -- and the records
+ * are stored once the passes left are fewer than M: 32 M bytes however many
+ * groups ran.  The groups need a.w + 1 exact, so they stop below 2^24. */
+template <bool SQUARES, uint32_t M>
+__device__ __forceinline__ void accumulateBuckets(const float4* __restrict__ rad, float4* __restrict__ acc, float4* __restrict__ sq,
+                                                  float4* __restrict__ bk, uint32_t npx, uint32_t p, unsigned long long f0,
+                                                  uint32_t count, uint32_t window) {
+    static_assert(M == 2 || M == 4 || M == 8 || M == 16, "bucket counts the interface allows");
+    float4 a = acc[p];
+    float4 q = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    if (SQUARES) q = sq[p];
+    const auto take = [&](uint32_t k) {
+        const uint32_t slot = (uint32_t)((f0 + k) % window);
+        const float4 r = rad[(size_t)slot * npx + p];
+        a.x = a.x + r.x; a.y = a.y + r.y; a.z = a.z + r.z; a.w = a.w + 1.0f;
+        if (SQUARES) {
+            q.x = q.x + r.x * r.x; q.y = q.y + r.y * r.y; q.z = q.z + r.z * r.z;
+            const float l = (0.2126f * r.x + 0.7152f * r.y) + 0.0722f * r.z;
+            q.w = q.w + l * l;
+        }
+        return r;
+    };
+    uint32_t k = 0;
+    while (k < count) {
+        const uint32_t j = (uint32_t)a.w & (M - 1u);
+        if (j == 0u && count - k >= M && a.w < 16777216.0f - (float)M) {
+            float4 b[M];
+#pragma unroll
+            for (uint32_t i = 0; i < M; ++i) b[i] = bk[(size_t)i * npx + p];
+            do {
+#pragma unroll
+                for (uint32_t i = 0; i < M; ++i) {
+                    const float4 r = take(k + i);
+                    b[i].x = b[i].x + r.x; b[i].y = b[i].y + r.y; b[i].z = b[i].z + r.z; b[i].w = b[i].w + 1.0f;
+                }
+                k += M;
+            } while (count - k >= M && a.w < 16777216.0f - (float)M);
+#pragma unroll
+            for (uint32_t i = 0; i < M; ++i) bk[(size_t)i * npx + p] = b[i];
+        } else {
+            const float4 r = take(k);
+            float4* rec = bk + (size_t)j * npx + p;
+            float4 b = *rec;
+            b.x = b.x + r.x; b.y = b.y + r.y; b.z = b.z + r.z; b.w = b.w + 1.0f;
+            *rec = b;
+            ++k;
+        }
+    }
+    acc[p] = a;
+    if (SQUARES) sq[p] = q;
+}
+
+/* k_accumulate with the sample buckets on: a kernel of its own, chosen only
+ * then -- k_accumulate's text and arguments stay what they were. */
+template <bool SQUARES, uint32_t M>
+__global__ __launch_bounds__(kBlock) void k_accumulate_buckets(const float4* __restrict__ rad, float4* __restrict__ acc,
+                                                               uint32_t npx, unsigned long long f0, uint32_t count, uint32_t window,
+                                                               uint32_t* __restrict__ frameDone, float4* __restrict__ sq,
+                                                               float4* __restrict__ bk) {
+    const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p < count * kStripes) frameDone[(p % kStripes) * window + (uint32_t)((f0 + p / kStripes) % window)] = 0u;
+    if (p >= npx) return;
+    accumulateBuckets<SQUARES, M>(rad, acc, sq, bk, npx, p, f0, count, window);
+}
+
+/* ... and k_accumulate_list: an inactive pixel's bucket records stay untouched too */
+template <bool SQUARES, uint32_t M>
+__global__ __launch_bounds__(kBlock) void k_accumulate_buckets_list(const float4* __restrict__ rad, float4* __restrict__ acc,
+                                                                    uint32_t npx, unsigned long long f0, uint32_t count, uint32_t window,
+                                                                    uint32_t* __restrict__ frameDone, float4* __restrict__ sq,
+                                                                    float4* __restrict__ bk, const uint32_t* __restrict__ list, uint32_t n) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < count * kStripes) frameDone[(i % kStripes) * window + (uint32_t)((f0 + i / kStripes) % window)] = 0u;
+    if (i >= n) return;
+    accumulateBuckets<SQUARES, M>(rad, acc, sq, bk, npx, list[i], f0, count, window);
+}
+
 /* wavefront_finalize.comp + RgbaToU32 (cvtps2dq round-to-even, packus saturation) */
 SURF_HD uint32_t packChannel(float v) {
     if (!(v >= -2147483648.0f && v < 2147483648.0f)) return 0u;

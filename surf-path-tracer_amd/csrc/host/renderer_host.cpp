@@ -230,6 +230,32 @@ surf_noise_summary WaveFrontRenderer::noiseEstimate() {
     return noiseEstimate(params, nullptr);
 }
 
+void WaveFrontRenderer::setSampleBuckets(U32 M) {
+    check(surf_set_sample_buckets(m_ctx, M), m_ctx, "surf_set_sample_buckets");
+}
+
+std::vector<F32> WaveFrontRenderer::readSampleBuckets() {
+    U32 M = 0;
+    check(surf_get_sample_buckets(m_ctx, &M), m_ctx, "surf_get_sample_buckets");
+    std::vector<F32> out((size_t)M * m_resolution.width * m_resolution.height * 4);
+    check(surf_read_sample_buckets(m_ctx, out.data()), m_ctx, "surf_read_sample_buckets");
+    return out;
+}
+
+std::vector<F32> WaveFrontRenderer::robust(const surf_robust_params& params, std::vector<uint8_t>* trim, surf_robust_summary* summary) {
+    const size_t npx = (size_t)m_resolution.width * m_resolution.height;
+    std::vector<F32> out(npx * 4);
+    if (trim) trim->assign(npx, 0);
+    check(surf_robust_accumulator(m_ctx, &params, out.data(), trim ? trim->data() : nullptr, summary), m_ctx, "surf_robust_accumulator");
+    return out;
+}
+
+std::vector<F32> WaveFrontRenderer::robust() {
+    surf_robust_params params;
+    check(surf_robust_default_params(&params), m_ctx, "surf_robust_default_params");
+    return robust(params);
+}
+
 void WaveFrontRenderer::setPixelMask(const std::vector<uint8_t>& mask) {
     if (!mask.empty() && mask.size() != (size_t)m_resolution.width * m_resolution.height)
         throw std::runtime_error("setPixelMask: the mask is not width*height bytes");

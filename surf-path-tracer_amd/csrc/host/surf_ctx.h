@@ -222,6 +222,20 @@ struct surf_ctx {
      * first switched on, kept when switched off, freed in surf_destroy */
     float4* sq = nullptr;
     bool sqOn = false;
+    /* the sample buckets beside the accumulator (surf_set_sample_buckets): bkM
+     * planes of npx records (sum r.x, sum r.y, sum r.z, samples), bucket-major,
+     * bkM = 0: off; bkPlanes of them allocated -- when first switched on or to a
+     * larger M, kept when switched off or to a smaller one, freed in surf_destroy */
+    float4* bk = nullptr;
+    uint32_t bkM = 0, bkPlanes = 0;
+    /* the robust estimate (surf_robust_*, host/robust.hip): rbOut, the output
+     * plane; rbTrim, the striped trimmed-pixel counters (4 KB) and behind them
+     * the trim image (1 B per pixel); rbIn, the accumulator and the M bucket
+     * planes surf_robust_image uploads (one allocation of (1 + M) * npx records) */
+    PlaneGroup<1> rbOut{"the robust estimate's image"};
+    PlaneGroup<1> rbTrim{"the robust estimate's trim image"};
+    PlaneGroup<1> rbIn{"surf_robust_image's planes"};
+    StageTimer<1> rbTime;          /* the last k_robust launch (surf_debug_robust_time) */
     /* the active-pixel mask (surf_set_pixel_mask, surf_mask_from_noise; host/adaptive.hip):
      * pmOn: a mask that leaves some pixel out is set (an all-ones mask is "no
      * mask"); then pmMask holds its npx bytes, pmList the pmActive ascending
@@ -359,6 +373,8 @@ void freeTemporal(surf_ctx* c);
 void freeSvgf(surf_ctx* c);
 /* defined in host/adaptive.hip: surf_destroy's part for the mask's buffers */
 void freeAdaptive(surf_ctx* c);
+/* defined in host/robust.hip: surf_destroy's part for the robust estimate's images */
+void freeRobust(surf_ctx* c);
 
 #define SURF_CHECK(ctx, call)                                                             \
     do {                                                                                  \

@@ -165,6 +165,13 @@ auto traceAnyCoopKernel(const surf_ctx* c, const Variant& v) { return kernel(SUR
 auto accumulateKernel(const surf_ctx* c) { return c->sqOn ? k_accumulate<true> : k_accumulate<false>; }
 /* ... and a masked stream's frames go through the active list */
 auto accumulateListKernel(const surf_ctx* c) { return c->sqOn ? k_accumulate_list<true> : k_accumulate_list<false>; }
+/* k_accumulate_buckets<SQUARES, M> / k_accumulate_buckets_list<SQUARES, M>: chosen instead while
+ * surf_set_sample_buckets has M planes on (c->bkM is 2, 4, 8 or 16) */
+#define SURF_PICK_BUCKETS(K, SQ, M) \
+    ((M) == 2u ? ((SQ) ? K<true, 2u> : K<false, 2u>) : (M) == 4u ? ((SQ) ? K<true, 4u> : K<false, 4u>) \
+     : (M) == 8u ? ((SQ) ? K<true, 8u> : K<false, 8u>) : ((SQ) ? K<true, 16u> : K<false, 16u>))
+auto accumulateBucketsKernel(const surf_ctx* c) { return SURF_PICK_BUCKETS(k_accumulate_buckets, c->sqOn, c->bkM); }
+auto accumulateBucketsListKernel(const surf_ctx* c) { return SURF_PICK_BUCKETS(k_accumulate_buckets_list, c->sqOn, c->bkM); }
 /* k_regen<MASKED> / k_regen_count<MASKED>: a masked stream issues frame-major over the active list */
 auto regenKernel(const surf_ctx* c) { return c->streamMasked ? k_regen<true> : k_regen<false>; }
 auto regenCountKernel(const surf_ctx* c) { return c->streamMasked ? k_regen_count<true> : k_regen_count<false>; }
@@ -701,7 +708,15 @@ int consumeSnap(surf_ctx* c) {
             if (!e) SURF_CHECK(c, hipEventCreate(&e));
         SURF_CHECK(c, hipEventRecord(c->accEv[0], c->stream));
     }
-    if (c->streamMasked)
+    if (c->bkM && c->streamMasked)
+        hipLaunchKernelGGL(accumulateBucketsListKernel(c), dim3((threads + kBlock - 1) / kBlock), dim3(kBlock), 0, c->stream, (const float4*)c->rad,
+                           c->acc, c->npx, (unsigned long long)c->accPasses, count, c->window, c->frameDone, c->sqOn ? c->sq : nullptr,
+                           c->bk, (const uint32_t*)c->pmList, c->pmActive);
+    else if (c->bkM)
+        hipLaunchKernelGGL(accumulateBucketsKernel(c), dim3((threads + kBlock - 1) / kBlock), dim3(kBlock), 0, c->stream, (const float4*)c->rad,
+                           c->acc, c->npx, (unsigned long long)c->accPasses, count, c->window, c->frameDone, c->sqOn ? c->sq : nullptr,
+                           c->bk);
+    else if (c->streamMasked)
         hipLaunchKernelGGL(accumulateListKernel(c), dim3((threads + kBlock - 1) / kBlock), dim3(kBlock), 0, c->stream, (const float4*)c->rad,
                            c->acc, c->npx, (unsigned long long)c->accPasses, count, c->window, c->frameDone, c->sqOn ? c->sq : nullptr,
                            (const uint32_t*)c->pmList, c->pmActive);
@@ -1175,12 +1190,14 @@ void surf_destroy(surf_ctx* c) {
     if (c->phaseLog) std::fclose(c->phaseLog);
     if (c->acc) (void)hipFree(c->acc);
     if (c->sq) (void)hipFree(c->sq);
+    if (c->bk) (void)hipFree(c->bk);
     for (auto& e : c->accEv) if (e) (void)hipEventDestroy(e);
     for (void*& p : c->aov) { if (p) (void)hipFree(p); p = nullptr; }
     for (void*& p : c->aovChain) { if (p) (void)hipFree(p); p = nullptr; }
     freeDenoise(c);
     freeTemporal(c);
     freeAdaptive(c);
+    freeRobust(c);
     if (c->dRows) (void)hipFree(c->dRows);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);
@@ -1404,6 +1421,7 @@ int surf_clear_accumulator(surf_ctx* c) {
     if (rc) return rc;
     SURF_CHECK(c, hipMemsetAsync(c->acc, 0, (size_t)c->npx * sizeof(float4), c->stream));
     if (c->sq) SURF_CHECK(c, hipMemsetAsync(c->sq, 0, (size_t)c->npx * sizeof(float4), c->stream));
+    if (c->bk) SURF_CHECK(c, hipMemsetAsync(c->bk, 0, (size_t)c->bkPlanes * c->npx * sizeof(float4), c->stream));
     SURF_CHECK(c, hipStreamSynchronize(c->stream));
     c->totalSamples = 0;
     std::memset(&c->stats, 0, sizeof c->stats);
@@ -1471,6 +1489,58 @@ static int copySquares(surf_ctx* c, void* dst, hipMemcpyKind kind) {
 int surf_read_sample_squares(surf_ctx* c, float* out) { return copySquares(c, out, hipMemcpyDeviceToHost); }
 
 int surf_copy_sample_squares_device(surf_ctx* c, void* dst) { return copySquares(c, dst, hipMemcpyDeviceToDevice); }
+
+int surf_set_sample_buckets(surf_ctx* c, uint32_t M) {
+    if (!c) return SURF_ERR_INVALID;
+    if (M != 0 && M != 2 && M != 4 && M != 8 && M != 16)
+        return fail(c, SURF_ERR_INVALID, "surf_set_sample_buckets: M is none of 0, 2, 4, 8 and 16");
+    SURF_CHECK(c, hipSetDevice(c->device));
+    int rc = ensureDrained(c);
+    if (rc) return rc;
+    if (c->totalSamples != 0)
+        return fail(c, SURF_ERR_INVALID, "surf_set_sample_buckets: the accumulator holds samples whose buckets are lost; call "
+                                         "surf_clear_accumulator first");
+    if (M > c->bkPlanes) {
+        const size_t bytes = (size_t)M * c->npx * sizeof(float4);
+        float4* planes = nullptr;
+        if (hipMalloc(&planes, bytes) != hipSuccess || !planes) {
+            (void)hipGetLastError();
+            return fail(c, SURF_ERR_OOM, "hipMalloc of the bucket planes (" + std::to_string(bytes) + " bytes) failed");
+        }
+        if (c->bk) (void)hipFree(c->bk);
+        c->bk = planes;
+        c->bkPlanes = M;
+    }
+    /* the accumulator is empty, so the planes are too: zeroed here whatever an earlier, other M left in them */
+    if (c->bk) {
+        SURF_CHECK(c, hipMemsetAsync(c->bk, 0, (size_t)c->bkPlanes * c->npx * sizeof(float4), c->stream));
+        SURF_CHECK(c, hipStreamSynchronize(c->stream));
+    }
+    c->bkM = M;
+    return SURF_OK;
+}
+
+int surf_get_sample_buckets(const surf_ctx* c, uint32_t* M) {
+    if (!c || !M) return SURF_ERR_INVALID;
+    *M = c->bkM;
+    return SURF_OK;
+}
+
+/* surf_read_sample_buckets / surf_copy_sample_buckets_device */
+static int copyBuckets(surf_ctx* c, void* dst, hipMemcpyKind kind) {
+    if (!c || !dst) return SURF_ERR_INVALID;
+    SURF_CHECK(c, hipSetDevice(c->device));
+    int rc = ensureDrained(c);
+    if (rc) return rc;
+    if (!c->bkM) return fail(c, SURF_ERR_INVALID, "sample buckets are off (surf_set_sample_buckets)");
+    SURF_CHECK(c, hipMemcpyAsync(dst, c->bk, (size_t)c->bkM * c->npx * sizeof(float4), kind, c->stream));
+    SURF_CHECK(c, hipStreamSynchronize(c->stream));
+    return SURF_OK;
+}
+
+int surf_read_sample_buckets(surf_ctx* c, float* out) { return copyBuckets(c, out, hipMemcpyDeviceToHost); }
+
+int surf_copy_sample_buckets_device(surf_ctx* c, void* dst) { return copyBuckets(c, dst, hipMemcpyDeviceToDevice); }
 
 int surf_read_aov(surf_ctx* c, int plane, void* out) {
     if (!c || !out || plane < 0 || plane >= SURF_AOV_COUNT) return SURF_ERR_INVALID;

@@ -20,6 +20,14 @@
  * parameters with max_samples = ADAPTIVE_MAX and min_samples = min(16,
  * ADAPTIVE_MAX)): PREFIX_adaptive.pfm is each pixel's mean over its own
  * samples, PREFIX_counts.pfm its sample count in all three channels.
+ * With ROBUST_M (2, 4, 8 or 16; ADAPTIVE_MAX may then be 0 for "no adaptive
+ * render") the render also keeps ROBUST_M sample buckets (setSampleBuckets)
+ * and the median-of-means estimate of the accumulator
+ * (WaveFrontRenderer::robust, surf_robust_accumulator) feeds the filters in the
+ * accumulator's place, through their image forms (surf_denoise_image,
+ * surf_denoise_sampled_image) with the renderer's feature buffers;
+ * PREFIX_robust.pfm is that estimate's mean, PREFIX_noisy.pfm stays the plain
+ * mean.  Wants about 32 samples per bucket.
  */
 #include "surf/surf_host.hpp"
 #include "indoor_scene.hpp"
@@ -32,15 +40,23 @@
 using namespace surf;
 
 int main(int argc, char** argv) {
-    if (argc != 6 && argc != 7) {
-        std::fprintf(stderr, "usage: %s ASSETS_DIR WIDTH HEIGHT SPP PREFIX [ADAPTIVE_MAX]\n", argv[0]);
+    if (argc < 6 || argc > 8) {
+        std::fprintf(stderr, "usage: %s ASSETS_DIR WIDTH HEIGHT SPP PREFIX [ADAPTIVE_MAX [ROBUST_M]]\n", argv[0]);
         return 2;
     }
     const std::string dir = argv[1], prefix = argv[5];
     const int w = std::atoi(argv[2]), h = std::atoi(argv[3]), spp = std::atoi(argv[4]);
     if (w <= 0 || h <= 0 || spp <= 0) { std::fprintf(stderr, "render_denoised: WIDTH, HEIGHT and SPP must be positive\n"); return 2; }
-    const int adaptiveMax = argc == 7 ? std::atoi(argv[6]) : 0;
-    if (argc == 7 && adaptiveMax < 2) { std::fprintf(stderr, "render_denoised: ADAPTIVE_MAX must be at least 2\n"); return 2; }
+    const int adaptiveMax = argc >= 7 ? std::atoi(argv[6]) : 0;
+    if (argc >= 7 && adaptiveMax < 2 && !(argc == 8 && adaptiveMax == 0)) {
+        std::fprintf(stderr, "render_denoised: ADAPTIVE_MAX must be at least 2\n");
+        return 2;
+    }
+    const int robustM = argc == 8 ? std::atoi(argv[7]) : 0;
+    if (argc == 8 && robustM != 2 && robustM != 4 && robustM != 8 && robustM != 16) {
+        std::fprintf(stderr, "render_denoised: ROBUST_M must be 2, 4, 8 or 16\n");
+        return 2;
+    }
     const U32 W = (U32)w, H = (U32)h;
     try {
         RenderContext context;            /* HIP device 0 */
@@ -51,6 +67,7 @@ int main(int argc, char** argv) {
         WaveFrontRenderer renderer(&context, nullptr, config, FramebufferSize{W, H}, worldCam, *indoor.scene);
         const bool sampled = spp >= 2;    /* one sample has no variance */
         if (sampled) renderer.setSampleSquares(true);
+        if (robustM) renderer.setSampleBuckets((U32)robustM);
         renderer.render(0.0f);
 
         std::vector<F32> noisy = renderer.readAccumulator();
@@ -59,7 +76,40 @@ int main(int argc, char** argv) {
             for (int k = 0; k < 3; ++k) noisy[4 * p + k] = noisy[4 * p + k] * inv;
             noisy[4 * p + 3] = 1.0f;
         }
-        const std::vector<F32> clean = renderer.denoise();
+        /* with ROBUST_M: the robust accumulator and the feature buffers the image forms of the filters take */
+        std::vector<F32> robustAcc, planes[3];
+        if (robustM) {
+            robustAcc = renderer.robust();
+            const int which[3] = {SURF_AOV_POSITION, SURF_AOV_NORMAL, SURF_AOV_ALBEDO};
+            for (int k = 0; k < 3; ++k) {
+                planes[k].resize((size_t)W * H * 4);
+                if (surf_read_aov(renderer.handle(), which[k], planes[k].data()) != SURF_OK) {
+                    std::fprintf(stderr, "render_denoised: surf_read_aov: %s\n", surf_last_error(renderer.handle()));
+                    return 1;
+                }
+            }
+            std::vector<F32> mean(robustAcc);
+            for (size_t p = 0; p < (size_t)W * H; ++p) {
+                const F32 inv = mean[4 * p + 3] > 0.0f ? 1.0f / mean[4 * p + 3] : 0.0f;
+                for (int k = 0; k < 3; ++k) mean[4 * p + k] = mean[4 * p + k] * inv;
+                mean[4 * p + 3] = 1.0f;
+            }
+            const std::string path = prefix + "_robust.pfm";
+            if (surf_write_pfm(path.c_str(), W, H, mean.data()) != SURF_OK) { std::fprintf(stderr, "cannot write %s\n", path.c_str()); return 1; }
+        }
+        std::vector<F32> clean;
+        if (robustM) {
+            surf_denoise_params dp;
+            surf_denoise_default_params(&dp);
+            clean.resize((size_t)W * H * 4);
+            if (surf_denoise_image(renderer.handle(), W, H, robustAcc.data(), planes[0].data(), planes[1].data(), planes[2].data(), &dp,
+                                   clean.data()) != SURF_OK) {
+                std::fprintf(stderr, "render_denoised: surf_denoise_image: %s\n", surf_last_error(renderer.handle()));
+                return 1;
+            }
+        } else {
+            clean = renderer.denoise();
+        }
         std::vector<U32> rgba8((size_t)W * H);
         if (surf_pack_rgba8(clean.data(), W * H, 1.0f, 1, rgba8.data()) != SURF_OK) {
             std::fprintf(stderr, "render_denoised: surf_pack_rgba8 failed\n");
@@ -72,7 +122,21 @@ int main(int argc, char** argv) {
             if (rc[k] != SURF_OK) { std::fprintf(stderr, "cannot write %s\n", paths[k].c_str()); return 1; }
         if (sampled) {
             const std::string path = prefix + "_sampled.pfm";
-            const std::vector<F32> guided = renderer.denoiseSampled();
+            std::vector<F32> guided;
+            if (robustM) {
+                surf_svgf_params sp;
+                surf_svgf_default_params(&sp);
+                const std::vector<F32> squares = renderer.readSampleSquares();
+                std::vector<F32> variance((size_t)W * H * 4);
+                guided.resize((size_t)W * H * 4);
+                if (surf_denoise_sampled_image(renderer.handle(), W, H, robustAcc.data(), squares.data(), planes[0].data(), planes[1].data(),
+                                               planes[2].data(), &sp, guided.data(), variance.data()) != SURF_OK) {
+                    std::fprintf(stderr, "render_denoised: surf_denoise_sampled_image: %s\n", surf_last_error(renderer.handle()));
+                    return 1;
+                }
+            } else {
+                guided = renderer.denoiseSampled();
+            }
             if (surf_write_pfm(path.c_str(), W, H, guided.data()) != SURF_OK) { std::fprintf(stderr, "cannot write %s\n", path.c_str()); return 1; }
         }
         if (adaptiveMax) {

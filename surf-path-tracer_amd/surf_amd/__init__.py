@@ -25,6 +25,8 @@ Mirrors the reference interface for the hot path:
     .set_pixel_mask(mask)      per-pixel sample mask: render() then traces the active pixels only (no reference counterpart)
     .mask_from_noise()         the mask from the noise estimate; .render_adaptive() the "render until converged" loop around it
     .finalize_weighted()       RGBA8 with each pixel divided by its own sample count
+    .set_sample_buckets(M)     M partial accumulators per pixel, .sample_buckets() reads them, bucket_halves() sums the half images
+    .robust()                  the median-of-means estimate of the accumulator with a Gini-adaptive trim (no reference counterpart)
 """
 from __future__ import annotations
 
@@ -144,6 +146,19 @@ class NoiseSummary(C.Structure):
 
     def as_dict(self) -> dict:
         return {"pixels": int(self.pixels), "above": int(self.above), "max_error": float(self.max_error)}
+
+
+class RobustParams(C.Structure):
+    """surf_robust_params: the factor on the Gini coefficient that decides how many bucket means are dropped."""
+    _fields_ = [("trim_scale", C.c_float), ("_pad", C.c_uint32)]
+
+
+class RobustSummary(C.Structure):
+    """surf_robust_summary: pixels looked at, pixels whose extreme bucket means were dropped."""
+    _fields_ = [("pixels", C.c_uint64), ("trimmed", C.c_uint64)]
+
+    def as_dict(self) -> dict:
+        return {"pixels": int(self.pixels), "trimmed": int(self.trimmed)}
 
 
 class AdaptiveMaskParams(C.Structure):
@@ -272,6 +287,14 @@ def load() -> C.CDLL:
         "surf_adaptive_mask_image_host": ([U32, U32, P, P, C.POINTER(AdaptiveMaskParams), P, P, C.POINTER(U32)], I32),
         "surf_render_adaptive": ([P, C.POINTER(AdaptiveParams), P, U32, C.POINTER(AdaptiveSummary)], I32),
         "surf_finalize_rgba8_weighted": ([P, I32, P], I32), "surf_pack_rgba8_weighted": ([P, U32, I32, P], I32),
+        "surf_set_sample_buckets": ([P, U32], I32), "surf_get_sample_buckets": ([P, C.POINTER(U32)], I32),
+        "surf_read_sample_buckets": ([P, P], I32), "surf_copy_sample_buckets_device": ([P, P], I32),
+        "surf_robust_default_params": ([C.POINTER(RobustParams)], I32),
+        "surf_robust_accumulator": ([P, C.POINTER(RobustParams), P, P, C.POINTER(RobustSummary)], I32),
+        "surf_robust_copy_device": ([P, C.POINTER(RobustParams), P], I32),
+        "surf_robust_image": ([P, U32, U32, P, P, C.POINTER(RobustParams), P, P, C.POINTER(RobustSummary)], I32),
+        "surf_robust_image_host": ([U32, U32, P, P, C.POINTER(RobustParams), P, P, C.POINTER(RobustSummary)], I32),
+        "surf_debug_robust_time": ([P, C.POINTER(F)], I32),
         "surf_mesh_data": ([P, C.POINTER(P), C.POINTER(P), C.POINTER(U32)], I32),
         "surf_mesh_destroy": ([P], None),
         "surf_ref_sinf": ([F], F), "surf_ref_cosf": ([F], F), "surf_ref_expf": ([F], F),
@@ -726,6 +749,53 @@ def noise_image_host(acc, squares, threshold=None, floor=None):
     p, s = noise_params(threshold, floor), NoiseSummary()
     _check(load().surf_noise_image_host(err.size, _ptr(a), _ptr(q), C.byref(p), _ptr(err), C.byref(s)), "surf_noise_image_host")
     return err, s.as_dict()
+
+
+def robust_params(trim_scale=None) -> RobustParams:
+    """surf_robust_default_params (trim_scale 1.0) with the given field replaced."""
+    p = RobustParams()
+    _check(load().surf_robust_default_params(C.byref(p)), "surf_robust_default_params")
+    if trim_scale is not None:
+        p.trim_scale = float(trim_scale)
+    return p
+
+
+def _robust_planes(acc, buckets):
+    """(npx, M, acc, buckets, out, trim): acc of any shape (..., 4), buckets (M, ..., 4), contiguous float32."""
+    a, b = (np.ascontiguousarray(v, dtype=np.float32) for v in (acc, buckets))
+    if a.ndim < 2 or a.shape[-1] != 4 or b.shape[1:] != a.shape:
+        raise ValueError(f"robust planes {a.shape}, {b.shape} are not an (..., 4) image and its (M, ..., 4) buckets")
+    return a.size // 4, b.shape[0], a, b, np.zeros_like(a), np.zeros(a.shape[:-1], np.uint8)
+
+
+def robust_image_host(acc, buckets, trim_scale=None):
+    """The CPU twin of robust_image (surf_robust_image_host): (accumulator plane, trim image, summary dict) of an
+    accumulator of any shape (..., 4) and its (M, ..., 4) bucket planes; bit-identical, no device."""
+    npx, m, a, b, out, trim = _robust_planes(acc, buckets)
+    p, s = robust_params(trim_scale), RobustSummary()
+    _check(load().surf_robust_image_host(npx, m, _ptr(a), _ptr(b), C.byref(p), _ptr(out), _ptr(trim), C.byref(s)), "surf_robust_image_host")
+    return out, trim, s.as_dict()
+
+
+def robust_image(renderer, acc, buckets, trim_scale=None):
+    """The robust estimate on the renderer's device of host planes (surf_robust_image), e.g. planes assembled from row
+    shards: (accumulator plane, trim image, summary dict)."""
+    return renderer.robust_image(acc, buckets, trim_scale)
+
+
+def bucket_halves(buckets) -> tuple:
+    """The two half images of (M, ..., 4) bucket planes: the sums of the even and of the odd planes, added in bucket
+    order in float32.  Accumulator planes of independent samples (w = the half's sample count)."""
+    b = np.asarray(buckets, dtype=np.float32)
+    if b.ndim < 3 or b.shape[-1] != 4 or b.shape[0] < 2:
+        raise ValueError(f"bucket planes {b.shape} are not (M, ..., 4) with M >= 2")
+    halves = []
+    for first in (0, 1):
+        s = np.zeros(b.shape[1:], np.float32)
+        for j in range(first, b.shape[0], 2):
+            s = s + b[j]
+        halves.append(s)
+    return halves[0], halves[1]
 
 
 _MASK_FIELDS = ("threshold", "floor", "min_samples", "max_samples", "dilate")
@@ -1242,6 +1312,55 @@ class Renderer:
         p, s = noise_params(threshold, floor), NoiseSummary()
         _check(load().surf_noise_image(self._h, err.size, _ptr(a), _ptr(q), C.byref(p), _ptr(err), C.byref(s)), "surf_noise_image", self._h)
         return err, s.as_dict()
+
+    def set_sample_buckets(self, m: int):
+        """Switches M sample buckets on (M = 2, 4, 8, 16) or off (0) (surf_set_sample_buckets): each sample is also summed
+        into the bucket its pixel's sample count selects.  Raises SURF_ERR_INVALID unless the accumulator is empty."""
+        _check(load().surf_set_sample_buckets(self._h, int(m)), "surf_set_sample_buckets", self._h)
+
+    def sample_bucket_count(self) -> int:
+        m = C.c_uint32()
+        _check(load().surf_get_sample_buckets(self._h, C.byref(m)), "surf_get_sample_buckets", self._h)
+        return int(m.value)
+
+    def sample_buckets(self) -> np.ndarray:
+        """The bucket planes of this shard's rows (surf_read_sample_buckets): (M, rows, width, 4) float32,
+        (sum r, sum g, sum b, samples) of the samples each bucket took."""
+        out = np.zeros((self.sample_bucket_count(), len(self.rows), self.width, 4), dtype=np.float32)
+        _check(load().surf_read_sample_buckets(self._h, _ptr(out)), "surf_read_sample_buckets", self._h)
+        return out
+
+    def copy_sample_buckets_to(self, device_ptr: int):
+        _check(load().surf_copy_sample_buckets_device(self._h, C.c_void_p(device_ptr)), "surf_copy_sample_buckets_device", self._h)
+
+    def robust(self, trim_scale=None, image: bool = True):
+        """(accumulator plane, trim image, summary dict) of this shard's rows (surf_robust_accumulator): the
+        median-of-means estimate from the sample buckets, an accumulator plane (mean = rgb / w); per pixel the bucket
+        means dropped at either end; {'pixels', 'trimmed'}.  image=False: no trim image is written, None returned."""
+        p, s = robust_params(trim_scale), RobustSummary()
+        out = np.zeros((len(self.rows), self.width, 4), np.float32)
+        trim = np.zeros((len(self.rows), self.width), np.uint8) if image else None
+        _check(load().surf_robust_accumulator(self._h, C.byref(p), _ptr(out), _ptr(trim) if image else None, C.byref(s)),
+               "surf_robust_accumulator", self._h)
+        return out, trim, s.as_dict()
+
+    def robust_image(self, acc, buckets, trim_scale=None):
+        """The same on host planes: acc of any shape (..., 4), buckets (M, ..., 4) (surf_robust_image)."""
+        npx, m, a, b, out, trim = _robust_planes(acc, buckets)
+        p, s = robust_params(trim_scale), RobustSummary()
+        _check(load().surf_robust_image(self._h, npx, m, _ptr(a), _ptr(b), C.byref(p), _ptr(out), _ptr(trim), C.byref(s)),
+               "surf_robust_image", self._h)
+        return out, trim, s.as_dict()
+
+    def copy_robust_to(self, device_ptr: int, trim_scale=None):
+        p = robust_params(trim_scale)
+        _check(load().surf_robust_copy_device(self._h, C.byref(p), C.c_void_p(device_ptr)), "surf_robust_copy_device", self._h)
+
+    def debug_robust_time(self) -> float:
+        """Device milliseconds of the last k_robust launch (surf_debug_robust_time)."""
+        ms = C.c_float()
+        _check(load().surf_debug_robust_time(self._h, C.byref(ms)), "surf_debug_robust_time", self._h)
+        return float(ms.value)
 
     def set_pixel_mask(self, mask):
         """The active-pixel mask of this shard (surf_set_pixel_mask): (rows, W) or flat, nonzero = active; None = every
