@@ -46,6 +46,9 @@ def load():
         "orc_scene_mesh_tris": ([P, P, I32], I32),
         "orc_scene_instance_count": ([P], U32), "orc_scene_light_count": ([P], U32),
         "orc_scene_set_camera": ([P, U32, U32], None), "orc_camera_ubo": ([P, P], None),
+        "orc_scene_set_view": ([P, P, P, F, F, F], None),
+        "orc_scene_set_background": ([P, I32, P, P, P], None),
+        "orc_scene_set_material": ([P, U32, P, P, P, F, F, F, F], I32),
         "orc_scene_export": ([P, I32, P], C.c_uint64),
         "orc_render": ([P, U32, U32, U32, U32, U32, U32, U32, I32, P, C.POINTER(Counters)], D),
         "orc_render_spp": ([P, U32, U32, U32, U32, U32, U32, U32, U32, I32, P, C.POINTER(Counters)], D),
@@ -76,6 +79,17 @@ def _p(a):
     return a.ctypes.data
 
 
+def _f3(v):
+    a = np.ascontiguousarray(v, np.float32)
+    if a.shape != (3,):
+        raise ValueError(f"{v!r} is not three floats")
+    return a
+
+
+# main.cpp:141-149 and :343-346
+DEFAULT_VIEW = {"pos": (0.0, 0.0, -7.0), "target": (0.0, 0.0, 0.0), "fov_y": 70.0, "focal": 7.0, "defocus": 0.5}
+DEFAULT_BACKGROUND = {"type": 1, "color": (0.0, 0.0, 0.0), "a": (0.8, 0.8, 0.8), "b": (0.1, 0.4, 0.6)}
+
 EXPORT_ORDER = ["triangles", "tri_ext", "blas_indices", "blas_nodes", "materials", "instances",
                 "tlas_indices", "tlas_nodes", "lights", "background"]
 
@@ -103,6 +117,42 @@ class OracleScene:
         buf = (C.c_uint8 * 128)()
         load().orc_camera_ubo(self._h, buf)
         return bytes(buf)
+
+    def set_view(self, pos=DEFAULT_VIEW["pos"], target=DEFAULT_VIEW["target"], fov_y=DEFAULT_VIEW["fov_y"],
+                 focal=DEFAULT_VIEW["focal"], defocus=DEFAULT_VIEW["defocus"]):
+        """Camera::Camera's arguments (camera.h:31); kept for every later camera_ubo()
+        and render, of any resolution.  The defaults are main.cpp:141-149."""
+        pos, target = _f3(pos), _f3(target)
+        load().orc_scene_set_view(self._h, _p(pos), _p(target), fov_y, focal, defocus)
+
+    def set_background(self, type=DEFAULT_BACKGROUND["type"], color=DEFAULT_BACKGROUND["color"],
+                       a=DEFAULT_BACKGROUND["a"], b=DEFAULT_BACKGROUND["b"]):
+        """SceneBackground (scene.h:18-26): type 0 solid colour, 1 gradient from a to b,
+        other black.  The defaults are main.cpp:343-346."""
+        color, a, b = _f3(color), _f3(a), _f3(b)
+        load().orc_scene_set_background(self._h, int(type), _p(color), _p(a), _p(b))
+
+    def materials(self) -> list[dict]:
+        """The Material records (material.h:6-19) in export()'s first-use order."""
+        m = np.frombuffer(self.export()["materials"], np.float32).reshape(-1, 16)
+        return [{"emit": float(r[0]), "refl": float(r[1]), "refr": float(r[2]), "ior": float(r[3]),
+                 "emit_color": tuple(map(float, r[4:7])), "albedo": tuple(map(float, r[8:11])),
+                 "absorption": tuple(map(float, r[12:15]))} for r in m]
+
+    def set_material(self, index, **fields):
+        """Replaces the given fields (materials()' names) of material `index` in export()'s
+        first-use order; the light list is collected again (scene.cpp:22-32)."""
+        cur = self.materials()
+        if not 0 <= index < len(cur):
+            raise IndexError(f"material {index}: the scene uses {len(cur)}")
+        unknown = [k for k in fields if k not in cur[index]]
+        if unknown:
+            raise TypeError(f"unknown material field {unknown[0]!r}")
+        m = dict(cur[index], **fields)
+        albedo, absorption, emit_color = _f3(m["albedo"]), _f3(m["absorption"]), _f3(m["emit_color"])
+        rc = load().orc_scene_set_material(self._h, index, _p(albedo), _p(absorption), _p(emit_color),
+                                           m["emit"], m["refl"], m["refr"], m["ior"])
+        assert rc == 0, rc
 
     def export(self) -> dict[str, bytes]:
         out = {}

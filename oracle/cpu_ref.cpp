@@ -510,7 +510,9 @@ struct Scene {
     std::vector<uint32_t> lights;
     /* SceneBackground (scene.h:18-26), main.cpp:343-346 */
     int bgType = 1; V3 bgColor = {0, 0, 0}, bgA = {0.8f, 0.8f, 0.8f}, bgB = {0.1f, 0.4f, 0.6f};
-    /* camera, camera.h:27-57 */
+    /* camera, camera.h:27-57; the view (position, target, fovY, focal length,
+     * defocus angle) is main.cpp:141-149 until orc_scene_set_view replaces it */
+    V3 viewPos = {0.0f, 0.0f, -7.0f}, viewTarget = {0.0f, 0.0f, 0.0f};
     V3 camPos, camFwd, camUp; float scrW = 0, scrH = 0, fovY = 70.0f, focal = 7.0f, defocus = 0.5f;
     V3 firstPixel, uVec, vVec;
     uint32_t stackMax = 0;
@@ -552,6 +554,12 @@ bool tlasTrace(const Scene& S, V3 o, V3 d, float& depth, Hit& hit, uint32_t& sta
 }
 
 /* ------------------------------------------------------------ scene setup */
+/* Scene::Scene's light collection, scene.cpp:22-32: instance order. */
+void collectLights(Scene& S) {
+    S.lights.clear();
+    for (uint32_t i = 0; i < S.inst.size(); ++i) if (S.inst[i].mat->isLight()) S.lights.push_back(i);
+}
+
 Scene* buildIndoor(const std::string& dir, int variant) {
     Scene* S = new Scene();
     const char* names[4] = {"susanne", "cube", "lens", "plane"};       /* main.cpp:163-166 */
@@ -631,14 +639,15 @@ Scene* buildIndoor(const std::string& dir, int variant) {
     /* Scene::Scene, scene.cpp:17-33 */
     InstPrims P; P.inst = &S->inst;
     buildBvh(S->tlas, P, (uint32_t)S->inst.size());
-    for (uint32_t i = 0; i < S->inst.size(); ++i) if (S->inst[i].mat->isLight()) S->lights.push_back(i);
+    collectLights(*S);
     return S;
 }
 
-/* Camera::Camera + generateViewPlane, camera.cpp:9-46; main.cpp:141-149 */
+/* Camera::Camera + generateViewPlane, camera.cpp:9-46, of the scene's stored
+ * view (main.cpp:141-149 by default) */
 void setCamera(Scene& S, uint32_t W, uint32_t H) {
-    S.camPos = mk(0.0f, 0.0f, -7.0f);
-    V3 target = mk(0.0f, 0.0f, 0.0f);
+    S.camPos = S.viewPos;
+    V3 target = S.viewTarget;
     S.scrW = (float)W; S.scrH = (float)H;
     S.camFwd = normalize(target - S.camPos);
     V3 r = normalize(cross(mk(0.0f, 1.0f, 0.0f), S.camFwd));
@@ -868,6 +877,52 @@ uint32_t orc_scene_instance_count(const orc_scene* h) { return (uint32_t)h->s->i
 uint32_t orc_scene_light_count(const orc_scene* h) { return (uint32_t)h->s->lights.size(); }
 
 void orc_scene_set_camera(orc_scene* h, uint32_t w, uint32_t ht) { setCamera(*h->s, w, ht); }
+
+/* Camera::Camera's arguments (camera.h:31, camera.cpp:9-26), kept for every
+ * later setCamera; the view plane of the current resolution is rebuilt at
+ * once (generateViewPlane, camera.cpp:28-46), since the render entry points
+ * only rebuild it when the resolution changes. */
+void orc_scene_set_view(orc_scene* h, const float* pos, const float* target, float fovY, float focal, float defocus) {
+    Scene& S = *h->s;
+    S.viewPos = mk(pos[0], pos[1], pos[2]);
+    S.viewTarget = mk(target[0], target[1], target[2]);
+    S.fovY = fovY; S.focal = focal; S.defocus = defocus;
+    setCamera(S, (uint32_t)S.scrW, (uint32_t)S.scrH);
+}
+
+/* SceneBackground (scene.h:18-26), read by Scene::sampleBackground
+ * (scene.cpp:35-51): type 0 the solid colour, 1 the gradient between A and B,
+ * anything else black. */
+void orc_scene_set_background(orc_scene* h, int type, const float* color, const float* A, const float* B) {
+    Scene& S = *h->s;
+    S.bgType = type;
+    S.bgColor = mk(color[0], color[1], color[2]);
+    S.bgA = mk(A[0], A[1], A[2]);
+    S.bgB = mk(B[0], B[1], B[2]);
+}
+
+/* Material (material.h:6-19) number `index` in orc_scene_export's first-use
+ * order; the light list is collected again as Scene::Scene does
+ * (scene.cpp:22-32), since Material::isLight may have changed.  Returns 0, or
+ * -1 for an index past the materials in use. */
+int orc_scene_set_material(orc_scene* h, uint32_t index, const float* albedo, const float* absorption, const float* emitColor,
+                           float emit, float refl, float refr, float ior) {
+    Scene& S = *h->s;
+    std::vector<const Material*> mats;
+    for (const Instance& in : S.inst) {
+        bool f = false; for (auto* m : mats) f |= (m == in.mat); if (!f) mats.push_back(in.mat);
+    }
+    if (index >= mats.size()) return -1;
+    for (Material* m : S.materials) {
+        if (m != mats[index]) continue;
+        m->albedo = mk(albedo[0], albedo[1], albedo[2]);
+        m->absorption = mk(absorption[0], absorption[1], absorption[2]);
+        m->emitColor = mk(emitColor[0], emitColor[1], emitColor[2]);
+        m->emit = emit; m->refl = refl; m->refr = refr; m->ior = ior;
+    }
+    collectLights(S);
+    return 0;
+}
 
 void orc_camera_ubo(const orc_scene* h, void* out) {
     const Scene& S = *h->s;

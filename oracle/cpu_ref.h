@@ -37,7 +37,13 @@ typedef struct {
 } orc_counters;
 
 /* variant 0: bundled indoor scene (reference main.cpp:161-346).
- * variant 1: C5 deep scene -- indoor scene + 648 Suzanne copies baked in one mesh. */
+ * variant 1: C5 deep scene -- indoor scene + 648 Suzanne copies baked in one mesh.
+ * variant 2: the indoor scene + 40 scattered cube / Suzanne / lens instances
+ *            (51 instances: the TLAS splits, the tables still fit LDS).
+ * variant 3: the same with 80 extras (91 instances: global tables).
+ * The scene starts with main.cpp's view (:141-149), background (:343-346) and
+ * materials (:173-202); orc_scene_set_view, orc_scene_set_background and
+ * orc_scene_set_material below edit them. */
 orc_scene* orc_scene_create(const char* assets_dir, int variant);
 void orc_scene_destroy(orc_scene*);
 
@@ -50,10 +56,23 @@ uint32_t orc_scene_light_count(const orc_scene*);
 /* GPUScene::update(dt) (scene.cpp:267-282): rotate instance 3, refit the TLAS. */
 void orc_scene_update(orc_scene*, float dt);
 
-/* Camera of main.cpp:141-149 for a W x H render. */
+/* Camera of the scene's view (main.cpp:141-149 until orc_scene_set_view) for a W x H render. */
 void orc_scene_set_camera(orc_scene*, uint32_t width, uint32_t height);
 /* Copy of the CameraUBO (128 B, camera.h:12-19) the camera produces. */
 void orc_camera_ubo(const orc_scene*, void* out128);
+
+/* Scene edits, for tests of what the bundled picture never reaches.
+ * The view: Camera::Camera's arguments (camera.h:31, camera.cpp:9-26).  It
+ * persists: every later camera, of any resolution, is built from it.  The
+ * defaults (0,0,-7), (0,0,0), 70, 7, 0.5 are main.cpp:141-149. */
+void orc_scene_set_view(orc_scene*, const float pos[3], const float target[3], float fovY, float focal, float defocus);
+/* SceneBackground (scene.h:18-26; Scene::sampleBackground, scene.cpp:35-51):
+ * type 0 solid colour, 1 gradient from A (down) to B (up), other: black. */
+void orc_scene_set_background(orc_scene*, int type, const float color[3], const float A[3], const float B[3]);
+/* Material (material.h:6-19) `index` in orc_scene_export's first-use order;
+ * the light list follows (scene.cpp:22-32).  -1 for an index out of range. */
+int orc_scene_set_material(orc_scene*, uint32_t index, const float albedo[3], const float absorption[3],
+                           const float emitColor[3], float emit, float refl, float refr, float ior);
 
 /* GPUBatcher layout export (scene.cpp:61-157), materials in first-use order.
  * which: 0 triangles(64B) 1 triExt(80B) 2 blasIdx(u32) 3 blasNodes(48B)

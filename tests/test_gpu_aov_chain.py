@@ -12,8 +12,8 @@ uint32 words.
 All frames are 100 x 37, the view of tests/test_gpu_aov.py.
 
 One branch has no case here: the tinted miss after at least one link.  The
-bundled room is closed, so no view of it reaches that branch, and the oracle
-loads no other scene.
+bundled room is closed, so no view of it reaches that branch; its case is in
+tests/test_gpu_scene_edges.py, where an edited scene opens the room.
 """
 import ctypes as C
 import os
