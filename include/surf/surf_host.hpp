@@ -396,6 +396,12 @@ public:
      * The form without arguments takes surf_robust_default_params. */
     std::vector<F32> robust(const surf_robust_params& params, std::vector<uint8_t>* trim = nullptr, surf_robust_summary* summary = nullptr);
     std::vector<F32> robust();
+    /* the dual-buffer non-local-means filter on the buckets' two half images (surf_denoise_nlm; needs
+     * setSampleBuckets): the filtered image, width*height*4 floats (rgb, 1); err non-NULL: it receives
+     * the per-pixel error estimate from the two filtered halves' difference, the same size.  Reads no
+     * feature buffer.  The form without arguments takes surf_nlm_default_params. */
+    std::vector<F32> denoiseNlm(const surf_nlm_params& params, std::vector<F32>* err = nullptr);
+    std::vector<F32> denoiseNlm();
     /* the active-pixel mask (surf_set_pixel_mask): width*height bytes, nonzero = active, render()
      * then traces those pixels only; an empty vector = every pixel.  pixelMask: the mask as set and,
      * where asked for, its active count. */

@@ -1104,6 +1104,96 @@ int surf_robust_image_host(uint32_t npx, uint32_t M, const float* acc, const flo
 /* Diagnostics: device time (HIP events) of the last k_robust launch on this context. */
 int surf_debug_robust_time(surf_ctx* ctx, float* kernel_ms);
 
+/* ---- dual-buffer non-local means for stills, fed by the sample buckets (no reference counterpart) ----
+ * The even and the odd buckets sum to two independent half images of the same
+ * picture.  Each half is filtered by non-local means whose patch weights are
+ * taken from the OTHER half (Rousselle, Knaus, Zwicker 2012): weights and
+ * values are independent, no feature plane is read, so the filter also works
+ * behind the lens blur, in mirrors and through glass, where the a-trous
+ * filters have no guide edges.  The two filtered halves' difference is a
+ * per-pixel estimate of the output's error.  Opt-in and a pure post-process:
+ * without a call to these entry points no kernel, launch, allocation or result
+ * bit differs; the calls leave the accumulator, the buckets, the squares,
+ * surf_stats and the counters untouched.
+ *
+ * The arithmetic (part of the interface: f32, uncontracted, / is IEEE, expf is
+ * glibc's; surf_denoise_nlm_image_host reproduces every bit).  Inputs: a full
+ * frame of W x H pixels, two planes H0, H1 of half accumulators (rgb sums,
+ * w = the half's sample count).  Parameters: search_radius r in 1..10,
+ * patch_radius f in 0..3, k finite and > 0, alpha finite and >= 0, eps finite
+ * and > 0.  Host constants: kk = k*k, cnt = (float)(3*(2f+1)*(2f+1)).
+ * clampF(x, y) clamps each coordinate to the frame.
+ *
+ * Prepare, per pixel p:  n0 = H0.w, n1 = H1.w;  ok = n0 > 0 && n1 > 0;  when
+ *   ok, c0_k = H0_k / n0 and c1_k = H1_k / n1;  valid = ok && all six
+ *   quotients finite;  an invalid pixel has c0 = c1 = (0, 0, 0).
+ *   v_k = 0.5f * ((c0_k - c1_k) * (c0_k - c1_k));  V(p)_k = the sum from 0.0f
+ *   of v_k over the nine texels clampF(x + dx, y + dy), dy = -1..1 outer and
+ *   dx = -1..1 inner, divided by 9.0f.
+ * Distance image of a search offset o = (dx, dy), at any unclamped texel s'
+ *   (up to f outside the frame):  a = clampF(s'), b = clampF(s' + o), g the
+ *   half the weights come from;  for k = x, y, z:
+ *     d  = Cg(a)_k - Cg(b)_k
+ *     vm = V(b)_k < V(a)_k ? V(b)_k : V(a)_k
+ *     num = d*d - alpha*(V(a)_k + vm)
+ *     den = eps + kk*(V(a)_k + V(b)_k)
+ *     d_k = num / den
+ *   d_o(s') = (d_x + d_y) + d_z.
+ * Patch distance of p and o:  for j = -f..f, R_j = the sum from 0.0f over
+ *   i = -f..f of d_o(p + (i, j));  S = the sum from 0.0f over j = -f..f of R_j;
+ *   D = S / cnt.  (Rows first, then the column of row sums: a separable
+ *   implementation on a tile is the definition.)
+ * Filtering half h with weights from g = 1 - h, for a valid p:  sumW = 0,
+ *   sum = 0;  the taps q = p + o, dy = -r..r outer and dx = -r..r inner;  a q
+ *   outside the frame or invalid is skipped;  the centre tap has w = 1.0f;
+ *   every other tap  e = D < 100.0f ? D : 100.0f  (a NaN becomes 100),
+ *   e = e > 0.0f ? e : 0.0f,  w = expf(-e);  sumW = sumW + w,
+ *   sum_k = sum_k + w * Ch(q)_k;  o_h(p) = sum / sumW.
+ * Output, valid p:  out_k = ((o0_k*n0) + (o1_k*n1)) / (n0 + n1), out.w = 1;
+ *   err_k = 0.25f * ((o0_k - o1_k)*(o0_k - o1_k)), err.w = 0.
+ *   Invalid p, n = n0 + n1, inv = n > 0 ? 1.0f/n : 0.0f:
+ *   out = ((H0.rgb + H1.rgb) * inv, 1), err = 0.
+ * The halves from the buckets (context form): half 0 is the sum from 0.0f of
+ *   the even planes j = 0, 2, ... in ascending order, half 1 the same over the
+ *   odd planes.
+ *
+ * Three launches: the halves (context form), prepare (c0 + validity, c1 and V
+ * packed into three 16-byte records per pixel), the filter -- both halves in
+ * one launch on 32 x 8 pixel tiles.  The filter stages the tile with its halo
+ * of r + f in LDS (40 bytes a texel) and computes each offset's distance image
+ * once per texel of the tile and its halo of f; where that layout exceeds
+ * 64 KiB (from r + f = 11) or under SURF_NLM_LDS=0 (read at surf_create*)
+ * every value comes from global memory.
+ * Identical bits either way.  MEASUREMENTS "Non-local means" has the errors
+ * and the costs. */
+typedef struct {
+    uint32_t search_radius, patch_radius;
+    float k, alpha, eps;
+    uint32_t _pad;
+} surf_nlm_params;
+/* r 5, f 2, k 0.45, alpha 1.0, eps 1e-10 */
+int surf_nlm_default_params(surf_nlm_params* params);
+/* The context form: the halves of the context's own buckets, filtered;
+ * out_rgba and out_err (may be NULL) height*width*4 floats.  Drains the
+ * stream.  SURF_ERR_INVALID for a NULL context, params or out_rgba, parameters
+ * outside the ranges above, while the buckets are off (surf_set_sample_buckets),
+ * and on a row shard -- a patch reads its neighbours' rows: assemble the
+ * shards' buckets and call surf_denoise_nlm_image; SURF_ERR_OOM when a scratch
+ * image cannot be allocated. */
+int surf_denoise_nlm(surf_ctx* ctx, const surf_nlm_params* params, float* out_rgba, float* out_err);
+/* ... the two images to buffers on the context's device (height*width*16 bytes each; dst_err_device may be NULL) */
+int surf_denoise_nlm_copy_device(surf_ctx* ctx, const surf_nlm_params* params, void* dst_rgba_device, void* dst_err_device);
+/* Host planes of a w x h frame (w*h in 1..2^27), w*h*4 floats each.  Needs no
+ * scene and no buckets on the context. */
+int surf_denoise_nlm_image(surf_ctx* ctx, uint32_t w, uint32_t h, const float* half0, const float* half1,
+                           const surf_nlm_params* params, float* out_rgba, float* out_err);
+/* The CPU twin; needs no device.  Bit-identical to surf_denoise_nlm_image. */
+int surf_denoise_nlm_image_host(uint32_t w, uint32_t h, const float* half0, const float* half1, const surf_nlm_params* params,
+                                float* out_rgba, float* out_err);
+/* Diagnostics: device times (HIP events) of the last run's halves, prepare and
+ * filter launches into kernel_ms[0..count); the image form has no halves launch. */
+int surf_debug_nlm_time(surf_ctx* ctx, float* kernel_ms, uint32_t count);
+
 /* ---- per-pixel sample masks and the adaptive loop (no reference counterpart) ----
  * A context carries an active-pixel mask: one byte per pixel of the shard in
  * shard order (rows*width), nonzero = active.  After surf_create* and after

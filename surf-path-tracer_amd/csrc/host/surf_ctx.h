@@ -236,6 +236,13 @@ struct surf_ctx {
     PlaneGroup<1> rbTrim{"the robust estimate's trim image"};
     PlaneGroup<1> rbIn{"surf_robust_image's planes"};
     StageTimer<1> rbTime;          /* the last k_robust launch (surf_debug_robust_time) */
+    /* the dual-buffer non-local-means filter (surf_denoise_nlm*, host/nlm.hip): nl, the two half planes (summed
+     * from the buckets or uploaded), the three prepared records (c0 + validity, c1 and V packed), then the output and its error
+     * estimate; nlStaged: the filter kernel stages its tile in LDS where the layout fits (SURF_NLM_LDS=0: every
+     * value from global memory; MEASUREMENTS "Non-local means") */
+    PlaneGroup<7> nl{"the non-local-means filter's planes"};
+    StageTimer<3> nlTime;          /* halves, prepare, filter of the last run (surf_debug_nlm_time) */
+    bool nlStaged = true;
     /* the active-pixel mask (surf_set_pixel_mask, surf_mask_from_noise; host/adaptive.hip):
      * pmOn: a mask that leaves some pixel out is set (an all-ones mask is "no
      * mask"); then pmMask holds its npx bytes, pmList the pmActive ascending
@@ -375,6 +382,8 @@ void freeSvgf(surf_ctx* c);
 void freeAdaptive(surf_ctx* c);
 /* defined in host/robust.hip: surf_destroy's part for the robust estimate's images */
 void freeRobust(surf_ctx* c);
+/* defined in host/nlm.hip: surf_destroy's part for the non-local-means filter's images */
+void freeNlm(surf_ctx* c);
 
 #define SURF_CHECK(ctx, call)                                                             \
     do {                                                                                  \

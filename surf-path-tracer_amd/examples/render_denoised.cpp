@@ -6,7 +6,7 @@
  * WaveFrontRenderer::denoise() with the default parameters (the
  * edge-avoiding a-trous filter on the first-hit feature buffers, surf_denoise).
  *
- * usage: render_denoised ASSETS_DIR WIDTH HEIGHT SPP PREFIX [ADAPTIVE_MAX]
+ * usage: render_denoised ASSETS_DIR WIDTH HEIGHT SPP PREFIX [ADAPTIVE_MAX [ROBUST_M [NLM]]]
  * Writes PREFIX_noisy.pfm (radiance sum over sample count) and
  * PREFIX_denoised.pfm (colour PFM, surf_write_pfm), and PREFIX_denoised.png:
  * the denoised image as the application would present it (surf_pack_rgba8
@@ -28,6 +28,11 @@
  * surf_denoise_sampled_image) with the renderer's feature buffers;
  * PREFIX_robust.pfm is that estimate's mean, PREFIX_noisy.pfm stays the plain
  * mean.  Wants about 32 samples per bucket.
+ * With NLM nonzero and ROBUST_M set also PREFIX_nlm.pfm: the buckets' two half
+ * images through the dual-buffer non-local-means filter
+ * (WaveFrontRenderer::denoiseNlm, surf_denoise_nlm) with the default
+ * parameters, which reads no feature buffer; every other output is what it is
+ * without it.
  */
 #include "surf/surf_host.hpp"
 #include "indoor_scene.hpp"
@@ -40,23 +45,24 @@
 using namespace surf;
 
 int main(int argc, char** argv) {
-    if (argc < 6 || argc > 8) {
-        std::fprintf(stderr, "usage: %s ASSETS_DIR WIDTH HEIGHT SPP PREFIX [ADAPTIVE_MAX [ROBUST_M]]\n", argv[0]);
+    if (argc < 6 || argc > 9) {
+        std::fprintf(stderr, "usage: %s ASSETS_DIR WIDTH HEIGHT SPP PREFIX [ADAPTIVE_MAX [ROBUST_M [NLM]]]\n", argv[0]);
         return 2;
     }
     const std::string dir = argv[1], prefix = argv[5];
     const int w = std::atoi(argv[2]), h = std::atoi(argv[3]), spp = std::atoi(argv[4]);
     if (w <= 0 || h <= 0 || spp <= 0) { std::fprintf(stderr, "render_denoised: WIDTH, HEIGHT and SPP must be positive\n"); return 2; }
     const int adaptiveMax = argc >= 7 ? std::atoi(argv[6]) : 0;
-    if (argc >= 7 && adaptiveMax < 2 && !(argc == 8 && adaptiveMax == 0)) {
+    if (argc >= 7 && adaptiveMax < 2 && !(argc >= 8 && adaptiveMax == 0)) {
         std::fprintf(stderr, "render_denoised: ADAPTIVE_MAX must be at least 2\n");
         return 2;
     }
-    const int robustM = argc == 8 ? std::atoi(argv[7]) : 0;
-    if (argc == 8 && robustM != 2 && robustM != 4 && robustM != 8 && robustM != 16) {
+    const int robustM = argc >= 8 ? std::atoi(argv[7]) : 0;
+    if (argc >= 8 && robustM != 2 && robustM != 4 && robustM != 8 && robustM != 16) {
         std::fprintf(stderr, "render_denoised: ROBUST_M must be 2, 4, 8 or 16\n");
         return 2;
     }
+    const bool nlm = argc == 9 && std::atoi(argv[8]) != 0;
     const U32 W = (U32)w, H = (U32)h;
     try {
         RenderContext context;            /* HIP device 0 */
@@ -96,6 +102,11 @@ int main(int argc, char** argv) {
             }
             const std::string path = prefix + "_robust.pfm";
             if (surf_write_pfm(path.c_str(), W, H, mean.data()) != SURF_OK) { std::fprintf(stderr, "cannot write %s\n", path.c_str()); return 1; }
+        }
+        if (robustM && nlm) {
+            const std::vector<F32> patched = renderer.denoiseNlm();
+            const std::string path = prefix + "_nlm.pfm";
+            if (surf_write_pfm(path.c_str(), W, H, patched.data()) != SURF_OK) { std::fprintf(stderr, "cannot write %s\n", path.c_str()); return 1; }
         }
         std::vector<F32> clean;
         if (robustM) {

@@ -27,6 +27,7 @@ Mirrors the reference interface for the hot path:
     .finalize_weighted()       RGBA8 with each pixel divided by its own sample count
     .set_sample_buckets(M)     M partial accumulators per pixel, .sample_buckets() reads them, bucket_halves() sums the half images
     .robust()                  the median-of-means estimate of the accumulator with a Gini-adaptive trim (no reference counterpart)
+    .denoise_nlm()             dual-buffer non-local means on the buckets' two half images: no feature plane, an error estimate beside it
 """
 from __future__ import annotations
 
@@ -159,6 +160,12 @@ class RobustSummary(C.Structure):
 
     def as_dict(self) -> dict:
         return {"pixels": int(self.pixels), "trimmed": int(self.trimmed)}
+
+
+class NlmParams(C.Structure):
+    """surf_nlm_params: the search and patch radii, the distance's scale k, the variance cancellation alpha, eps."""
+    _fields_ = [("search_radius", C.c_uint32), ("patch_radius", C.c_uint32), ("k", C.c_float), ("alpha", C.c_float), ("eps", C.c_float),
+                ("_pad", C.c_uint32)]
 
 
 class AdaptiveMaskParams(C.Structure):
@@ -295,6 +302,12 @@ def load() -> C.CDLL:
         "surf_robust_image": ([P, U32, U32, P, P, C.POINTER(RobustParams), P, P, C.POINTER(RobustSummary)], I32),
         "surf_robust_image_host": ([U32, U32, P, P, C.POINTER(RobustParams), P, P, C.POINTER(RobustSummary)], I32),
         "surf_debug_robust_time": ([P, C.POINTER(F)], I32),
+        "surf_nlm_default_params": ([C.POINTER(NlmParams)], I32),
+        "surf_denoise_nlm": ([P, C.POINTER(NlmParams), P, P], I32),
+        "surf_denoise_nlm_copy_device": ([P, C.POINTER(NlmParams), P, P], I32),
+        "surf_denoise_nlm_image": ([P, U32, U32, P, P, C.POINTER(NlmParams), P, P], I32),
+        "surf_denoise_nlm_image_host": ([U32, U32, P, P, C.POINTER(NlmParams), P, P], I32),
+        "surf_debug_nlm_time": ([P, C.POINTER(F), U32], I32),
         "surf_mesh_data": ([P, C.POINTER(P), C.POINTER(P), C.POINTER(U32)], I32),
         "surf_mesh_destroy": ([P], None),
         "surf_ref_sinf": ([F], F), "surf_ref_cosf": ([F], F), "surf_ref_expf": ([F], F),
@@ -781,6 +794,34 @@ def robust_image(renderer, acc, buckets, trim_scale=None):
     """The robust estimate on the renderer's device of host planes (surf_robust_image), e.g. planes assembled from row
     shards: (accumulator plane, trim image, summary dict)."""
     return renderer.robust_image(acc, buckets, trim_scale)
+
+
+def nlm_params(**params) -> NlmParams:
+    """surf_nlm_default_params (search_radius 5, patch_radius 2, k 0.45, alpha 1.0, eps 1e-10) with the given fields replaced."""
+    p = NlmParams()
+    _check(load().surf_nlm_default_params(C.byref(p)), "surf_nlm_default_params")
+    for name, v in params.items():
+        if name not in ("search_radius", "patch_radius", "k", "alpha", "eps"):
+            raise TypeError(f"surf_nlm_params has no field {name!r}")
+        setattr(p, name, int(v) if name.endswith("_radius") else float(v))
+    return p
+
+
+def _nlm_planes(half0, half1):
+    """(w, h, half0, half1, out, err): two (H, W, 4) half accumulators as contiguous float32."""
+    a, b = (np.ascontiguousarray(v, dtype=np.float32) for v in (half0, half1))
+    if a.ndim != 3 or a.shape[-1] != 4 or b.shape != a.shape:
+        raise ValueError(f"half planes {a.shape}, {b.shape} are not two (H, W, 4) images of one size")
+    return a.shape[1], a.shape[0], a, b, np.zeros_like(a), np.zeros_like(a)
+
+
+def denoise_nlm_image_host(half0, half1, **params):
+    """The CPU twin of Renderer.denoise_nlm_image (surf_denoise_nlm_image_host): (image, err), each (H, W, 4) float32;
+    bit-identical, no device."""
+    w, h, a, b, out, err = _nlm_planes(half0, half1)
+    p = nlm_params(**params)
+    _check(load().surf_denoise_nlm_image_host(w, h, _ptr(a), _ptr(b), C.byref(p), _ptr(out), _ptr(err)), "surf_denoise_nlm_image_host")
+    return out, err
 
 
 def bucket_halves(buckets) -> tuple:
@@ -1355,6 +1396,37 @@ class Renderer:
     def copy_robust_to(self, device_ptr: int, trim_scale=None):
         p = robust_params(trim_scale)
         _check(load().surf_robust_copy_device(self._h, C.byref(p), C.c_void_p(device_ptr)), "surf_robust_copy_device", self._h)
+
+    def denoise_nlm(self, **params):
+        """(image, err) of the dual-buffer non-local-means filter on the halves of this context's sample buckets
+        (surf_denoise_nlm; nlm_params' names): each half filtered with patch weights from the other, recombined by
+        sample count -- (H, W, 4) float32 with w = 1 -- and the per-pixel error estimate from the two filtered halves'
+        difference.  Reads no feature plane.  Needs set_sample_buckets; raises SURF_ERR_INVALID on a row shard (see
+        denoise_nlm_image)."""
+        p = nlm_params(**params)
+        out, err = (np.zeros((self.height, self.width, 4), dtype=np.float32) for _ in range(2))
+        _check(load().surf_denoise_nlm(self._h, C.byref(p), _ptr(out), _ptr(err)), "surf_denoise_nlm", self._h)
+        return out, err
+
+    def denoise_nlm_image(self, half0, half1, **params):
+        """The same filter on two host half accumulators of any full frame (surf_denoise_nlm_image), e.g.
+        bucket_halves() of planes assembled from row shards: (image, err)."""
+        w, h, a, b, out, err = _nlm_planes(half0, half1)
+        p = nlm_params(**params)
+        _check(load().surf_denoise_nlm_image(self._h, w, h, _ptr(a), _ptr(b), C.byref(p), _ptr(out), _ptr(err)), "surf_denoise_nlm_image",
+               self._h)
+        return out, err
+
+    def copy_denoise_nlm_to(self, device_ptr: int, err_device_ptr: int = None, **params):
+        p = nlm_params(**params)
+        _check(load().surf_denoise_nlm_copy_device(self._h, C.byref(p), C.c_void_p(device_ptr), C.c_void_p(err_device_ptr)),
+               "surf_denoise_nlm_copy_device", self._h)
+
+    def debug_nlm_time(self) -> list:
+        """Device milliseconds of the last non-local-means run's launches (surf_debug_nlm_time): halves, prepare, filter."""
+        ms = (C.c_float * 3)()
+        _check(load().surf_debug_nlm_time(self._h, ms, 3), "surf_debug_nlm_time", self._h)
+        return [float(v) for v in ms]
 
     def debug_robust_time(self) -> float:
         """Device milliseconds of the last k_robust launch (surf_debug_robust_time)."""
