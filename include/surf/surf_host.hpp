@@ -418,6 +418,19 @@ public:
      * surf_adaptive_default_params. */
     surf_adaptive_summary renderAdaptive(const surf_adaptive_params& params, std::vector<U32>* roundActive = nullptr);
     surf_adaptive_summary renderAdaptive();
+    /* filters the buckets' halves, builds the mask from the filter's error estimate and sets it
+     * (surf_mask_from_nlm); returns the active count.  Needs setSampleBuckets. */
+    U32 maskFromNlm(const surf_nlm_params& nlm, const surf_error_mask_params& params);
+    /* renders until the filtered picture has converged (surf_render_adaptive_nlm, whose header comment
+     * defines the loop): 1-sample frames from the renderer's next sample index on an empty
+     * accumulator, with setSampleBuckets; the camera and the scene are pushed first, as render()
+     * pushes them.  image and err non-NULL: the filter's two outputs of the final state, width*height*4
+     * floats each; roundActive non-NULL: the active count of each round.  params' first_sample_index
+     * and max_segments are replaced by the renderer's.  The form without params takes
+     * surf_adaptive_nlm_default_params. */
+    surf_adaptive_nlm_summary renderAdaptiveNlm(const surf_adaptive_nlm_params& params, std::vector<F32>* image = nullptr,
+                                                std::vector<F32>* err = nullptr, std::vector<U32>* roundActive = nullptr);
+    surf_adaptive_nlm_summary renderAdaptiveNlm(std::vector<F32>* image = nullptr);
     /* RGBA8 with each pixel divided by its own sample count (surf_finalize_rgba8_weighted) */
     std::vector<U32> finalizeWeighted(bool display = false);
     /* clearAccumulator() for that loop: the next render() goes on with the sample indices after

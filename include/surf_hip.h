@@ -1301,6 +1301,129 @@ int surf_adaptive_default_params(surf_adaptive_params* params);
 int surf_render_adaptive(surf_ctx* ctx, const surf_adaptive_params* params, uint32_t* round_active, uint32_t round_cap,
                          surf_adaptive_summary* summary);
 
+/* ---- the mask from the non-local-means filter's error estimate, and the loop around it (no reference counterpart) ----
+ * surf_mask_from_noise asks whether the UNFILTERED pixel has converged.  Who
+ * shows the non-local-means output wants another answer: the filter removes
+ * noise cheaply in smooth regions and cannot at edges, in caustics and in fine
+ * detail, and its second output, err, estimates per pixel how wrong the
+ * FILTERED picture still is (Rousselle, Knaus, Zwicker 2012).  The entry points
+ * below turn (out, err) into an active-pixel mask and run the adaptive loop on
+ * it.  Opt-in: without a call to them no kernel, launch, allocation or result
+ * bit differs.
+ *
+ * The mask.  Inputs, full-frame W x H planes of 16-byte records: out, the
+ * filter's result; err, its error plane; A, the accumulator, read only for A.w.
+ * Parameters (surf_error_mask_params): threshold finite and > 0 -- a relative
+ * RMS error; floor finite and > 0; min_samples >= 2; max_samples >=
+ * min_samples; smooth in 0..3; dilate in 0..2.  Host constants, f32:
+ * tt = threshold*threshold, ff = floor*floor, cnt = (float)((2 smooth + 1)^2).
+ * The arithmetic is part of the interface: f32, uncontracted, / IEEE, every
+ * sum starting from 0.0f in the order given; surf_error_mask_image_host
+ * reproduces every bit.  With o = out(p), e = err(p):
+ *   num = (e.x + e.y) + e.z
+ *   den = (((o.x*o.x) + (o.y*o.y)) + (o.z*o.z)) + ff
+ *   rel(p) = num / den
+ *   S(p): smooth == 0: rel(p).  Otherwise, clampF clamping each coordinate to
+ *         the frame: for j = -smooth..smooth, R_j = the sum from 0.0f over
+ *         i = -smooth..smooth of rel(clampF(p + (i, j))); S = (the sum from
+ *         0.0f over j = -smooth..smooth of R_j) / cnt.  (Rows first, then the
+ *         column of row sums, as the filter's V and patch distance.)
+ *   raw(p)    = !(A.w >= (float)min_samples) || !(S(p) <= tt)     (a NaN counts as noisy)
+ *   active(p), the mask byte and the ascending list: exactly surf_mask_from_noise's --
+ *               (some q with |dx| <= dilate, |dy| <= dilate inside the frame has raw(q))
+ *               && A(p).w < (float)max_samples
+ * The estimate is one squared difference per pixel, so unsmoothed it is very
+ * noisy: that is what `smooth` is for.  A pixel the filter marked invalid has
+ * err = 0, so rel = 0 there: it is quiet unless it is below min_samples (its
+ * neighbours' S still take its 0).
+ * Launches: the mask kernel, 256 threads per 32 x 8 tile, takes rel of the
+ * tile and its halo of smooth + dilate (at most 5: 42 x 18 texels, 32 B read
+ * per texel) into LDS, then the row sums, then the column sums and the raw
+ * flags of the tile and its halo of dilate, ORs them and writes one byte per
+ * pixel: 6 KB of LDS, no scratch; then surf_mask_from_noise's order-preserving
+ * compaction.  A pointwise pre-pass that wrote rel to a plane of its own (4 B
+ * per pixel) for the mask kernel to stage from was measured and was slower at
+ * 1280 x 720 and 1920 x 1080 (MEASUREMENTS "Error-driven adaptive sampling"). */
+typedef struct {
+    float threshold, floor;
+    uint32_t min_samples, max_samples, smooth, dilate, _pad[2];
+} surf_error_mask_params;
+/* threshold 0.1, floor 0.01, min_samples 16, max_samples 1024, smooth 3, dilate 1 */
+int surf_error_mask_default_params(surf_error_mask_params* params);
+/* Host planes of any w x h frame (w*h*4 floats each), e.g. surf_denoise_nlm_image's
+ * two outputs and an assembled accumulator.  mask_out: w*h bytes; list_out (w*h
+ * words, the first *count written) may be NULL.  Needs no scene and no buckets;
+ * leaves the context's mask alone.  SURF_ERR_INVALID for a NULL context, plane,
+ * params, mask_out or count, an empty frame or one of more than 2^31 pixels, and
+ * parameters outside the ranges above. */
+int surf_error_mask_image(surf_ctx* ctx, uint32_t w, uint32_t h, const float* out_rgba, const float* err, const float* acc,
+                          const surf_error_mask_params* params, uint8_t* mask_out, uint32_t* list_out, uint32_t* count);
+/* The CPU twin; needs no device.  Bit-identical to surf_error_mask_image. */
+int surf_error_mask_image_host(uint32_t w, uint32_t h, const float* out_rgba, const float* err, const float* acc,
+                               const surf_error_mask_params* params, uint8_t* mask_out, uint32_t* list_out, uint32_t* count);
+/* The context form: the halves of the context's buckets through the filter
+ * (surf_denoise_nlm's launches), the mask from its out and err and the
+ * context's accumulator, set as surf_mask_from_noise sets it; everything stays
+ * on the device, the count comes back.  Drains and ends the stream.
+ * SURF_ERR_INVALID for a NULL context, bad parameters of either kind, while the
+ * buckets are off and on a row shard. */
+int surf_mask_from_nlm(surf_ctx* ctx, const surf_nlm_params* nlm_params, const surf_error_mask_params* mask_params,
+                       uint32_t* active_count);
+/* Diagnostics: device times (HIP events) of the last mask's kernel and of its
+ * compaction into kernel_ms[0..count). */
+int surf_debug_error_mask_time(surf_ctx* ctx, float* kernel_ms, uint32_t count);
+
+/* "Render until the filtered picture has converged".  Needs the buckets on
+ * (any M), an empty accumulator and a context that owns every row of the frame
+ * (SURF_ERR_INVALID otherwise, surf_last_error names the cause); the squares
+ * plane is not needed.  Renders 1-sample frames.  The definition, part of the
+ * interface:
+ *   1. mask = every pixel; render mask.min_samples frames from
+ *      first_sample_index; f = min_samples
+ *   2. repeat: filter the context's halves (nlm) and build the mask from its
+ *              out and err (surf_mask_from_nlm);
+ *              stop when no pixel is active or f == mask.max_samples;
+ *              nb = min(batch, max_samples - f);
+ *              render nb frames at first_sample_index + f under the mask; f += nb
+ *   3. the final mask stays set
+ * The filter run that ends the loop is of the final state, so the loop also
+ * returns that out and err without another launch: out_rgba and out_err, each
+ * height*width*4 floats, each may be NULL.  round_active[r] (the first
+ * min(rounds, round_cap) entries; may be NULL) is the active count round r of
+ * step 2 rendered with.  Between rounds nothing but the active count crosses
+ * to the host.  Summary, of the final state: rounds (renders of step 2),
+ * frames = f, active_last (the final mask's count), samples (camera samples
+ * traced, step 1 included), above (the pixels with A.w >= min_samples and
+ * !(S <= tt): what the cap or nothing stopped), max_error (the largest S that
+ * is no NaN, 0 when there is none; counted by integer adds and an integer max
+ * of an order-preserving key, so independent of the order blocks arrive in).
+ * batch >= 1.
+ * Known limits: stopping on an estimate made from the same samples biases the
+ * result slightly; smooth, dilate and min_samples are the mitigation.  A
+ * heavy-tailed pixel -- one whose halves keep disagreeing -- stays active until
+ * max_samples.  Each round drains the stream and runs the filter, so small
+ * batches cost throughput.  INTEGRATION 13 and MEASUREMENTS "Error-driven
+ * adaptive sampling" say what the loop gains over uniform sampling. */
+typedef struct {
+    surf_error_mask_params mask;
+    surf_nlm_params nlm;
+    uint32_t batch, max_segments, first_sample_index, _pad;
+} surf_adaptive_nlm_params;
+typedef struct {
+    uint32_t rounds, frames, active_last, _pad;
+    uint64_t samples, above;
+    float max_error;
+    uint32_t _pad2;
+} surf_adaptive_nlm_summary;
+/* the mask defaults, surf_nlm_default_params, batch 64, max_segments 0, first_sample_index 0 */
+int surf_adaptive_nlm_default_params(surf_adaptive_nlm_params* params);
+int surf_render_adaptive_nlm(surf_ctx* ctx, const surf_adaptive_nlm_params* params, float* out_rgba, float* out_err,
+                             uint32_t* round_active, uint32_t round_cap, surf_adaptive_nlm_summary* summary);
+/* ... the two images to buffers on the context's device (height*width*16 bytes each; each may be NULL) */
+int surf_render_adaptive_nlm_copy_device(surf_ctx* ctx, const surf_adaptive_nlm_params* params, void* dst_rgba_device,
+                                         void* dst_err_device, uint32_t* round_active, uint32_t round_cap,
+                                         surf_adaptive_nlm_summary* summary);
+
 /* RGBA8 of the accumulator with each pixel divided by its own sample count:
  *   inv = A.w > 0 ? 1.0f/A.w : 0.0f;  channel k = packChannel((a_k*inv)*255.0f), alpha included
  * (packChannel: surf_finalize_rgba8's rounding and saturation), and with

@@ -1,14 +1,15 @@
 /*
  * adaptive_kernels.h -- the active-pixel mask from the noise estimate
  * (surf_mask_from_noise, surf_adaptive_mask_image; include/surf_hip.h gives
- * the arithmetic): the per-pixel rule, the flags kernel that dilates it, and
- * the order-preserving compaction of the byte mask into the ascending list a
- * masked stream issues from.  No reference counterpart.
+ * the arithmetic): the per-pixel rule and the flags kernel that dilates it.
+ * The order-preserving compaction of the byte mask into the ascending list a
+ * masked stream issues from is compact_kernels.h's.  No reference counterpart.
  *
  * adaptiveRaw and adaptiveActive below are the only place the rule is
  * written; the kernel and the host twin call them on the same values.
  */
 #pragma once
+#include "compact_kernels.h"        /* the byte mask's compaction into the ascending list */
 #include "denoise_kernels.h"        /* the 32 x 8 tile */
 #include "sampled_kernels.h"        /* noiseError */
 #include "types.h"
@@ -18,7 +19,6 @@ namespace surfdev {
 constexpr int kAdaptiveMaxDilate = 2;
 /* the tile and its widest halo: 36 x 12 flags, 432 B of static LDS */
 constexpr int kAdaptiveTileW = kDenoiseTileW + 2 * kAdaptiveMaxDilate, kAdaptiveTileH = kDenoiseTileH + 2 * kAdaptiveMaxDilate;
-constexpr uint32_t kCompactBlock = 256;      /* pixels per block of the compaction */
 
 /* the parameters as the kernel takes them */
 struct AdaptiveRule {
@@ -69,58 +69,6 @@ static __global__ __launch_bounds__(256) void k_adaptive_flags(const float4* __r
         for (int dx = 0; dx <= 2 * d; ++dx) any |= raw[(ty + dy) * kAdaptiveTileW + (tx + dx)];
     const size_t p = (size_t)y * W + x;
     mask[p] = adaptiveActive(any != 0u, A[p], R) ? 1 : 0;
-}
-
-/* Compaction, step 1: blk[b] = the nonzero bytes among pixels [256 b, 256 b + 256). */
-static __global__ __launch_bounds__(kCompactBlock) void k_compact_count(const uint8_t* __restrict__ mask, uint32_t n,
-                                                                        uint32_t* __restrict__ blk) {
-    __shared__ uint32_t wv[kCompactBlock / 64];
-    const uint32_t p = blockIdx.x * kCompactBlock + threadIdx.x;
-    const bool on = p < n && mask[p] != 0;
-    const unsigned long long votes = __ballot(on);
-    if ((threadIdx.x & 63u) == 0u) wv[threadIdx.x >> 6] = (uint32_t)__popcll(votes);
-    __syncthreads();
-    if (threadIdx.x == 0) blk[blockIdx.x] = (wv[0] + wv[1]) + (wv[2] + wv[3]);
-}
-
-/* Step 2, one block of 1024 threads: the block counts become their exclusive
- * prefix sums, blk[nb] the total.  Each thread takes a run of consecutive
- * counts; the 1024 run sums are scanned in LDS (k_binscan's pattern). */
-static __global__ __launch_bounds__(1024) void k_compact_scan(uint32_t* __restrict__ blk, uint32_t nb) {
-    __shared__ uint32_t part[1024];
-    const uint32_t t = threadIdx.x;
-    const uint32_t per = (nb + 1023u) / 1024u;
-    const uint32_t a = t * per < nb ? t * per : nb, b = a + per < nb ? a + per : nb;
-    uint32_t sum = 0;
-    for (uint32_t k = a; k < b; ++k) sum += blk[k];
-    part[t] = sum;
-    __syncthreads();
-    for (uint32_t off = 1; off < 1024u; off <<= 1) {
-        const uint32_t v = t >= off ? part[t - off] : 0u;
-        __syncthreads();
-        part[t] += v;
-        __syncthreads();
-    }
-    uint32_t run = part[t] - sum;
-    for (uint32_t k = a; k < b; ++k) { const uint32_t c = blk[k]; blk[k] = run; run += c; }
-    if (t == 1023u) blk[nb] = part[1023];
-}
-
-/* Step 3: pixel p's index goes to list[blk[b] + active pixels of the block's
- * earlier waves + active lanes below it in its wave]. */
-static __global__ __launch_bounds__(kCompactBlock) void k_compact_scatter(const uint8_t* __restrict__ mask, uint32_t n,
-                                                                          const uint32_t* __restrict__ blk, uint32_t* __restrict__ list) {
-    __shared__ uint32_t wv[kCompactBlock / 64];
-    const uint32_t p = blockIdx.x * kCompactBlock + threadIdx.x;
-    const bool on = p < n && mask[p] != 0;
-    const unsigned long long votes = __ballot(on);
-    const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
-    if (lane == 0u) wv[w] = (uint32_t)__popcll(votes);
-    __syncthreads();
-    if (!on) return;
-    uint32_t base = blk[blockIdx.x];
-    for (uint32_t k = 0; k < w; ++k) base += wv[k];
-    list[base + (uint32_t)__popcll(votes & ((1ull << lane) - 1ull))] = p;
 }
 
 #endif  /* HIP */

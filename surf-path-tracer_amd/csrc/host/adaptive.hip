@@ -4,8 +4,10 @@
  * surf_render_adaptive; include/surf_hip.h): the mask's buffers on a context,
  * parameter checks, the launches that turn (A, Q) into the byte mask and its
  * ascending list, the CPU twin, and the loop around surf_render.  The rule
- * lives in device/adaptive_kernels.h; what a masked stream does with the list
- * is the sample stream's business (surf_hip.hip).
+ * lives in device/adaptive_kernels.h, the mask's buffers and the compaction's
+ * launches in host/mask_host.h (host/error_mask.hip builds masks too); what a
+ * masked stream does with the list is the sample stream's business
+ * (surf_hip.hip).
  */
 #include "host/surf_ctx.h"
 
@@ -14,6 +16,7 @@
 #include <cstring>
 
 #include "device/adaptive_kernels.h"
+#include "host/mask_host.h"
 
 namespace {
 
@@ -37,41 +40,13 @@ const char* frameError(uint32_t w, uint32_t h, const float* acc, const float* sq
     return nullptr;
 }
 
-uint32_t compactBlocks(size_t npx) { return (uint32_t)((npx + kCompactBlock - 1) / kCompactBlock); }
-
-/* the three buffers of a mask of npx pixels: bytes, list, block counts + total */
-int allocMask(surf_ctx* c, size_t npx, uint8_t** mask, uint32_t** list, uint32_t** blk) {
-    const size_t nb = compactBlocks(npx);
-    if (hipMalloc((void**)mask, npx) != hipSuccess || hipMalloc((void**)list, npx * sizeof(uint32_t)) != hipSuccess ||
-        hipMalloc((void**)blk, (nb + 1) * sizeof(uint32_t)) != hipSuccess) {
-        (void)hipGetLastError();
-        for (void* p : {(void*)*mask, (void*)*list, (void*)*blk})
-            if (p) (void)hipFree(p);
-        *mask = nullptr; *list = nullptr; *blk = nullptr;
-        return fail(c, SURF_ERR_OOM, "hipMalloc of a pixel mask of " + std::to_string(npx) + " pixels failed");
-    }
-    return SURF_OK;
-}
-
-int ensureContextMask(surf_ctx* c) {
-    if (c->pmMask) return SURF_OK;
-    return allocMask(c, c->npx, &c->pmMask, &c->pmList, &c->pmBlk);
-}
-
 /* The byte mask of device planes of a w x h frame, then its ascending list;
  * the count is read back (one synchronisation). */
 int runMask(surf_ctx* c, uint32_t w, uint32_t h, const float4* A, const float4* Q, const surf_adaptive_mask_params& P, uint8_t* mask,
             uint32_t* list, uint32_t* blk, uint32_t* count) {
-    const uint32_t npx = w * h, nb = compactBlocks(npx);
     const dim3 tiles((w + kDenoiseTileW - 1) / kDenoiseTileW, (h + kDenoiseTileH - 1) / kDenoiseTileH);
     hipLaunchKernelGGL(k_adaptive_flags, tiles, dim3(256), 0, c->stream, A, Q, mask, (int)w, (int)h, ruleOf(P));
-    hipLaunchKernelGGL(k_compact_count, dim3(nb), dim3(kCompactBlock), 0, c->stream, (const uint8_t*)mask, npx, blk);
-    hipLaunchKernelGGL(k_compact_scan, dim3(1), dim3(1024), 0, c->stream, blk, nb);
-    hipLaunchKernelGGL(k_compact_scatter, dim3(nb), dim3(kCompactBlock), 0, c->stream, (const uint8_t*)mask, npx, (const uint32_t*)blk, list);
-    SURF_CHECK(c, hipGetLastError());
-    SURF_CHECK(c, hipMemcpyAsync(count, blk + nb, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-    SURF_CHECK(c, hipStreamSynchronize(c->stream));
-    return SURF_OK;
+    return compactMask(c, w * h, mask, list, blk, count);
 }
 
 }  // namespace
@@ -162,15 +137,7 @@ int surf_adaptive_mask_image(surf_ctx* c, uint32_t w, uint32_t h, const float* a
     const size_t npx = (size_t)w * h;
     int rc = c->sdAQ.grow(c, npx);
     if (rc) return rc;
-    if (npx > c->adImgCap) {
-        SURF_CHECK(c, hipStreamSynchronize(c->stream));
-        for (void* q : {(void*)c->adImgMask, (void*)c->adImgList, (void*)c->adImgBlk})
-            if (q) (void)hipFree(q);
-        c->adImgMask = nullptr; c->adImgList = nullptr; c->adImgBlk = nullptr;
-        c->adImgCap = 0;
-        if ((rc = allocMask(c, npx, &c->adImgMask, &c->adImgList, &c->adImgBlk))) return rc;
-        c->adImgCap = npx;
-    }
+    if ((rc = ensureImageMask(c, npx))) return rc;
     SURF_CHECK(c, hipMemcpyAsync(c->sdAQ[0], acc, npx * sizeof(float4), hipMemcpyHostToDevice, c->stream));
     SURF_CHECK(c, hipMemcpyAsync(c->sdAQ[1], squares, npx * sizeof(float4), hipMemcpyHostToDevice, c->stream));
     uint32_t n = 0;

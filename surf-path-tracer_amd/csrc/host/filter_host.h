@@ -1,8 +1,9 @@
 /*
  * filter_host.h -- internal: what the image-space filters (host/denoise.hip,
- * temporal.hip, svgf.hip, adaptive.hip) share: the fixed-sigma denoiser's
- * entry points for the other filters, the one driver of the a-trous iterations
- * on the device, and the host twins' copy of a caller's plane.  Includes no
+ * temporal.hip, svgf.hip, adaptive.hip, nlm.hip, error_mask.hip) share: the
+ * fixed-sigma denoiser's entry points for the other filters, the non-local-means
+ * filter's context run for the mask built from it, the one driver of the a-trous
+ * iterations on the device, and the host twins' copy of a caller's plane.  Includes no
  * kernel: the driver is handed the launch of an iteration.
  */
 #pragma once
@@ -21,6 +22,14 @@ namespace surfhost {
 const char* denoiseParamsError(const surf_denoise_params* p);
 int denoisePlanes(surf_ctx* c, uint32_t w, uint32_t h, const float4* acc, const float4* pos, const float4* nrm, const float4* alb,
                   const surf_denoise_params& P, const float4** result);
+
+/* defined in host/nlm.hip: NULL when the parameters are valid, else what is
+ * wrong with them; and the context form's run without its copies -- the checks
+ * (`who` names the caller in a message), the drain, the halves of the context's
+ * buckets, prepare and filter.  *out and *err: the scratch images holding the
+ * two results, valid until the next non-local-means run.  Waits for them. */
+const char* nlmParamsError(const surf_nlm_params* p);
+int nlmContextPlanes(surf_ctx* c, const surf_nlm_params* p, const char* who, const float4** out, const float4** err);
 
 /* the grid of 32 x 8 pixel tiles covering a w x h frame */
 inline dim3 tileGrid(uint32_t w, uint32_t h) { return dim3((w + kDenoiseTileW - 1) / kDenoiseTileW, (h + kDenoiseTileH - 1) / kDenoiseTileH); }

@@ -67,6 +67,22 @@ int runNlm(surf_ctx* c, uint32_t w, uint32_t h, const float4* H0, const float4* 
 
 int nlmContext(surf_ctx* c, const surf_nlm_params* p, void* out, void* outErr, hipMemcpyKind kind, const char* who) {
     if (!c || !out) return SURF_ERR_INVALID;
+    const float4* dOut = nullptr;
+    const float4* dErr = nullptr;
+    int rc = nlmContextPlanes(c, p, who, &dOut, &dErr);
+    if (rc) return rc;
+    const size_t bytes = (size_t)c->npx * sizeof(float4);
+    SURF_CHECK(c, hipMemcpyAsync(out, dOut, bytes, kind, c->stream));
+    if (outErr) SURF_CHECK(c, hipMemcpyAsync(outErr, dErr, bytes, kind, c->stream));
+    SURF_CHECK(c, hipStreamSynchronize(c->stream));
+    return SURF_OK;
+}
+
+}  // namespace
+
+const char* surfhost::nlmParamsError(const surf_nlm_params* p) { return nlmParamError(p); }
+
+int surfhost::nlmContextPlanes(surf_ctx* c, const surf_nlm_params* p, const char* who, const float4** out, const float4** err) {
     if (const char* why = nlmParamError(p)) return fail(c, SURF_ERR_INVALID, std::string(who) + ": " + why);
     if (!c->bkM) return fail(c, SURF_ERR_INVALID, std::string(who) + ": sample buckets are off (surf_set_sample_buckets)");
     if (c->rows.size() != c->height)
@@ -82,14 +98,10 @@ int nlmContext(surf_ctx* c, const surf_nlm_params* p, void* out, void* outErr, h
     SURF_CHECK(c, hipGetLastError());
     SURF_CHECK(c, c->nlTime.mark(1, c->stream));
     if ((rc = runNlm(c, c->width, c->height, c->nl[kH0], c->nl[kH1], *p))) return rc;
-    const size_t bytes = (size_t)c->npx * sizeof(float4);
-    SURF_CHECK(c, hipMemcpyAsync(out, c->nl[kOut], bytes, kind, c->stream));
-    if (outErr) SURF_CHECK(c, hipMemcpyAsync(outErr, c->nl[kErr], bytes, kind, c->stream));
-    SURF_CHECK(c, hipStreamSynchronize(c->stream));
+    *out = c->nl[kOut];
+    *err = c->nl[kErr];
     return SURF_OK;
 }
-
-}  // namespace
 
 void surfhost::freeNlm(surf_ctx* c) {
     c->nl.free();

@@ -312,6 +312,40 @@ surf_adaptive_summary WaveFrontRenderer::renderAdaptive() {
     return renderAdaptive(params, nullptr);
 }
 
+U32 WaveFrontRenderer::maskFromNlm(const surf_nlm_params& nlm, const surf_error_mask_params& params) {
+    uint32_t n = 0;
+    check(surf_mask_from_nlm(m_ctx, &nlm, &params, &n), m_ctx, "surf_mask_from_nlm");
+    return n;
+}
+
+surf_adaptive_nlm_summary WaveFrontRenderer::renderAdaptiveNlm(const surf_adaptive_nlm_params& params, std::vector<F32>* image,
+                                                               std::vector<F32>* err, std::vector<U32>* roundActive) {
+    pushSceneAndCamera();
+    surf_adaptive_nlm_params p = params;
+    p.first_sample_index = m_firstSample + m_totalSamples;
+    p.max_segments = m_config.maxSegments;
+    const U32 cap = p.batch ? (p.mask.max_samples - std::min(p.mask.min_samples, p.mask.max_samples)) / p.batch + 1u : 0u;
+    if (roundActive) roundActive->assign(cap, 0u);
+    const size_t floats = (size_t)m_resolution.width * m_resolution.height * 4;
+    if (image) image->assign(floats, 0.0f);
+    if (err) err->assign(floats, 0.0f);
+    surf_adaptive_nlm_summary summary{};
+    check(surf_render_adaptive_nlm(m_ctx, &p, image ? image->data() : nullptr, err ? err->data() : nullptr,
+                                   roundActive ? roundActive->data() : nullptr, roundActive ? cap : 0u, &summary),
+          m_ctx, "surf_render_adaptive_nlm");
+    if (roundActive) roundActive->resize(summary.rounds);
+    m_totalSamples += summary.frames;
+    m_frameInfo.totalSamples = m_totalSamples;
+    m_energyStale = true;
+    return summary;
+}
+
+surf_adaptive_nlm_summary WaveFrontRenderer::renderAdaptiveNlm(std::vector<F32>* image) {
+    surf_adaptive_nlm_params params;
+    check(surf_adaptive_nlm_default_params(&params), m_ctx, "surf_adaptive_nlm_default_params");
+    return renderAdaptiveNlm(params, image, nullptr, nullptr);
+}
+
 std::vector<U32> WaveFrontRenderer::finalizeWeighted(bool display) {
     std::vector<U32> out((size_t)m_resolution.width * m_resolution.height);
     check(surf_finalize_rgba8_weighted(m_ctx, display ? 1 : 0, out.data()), m_ctx, "surf_finalize_rgba8_weighted");

@@ -243,6 +243,11 @@ struct surf_ctx {
     PlaneGroup<7> nl{"the non-local-means filter's planes"};
     StageTimer<3> nlTime;          /* halves, prepare, filter of the last run (surf_debug_nlm_time) */
     bool nlStaged = true;
+    /* the mask from that filter's error estimate (surf_error_mask_image, surf_mask_from_nlm, surf_render_adaptive_nlm;
+     * host/error_mask.hip): em, one record, the loop's summary counters; emIn, the three planes the image form uploads */
+    PlaneGroup<1> em{"the error mask's counters"};
+    PlaneGroup<3> emIn{"surf_error_mask_image's planes"};
+    StageTimer<2> emTime;          /* mask kernel, compaction of the last run (surf_debug_error_mask_time) */
     /* the active-pixel mask (surf_set_pixel_mask, surf_mask_from_noise; host/adaptive.hip):
      * pmOn: a mask that leaves some pixel out is set (an all-ones mask is "no
      * mask"); then pmMask holds its npx bytes, pmList the pmActive ascending
@@ -384,6 +389,8 @@ void freeAdaptive(surf_ctx* c);
 void freeRobust(surf_ctx* c);
 /* defined in host/nlm.hip: surf_destroy's part for the non-local-means filter's images */
 void freeNlm(surf_ctx* c);
+/* defined in host/error_mask.hip: surf_destroy's part for the error mask's images */
+void freeErrorMask(surf_ctx* c);
 
 #define SURF_CHECK(ctx, call)                                                             \
     do {                                                                                  \

@@ -1200,6 +1200,7 @@ void surf_destroy(surf_ctx* c) {
     freeAdaptive(c);
     freeRobust(c);
     freeNlm(c);
+    freeErrorMask(c);
     if (c->dRows) (void)hipFree(c->dRows);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);

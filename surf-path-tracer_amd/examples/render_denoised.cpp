@@ -32,7 +32,12 @@
  * images through the dual-buffer non-local-means filter
  * (WaveFrontRenderer::denoiseNlm, surf_denoise_nlm) with the default
  * parameters, which reads no feature buffer; every other output is what it is
- * without it.
+ * without it.  With NLM = 2 the accumulator is at the end cleared once more
+ * and the frame rendered until the FILTERED picture has converged
+ * (WaveFrontRenderer::renderAdaptiveNlm, surf_render_adaptive_nlm: the default
+ * parameters with max_samples = ADAPTIVE_MAX, or 4 * SPP without one, and
+ * min_samples = min(16, max_samples)): PREFIX_nlm_adaptive.pfm is the filter's
+ * image of the final state; every other output is what it is with NLM = 1.
  */
 #include "surf/surf_host.hpp"
 #include "indoor_scene.hpp"
@@ -63,6 +68,7 @@ int main(int argc, char** argv) {
         return 2;
     }
     const bool nlm = argc == 9 && std::atoi(argv[8]) != 0;
+    const bool nlmAdaptive = argc == 9 && std::atoi(argv[8]) == 2;
     const U32 W = (U32)w, H = (U32)h;
     try {
         RenderContext context;            /* HIP device 0 */
@@ -171,6 +177,20 @@ int main(int argc, char** argv) {
             }
             std::printf("{\"adaptive_frames\": %u, \"adaptive_rounds\": %u, \"adaptive_samples\": %llu}\n", sum.frames, sum.rounds,
                         (unsigned long long)sum.samples);
+        }
+        if (robustM && nlmAdaptive) {
+            renderer.clearAccumulator();
+            surf_adaptive_nlm_params np;
+            surf_adaptive_nlm_default_params(&np);
+            np.mask.max_samples = adaptiveMax >= 2 ? (U32)adaptiveMax : 4u * (U32)spp;
+            np.mask.min_samples = np.mask.min_samples < np.mask.max_samples ? np.mask.min_samples : np.mask.max_samples;
+            if (np.mask.min_samples < 2) np.mask.min_samples = np.mask.max_samples = 2;
+            std::vector<F32> image;
+            const surf_adaptive_nlm_summary sum = renderer.renderAdaptiveNlm(np, &image);
+            const std::string path = prefix + "_nlm_adaptive.pfm";
+            if (surf_write_pfm(path.c_str(), W, H, image.data()) != SURF_OK) { std::fprintf(stderr, "cannot write %s\n", path.c_str()); return 1; }
+            std::printf("{\"nlm_adaptive_frames\": %u, \"nlm_adaptive_rounds\": %u, \"nlm_adaptive_samples\": %llu, \"nlm_adaptive_above\": %llu}\n",
+                        sum.frames, sum.rounds, (unsigned long long)sum.samples, (unsigned long long)sum.above);
         }
         std::printf("{\"width\": %u, \"height\": %u, \"spp\": %d}\n", W, H, spp);
     } catch (const std::exception& e) {

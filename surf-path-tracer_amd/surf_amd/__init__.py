@@ -28,6 +28,7 @@ Mirrors the reference interface for the hot path:
     .set_sample_buckets(M)     M partial accumulators per pixel, .sample_buckets() reads them, bucket_halves() sums the half images
     .robust()                  the median-of-means estimate of the accumulator with a Gini-adaptive trim (no reference counterpart)
     .denoise_nlm()             dual-buffer non-local means on the buckets' two half images: no feature plane, an error estimate beside it
+    .render_adaptive_nlm()     the adaptive loop driven by that error estimate (.mask_from_nlm() builds its mask); returns the filtered image
 """
 from __future__ import annotations
 
@@ -187,6 +188,25 @@ class AdaptiveSummary(C.Structure):
                 ("samples", C.c_uint64), ("noise", NoiseSummary)]
 
 
+class ErrorMaskParams(C.Structure):
+    """surf_error_mask_params: the relative RMS error a filtered pixel may keep and its floor, the sample counts a pixel
+    stays active below / stops at, the box radius the estimate is smoothed with, and the dilation of the noisy pixels."""
+    _fields_ = [("threshold", C.c_float), ("floor", C.c_float), ("min_samples", C.c_uint32), ("max_samples", C.c_uint32),
+                ("smooth", C.c_uint32), ("dilate", C.c_uint32), ("_pad", C.c_uint32 * 2)]
+
+
+class AdaptiveNlmParams(C.Structure):
+    """surf_adaptive_nlm_params: the mask's parameters, the filter's and the loop's."""
+    _fields_ = [("mask", ErrorMaskParams), ("nlm", NlmParams), ("batch", C.c_uint32), ("max_segments", C.c_uint32),
+                ("first_sample_index", C.c_uint32), ("_pad", C.c_uint32)]
+
+
+class AdaptiveNlmSummary(C.Structure):
+    """surf_adaptive_nlm_summary."""
+    _fields_ = [("rounds", C.c_uint32), ("frames", C.c_uint32), ("active_last", C.c_uint32), ("_pad", C.c_uint32),
+                ("samples", C.c_uint64), ("above", C.c_uint64), ("max_error", C.c_float), ("_pad2", C.c_uint32)]
+
+
 _lib = None
 
 # Byte sizes of the reference records (include/surf_hip.h static_asserts).
@@ -308,6 +328,14 @@ def load() -> C.CDLL:
         "surf_denoise_nlm_image": ([P, U32, U32, P, P, C.POINTER(NlmParams), P, P], I32),
         "surf_denoise_nlm_image_host": ([U32, U32, P, P, C.POINTER(NlmParams), P, P], I32),
         "surf_debug_nlm_time": ([P, C.POINTER(F), U32], I32),
+        "surf_error_mask_default_params": ([C.POINTER(ErrorMaskParams)], I32),
+        "surf_error_mask_image": ([P, U32, U32, P, P, P, C.POINTER(ErrorMaskParams), P, P, C.POINTER(U32)], I32),
+        "surf_error_mask_image_host": ([U32, U32, P, P, P, C.POINTER(ErrorMaskParams), P, P, C.POINTER(U32)], I32),
+        "surf_mask_from_nlm": ([P, C.POINTER(NlmParams), C.POINTER(ErrorMaskParams), C.POINTER(U32)], I32),
+        "surf_debug_error_mask_time": ([P, C.POINTER(F), U32], I32),
+        "surf_adaptive_nlm_default_params": ([C.POINTER(AdaptiveNlmParams)], I32),
+        "surf_render_adaptive_nlm": ([P, C.POINTER(AdaptiveNlmParams), P, P, P, U32, C.POINTER(AdaptiveNlmSummary)], I32),
+        "surf_render_adaptive_nlm_copy_device": ([P, C.POINTER(AdaptiveNlmParams), P, P, P, U32, C.POINTER(AdaptiveNlmSummary)], I32),
         "surf_mesh_data": ([P, C.POINTER(P), C.POINTER(P), C.POINTER(U32)], I32),
         "surf_mesh_destroy": ([P], None),
         "surf_ref_sinf": ([F], F), "surf_ref_cosf": ([F], F), "surf_ref_expf": ([F], F),
@@ -884,6 +912,57 @@ def adaptive_mask_image_host(acc, squares, **params):
     p, n = adaptive_mask_params(**params), C.c_uint32()
     _check(load().surf_adaptive_mask_image_host(w, h, _ptr(a), _ptr(q), C.byref(p), _ptr(mask), _ptr(lst), C.byref(n)),
            "surf_adaptive_mask_image_host")
+    return mask, lst[:n.value].copy()
+
+
+_ERROR_MASK_FIELDS = ("threshold", "floor", "min_samples", "max_samples", "smooth", "dilate")
+_NLM_FIELDS = ("search_radius", "patch_radius", "k", "alpha", "eps")
+
+
+def error_mask_params(**params) -> ErrorMaskParams:
+    """surf_error_mask_default_params (threshold 0.1, floor 0.01, min_samples 16, max_samples 1024, smooth 3, dilate 1)
+    with the given fields replaced."""
+    p = ErrorMaskParams()
+    _check(load().surf_error_mask_default_params(C.byref(p)), "surf_error_mask_default_params")
+    for k, v in params.items():
+        if k not in _ERROR_MASK_FIELDS:
+            raise TypeError(f"unknown error mask parameter {k!r}")
+        setattr(p, k, float(v) if k in ("threshold", "floor") else int(v))
+    return p
+
+
+def adaptive_nlm_params(**params) -> AdaptiveNlmParams:
+    """surf_adaptive_nlm_default_params (the mask's and the filter's defaults, batch 64, max_segments 0,
+    first_sample_index 0) with the given fields replaced; the mask's and the filter's fields are given by their own names."""
+    p = AdaptiveNlmParams()
+    _check(load().surf_adaptive_nlm_default_params(C.byref(p)), "surf_adaptive_nlm_default_params")
+    p.mask = error_mask_params(**{k: v for k, v in params.items() if k in _ERROR_MASK_FIELDS})
+    p.nlm = nlm_params(**{k: v for k, v in params.items() if k in _NLM_FIELDS})
+    for k, v in params.items():
+        if k in _ERROR_MASK_FIELDS or k in _NLM_FIELDS:
+            continue
+        if k not in ("batch", "max_segments", "first_sample_index"):
+            raise TypeError(f"unknown adaptive parameter {k!r}")
+        setattr(p, k, int(v))
+    return p
+
+
+def _error_mask_planes(out, err, acc):
+    o, e, a = (np.ascontiguousarray(v, dtype=np.float32) for v in (out, err, acc))
+    if o.ndim != 3 or o.shape[2] != 4 or e.shape != o.shape or a.shape != o.shape:
+        raise ValueError(f"mask planes {o.shape}, {e.shape}, {a.shape} are not three (H, W, 4) images of one size")
+    h, w = o.shape[:2]
+    return w, h, o, e, a, np.zeros((h, w), np.uint8), np.zeros(h * w, np.uint32)
+
+
+def error_mask_image_host(out, err, acc, **params):
+    """The CPU twin of Renderer.error_mask_image (surf_error_mask_image_host): (mask (H, W) uint8, the ascending list of
+    active pixel indices) of the non-local-means filter's two outputs and the accumulator, each (H, W, 4);
+    bit-identical, no device."""
+    w, h, o, e, a, mask, lst = _error_mask_planes(out, err, acc)
+    p, n = error_mask_params(**params), C.c_uint32()
+    _check(load().surf_error_mask_image_host(w, h, _ptr(o), _ptr(e), _ptr(a), C.byref(p), _ptr(mask), _ptr(lst), C.byref(n)),
+           "surf_error_mask_image_host")
     return mask, lst[:n.value].copy()
 
 
@@ -1474,6 +1553,42 @@ class Renderer:
         _check(load().surf_render_adaptive(self._h, C.byref(p), _ptr(ra), round_cap, C.byref(s)), "surf_render_adaptive", self._h)
         return {"rounds": int(s.rounds), "frames": int(s.frames), "active_last": int(s.active_last), "samples": int(s.samples),
                 "noise": s.noise.as_dict(), "round_active": [int(v) for v in ra[:min(int(s.rounds), round_cap)]]}
+
+    def error_mask_image(self, out, err, acc, **params):
+        """The mask from the non-local-means filter's error estimate on host planes of any (H, W, 4) frame
+        (surf_error_mask_image; parameters as error_mask_params): (mask, ascending list).  Leaves this context's mask alone."""
+        w, h, o, e, a, mask, lst = _error_mask_planes(out, err, acc)
+        p, n = error_mask_params(**params), C.c_uint32()
+        _check(load().surf_error_mask_image(self._h, w, h, _ptr(o), _ptr(e), _ptr(a), C.byref(p), _ptr(mask), _ptr(lst), C.byref(n)),
+               "surf_error_mask_image", self._h)
+        return mask, lst[:n.value].copy()
+
+    def mask_from_nlm(self, nlm=None, **params) -> int:
+        """Filters the halves of this context's buckets, builds the mask from the filter's error estimate and sets it
+        (surf_mask_from_nlm; nlm: a dict of nlm_params' fields, params as error_mask_params); returns the active count.
+        Needs set_sample_buckets; refused on a row shard."""
+        fp, p, n = nlm_params(**(nlm or {})), error_mask_params(**params), C.c_uint32()
+        _check(load().surf_mask_from_nlm(self._h, C.byref(fp), C.byref(p), C.byref(n)), "surf_mask_from_nlm", self._h)
+        return int(n.value)
+
+    def render_adaptive_nlm(self, round_cap: int = 4096, **params) -> dict:
+        """Renders until the filtered picture has converged (surf_render_adaptive_nlm; parameters as adaptive_nlm_params):
+        needs sample buckets on and an empty accumulator.  Returns {'rounds', 'frames', 'active_last', 'samples', 'above',
+        'max_error', 'round_active', 'image', 'err'}: image and err are the filter's two outputs of the final state."""
+        p, s = adaptive_nlm_params(**params), AdaptiveNlmSummary()
+        ra = np.zeros(max(1, round_cap), np.uint32)
+        out, err = (np.zeros((self.height, self.width, 4), dtype=np.float32) for _ in range(2))
+        _check(load().surf_render_adaptive_nlm(self._h, C.byref(p), _ptr(out), _ptr(err), _ptr(ra), round_cap, C.byref(s)),
+               "surf_render_adaptive_nlm", self._h)
+        return {"rounds": int(s.rounds), "frames": int(s.frames), "active_last": int(s.active_last), "samples": int(s.samples),
+                "above": int(s.above), "max_error": np.float32(s.max_error),
+                "round_active": [int(v) for v in ra[:min(int(s.rounds), round_cap)]], "image": out, "err": err}
+
+    def debug_error_mask_time(self) -> list:
+        """Device milliseconds of the last error mask's launches (surf_debug_error_mask_time): mask kernel, compaction."""
+        ms = (C.c_float * 2)()
+        _check(load().surf_debug_error_mask_time(self._h, ms, 2), "surf_debug_error_mask_time", self._h)
+        return [float(v) for v in ms]
 
     def finalize_weighted(self, display: bool = False) -> np.ndarray:
         """RGBA8 with each pixel divided by its own sample count (surf_finalize_rgba8_weighted)."""
