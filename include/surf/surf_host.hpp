@@ -402,6 +402,12 @@ public:
      * feature buffer.  The form without arguments takes surf_nlm_default_params. */
     std::vector<F32> denoiseNlm(const surf_nlm_params& params, std::vector<F32>* err = nullptr);
     std::vector<F32> denoiseNlm();
+    /* the first-order feature regression filter on the same two half images and the feature buffers
+     * surf_set_filter_guides selects (surf_denoise_regress; needs setSampleBuckets): the filtered image
+     * and, err non-NULL, its error estimate, as denoiseNlm returns them.  The form without arguments
+     * takes surf_regress_default_params. */
+    std::vector<F32> denoiseRegress(const surf_regress_params& params, std::vector<F32>* err = nullptr);
+    std::vector<F32> denoiseRegress();
     /* the active-pixel mask (surf_set_pixel_mask): width*height bytes, nonzero = active, render()
      * then traces those pixels only; an empty vector = every pixel.  pixelMask: the mask as set and,
      * where asked for, its active count. */

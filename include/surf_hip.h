@@ -1194,6 +1194,102 @@ int surf_denoise_nlm_image_host(uint32_t w, uint32_t h, const float* half0, cons
  * filter launches into kernel_ms[0..count); the image form has no halves launch. */
 int surf_debug_nlm_time(surf_ctx* ctx, float* kernel_ms, uint32_t count);
 
+/* ---- first-order feature regression on the half images (no reference counterpart) ----
+ * The filter that joins the two half images of the sample buckets with the
+ * noise-free feature planes: around every pixel each half's colour is fitted,
+ * by weighted least squares, as a first-order function of the features
+ * (normal, albedo, relative depth) with the non-local-means filter's
+ * cross-half patch weights, and the fit is evaluated at the pixel itself
+ * (Moon, Carr, Yoon 2014; Bitterli et al. 2016 without the collaborative
+ * step).  Where the features explain the picture the fit follows them across
+ * the window instead of averaging over them; where they do not (a miss, a
+ * singular system) it is the non-local-means average.  Opt-in and a pure
+ * post-process, as surf_denoise_nlm is: without a call nothing differs, and a
+ * call leaves the accumulator, the buckets, the squares, surf_stats, the
+ * counters and the cached feature planes as they are.
+ *
+ * The arithmetic (part of the interface: f32, uncontracted, / is IEEE, expf is
+ * glibc's; surf_denoise_regress_image_host reproduces every bit).  Inputs: a
+ * full frame of W x H pixels, the half accumulators H0, H1 as above, and the
+ * three planes position, normal, albedo as surf_read_aov defines them.
+ * Parameters: search_radius r, patch_radius f, k, alpha, eps as in
+ * surf_nlm_params, and ridge finite and > 0.
+ *
+ * Prepare, the distance images and the patch distances D_0(p, o), D_1(p, o)
+ *   are surf_denoise_nlm's, word for word; so is the weight
+ *   w(D) = expf(-max(min(D, 100), 0)) (a NaN becomes 100).
+ * Feature record of a pixel:  N = normal.xyz, a = albedo.xyz, z = position.w,
+ *   hit = albedo.w != 0.
+ * Features of a tap q against the centre p:  phi_0..2 = N(q) - N(p);
+ *   phi_3..5 = a(q) - a(p);  phi_6 = (z(q) - z(p)) / z(p);  phi_7 = 1.0f (the
+ *   constant goes last: its unknown is the prediction at p and needs no back
+ *   substitution).
+ * A pixel p that is invalid in surf_denoise_nlm's sense has that filter's
+ *   invalid output.  For a valid p, per half h with g = 1 - h, the sums start
+ *   at 0.0f and the taps q = p + o are taken dy = -r..r outer, dx = -r..r
+ *   inner.  The centre tap has w = 1.0f, every other tap w = w(D_g(p, o)).
+ *   p a miss:  every q inside the frame and valid is taken, at order zero:
+ *     A_77 = A_77 + w;  b_7c = b_7c + w * Ch(q)_c  -- surf_denoise_nlm's sums.
+ *   p a hit:  q is taken when it is inside the frame, valid, a hit itself and
+ *     phi_0..6 are all finite (x - x == 0.0f).  pp_ij = phi_i * phi_j,
+ *     A_ij = A_ij + w * pp_ij for i <= j;  u_i = w * phi_i,
+ *     b_ic = b_ic + u_i * Ch(q)_c for the channels c = x, y, z.
+ *     (A hit p whose own record is not finite -- z(p) = 0, say -- rejects every
+ *     tap, its own included: 0 / 0, a NaN in, a NaN out.)
+ * Solve, p a hit, per half:  sw = A_77;  zero_c = b_7c / sw;
+ *   A_jj = A_jj + ridge * sw for j = 0..6.  For k = 0..6 in turn:  d_k = A_kk;
+ *   for i = k+1..7:  l = A_ki / d_k;  A_ij = A_ij - l * A_kj for j = i..7;
+ *   b_ic = b_ic - l * b_kc.  Then d_7 = A_77, beta_c = b_7c / d_7.  When every
+ *   d_0..7 is finite and > 0 and the three beta_c are finite, o_h = beta, else
+ *   o_h = zero.  p a miss:  o_h = zero.
+ * Output, valid p:  surf_denoise_nlm's, from o_0 and o_1:
+ *   out_k = ((o0_k*n0) + (o1_k*n1)) / (n0 + n1), out.w = 1;
+ *   err_k = 0.25f * ((o0_k - o1_k)*(o0_k - o1_k)), err.w = 0.
+ * On a frame whose pixels are all hits with the same feature record every
+ * phi_0..6 and every l is 0: the result is surf_denoise_nlm_image's at the same
+ * r, f, k, alpha, eps, bit for bit.
+ *
+ * Three launches: the halves (context form) and prepare are the
+ * non-local-means filter's kernels; the filter handles both halves in one
+ * launch on 32 x 8 pixel tiles, a pixel's 2 x (36 + 24) sums in registers,
+ * at most two waves a SIMD.  It stages what the non-local-means kernel
+ * stages and the feature records of the tile with its halo of r (32 bytes a
+ * texel) in LDS: 68,128 B at the defaults, two workgroups a compute unit up
+ * to 80 KiB, one from (6, 3) on, 129,728 B at (10, 3) -- every r and f in
+ * range fits the 160 KiB of a compute unit.  Past that bound, or under
+ * SURF_REGRESS_LDS=0 (read at surf_create*), every value comes from global
+ * memory.  Identical bits either way.  MEASUREMENTS "First-order regression"
+ * has the errors and the costs. */
+typedef struct {
+    uint32_t search_radius, patch_radius;
+    float k, alpha, eps, ridge;
+} surf_regress_params;
+/* r 5, f 2, k 0.7, alpha 1.0, eps 1e-10, ridge 0.1 */
+int surf_regress_default_params(surf_regress_params* params);
+/* The context form: the halves of the context's own buckets and the planes
+ * surf_set_filter_guides selects (first hit or chain, computed if need be, as
+ * surf_denoise reads them); out_rgba and out_err (may be NULL) height*width*4
+ * floats.  Drains the stream.  SURF_ERR_INVALID for a NULL context, params or
+ * out_rgba, parameters outside the ranges above, while the buckets are off
+ * (surf_set_sample_buckets), and on a row shard: assemble the shards' buckets
+ * and planes and call surf_denoise_regress_image; SURF_ERR_OOM when a scratch
+ * image cannot be allocated. */
+int surf_denoise_regress(surf_ctx* ctx, const surf_regress_params* params, float* out_rgba, float* out_err);
+/* ... the two images to buffers on the context's device (height*width*16 bytes each; dst_err_device may be NULL) */
+int surf_denoise_regress_copy_device(surf_ctx* ctx, const surf_regress_params* params, void* dst_rgba_device, void* dst_err_device);
+/* Host planes of a w x h frame (w*h in 1..2^27), w*h*4 floats each.  Needs no
+ * scene and no buckets on the context. */
+int surf_denoise_regress_image(surf_ctx* ctx, uint32_t w, uint32_t h, const float* half0, const float* half1, const float* position,
+                               const float* normal, const float* albedo, const surf_regress_params* params, float* out_rgba,
+                               float* out_err);
+/* The CPU twin; needs no device.  Bit-identical to surf_denoise_regress_image. */
+int surf_denoise_regress_image_host(uint32_t w, uint32_t h, const float* half0, const float* half1, const float* position,
+                                    const float* normal, const float* albedo, const surf_regress_params* params, float* out_rgba,
+                                    float* out_err);
+/* Diagnostics: device times (HIP events) of the last run's halves, prepare and
+ * filter launches into kernel_ms[0..count); the image form has no halves launch. */
+int surf_debug_regress_time(surf_ctx* ctx, float* kernel_ms, uint32_t count);
+
 /* ---- per-pixel sample masks and the adaptive loop (no reference counterpart) ----
  * A context carries an active-pixel mask: one byte per pixel of the shard in
  * shard order (rows*width), nonzero = active.  After surf_create* and after

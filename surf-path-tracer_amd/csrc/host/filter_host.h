@@ -1,6 +1,6 @@
 /*
  * filter_host.h -- internal: what the image-space filters (host/denoise.hip,
- * temporal.hip, svgf.hip, adaptive.hip, nlm.hip, error_mask.hip) share: the
+ * temporal.hip, svgf.hip, adaptive.hip, nlm.hip, regress.hip, error_mask.hip) share: the
  * fixed-sigma denoiser's entry points for the other filters, the non-local-means
  * filter's context run for the mask built from it, the one driver of the a-trous
  * iterations on the device, and the host twins' copy of a caller's plane.  Includes no

@@ -269,6 +269,19 @@ std::vector<F32> WaveFrontRenderer::denoiseNlm() {
     return denoiseNlm(params);
 }
 
+std::vector<F32> WaveFrontRenderer::denoiseRegress(const surf_regress_params& params, std::vector<F32>* err) {
+    std::vector<F32> out((size_t)m_resolution.width * m_resolution.height * 4);
+    if (err) err->assign(out.size(), 0.0f);
+    check(surf_denoise_regress(m_ctx, &params, out.data(), err ? err->data() : nullptr), m_ctx, "surf_denoise_regress");
+    return out;
+}
+
+std::vector<F32> WaveFrontRenderer::denoiseRegress() {
+    surf_regress_params params;
+    check(surf_regress_default_params(&params), m_ctx, "surf_regress_default_params");
+    return denoiseRegress(params);
+}
+
 void WaveFrontRenderer::setPixelMask(const std::vector<uint8_t>& mask) {
     if (!mask.empty() && mask.size() != (size_t)m_resolution.width * m_resolution.height)
         throw std::runtime_error("setPixelMask: the mask is not width*height bytes");

@@ -243,7 +243,15 @@ struct surf_ctx {
     PlaneGroup<7> nl{"the non-local-means filter's planes"};
     StageTimer<3> nlTime;          /* halves, prepare, filter of the last run (surf_debug_nlm_time) */
     bool nlStaged = true;
-    /* the mask from that filter's error estimate (surf_error_mask_image, surf_mask_from_nlm, surf_render_adaptive_nlm;
+    /* the first-order feature regression filter (surf_denoise_regress*, host/regress.hip): rg, the planes nl holds
+     * and behind them the three feature planes the image form uploads; rgStaged: the filter kernel stages its tile
+     * in LDS where the layout fits (SURF_REGRESS_LDS=0: every value from global memory; MEASUREMENTS "First-order
+     * regression"); rgLdsSet: the staged kernel's dynamic LDS limit has been raised */
+    PlaneGroup<10> rg{"the regression filter's planes"};
+    StageTimer<3> rgTime;          /* halves, prepare, filter of the last run (surf_debug_regress_time) */
+    bool rgStaged = true;
+    bool rgLdsSet = false;
+    /* the mask from the non-local-means filter's error estimate (surf_error_mask_image, surf_mask_from_nlm, surf_render_adaptive_nlm;
      * host/error_mask.hip): em, one record, the loop's summary counters; emIn, the three planes the image form uploads */
     PlaneGroup<1> em{"the error mask's counters"};
     PlaneGroup<3> emIn{"surf_error_mask_image's planes"};
@@ -389,6 +397,8 @@ void freeAdaptive(surf_ctx* c);
 void freeRobust(surf_ctx* c);
 /* defined in host/nlm.hip: surf_destroy's part for the non-local-means filter's images */
 void freeNlm(surf_ctx* c);
+/* defined in host/regress.hip: surf_destroy's part for the regression filter's images */
+void freeRegress(surf_ctx* c);
 /* defined in host/error_mask.hip: surf_destroy's part for the error mask's images */
 void freeErrorMask(surf_ctx* c);
 

@@ -1117,6 +1117,7 @@ int createCtx(int dev, uint32_t w, uint32_t h, std::vector<uint32_t> rows, surf_
     if (const char* e = std::getenv("SURF_DENOISE_LDS")) c->dnLdsMax = (uint32_t)std::max(0, std::atoi(e));
     if (const char* e = std::getenv("SURF_SVGF_LDS")) c->svVarStaged = std::atoi(e) != 0;
     if (const char* e = std::getenv("SURF_NLM_LDS")) c->nlStaged = std::atoi(e) != 0;
+    if (const char* e = std::getenv("SURF_REGRESS_LDS")) c->rgStaged = std::atoi(e) != 0;
     c->width = w;
     c->height = h;
     c->rows = std::move(rows);
@@ -1200,6 +1201,7 @@ void surf_destroy(surf_ctx* c) {
     freeAdaptive(c);
     freeRobust(c);
     freeNlm(c);
+    freeRegress(c);
     freeErrorMask(c);
     if (c->dRows) (void)hipFree(c->dRows);
     if (c->ev0) (void)hipEventDestroy(c->ev0);

@@ -38,6 +38,10 @@
  * parameters with max_samples = ADAPTIVE_MAX, or 4 * SPP without one, and
  * min_samples = min(16, max_samples)): PREFIX_nlm_adaptive.pfm is the filter's
  * image of the final state; every other output is what it is with NLM = 1.
+ * With NLM = 3 also PREFIX_regress.pfm: the two half images and the first-hit
+ * feature buffers through the first-order feature regression filter
+ * (WaveFrontRenderer::denoiseRegress, surf_denoise_regress) with the default
+ * parameters; every other output is what it is with NLM = 1.
  */
 #include "surf/surf_host.hpp"
 #include "indoor_scene.hpp"
@@ -69,6 +73,7 @@ int main(int argc, char** argv) {
     }
     const bool nlm = argc == 9 && std::atoi(argv[8]) != 0;
     const bool nlmAdaptive = argc == 9 && std::atoi(argv[8]) == 2;
+    const bool regress = argc == 9 && std::atoi(argv[8]) == 3;
     const U32 W = (U32)w, H = (U32)h;
     try {
         RenderContext context;            /* HIP device 0 */
@@ -113,6 +118,11 @@ int main(int argc, char** argv) {
             const std::vector<F32> patched = renderer.denoiseNlm();
             const std::string path = prefix + "_nlm.pfm";
             if (surf_write_pfm(path.c_str(), W, H, patched.data()) != SURF_OK) { std::fprintf(stderr, "cannot write %s\n", path.c_str()); return 1; }
+        }
+        if (robustM && regress) {
+            const std::vector<F32> fitted = renderer.denoiseRegress();
+            const std::string path = prefix + "_regress.pfm";
+            if (surf_write_pfm(path.c_str(), W, H, fitted.data()) != SURF_OK) { std::fprintf(stderr, "cannot write %s\n", path.c_str()); return 1; }
         }
         std::vector<F32> clean;
         if (robustM) {

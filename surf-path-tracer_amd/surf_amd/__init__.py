@@ -28,6 +28,7 @@ Mirrors the reference interface for the hot path:
     .set_sample_buckets(M)     M partial accumulators per pixel, .sample_buckets() reads them, bucket_halves() sums the half images
     .robust()                  the median-of-means estimate of the accumulator with a Gini-adaptive trim (no reference counterpart)
     .denoise_nlm()             dual-buffer non-local means on the buckets' two half images: no feature plane, an error estimate beside it
+    .denoise_regress()         first-order regression of the two half images on the feature planes with those patch weights
     .render_adaptive_nlm()     the adaptive loop driven by that error estimate (.mask_from_nlm() builds its mask); returns the filtered image
 """
 from __future__ import annotations
@@ -167,6 +168,12 @@ class NlmParams(C.Structure):
     """surf_nlm_params: the search and patch radii, the distance's scale k, the variance cancellation alpha, eps."""
     _fields_ = [("search_radius", C.c_uint32), ("patch_radius", C.c_uint32), ("k", C.c_float), ("alpha", C.c_float), ("eps", C.c_float),
                 ("_pad", C.c_uint32)]
+
+
+class RegressParams(C.Structure):
+    """surf_regress_params: surf_nlm_params' radii, k, alpha and eps, and the ridge of the regression."""
+    _fields_ = [("search_radius", C.c_uint32), ("patch_radius", C.c_uint32), ("k", C.c_float), ("alpha", C.c_float), ("eps", C.c_float),
+                ("ridge", C.c_float)]
 
 
 class AdaptiveMaskParams(C.Structure):
@@ -328,6 +335,12 @@ def load() -> C.CDLL:
         "surf_denoise_nlm_image": ([P, U32, U32, P, P, C.POINTER(NlmParams), P, P], I32),
         "surf_denoise_nlm_image_host": ([U32, U32, P, P, C.POINTER(NlmParams), P, P], I32),
         "surf_debug_nlm_time": ([P, C.POINTER(F), U32], I32),
+        "surf_regress_default_params": ([C.POINTER(RegressParams)], I32),
+        "surf_denoise_regress": ([P, C.POINTER(RegressParams), P, P], I32),
+        "surf_denoise_regress_copy_device": ([P, C.POINTER(RegressParams), P, P], I32),
+        "surf_denoise_regress_image": ([P, U32, U32, P, P, P, P, P, C.POINTER(RegressParams), P, P], I32),
+        "surf_denoise_regress_image_host": ([U32, U32, P, P, P, P, P, C.POINTER(RegressParams), P, P], I32),
+        "surf_debug_regress_time": ([P, C.POINTER(F), U32], I32),
         "surf_error_mask_default_params": ([C.POINTER(ErrorMaskParams)], I32),
         "surf_error_mask_image": ([P, U32, U32, P, P, P, C.POINTER(ErrorMaskParams), P, P, C.POINTER(U32)], I32),
         "surf_error_mask_image_host": ([U32, U32, P, P, P, C.POINTER(ErrorMaskParams), P, P, C.POINTER(U32)], I32),
@@ -849,6 +862,36 @@ def denoise_nlm_image_host(half0, half1, **params):
     w, h, a, b, out, err = _nlm_planes(half0, half1)
     p = nlm_params(**params)
     _check(load().surf_denoise_nlm_image_host(w, h, _ptr(a), _ptr(b), C.byref(p), _ptr(out), _ptr(err)), "surf_denoise_nlm_image_host")
+    return out, err
+
+
+def regress_params(**params) -> RegressParams:
+    """surf_regress_default_params (search_radius 5, patch_radius 2, k 0.7, alpha 1.0, eps 1e-10, ridge 0.1) with the
+    given fields replaced."""
+    p = RegressParams()
+    _check(load().surf_regress_default_params(C.byref(p)), "surf_regress_default_params")
+    for name, v in params.items():
+        if name not in ("search_radius", "patch_radius", "k", "alpha", "eps", "ridge"):
+            raise TypeError(f"surf_regress_params has no field {name!r}")
+        setattr(p, name, int(v) if name.endswith("_radius") else float(v))
+    return p
+
+
+def _regress_planes(half0, half1, planes):
+    """(w, h, [half0, half1, position, normal, albedo], out, err): (H, W, 4) images of one size as contiguous float32;
+    planes is Renderer.aov()'s dict or a (position, normal, albedo) sequence."""
+    w, h, a, b, out, err = _nlm_planes(half0, half1)
+    _, _, f = _denoise_planes(a, planes)
+    return w, h, [a, b] + f[1:], out, err
+
+
+def denoise_regress_image_host(half0, half1, planes, **params):
+    """The CPU twin of Renderer.denoise_regress_image (surf_denoise_regress_image_host): (image, err), each (H, W, 4)
+    float32; bit-identical, no device."""
+    w, h, a, out, err = _regress_planes(half0, half1, planes)
+    p = regress_params(**params)
+    _check(load().surf_denoise_regress_image_host(w, h, *(_ptr(v) for v in a), C.byref(p), _ptr(out), _ptr(err)),
+           "surf_denoise_regress_image_host")
     return out, err
 
 
@@ -1505,6 +1548,38 @@ class Renderer:
         """Device milliseconds of the last non-local-means run's launches (surf_debug_nlm_time): halves, prepare, filter."""
         ms = (C.c_float * 3)()
         _check(load().surf_debug_nlm_time(self._h, ms, 3), "surf_debug_nlm_time", self._h)
+        return [float(v) for v in ms]
+
+    def denoise_regress(self, **params):
+        """(image, err) of the first-order feature regression filter (surf_denoise_regress; regress_params' names): each
+        half of this context's sample buckets fitted around every pixel as a first-order function of normal, albedo and
+        relative depth with the non-local-means patch weights of the other half, evaluated at the pixel; recombined
+        and with an error estimate as denoise_nlm's.  Reads the planes set_filter_guides selects.  Needs
+        set_sample_buckets; raises SURF_ERR_INVALID on a row shard (see denoise_regress_image)."""
+        p = regress_params(**params)
+        out, err = (np.zeros((self.height, self.width, 4), dtype=np.float32) for _ in range(2))
+        _check(load().surf_denoise_regress(self._h, C.byref(p), _ptr(out), _ptr(err)), "surf_denoise_regress", self._h)
+        return out, err
+
+    def denoise_regress_image(self, half0, half1, planes, **params):
+        """The same filter on host planes of any full frame (surf_denoise_regress_image): two half accumulators, e.g.
+        bucket_halves() of planes assembled from row shards, and Renderer.aov()'s dict or (position, normal, albedo):
+        (image, err)."""
+        w, h, a, out, err = _regress_planes(half0, half1, planes)
+        p = regress_params(**params)
+        _check(load().surf_denoise_regress_image(self._h, w, h, *(_ptr(v) for v in a), C.byref(p), _ptr(out), _ptr(err)),
+               "surf_denoise_regress_image", self._h)
+        return out, err
+
+    def copy_denoise_regress_to(self, device_ptr: int, err_device_ptr: int = None, **params):
+        p = regress_params(**params)
+        _check(load().surf_denoise_regress_copy_device(self._h, C.byref(p), C.c_void_p(device_ptr), C.c_void_p(err_device_ptr)),
+               "surf_denoise_regress_copy_device", self._h)
+
+    def debug_regress_time(self) -> list:
+        """Device milliseconds of the last regression run's launches (surf_debug_regress_time): halves, prepare, filter."""
+        ms = (C.c_float * 3)()
+        _check(load().surf_debug_regress_time(self._h, ms, 3), "surf_debug_regress_time", self._h)
         return [float(v) for v in ms]
 
     def debug_robust_time(self) -> float:
