@@ -10,11 +10,17 @@
  * the header states.  It is written once, in the SURF_HD functions below:
  * nlmPrepare (the half means, their validity, the variance estimate),
  * nlmDistance (one texel of a search offset's distance image), nlmPatch (the
- * row sums, then their sum), nlmTap (the weighted sums) and
- * nlmOutput.  nlmPixel strings them together for a pixel whose every value
- * comes from a Fetch object: the global kernel and the host twin call it.  The
- * staged kernel calls the same pieces around its LDS copy of the tile and of
- * the distance image: identical bits.
+ * row sums, then their sum), nlmWeight, nlmTap (the weighted sums) and
+ * nlmOutput.
+ *
+ * The walk over a pixel's taps -- which taps exist, each tap's two patch
+ * distances and its two cross-half weights -- is written once in each of two
+ * forms, for this filter and for whatever else weights the halves this way
+ * (device/regress_kernels.h): nlmWalk, every value from a Fetch object, which
+ * the global kernels and the host twins call, and nlmWalkStaged, the same
+ * pieces around an LDS copy of the tile and of the distance image: identical
+ * bits.  What a tap is added to is the walk's template argument, a consumer
+ * (NlmTaps states the interface); the walks know nothing of their consumers.
  */
 #pragma once
 #include "denoise_kernels.h"    /* the 32 x 8 tile: tilePixel */
@@ -162,10 +168,8 @@ SURF_HD NlmSums nlmZero() {
     s.s1 = mk3(0.0f, 0.0f, 0.0f);
     return s;
 }
-/* one accepted tap: half 0 takes the weight of the distance in half 1 (D1) and the other way round */
-SURF_HD void nlmTap(NlmSums& s, bool centre, float D0, float D1, float4 Cq0, float4 Cq1) {
-    const float w0 = centre ? 1.0f : nlmWeight(D1);
-    const float w1 = centre ? 1.0f : nlmWeight(D0);
+/* one taken tap: its two weights and the two halves' colours there */
+SURF_HD void nlmTap(NlmSums& s, float w0, float w1, float4 Cq0, float4 Cq1) {
     s.w0 = s.w0 + w0;
     s.s0.x = s.s0.x + w0 * Cq0.x;
     s.s0.y = s.s0.y + w0 * Cq0.y;
@@ -175,6 +179,23 @@ SURF_HD void nlmTap(NlmSums& s, bool centre, float D0, float D1, float4 Cq0, flo
     s.s1.y = s.s1.y + w1 * Cq1.y;
     s.s1.z = s.s1.z + w1 * Cq1.z;
 }
+
+/* A consumer of the walks below says three things.  take(qx, qy): whether the
+ * tap at an in-frame pixel whose colour is valid is taken at all -- asked
+ * before the patch sum.  add(w0, w1, Cq0, Cq1): what a taken tap is added to.
+ * And, for the staged walk alone, what it keeps in LDS beside the walk's own
+ * planes: ldsFloat4s(K) records, which stage(lds, bx, by, W, H, K) fills for
+ * the tile at (bx, by) before the walk's first barrier and begin(x, y, inside)
+ * may read after it.  This one is the
+ * non-local-means filter's: every tap, into the weighted sums, nothing staged. */
+struct NlmTaps {
+    NlmSums s = nlmZero();
+    SURF_HD bool take(int, int) { return true; }
+    SURF_HD void add(float w0, float w1, float4 Cq0, float4 Cq1) { nlmTap(s, w0, w1, Cq0, Cq1); }
+    SURF_HD static size_t ldsFloat4s(const NlmConsts&) { return 0; }
+    SURF_HD void stage(float4*, int, int, int, int, const NlmConsts&) {}
+    SURF_HD void begin(int, int, bool) {}
+};
 
 /* the output records of a pixel: valid with the sums of its taps, else the plain mean */
 SURF_HD void nlmOutput(bool valid, float4 h0, float4 h1, const NlmSums& s, float4& out, float4& err) {
@@ -206,12 +227,15 @@ struct NlmFetchPlanes {
     }
 };
 
-/* The sums of a VALID pixel (x, y), every value from fetch.c / fetch.v at
- * in-frame texels: the taps dy outer and dx inner, each tap's two patch
- * distances computed texel by texel. */
-template <class Fetch>
-SURF_HD NlmSums nlmPixel(int x, int y, int W, int H, const NlmConsts& K, const Fetch& fetch) {
-    NlmSums s = nlmZero();
+/* The taps of a VALID pixel (x, y), every value from fetch.c / fetch.v at
+ * in-frame texels: the taps dy outer and dx inner, each taken tap's two patch
+ * distances computed texel by texel; half 0 takes the weight of the distance
+ * in half 1 (D1) and the other way round, the centre tap weight 1 -- written
+ * as one branch on the centre, not as two selects after the patch sum: the
+ * same values, and the form in which the compiler keeps the centre's jump past
+ * the exponentials (MEASUREMENTS "One stills walk"). */
+template <class Fetch, class Taps>
+SURF_HD void nlmWalk(int x, int y, int W, int H, const NlmConsts& K, const Fetch& fetch, Taps& taps) {
     for (int dy = -K.r; dy <= K.r; ++dy) {
         const int qy = y + dy;
         if (qy < 0 || qy >= H) continue;
@@ -220,150 +244,144 @@ SURF_HD NlmSums nlmPixel(int x, int y, int W, int H, const NlmConsts& K, const F
             if (qx < 0 || qx >= W) continue;
             const float4 Cq0 = fetch.c(0, qx, qy);
             if (Cq0.w == 0.0f) continue;
+            if (!taps.take(qx, qy)) continue;
             const float4 Cq1 = fetch.c(1, qx, qy);
             const bool centre = dx == 0 && dy == 0;
-            float D0 = 0.0f, D1 = 0.0f;
-            if (!centre)
+            float w0 = 1.0f, w1 = 1.0f;
+            if (!centre) {
+                float D0, D1;
                 nlmPatch(x, y, K.f, K.cnt, [&](int sx, int sy) {
                     const int ax = nlmClamp(sx, W), ay = nlmClamp(sy, H), bx = nlmClamp(sx + dx, W), by = nlmClamp(sy + dy, H);
                     const float4 Va = fetch.v(ax, ay), Vb = fetch.v(bx, by);
                     return make_float2(nlmDistance(fetch.c(0, ax, ay), fetch.c(0, bx, by), Va, Vb, K),
                                        nlmDistance(fetch.c(1, ax, ay), fetch.c(1, bx, by), Va, Vb, K));
                 }, D0, D1);
-            nlmTap(s, centre, D0, D1, Cq0, Cq1);
+                w0 = nlmWeight(D1);
+                w1 = nlmWeight(D0);
+            }
+            taps.add(w0, w1, Cq0, Cq1);
         }
     }
-    return s;
+}
+
+/* the sums of a VALID pixel: the global kernel's and the host twin's pixel function */
+template <class Fetch>
+SURF_HD NlmSums nlmPixel(int x, int y, int W, int H, const NlmConsts& K, const Fetch& fetch) {
+    NlmTaps taps;
+    nlmWalk(x, y, W, H, K, fetch, taps);
+    return taps.s;
 }
 
 #if defined(__HIPCC__) || defined(__HIP__)
 
-/* The halves of n pixels from M bucket planes n records apart: half 0 the even
- * planes added in ascending order to 0, half 1 the odd ones. */
-static __global__ __launch_bounds__(256) void k_nlm_halves(const float4* __restrict__ bk, uint32_t M, uint32_t n, float4* __restrict__ H0,
-                                                           float4* __restrict__ H1) {
-    const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= n) return;
-    float4 s[2] = {make_float4(0.0f, 0.0f, 0.0f, 0.0f), make_float4(0.0f, 0.0f, 0.0f, 0.0f)};
-    for (uint32_t j = 0; j < M; j += 2) {
-#pragma unroll
-        for (uint32_t h = 0; h < 2; ++h) {
-            const float4 b = bk[(size_t)(j + h) * n + p];
-            s[h] = make_float4(s[h].x + b.x, s[h].y + b.y, s[h].z + b.z, s[h].w + b.w);
+/* The staged walk of a 256-thread block on its 32 x 8 pixel tile.  The block
+ * copies the in-frame part of the tile with its halo of r + f -- the ten values
+ * of a prepared record, 40 bytes -- into dynamic LDS (nlmLdsBytes; what the
+ * consumer stages lies between the two float4 planes and the float2 plane).
+ * Then, for every search offset but the centre, the block computes the
+ * offset's distance image once per texel of the tile with its halo of f (both
+ * halves, one float2) into LDS, meets at a barrier, and every valid pixel
+ * whose tap is taken sums its patch from there: rows first, then the row
+ * sums, as nlmPatch states -- the values and the order of nlmWalk.  A second
+ * barrier ends the offset.  Every LDS read is at a texel clamped to the frame,
+ * which lies in the staged part: the tile holds a frame pixel, so clamping a
+ * texel of the tile's halo to the frame leaves it inside the halo.  Consecutive
+ * lanes read consecutive 16-byte or 8-byte texels of a plane's row.  Every
+ * thread of the block calls it, pixels outside the frame included (they take
+ * no tap); returns whether the pixel is inside and valid. */
+template <class Taps>
+__device__ __forceinline__ bool nlmWalkStaged(float4* lds, const TilePixel& px, const float4* __restrict__ C0, const float4* __restrict__ C1,
+                                              const float4* __restrict__ V, int W, int H, const NlmConsts& K, Taps& taps) {
+    const int x = px.x, y = px.y;
+    const int halo = K.r + K.f;
+    const int tw = nlmTileW(halo), th = nlmTileH(halo), x0 = px.bx - halo, y0 = px.by - halo;
+    const int dw = nlmTileW(K.f), dn = (int)nlmDistTexels(K.f), dx0 = px.bx - K.f, dy0 = px.by - K.f;
+    const int texels = tw * th;
+    float4* t0 = lds;
+    float4* t1 = t0 + texels;
+    float4* tTaps = t1 + texels;
+    float2* tV = reinterpret_cast<float2*>(tTaps + Taps::ldsFloat4s(K));
+    float2* tD = tV + texels;
+    for (int t = (int)threadIdx.x; t < texels; t += 256) {
+        const int ly = t / tw, lx = t - ly * tw;
+        const int gx = x0 + lx, gy = y0 + ly;
+        if (gx >= 0 && gx < W && gy >= 0 && gy < H) {
+            const size_t g = (size_t)gy * W + gx;
+            const float4 vv = V[g];
+            t0[t] = C0[g];
+            t1[t] = C1[g];
+            tV[t] = make_float2(vv.x, vv.y);
         }
     }
-    H0[p] = s[0];
-    H1[p] = s[1];
-}
-
-/* Prepare: one thread per pixel of the 32 x 8 tiles; the nine neighbours' half
- * records come from global memory (the 3 x 3 windows of a tile overlap in L1). */
-static __global__ __launch_bounds__(256) void k_nlm_prepare(const float4* __restrict__ H0, const float4* __restrict__ H1, int W, int H,
-                                                            float4* __restrict__ C0, float4* __restrict__ C1, float4* __restrict__ V) {
-    const TilePixel px = tilePixel(W, H);
-    if (!px.inside) return;
-    const NlmFetchHalves fetch{H0, H1, W};
-    float4 c0, c1, v;
-    nlmPrepare(px.x, px.y, W, H, fetch, c0, c1, v);
-    C0[px.p] = c0;
-    C1[px.p] = c1;
-    V[px.p] = v;
+    taps.stage(tTaps, px.bx, px.by, W, H, K);
+    __syncthreads();
+    taps.begin(x, y, px.inside);
+    const auto var = [&](int i) { return make_float4(t1[i].w, tV[i].x, tV[i].y, 0.0f); };
+    const auto at = [&](int qx, int qy) { return (qy - y0) * tw + (qx - x0); };
+    /* the distance texels this thread computes for every offset, clamped to the frame */
+    int ai[kNlmDistPerThread], sx[kNlmDistPerThread], sy[kNlmDistPerThread];
+#pragma unroll
+    for (int k = 0; k < kNlmDistPerThread; ++k) {
+        const int t = (int)threadIdx.x + 256 * k;
+        const int ly = t / dw, lx = t - ly * dw;
+        sx[k] = dx0 + lx;
+        sy[k] = dy0 + ly;
+        ai[k] = t < dn ? at(nlmClamp(sx[k], W), nlmClamp(sy[k], H)) : -1;
+    }
+    const bool valid = px.inside && t0[at(x, y)].w != 0.0f;
+    for (int dy = -K.r; dy <= K.r; ++dy) {
+        for (int dx = -K.r; dx <= K.r; ++dx) {
+            const bool centre = dx == 0 && dy == 0;
+            if (!centre) {
+#pragma unroll
+                for (int k = 0; k < kNlmDistPerThread; ++k) {
+                    if (ai[k] < 0) continue;
+                    const int bi = at(nlmClamp(sx[k] + dx, W), nlmClamp(sy[k] + dy, H));
+                    const float4 Va = var(ai[k]), Vb = var(bi);
+                    tD[(int)threadIdx.x + 256 * k] =
+                        make_float2(nlmDistance(t0[ai[k]], t0[bi], Va, Vb, K), nlmDistance(t1[ai[k]], t1[bi], Va, Vb, K));
+                }
+                __syncthreads();
+            }
+            const int qx = x + dx, qy = y + dy;
+            if (valid && qx >= 0 && qx < W && qy >= 0 && qy < H) {
+                const int qi = at(qx, qy);
+                const float4 Cq0 = t0[qi];
+                if (Cq0.w != 0.0f && taps.take(qx, qy)) {
+                    float D0 = 0.0f, D1 = 0.0f;
+                    if (!centre) nlmPatch(x, y, K.f, K.cnt, [&](int ux, int uy) { return tD[(uy - dy0) * dw + (ux - dx0)]; }, D0, D1);
+                    const float w0 = centre ? 1.0f : nlmWeight(D1);
+                    const float w1 = centre ? 1.0f : nlmWeight(D0);
+                    taps.add(w0, w1, Cq0, t1[qi]);
+                }
+            }
+            if (!centre) __syncthreads();
+        }
+    }
+    return valid;
 }
 
 /* The filter: 256 threads on a 32 x 8 pixel tile, both halves in one launch
  * (the taps, their validity and the variance records are shared by the two).
- * STAGED: the block copies the in-frame part of the tile with its halo of
- * r + f -- the ten values of a prepared record, 40 bytes -- into dynamic LDS
- * (nlmLdsBytes).  Then, for
- * every search offset but the centre, the block computes the offset's
- * distance image once per texel of the tile with its halo of f (both halves,
- * one float2) into LDS, meets at a barrier, and every valid pixel whose tap is
- * accepted sums its patch from there: rows first, then the row sums, as
- * nlmPatch states -- the values and the order of nlmPixel.  A second barrier
- * ends the offset.  Every LDS read is at a texel clamped to the frame, which
- * lies in the staged part: the tile holds a frame pixel, so clamping a texel
- * of the tile's halo to the frame leaves it inside the halo.  Consecutive lanes
- * read consecutive 16-byte or 8-byte texels of a plane's row.
- * Not STAGED: nlmPixel on global memory. */
+ * STAGED: nlmWalkStaged.  Not STAGED: nlmWalk on global memory. */
 template <bool STAGED>
 __global__ __launch_bounds__(256) void k_nlm(const float4* __restrict__ C0, const float4* __restrict__ C1, const float4* __restrict__ V,
                                              const float4* __restrict__ H0, const float4* __restrict__ H1, float4* __restrict__ out,
                                              float4* __restrict__ err, int W, int H, NlmConsts K) {
     extern __shared__ float4 nlmTile[];
     const TilePixel px = tilePixel(W, H);
-    const int x = px.x, y = px.y;
-    NlmSums s = nlmZero();
+    NlmTaps taps;
     bool valid = false;
     if (STAGED) {
-        const int halo = K.r + K.f;
-        const int tw = nlmTileW(halo), th = nlmTileH(halo), x0 = px.bx - halo, y0 = px.by - halo;
-        const int dw = nlmTileW(K.f), dn = (int)nlmDistTexels(K.f), dx0 = px.bx - K.f, dy0 = px.by - K.f;
-        const int texels = tw * th;
-        float4* t0 = nlmTile;
-        float4* t1 = nlmTile + texels;
-        float2* tV = reinterpret_cast<float2*>(nlmTile + 2 * texels);
-        float2* tD = tV + texels;
-        for (int t = (int)threadIdx.x; t < texels; t += 256) {
-            const int ly = t / tw, lx = t - ly * tw;
-            const int gx = x0 + lx, gy = y0 + ly;
-            if (gx >= 0 && gx < W && gy >= 0 && gy < H) {
-                const size_t g = (size_t)gy * W + gx;
-                const float4 vv = V[g];
-                t0[t] = C0[g];
-                t1[t] = C1[g];
-                tV[t] = make_float2(vv.x, vv.y);
-            }
-        }
-        __syncthreads();
-        const auto var = [&](int i) { return make_float4(t1[i].w, tV[i].x, tV[i].y, 0.0f); };
-        const auto at = [&](int qx, int qy) { return (qy - y0) * tw + (qx - x0); };
-        /* the distance texels this thread computes for every offset, clamped to the frame */
-        int ai[kNlmDistPerThread], sx[kNlmDistPerThread], sy[kNlmDistPerThread];
-#pragma unroll
-        for (int k = 0; k < kNlmDistPerThread; ++k) {
-            const int t = (int)threadIdx.x + 256 * k;
-            const int ly = t / dw, lx = t - ly * dw;
-            sx[k] = dx0 + lx;
-            sy[k] = dy0 + ly;
-            ai[k] = t < dn ? at(nlmClamp(sx[k], W), nlmClamp(sy[k], H)) : -1;
-        }
-        valid = px.inside && t0[at(x, y)].w != 0.0f;
-        for (int dy = -K.r; dy <= K.r; ++dy) {
-            for (int dx = -K.r; dx <= K.r; ++dx) {
-                const bool centre = dx == 0 && dy == 0;
-                if (!centre) {
-#pragma unroll
-                    for (int k = 0; k < kNlmDistPerThread; ++k) {
-                        if (ai[k] < 0) continue;
-                        const int bi = at(nlmClamp(sx[k] + dx, W), nlmClamp(sy[k] + dy, H));
-                        const float4 Va = var(ai[k]), Vb = var(bi);
-                        tD[(int)threadIdx.x + 256 * k] =
-                            make_float2(nlmDistance(t0[ai[k]], t0[bi], Va, Vb, K), nlmDistance(t1[ai[k]], t1[bi], Va, Vb, K));
-                    }
-                    __syncthreads();
-                }
-                const int qx = x + dx, qy = y + dy;
-                if (valid && qx >= 0 && qx < W && qy >= 0 && qy < H) {
-                    const int qi = at(qx, qy);
-                    const float4 Cq0 = t0[qi];
-                    if (Cq0.w != 0.0f) {
-                        float D0 = 0.0f, D1 = 0.0f;
-                        if (!centre) nlmPatch(x, y, K.f, K.cnt, [&](int ux, int uy) { return tD[(uy - dy0) * dw + (ux - dx0)]; }, D0, D1);
-                        nlmTap(s, centre, D0, D1, Cq0, t1[qi]);
-                    }
-                }
-                if (!centre) __syncthreads();
-            }
-        }
+        valid = nlmWalkStaged(nlmTile, px, C0, C1, V, W, H, K, taps);
         if (!px.inside) return;
     } else {
         if (!px.inside) return;
         valid = C0[px.p].w != 0.0f;
-        const NlmFetchPlanes fetch{C0, C1, V, W};
-        if (valid) s = nlmPixel(x, y, W, H, K, fetch);
+        if (valid) nlmWalk(px.x, px.y, W, H, K, NlmFetchPlanes{C0, C1, V, W}, taps);
     }
     float4 o, e;
-    nlmOutput(valid, H0[px.p], H1[px.p], s, o, e);
+    nlmOutput(valid, H0[px.p], H1[px.p], taps.s, o, e);
     out[px.p] = o;
     err[px.p] = e;
 }

@@ -13,10 +13,12 @@
  * the SURF_HD functions below: regressPack (the feature record of a pixel),
  * regressPhi (a tap's features against the centre), regressTap / regressTap0
  * (the normal equations' sums of order one and order zero), regressSolve (the
- * ridge, the elimination, the fallback).  regressPixel strings them together
- * for a pixel whose every value comes from a Fetch object: the global kernel
- * and the host twin call it.  The staged kernel calls the same pieces around
- * its LDS copy of the tile: identical bits.
+ * ridge, the elimination, the fallback).  The walk over the taps is
+ * nlm_kernels.h's too, in both its forms: RegressTaps is the consumer that
+ * says which taps the regression takes and adds them to the normal
+ * equations, from feature planes in memory (regressPixel: the global kernel
+ * and the host twin) or from the staged kernel's LDS copy of them: identical
+ * bits.
  */
 #pragma once
 #include "nlm_kernels.h"
@@ -160,113 +162,83 @@ SURF_HD NlmSums regressSums(RegressAcc& a0, RegressAcc& a1, float ridge, bool or
     return s;
 }
 
-/* the prepared records and the three feature planes in memory (device global memory, host arrays) */
-struct RegressFetchPlanes {
-    NlmFetchPlanes nlm;
-    const float4* P;
-    const float4* N;
-    const float4* A;
-    SURF_HD float4 c(int g, int x, int y) const { return nlm.c(g, x, y); }
-    SURF_HD float4 v(int x, int y) const { return nlm.v(x, y); }
+/* the three feature planes in memory (device global memory, host arrays) */
+struct RegressFetchFeat {
+    const float4 *P, *N, *A;
+    int W;
     SURF_HD void feat(int x, int y, float4& F0, float4& F1) const {
-        const size_t i = (size_t)y * nlm.W + x;
+        const size_t i = (size_t)y * W + x;
         regressPack(P[i], N[i], A[i], F0, F1);
     }
 };
 
-/* The predictions of a colour-VALID pixel (x, y), every value from fetch at
- * in-frame texels: the taps dy outer and dx inner, each tap's two patch
- * distances computed texel by texel as nlmPixel computes them. */
-template <class Fetch>
-SURF_HD NlmSums regressPixel(int x, int y, int W, int H, const RegressConsts& R, const Fetch& fetch) {
-    const NlmConsts& K = R.n;
+/* The regression as a consumer of nlm_kernels.h's walks (NlmTaps states the
+ * interface), the feature records from feat: begin() zeroes the two halves'
+ * sums and keeps the centre's feature record; a hit centre takes the taps
+ * that are hits with finite features, at order one, a miss centre every tap,
+ * at order zero. */
+template <class Feat>
+struct RegressTaps {
+    Feat feat;
     RegressAcc a0, a1;
-    regressZero(a0);
-    regressZero(a1);
     float4 P0, P1;
-    fetch.feat(x, y, P0, P1);
-    const bool hit = P1.w != 0.0f;
-    for (int dy = -K.r; dy <= K.r; ++dy) {
-        const int qy = y + dy;
-        if (qy < 0 || qy >= H) continue;
-        for (int dx = -K.r; dx <= K.r; ++dx) {
-            const int qx = x + dx;
-            if (qx < 0 || qx >= W) continue;
-            const float4 Cq0 = fetch.c(0, qx, qy);
-            if (Cq0.w == 0.0f) continue;
-            float phi[kRegressDim];
-            if (hit) {
-                float4 Q0, Q1;
-                fetch.feat(qx, qy, Q0, Q1);
-                if (Q1.w == 0.0f) continue;
-                if (!regressPhi(P0, P1, Q0, Q1, phi)) continue;
-            }
-            const float4 Cq1 = fetch.c(1, qx, qy);
-            const bool centre = dx == 0 && dy == 0;
-            float D0 = 0.0f, D1 = 0.0f;
-            if (!centre)
-                nlmPatch(x, y, K.f, K.cnt, [&](int sx, int sy) {
-                    const int ax = nlmClamp(sx, W), ay = nlmClamp(sy, H), bx = nlmClamp(sx + dx, W), by = nlmClamp(sy + dy, H);
-                    const float4 Va = fetch.v(ax, ay), Vb = fetch.v(bx, by);
-                    return make_float2(nlmDistance(fetch.c(0, ax, ay), fetch.c(0, bx, by), Va, Vb, K),
-                                       nlmDistance(fetch.c(1, ax, ay), fetch.c(1, bx, by), Va, Vb, K));
-                }, D0, D1);
-            const float w0 = centre ? 1.0f : nlmWeight(D1);
-            const float w1 = centre ? 1.0f : nlmWeight(D0);
-            if (hit) regressTap(a0, a1, w0, w1, phi, Cq0, Cq1);
-            else regressTap0(a0, a1, w0, w1, Cq0, Cq1);
-        }
+    bool hit;
+    float phi[kRegressDim];
+    SURF_HD void begin(int x, int y, bool inside) {
+        regressZero(a0);
+        regressZero(a1);
+        P0 = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        P1 = P0;
+        if (inside) feat.feat(x, y, P0, P1);
+        hit = P1.w != 0.0f;
     }
-    return regressSums(a0, a1, R.ridge, hit);
+    SURF_HD bool take(int qx, int qy) {
+        if (!hit) return true;
+        float4 Q0, Q1;
+        feat.feat(qx, qy, Q0, Q1);
+        return Q1.w != 0.0f && regressPhi(P0, P1, Q0, Q1, phi);
+    }
+    SURF_HD void add(float w0, float w1, float4 Cq0, float4 Cq1) {
+        if (hit) regressTap(a0, a1, w0, w1, phi, Cq0, Cq1);
+        else regressTap0(a0, a1, w0, w1, Cq0, Cq1);
+    }
+    SURF_HD NlmSums sums(float ridge) { return regressSums(a0, a1, ridge, hit); }
+};
+
+/* the predictions of a colour-VALID pixel (x, y): the global kernel's and the host twin's pixel function */
+template <class Fetch, class Feat>
+SURF_HD NlmSums regressPixel(int x, int y, int W, int H, const RegressConsts& R, const Fetch& fetch, const Feat& feat) {
+    RegressTaps<Feat> taps{feat};
+    taps.begin(x, y, true);
+    nlmWalk(x, y, W, H, R.n, fetch, taps);
+    return taps.sums(R.ridge);
 }
 
 #if defined(__HIPCC__) || defined(__HIP__)
 
-/* The filter: 256 threads on a 32 x 8 pixel tile, both halves in one launch
- * (the taps, the features and their products are shared by the two).
- * STAGED: as k_nlm<true> -- the prepared records of the tile with its halo of
- * r + f and each search offset's distance image in dynamic LDS -- and beside
- * them the feature records of the in-frame part of the tile with its halo of
- * r (regressLdsBytes).  A tap reads its two colour records and its two
- * feature records from there, consecutive lanes consecutive 16-byte texels of
- * a plane's row; the centre's feature record stays in registers.
- * Not STAGED: regressPixel on global memory.
- * At most two waves a SIMD: the 120 sums of a pixel's two halves stay in registers. */
-template <bool STAGED>
-__global__ __launch_bounds__(256, 2) void k_regress(const float4* __restrict__ C0, const float4* __restrict__ C1, const float4* __restrict__ V,
-                                                    const float4* __restrict__ H0, const float4* __restrict__ H1,
-                                                    const float4* __restrict__ P, const float4* __restrict__ N,
-                                                    const float4* __restrict__ A, float4* __restrict__ out, float4* __restrict__ err,
-                                                    int W, int H, RegressConsts R) {
-    extern __shared__ float4 regressTile[];
-    const NlmConsts& K = R.n;
-    const TilePixel px = tilePixel(W, H);
-    const int x = px.x, y = px.y;
-    NlmSums s = nlmZero();
-    bool valid = false;
-    if (STAGED) {
-        const int halo = K.r + K.f;
-        const int tw = nlmTileW(halo), th = nlmTileH(halo), x0 = px.bx - halo, y0 = px.by - halo;
-        const int fw = nlmTileW(K.r), fx0 = px.bx - K.r, fy0 = px.by - K.r, ftexels = (int)regressFeatTexels(K.r);
-        const int dw = nlmTileW(K.f), dn = (int)nlmDistTexels(K.f), dx0 = px.bx - K.f, dy0 = px.by - K.f;
-        const int texels = tw * th;
-        float4* t0 = regressTile;
-        float4* t1 = t0 + texels;
-        float4* tF0 = t1 + texels;
+/* the feature records of the tile at (x0 + r, y0 + r) with its halo of r in LDS */
+struct RegressLdsFeat {
+    const float4 *F0, *F1;
+    int w, x0, y0;
+    __device__ __forceinline__ void feat(int x, int y, float4& Q0, float4& Q1) const {
+        const int i = (y - y0) * w + (x - x0);
+        Q0 = F0[i];
+        Q1 = F1[i];
+    }
+};
+
+/* ... and the staged walk's consumer: the feature records of the in-frame
+ * part of the tile with its halo of r staged beside the walk's planes
+ * (regressLdsBytes).  A tap reads its two feature records from there,
+ * consecutive lanes consecutive 16-byte texels of a plane's row; the centre's
+ * feature record stays in registers. */
+struct RegressStagedTaps : RegressTaps<RegressLdsFeat> {
+    const float4 *P, *N, *A;
+    __device__ __forceinline__ static size_t ldsFloat4s(const NlmConsts& K) { return 2 * regressFeatTexels(K.r); }
+    __device__ __forceinline__ void stage(float4* lds, int bx, int by, int W, int H, const NlmConsts& K) {
+        const int fw = nlmTileW(K.r), fx0 = bx - K.r, fy0 = by - K.r, ftexels = (int)regressFeatTexels(K.r);
+        float4* tF0 = lds;
         float4* tF1 = tF0 + ftexels;
-        float2* tV = reinterpret_cast<float2*>(tF1 + ftexels);
-        float2* tD = tV + texels;
-        for (int t = (int)threadIdx.x; t < texels; t += 256) {
-            const int ly = t / tw, lx = t - ly * tw;
-            const int gx = x0 + lx, gy = y0 + ly;
-            if (gx >= 0 && gx < W && gy >= 0 && gy < H) {
-                const size_t g = (size_t)gy * W + gx;
-                const float4 vv = V[g];
-                t0[t] = C0[g];
-                t1[t] = C1[g];
-                tV[t] = make_float2(vv.x, vv.y);
-            }
-        }
         for (int t = (int)threadIdx.x; t < ftexels; t += 256) {
             const int ly = t / fw, lx = t - ly * fw;
             const int gx = fx0 + lx, gy = fy0 + ly;
@@ -278,74 +250,35 @@ __global__ __launch_bounds__(256, 2) void k_regress(const float4* __restrict__ C
                 tF1[t] = F1;
             }
         }
-        __syncthreads();
-        const auto var = [&](int i) { return make_float4(t1[i].w, tV[i].x, tV[i].y, 0.0f); };
-        const auto at = [&](int qx, int qy) { return (qy - y0) * tw + (qx - x0); };
-        const auto fat = [&](int qx, int qy) { return (qy - fy0) * fw + (qx - fx0); };
-        /* the distance texels this thread computes for every offset, clamped to the frame */
-        int ai[kNlmDistPerThread], sx[kNlmDistPerThread], sy[kNlmDistPerThread];
-#pragma unroll
-        for (int k = 0; k < kNlmDistPerThread; ++k) {
-            const int t = (int)threadIdx.x + 256 * k;
-            const int ly = t / dw, lx = t - ly * dw;
-            sx[k] = dx0 + lx;
-            sy[k] = dy0 + ly;
-            ai[k] = t < dn ? at(nlmClamp(sx[k], W), nlmClamp(sy[k], H)) : -1;
-        }
-        valid = px.inside && t0[at(x, y)].w != 0.0f;
-        float4 P0 = make_float4(0.0f, 0.0f, 0.0f, 0.0f), P1 = P0;
-        if (px.inside) {
-            P0 = tF0[fat(x, y)];
-            P1 = tF1[fat(x, y)];
-        }
-        const bool hit = P1.w != 0.0f;
-        RegressAcc a0, a1;
-        regressZero(a0);
-        regressZero(a1);
-        for (int dy = -K.r; dy <= K.r; ++dy) {
-            for (int dx = -K.r; dx <= K.r; ++dx) {
-                const bool centre = dx == 0 && dy == 0;
-                if (!centre) {
-#pragma unroll
-                    for (int k = 0; k < kNlmDistPerThread; ++k) {
-                        if (ai[k] < 0) continue;
-                        const int bi = at(nlmClamp(sx[k] + dx, W), nlmClamp(sy[k] + dy, H));
-                        const float4 Va = var(ai[k]), Vb = var(bi);
-                        tD[(int)threadIdx.x + 256 * k] =
-                            make_float2(nlmDistance(t0[ai[k]], t0[bi], Va, Vb, K), nlmDistance(t1[ai[k]], t1[bi], Va, Vb, K));
-                    }
-                    __syncthreads();
-                }
-                const int qx = x + dx, qy = y + dy;
-                if (valid && qx >= 0 && qx < W && qy >= 0 && qy < H) {
-                    const int qi = at(qx, qy);
-                    const float4 Cq0 = t0[qi];
-                    bool take = Cq0.w != 0.0f;
-                    float phi[kRegressDim];
-                    if (take && hit) {
-                        const int fi = fat(qx, qy);
-                        const float4 Q1 = tF1[fi];
-                        take = Q1.w != 0.0f && regressPhi(P0, P1, tF0[fi], Q1, phi);
-                    }
-                    if (take) {
-                        float D0 = 0.0f, D1 = 0.0f;
-                        if (!centre) nlmPatch(x, y, K.f, K.cnt, [&](int ux, int uy) { return tD[(uy - dy0) * dw + (ux - dx0)]; }, D0, D1);
-                        const float w0 = centre ? 1.0f : nlmWeight(D1);
-                        const float w1 = centre ? 1.0f : nlmWeight(D0);
-                        if (hit) regressTap(a0, a1, w0, w1, phi, Cq0, t1[qi]);
-                        else regressTap0(a0, a1, w0, w1, Cq0, t1[qi]);
-                    }
-                }
-                if (!centre) __syncthreads();
-            }
-        }
+        feat = RegressLdsFeat{tF0, tF1, fw, fx0, fy0};
+    }
+};
+
+/* The filter: 256 threads on a 32 x 8 pixel tile, both halves in one launch
+ * (the taps, the features and their products are shared by the two).
+ * STAGED: nlmWalkStaged with the feature records staged beside its planes.
+ * Not STAGED: regressPixel on global memory.
+ * At most two waves a SIMD: the 120 sums of a pixel's two halves stay in registers. */
+template <bool STAGED>
+__global__ __launch_bounds__(256, 2) void k_regress(const float4* __restrict__ C0, const float4* __restrict__ C1, const float4* __restrict__ V,
+                                                    const float4* __restrict__ H0, const float4* __restrict__ H1,
+                                                    const float4* __restrict__ P, const float4* __restrict__ N,
+                                                    const float4* __restrict__ A, float4* __restrict__ out, float4* __restrict__ err,
+                                                    int W, int H, RegressConsts R) {
+    extern __shared__ float4 regressTile[];
+    const TilePixel px = tilePixel(W, H);
+    NlmSums s = nlmZero();
+    bool valid = false;
+    if (STAGED) {
+        RegressStagedTaps taps;
+        taps.P = P, taps.N = N, taps.A = A;
+        valid = nlmWalkStaged(regressTile, px, C0, C1, V, W, H, R.n, taps);
         if (!px.inside) return;
-        if (valid) s = regressSums(a0, a1, R.ridge, hit);
+        if (valid) s = taps.sums(R.ridge);
     } else {
         if (!px.inside) return;
         valid = C0[px.p].w != 0.0f;
-        const RegressFetchPlanes fetch{NlmFetchPlanes{C0, C1, V, W}, P, N, A};
-        if (valid) s = regressPixel(x, y, W, H, R, fetch);
+        if (valid) s = regressPixel(px.x, px.y, W, H, R, NlmFetchPlanes{C0, C1, V, W}, RegressFetchFeat{P, N, A, W});
     }
     float4 o, e;
     nlmOutput(valid, H0[px.p], H1[px.p], s, o, e);

@@ -3,17 +3,16 @@
  * (surf_set_pixel_mask, surf_mask_from_noise, surf_adaptive_mask_image*,
  * surf_render_adaptive; include/surf_hip.h): the mask's buffers on a context,
  * parameter checks, the launches that turn (A, Q) into the byte mask and its
- * ascending list, the CPU twin, and the loop around surf_render.  The rule
- * lives in device/adaptive_kernels.h, the mask's buffers and the compaction's
- * launches in host/mask_host.h (host/error_mask.hip builds masks too); what a
+ * ascending list, the CPU twin, and the adaptive loop on this mask.  The rule
+ * lives in device/adaptive_kernels.h; the mask's buffers, the compaction's
+ * launches, the twin's dilation and the loop itself in host/mask_host.h
+ * (host/error_mask.hip builds masks too); what a
  * masked stream does with the list is the sample stream's business
  * (surf_hip.hip).
  */
-#include "host/surf_ctx.h"
+#include "host/filter_host.h"
 
-#include <algorithm>
 #include <cmath>
-#include <cstring>
 
 #include "device/adaptive_kernels.h"
 #include "host/mask_host.h"
@@ -44,8 +43,7 @@ const char* frameError(uint32_t w, uint32_t h, const float* acc, const float* sq
  * the count is read back (one synchronisation). */
 int runMask(surf_ctx* c, uint32_t w, uint32_t h, const float4* A, const float4* Q, const surf_adaptive_mask_params& P, uint8_t* mask,
             uint32_t* list, uint32_t* blk, uint32_t* count) {
-    const dim3 tiles((w + kDenoiseTileW - 1) / kDenoiseTileW, (h + kDenoiseTileH - 1) / kDenoiseTileH);
-    hipLaunchKernelGGL(k_adaptive_flags, tiles, dim3(256), 0, c->stream, A, Q, mask, (int)w, (int)h, ruleOf(P));
+    hipLaunchKernelGGL(k_adaptive_flags, tileGrid(w, h), dim3(256), 0, c->stream, A, Q, mask, (int)w, (int)h, ruleOf(P));
     return compactMask(c, w * h, mask, list, blk, count);
 }
 
@@ -142,11 +140,7 @@ int surf_adaptive_mask_image(surf_ctx* c, uint32_t w, uint32_t h, const float* a
     SURF_CHECK(c, hipMemcpyAsync(c->sdAQ[1], squares, npx * sizeof(float4), hipMemcpyHostToDevice, c->stream));
     uint32_t n = 0;
     if ((rc = runMask(c, w, h, c->sdAQ[0], c->sdAQ[1], *p, c->adImgMask, c->adImgList, c->adImgBlk, &n))) return rc;
-    SURF_CHECK(c, hipMemcpyAsync(maskOut, c->adImgMask, npx, hipMemcpyDeviceToHost, c->stream));
-    if (listOut && n) SURF_CHECK(c, hipMemcpyAsync(listOut, c->adImgList, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-    SURF_CHECK(c, hipStreamSynchronize(c->stream));
-    *count = n;
-    return SURF_OK;
+    return copyImageMask(c, npx, n, maskOut, listOut, count);
 }
 
 /* The CPU twin: adaptiveRaw and adaptiveActive compiled for the host. */
@@ -157,24 +151,10 @@ int surf_adaptive_mask_image_host(uint32_t w, uint32_t h, const float* acc, cons
     if (const char* why = maskParamError(p)) return fail(nullptr, SURF_ERR_INVALID, std::string("surf_adaptive_mask_image_host: ") + why);
     const size_t npx = (size_t)w * h;
     const AdaptiveRule R = ruleOf(*p);
-    std::vector<float4> A(npx), Q(npx);                          /* the caller's planes need not be 16-byte aligned */
-    std::memcpy(A.data(), acc, npx * sizeof(float4));
-    std::memcpy(Q.data(), squares, npx * sizeof(float4));
+    const std::vector<float4> A = hostPlane(acc, npx), Q = hostPlane(squares, npx);
     std::vector<uint8_t> raw(npx);
     for (size_t q = 0; q < npx; ++q) raw[q] = adaptiveRaw(A[q], Q[q], R) ? 1 : 0;
-    uint32_t n = 0;
-    const int d = R.dilate, W = (int)w, H = (int)h;
-    for (int y = 0; y < H; ++y)
-        for (int x = 0; x < W; ++x) {
-            bool any = false;
-            for (int qy = std::max(0, y - d); qy <= std::min(H - 1, y + d); ++qy)
-                for (int qx = std::max(0, x - d); qx <= std::min(W - 1, x + d); ++qx) any = any || raw[(size_t)qy * W + qx] != 0;
-            const size_t q = (size_t)y * W + x;
-            const bool on = adaptiveActive(any, A[q], R);
-            maskOut[q] = on ? 1 : 0;
-            if (on) { if (listOut) listOut[n] = (uint32_t)q; ++n; }
-        }
-    *count = n;
+    *count = dilateAndList(raw.data(), (int)w, (int)h, R.dilate, [&](size_t q, bool any) { return adaptiveActive(any, A[q], R); }, maskOut, listOut);
     return SURF_OK;
 }
 
@@ -190,34 +170,14 @@ int surf_render_adaptive(surf_ctx* c, const surf_adaptive_params* p, uint32_t* r
     if (!c) return fail(nullptr, SURF_ERR_INVALID, "surf_render_adaptive: ctx is NULL");
     if (!p || !sum) return fail(c, SURF_ERR_INVALID, "surf_render_adaptive: NULL argument");
     if (const char* why = maskParamError(&p->mask)) return fail(c, SURF_ERR_INVALID, std::string("surf_render_adaptive: ") + why);
-    if (p->batch == 0) return fail(c, SURF_ERR_INVALID, "surf_render_adaptive: batch is 0");
-    if ((uint64_t)p->first_sample_index + p->mask.max_samples > 0xffffffffull)
-        return fail(c, SURF_ERR_INVALID, "surf_render_adaptive: first_sample_index + max_samples exceeds 32 bits");
+    if (const char* why = roundsParamError(*p)) return fail(c, SURF_ERR_INVALID, std::string("surf_render_adaptive: ") + why);
     if (!c->sqOn) return fail(c, SURF_ERR_INVALID, "surf_render_adaptive: sample squares are off (surf_set_sample_squares)");
-    SURF_CHECK(c, hipSetDevice(c->device));
-    int rc = drainStream(c);
+    int rc = startRounds(c, "surf_render_adaptive");
     if (rc) return rc;
-    if (c->totalSamples != 0)
-        return fail(c, SURF_ERR_INVALID, "surf_render_adaptive: the accumulator holds samples; call surf_clear_accumulator first");
     if (p->mask.dilate > 0 && c->rows.size() != c->height)
         return fail(c, SURF_ERR_INVALID, "surf_render_adaptive: a dilation needs the neighbouring rows, this context holds a row shard");
-    std::memset(sum, 0, sizeof *sum);
-    const uint64_t before = c->stats.samples;
-    if ((rc = surf_set_pixel_mask(c, nullptr))) return rc;
-    if ((rc = surf_render(c, p->mask.min_samples, p->first_sample_index, p->max_segments, 1))) return rc;
-    uint32_t f = p->mask.min_samples, active = 0;
-    for (;;) {
-        if ((rc = surf_mask_from_noise(c, &p->mask, &active))) return rc;
-        if (active == 0 || f == p->mask.max_samples) break;
-        const uint32_t nb = std::min(p->batch, p->mask.max_samples - f);
-        if (roundActive && sum->rounds < roundCap) roundActive[sum->rounds] = active;
-        if ((rc = surf_render(c, nb, p->first_sample_index + f, p->max_segments, 1))) return rc;
-        f += nb;
-        ++sum->rounds;
-    }
-    sum->frames = f;
-    sum->active_last = active;
-    sum->samples = c->stats.samples - before;
+    if ((rc = renderRounds(c, *p, roundActive, roundCap, sum, [&](uint32_t* active) { return surf_mask_from_noise(c, &p->mask, active); })))
+        return rc;
     const surf_noise_params np{p->mask.threshold, p->mask.floor};
     return surf_noise_estimate(c, &np, nullptr, &sum->noise);
 }

@@ -3,8 +3,8 @@
  * error estimate and the adaptive loop on it (surf_error_mask_image*,
  * surf_mask_from_nlm, surf_render_adaptive_nlm*; include/surf_hip.h):
  * parameter checks, the host constants, the mask launch in front of the
- * shared compaction, the CPU twin, and the loop around
- * surf_render and the filter's context run (host/nlm.hip).  The rule lives in
+ * shared compaction, the CPU twin, and the adaptive loop (host/mask_host.h)
+ * on the filter's context run (host/nlm.hip) and this mask.  The rule lives in
  * device/error_mask_kernels.h.
  */
 #include "host/filter_host.h"
@@ -93,33 +93,16 @@ int adaptiveNlm(surf_ctx* c, const surf_adaptive_nlm_params* p, void* outImg, vo
     if (!p || !sum) return fail(c, SURF_ERR_INVALID, std::string(who) + ": NULL argument");
     if (const char* why = errorParamError(&p->mask)) return fail(c, SURF_ERR_INVALID, std::string(who) + ": " + why);
     if (const char* why = nlmParamsError(&p->nlm)) return fail(c, SURF_ERR_INVALID, std::string(who) + ": nlm " + why);
-    if (p->batch == 0) return fail(c, SURF_ERR_INVALID, std::string(who) + ": batch is 0");
-    if ((uint64_t)p->first_sample_index + p->mask.max_samples > 0xffffffffull)
-        return fail(c, SURF_ERR_INVALID, std::string(who) + ": first_sample_index + max_samples exceeds 32 bits");
+    if (const char* why = roundsParamError(*p)) return fail(c, SURF_ERR_INVALID, std::string(who) + ": " + why);
     if (!c->bkM) return fail(c, SURF_ERR_INVALID, std::string(who) + ": sample buckets are off (surf_set_sample_buckets)");
     if (c->rows.size() != c->height)
         return fail(c, SURF_ERR_INVALID, std::string(who) + ": the filter and the mask need every row of the frame, this context holds a row shard");
-    SURF_CHECK(c, hipSetDevice(c->device));
-    int rc = drainStream(c);
+    int rc = startRounds(c, who);
     if (rc) return rc;
-    if (c->totalSamples != 0)
-        return fail(c, SURF_ERR_INVALID, std::string(who) + ": the accumulator holds samples; call surf_clear_accumulator first");
-    std::memset(sum, 0, sizeof *sum);
-    const uint64_t before = c->stats.samples;
-    if ((rc = surf_set_pixel_mask(c, nullptr))) return rc;
-    if ((rc = surf_render(c, p->mask.min_samples, p->first_sample_index, p->max_segments, 1))) return rc;
-    uint32_t f = p->mask.min_samples, active = 0;
-    const float4* dOut = nullptr;
-    const float4* dErr = nullptr;
-    for (;;) {
-        if ((rc = maskFromNlm(c, &p->nlm, &p->mask, who, true, &active, &dOut, &dErr))) return rc;
-        if (active == 0 || f == p->mask.max_samples) break;
-        const uint32_t nb = std::min(p->batch, p->mask.max_samples - f);
-        if (roundActive && sum->rounds < roundCap) roundActive[sum->rounds] = active;
-        if ((rc = surf_render(c, nb, p->first_sample_index + f, p->max_segments, 1))) return rc;
-        f += nb;
-        ++sum->rounds;
-    }
+    const float4 *dOut = nullptr, *dErr = nullptr;
+    if ((rc = renderRounds(c, *p, roundActive, roundCap, sum,
+                           [&](uint32_t* active) { return maskFromNlm(c, &p->nlm, &p->mask, who, true, active, &dOut, &dErr); })))
+        return rc;
     /* the last filter run and mask are of the final state: its images and its counters */
     ErrorStats st{};
     const size_t bytes = (size_t)c->npx * sizeof(float4);
@@ -127,9 +110,6 @@ int adaptiveNlm(surf_ctx* c, const surf_adaptive_nlm_params* p, void* outImg, vo
     if (outImg) SURF_CHECK(c, hipMemcpyAsync(outImg, dOut, bytes, kind, c->stream));
     if (outErr) SURF_CHECK(c, hipMemcpyAsync(outErr, dErr, bytes, kind, c->stream));
     SURF_CHECK(c, hipStreamSynchronize(c->stream));
-    sum->frames = f;
-    sum->active_last = active;
-    sum->samples = c->stats.samples - before;
     sum->above = st.above;
     sum->max_error = st.maxKey ? errorFromKey(st.maxKey) : 0.0f;
     return SURF_OK;
@@ -172,11 +152,7 @@ int surf_error_mask_image(surf_ctx* c, uint32_t w, uint32_t h, const float* out,
     SURF_CHECK(c, hipMemcpyAsync(c->emIn[2], acc, bytes, hipMemcpyHostToDevice, c->stream));
     uint32_t n = 0;
     if ((rc = runErrorMask(c, w, h, c->emIn[0], c->emIn[1], c->emIn[2], *p, false, c->adImgMask, c->adImgList, c->adImgBlk, &n))) return rc;
-    SURF_CHECK(c, hipMemcpyAsync(maskOut, c->adImgMask, npx, hipMemcpyDeviceToHost, c->stream));
-    if (listOut && n) SURF_CHECK(c, hipMemcpyAsync(listOut, c->adImgList, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-    SURF_CHECK(c, hipStreamSynchronize(c->stream));
-    *count = n;
-    return SURF_OK;
+    return copyImageMask(c, npx, n, maskOut, listOut, count);
 }
 
 /* The CPU twin: errorRel, errorBox, errorRaw and errorActive compiled for the host. */
@@ -198,19 +174,7 @@ int surf_error_mask_image_host(uint32_t w, uint32_t h, const float* out, const f
             const size_t q = (size_t)y * W + x;
             raw[q] = errorRaw(A[q].w, errorBox(x, y, R, at), R) ? 1 : 0;
         }
-    uint32_t n = 0;
-    const int d = R.dilate;
-    for (int y = 0; y < H; ++y)
-        for (int x = 0; x < W; ++x) {
-            bool any = false;
-            for (int qy = std::max(0, y - d); qy <= std::min(H - 1, y + d); ++qy)
-                for (int qx = std::max(0, x - d); qx <= std::min(W - 1, x + d); ++qx) any = any || raw[(size_t)qy * W + qx] != 0;
-            const size_t q = (size_t)y * W + x;
-            const bool on = errorActive(any, A[q].w, R);
-            maskOut[q] = on ? 1 : 0;
-            if (on) { if (listOut) listOut[n] = (uint32_t)q; ++n; }
-        }
-    *count = n;
+    *count = dilateAndList(raw.data(), W, H, R.dilate, [&](size_t q, bool any) { return errorActive(any, A[q].w, R); }, maskOut, listOut);
     return SURF_OK;
 }
 
@@ -224,8 +188,7 @@ int surf_mask_from_nlm(surf_ctx* c, const surf_nlm_params* np, const surf_error_
                                          "shard; assemble the planes and use surf_denoise_nlm_image and surf_error_mask_image");
     SURF_CHECK(c, hipSetDevice(c->device));
     uint32_t n = 0;
-    const float4* dOut = nullptr;
-    const float4* dErr = nullptr;
+    const float4 *dOut = nullptr, *dErr = nullptr;
     if (int rc = maskFromNlm(c, np, mp, "surf_mask_from_nlm", false, &n, &dOut, &dErr)) return rc;
     if (count) *count = n;
     return SURF_OK;

@@ -2,12 +2,17 @@
  * mask_host.h -- internal: what the two builders of an active-pixel mask
  * (host/adaptive.hip from the noise estimate, host/error_mask.hip from the
  * non-local-means filter's error estimate) share: the mask's three buffers on a
- * context or for an image call, and the launches that compact a byte mask into
- * its ascending list.  Include after the kernels (device/compact_kernels.h):
- * the launches are of the including translation unit's copies.
+ * context or for an image call, the launches that compact a byte mask into
+ * its ascending list, the image forms' copy-out, the CPU twins' dilation, and
+ * the adaptive loop around surf_render, which is handed the mask's builder.
+ * Include after the kernels (device/compact_kernels.h): the launches are of
+ * the including translation unit's copies.
  */
 #pragma once
 #include "host/surf_ctx.h"
+
+#include <algorithm>
+#include <cstring>
 
 #include "device/compact_kernels.h"
 
@@ -63,6 +68,79 @@ int compactMask(surf_ctx* c, uint32_t npx, const uint8_t* mask, uint32_t* list, 
     if (int rc = queueCompaction(c, npx, mask, list, blk)) return rc;
     SURF_CHECK(c, hipMemcpyAsync(count, blk + compactBlocks(npx), sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
     SURF_CHECK(c, hipStreamSynchronize(c->stream));
+    return SURF_OK;
+}
+
+/* the end of an image form: the mask of npx pixels in c->adImgMask and the n entries of its list copied out */
+int copyImageMask(surf_ctx* c, size_t npx, uint32_t n, uint8_t* maskOut, uint32_t* listOut, uint32_t* count) {
+    SURF_CHECK(c, hipMemcpyAsync(maskOut, c->adImgMask, npx, hipMemcpyDeviceToHost, c->stream));
+    if (listOut && n) SURF_CHECK(c, hipMemcpyAsync(listOut, c->adImgList, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    SURF_CHECK(c, hipStreamSynchronize(c->stream));
+    *count = n;
+    return SURF_OK;
+}
+
+/* The CPU twins' second pass over a W x H plane of raw flags: pixel q is on
+ * where active(q, any), any: a raw flag is set within d pixels of it in the
+ * frame.  Writes the byte mask and, where asked for, its list; returns the count. */
+template <class Active>
+uint32_t dilateAndList(const uint8_t* raw, int W, int H, int d, const Active& active, uint8_t* maskOut, uint32_t* listOut) {
+    uint32_t n = 0;
+    for (int y = 0; y < H; ++y)
+        for (int x = 0; x < W; ++x) {
+            bool any = false;
+            for (int qy = std::max(0, y - d); qy <= std::min(H - 1, y + d); ++qy)
+                for (int qx = std::max(0, x - d); qx <= std::min(W - 1, x + d); ++qx) any = any || raw[(size_t)qy * W + qx] != 0;
+            const size_t q = (size_t)y * W + x;
+            const bool on = active(q, any);
+            maskOut[q] = on ? 1 : 0;
+            if (on) { if (listOut) listOut[n] = (uint32_t)q; ++n; }
+        }
+    return n;
+}
+
+/* The adaptive loop ("render until nothing is active") for parameters P with
+ * batch, max_segments, first_sample_index and mask.min/max_samples and a
+ * summary S with rounds, frames, active_last and samples, in three steps: an
+ * entry point puts its own refusals between them, in its order.  What is wrong
+ * with the loop's parameters, or NULL ... */
+template <class P>
+const char* roundsParamError(const P& p) {
+    if (p.batch == 0) return "batch is 0";
+    if ((uint64_t)p.first_sample_index + p.mask.max_samples > 0xffffffffull) return "first_sample_index + max_samples exceeds 32 bits";
+    return nullptr;
+}
+/* ... the stream drained and the accumulator found empty ... */
+int startRounds(surf_ctx* c, const std::string& who) {
+    SURF_CHECK(c, hipSetDevice(c->device));
+    if (int rc = drainStream(c)) return rc;
+    if (c->totalSamples != 0) return fail(c, SURF_ERR_INVALID, who + ": the accumulator holds samples; call surf_clear_accumulator first");
+    return SURF_OK;
+}
+/* ... and the rounds: min_samples frames of every pixel, then mask(&active),
+ * which builds and sets the mask, and batches under it until nothing is active
+ * or max_samples frames are rendered; roundActive[r], r < roundCap: the count
+ * round r rendered with.  Zeroes *sum, fills the four fields. */
+template <class P, class S, class Mask>
+int renderRounds(surf_ctx* c, const P& p, uint32_t* roundActive, uint32_t roundCap, S* sum, const Mask& mask) {
+    std::memset(sum, 0, sizeof *sum);
+    const uint64_t before = c->stats.samples;
+    int rc = surf_set_pixel_mask(c, nullptr);
+    if (rc) return rc;
+    if ((rc = surf_render(c, p.mask.min_samples, p.first_sample_index, p.max_segments, 1))) return rc;
+    uint32_t f = p.mask.min_samples, active = 0;
+    for (;;) {
+        if ((rc = mask(&active))) return rc;
+        if (active == 0 || f == p.mask.max_samples) break;
+        const uint32_t nb = std::min(p.batch, p.mask.max_samples - f);
+        if (roundActive && sum->rounds < roundCap) roundActive[sum->rounds] = active;
+        if ((rc = surf_render(c, nb, p.first_sample_index + f, p.max_segments, 1))) return rc;
+        f += nb;
+        ++sum->rounds;
+    }
+    sum->frames = f;
+    sum->active_last = active;
+    sum->samples = c->stats.samples - before;
     return SURF_OK;
 }
 

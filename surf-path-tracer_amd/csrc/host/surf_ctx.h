@@ -236,18 +236,21 @@ struct surf_ctx {
     PlaneGroup<1> rbTrim{"the robust estimate's trim image"};
     PlaneGroup<1> rbIn{"surf_robust_image's planes"};
     StageTimer<1> rbTime;          /* the last k_robust launch (surf_debug_robust_time) */
-    /* the dual-buffer non-local-means filter (surf_denoise_nlm*, host/nlm.hip): nl, the two half planes (summed
-     * from the buckets or uploaded), the three prepared records (c0 + validity, c1 and V packed), then the output and its error
-     * estimate; nlStaged: the filter kernel stages its tile in LDS where the layout fits (SURF_NLM_LDS=0: every
-     * value from global memory; MEASUREMENTS "Non-local means") */
+    /* the stills filters on the sample buckets' halves (host/nlm.hip's driver).  nl: the two half planes (summed from the
+     * buckets or uploaded), the three prepared records (c0 + validity, c1 and V packed), then the output and its error
+     * estimate -- one set for both filters.  Their lifetime: a result in nl is good until the next stills filter runs on
+     * the context.  Every public entry copies its results out before it returns, and the mask built from the filter's
+     * planes (host/error_mask.hip) consumes them before anything else runs.
+     * The dual-buffer non-local-means filter (surf_denoise_nlm*, host/nlm.hip): nlStaged: the filter kernel stages its
+     * tile in LDS where the layout fits (SURF_NLM_LDS=0: every value from global memory; MEASUREMENTS "Non-local means") */
     PlaneGroup<7> nl{"the non-local-means filter's planes"};
     StageTimer<3> nlTime;          /* halves, prepare, filter of the last run (surf_debug_nlm_time) */
     bool nlStaged = true;
-    /* the first-order feature regression filter (surf_denoise_regress*, host/regress.hip): rg, the planes nl holds
-     * and behind them the three feature planes the image form uploads; rgStaged: the filter kernel stages its tile
-     * in LDS where the layout fits (SURF_REGRESS_LDS=0: every value from global memory; MEASUREMENTS "First-order
-     * regression"); rgLdsSet: the staged kernel's dynamic LDS limit has been raised */
-    PlaneGroup<10> rg{"the regression filter's planes"};
+    /* the first-order feature regression filter (surf_denoise_regress*, host/regress.hip): rgIn, the three feature planes
+     * the image form uploads; rgStaged: the filter kernel stages its tile in LDS where the layout fits (SURF_REGRESS_LDS=0:
+     * every value from global memory; MEASUREMENTS "First-order regression"); rgLdsSet: the staged kernel's dynamic LDS
+     * limit has been raised */
+    PlaneGroup<3> rgIn{"the regression filter's planes"};
     StageTimer<3> rgTime;          /* halves, prepare, filter of the last run (surf_debug_regress_time) */
     bool rgStaged = true;
     bool rgLdsSet = false;
@@ -395,9 +398,9 @@ void freeSvgf(surf_ctx* c);
 void freeAdaptive(surf_ctx* c);
 /* defined in host/robust.hip: surf_destroy's part for the robust estimate's images */
 void freeRobust(surf_ctx* c);
-/* defined in host/nlm.hip: surf_destroy's part for the non-local-means filter's images */
+/* defined in host/nlm.hip: surf_destroy's part for the stills filters' images */
 void freeNlm(surf_ctx* c);
-/* defined in host/regress.hip: surf_destroy's part for the regression filter's images */
+/* defined in host/regress.hip: surf_destroy's part for the regression filter's uploaded planes */
 void freeRegress(surf_ctx* c);
 /* defined in host/error_mask.hip: surf_destroy's part for the error mask's images */
 void freeErrorMask(surf_ctx* c);

@@ -24,7 +24,7 @@ from test_temporal_host import shifted
 
 F = np.float32
 SIZES = [(5, 3), (33, 9)]
-TWINS = ("denoise", "temporal", "svgf", "svgf_ext", "firefly", "denoise_sampled", "noise", "adaptive_mask")
+TWINS = ("denoise", "temporal", "svgf", "svgf_ext", "firefly", "denoise_sampled", "noise", "adaptive_mask", "error_mask")
 
 
 @functools.lru_cache(maxsize=None)
@@ -165,8 +165,15 @@ def twin_calls(prev, cur, shift, ctx=None):
         ok(fn("adaptive_mask")(*head, w, h, ptr(a), ptr(q), C.byref(p), ptr(mask), ptr(lst), C.byref(n)), "adaptive_mask")
         return [mask, lst[:n.value], np.array([n.value], np.uint32)]
 
+    def error_mask():
+        a = [pl(cur[k]) for k in ("acc", "squares", "acc")]               # out, err, acc
+        mask, lst = placed(np.zeros(npx, np.uint8), shift), placed(np.zeros(npx, np.uint32), shift)
+        p, n = surf_amd.error_mask_params(threshold=0.2, min_samples=2, max_samples=4), C.c_uint32()
+        ok(fn("error_mask")(*head, w, h, *[ptr(x) for x in a], C.byref(p), ptr(mask), ptr(lst), C.byref(n)), "error_mask")
+        return [mask, lst[:n.value], np.array([n.value], np.uint32)]
+
     return {"denoise": denoise, "temporal": temporal, "svgf": lambda: svgf(False), "svgf_ext": lambda: svgf(True), "firefly": firefly,
-            "denoise_sampled": denoise_sampled, "noise": noise, "adaptive_mask": adaptive_mask}
+            "denoise_sampled": denoise_sampled, "noise": noise, "adaptive_mask": adaptive_mask, "error_mask": error_mask}
 
 
 def words(a):

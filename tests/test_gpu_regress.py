@@ -22,10 +22,11 @@ import surf_amd
 from surf_amd import ShardSpec
 from test_denoise_host import assert_images_equal
 from test_gpu_nlm import COUNTERS, FRAMES, device_buffer_reader, renderer
-from test_nlm_host import RADII
+from test_nlm_adaptive_host import NLM_SMALL, np_error_mask
+from test_nlm_host import RADII, expected as nlm_expected, frame as nlm_frame, np_nlm
 from test_regress_host import FRAMES as NAMES, OTHER_SCALARS, assert_regress_equal, case, expected, np_regress
-from test_robust_host import np_halves
-from test_sampled_host import H, W
+from test_robust_host import np_buckets, np_halves
+from test_sampled_host import H, W, oracle_samples
 
 pytestmark = pytest.mark.gpu
 SURF_ERR_INVALID = -1
@@ -235,6 +236,42 @@ def test_call_changes_nothing_else(product_scene):
     finally:
         for r in rs:
             r.close()
+
+
+def test_the_two_filters_share_one_set_of_planes(product_scene):
+    """The regression runs in the non-local-means filter's seven planes.  On one context: the non-local-means image
+    form on a 33 x 9 frame; the regression's image form on a 100 x 37 one, so that the shared planes grow under the
+    first result; the first call again; the mask from the filter's run on the context's own buckets; the regression's
+    context form.  Every result against its numpy restatement, and the non-local-means times untouched by a
+    regression call."""
+    rf = (5, 2)
+    sp = dict(search_radius=rf[0], patch_radius=rf[1])
+    small = dict(search_radius=3, patch_radius=1)
+    samples, _, _ = oracle_samples(16)
+    M = 4
+    A, B = np_buckets(samples[:8], M)
+    r = renderer(product_scene, M)
+    try:
+        r.render(8, 0)
+        assert_regress_equal(r.denoise_nlm_image(*nlm_frame("b5"), **sp), nlm_expected("b5", rf)[:2], "1. non-local means, 33 x 9")
+        ms = r.debug_nlm_time()
+        assert ms[1] > 0.0 and ms[2] > 0.0, ms
+        assert_regress_equal(r.denoise_regress_image(*case("a"), **sp), expected("a", rf), "2. regression, 100 x 37")
+        assert r.debug_nlm_time() == ms, "a regression call changed surf_debug_nlm_time"
+        assert_regress_equal(r.denoise_nlm_image(*nlm_frame("b5"), **sp), nlm_expected("b5", rf)[:2], "3. non-local means again")
+        out, err, _ = np_nlm(*np_halves(B), **NLM_SMALL)
+        p = dict(threshold=0.12, min_samples=4, max_samples=36, smooth=1, dilate=1)
+        want_mask, want_list, _, _ = np_error_mask(out, err, A, **p)
+        assert 0 < len(want_list) < W * H
+        assert r.mask_from_nlm(nlm=NLM_SMALL, **p) == len(want_list), "4. the mask's count"
+        m, n = r.pixel_mask()
+        assert np.array_equal(m, want_mask) and n == len(want_list), "4. the mask"
+        h0, h1 = np_halves(r.sample_buckets())
+        assert_images_equal(h0, np_halves(B)[0], "the context's half 0")
+        assert_images_equal(h1, np_halves(B)[1], "the context's half 1")
+        assert_regress_equal(r.denoise_regress(**small), np_regress(h0, h1, r.aov(), **small), "5. regression on the context")
+    finally:
+        r.close()
 
 
 def test_lifecycle(product_scene):
