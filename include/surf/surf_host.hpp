@@ -439,6 +439,9 @@ public:
     surf_adaptive_nlm_summary renderAdaptiveNlm(std::vector<F32>* image = nullptr);
     /* RGBA8 with each pixel divided by its own sample count (surf_finalize_rgba8_weighted) */
     std::vector<U32> finalizeWeighted(bool display = false);
+    /* the display stage on the accumulator (surf_display): metered or manual exposure, optional bloom, tone curve,
+     * transfer function, ordered dither; width*height RGBA8 words, *meter (may be NULL) the meter's result */
+    std::vector<U32> display(const surf_display_params& params, surf_display_meter_result* meter = nullptr);
     /* clearAccumulator() for that loop: the next render() goes on with the sample indices after
      * those already rendered instead of repeating the cleared frame's sample stream (a plain
      * clearAccumulator() starts again from sample 0, as the reference does) */

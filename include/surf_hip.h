@@ -1529,6 +1529,127 @@ int surf_finalize_rgba8_weighted(surf_ctx* ctx, int display, uint32_t* out_rgba8
 /* The CPU twin on n records of a host plane; needs no device.  Bit-identical. */
 int surf_pack_rgba8_weighted(const float* acc, uint32_t n, int display, uint32_t* out_rgba8);
 
+/* ---- the display stage: metered exposure, bloom, tone curve, transfer, dither (no reference counterpart) ----
+ * The road from any float RGBA image of this library -- the accumulator, the
+ * robust estimate, a filter's output -- to RGBA8 words for a viewer, beside
+ * surf_finalize_rgba8 / surf_display_rgba8, which reproduce the reference's
+ * clamp (and sqrt of the 8-bit value) and stay as they are.  Opt-in and a
+ * pure post-process: without a call to these entry points no kernel, launch,
+ * allocation or result bit differs; the calls leave the accumulator, the
+ * buckets, the squares, surf_stats and the counters untouched.
+ *
+ * The arithmetic (part of the interface: f32, uncontracted, / and sqrtf are
+ * IEEE, expf is glibc's and evaluated on the host only;
+ * surf_display_image_host reproduces every bit).  Input: a frame of W x H
+ * records (rgb sums, w = the pixel's weight: 1 for a filter's output, the
+ * sample count for an accumulator).
+ *
+ * 1. Colour.  n = .w;  c_k = n > 0 ? rgb_k / n : 0;  then c_k = c_k > 0 ? c_k : 0
+ *    (a NaN or a negative value becomes 0, +inf stays).
+ * 2. Luminance.  L = (0.2126f*c_x + 0.7152f*c_y) + 0.0722f*c_z.
+ * 3. Meter (always runs; in manual mode it only fills *meter).  b = bits(L) >> 20.
+ *    b < 888 (L < 2^-16): the pixel counts in `black` and nowhere else.  Else
+ *    bin = b - 888, capped at 255: 8 bins per octave over 2^-16 .. 2^16, +inf in
+ *    bin 255; hist[bin] and `counted` count it.  median_bin m = the smallest bin
+ *    with 2 * (hist[0] + .. + hist[m]) >= counted, in 64-bit integers (0 when
+ *    counted = 0).  Lm = the float whose bits are ((m + 888) << 20) | 0x80000.
+ *    Auto: scale = key / Lm, then scale = scale < min_scale ? min_scale : scale,
+ *    then scale = scale > max_scale ? max_scale : scale; counted = 0: scale = 1.
+ *    Manual: scale = exposure.
+ * 4. Exposed colour.  e_k = c_k * scale.
+ * 5. Bloom, bloom_radius R > 0.  Host constants: sigma = 0.5f*R;
+ *    g_i = expf(-(float)(i*i) / (2.0f*sigma*sigma)), i = 0..R;  S = g_0, then
+ *    S = S + (g_i + g_i) for i = 1..R;  wn_i = g_i / S.
+ *    B_k = (e_k - bloom_threshold) > 0 ? e_k - bloom_threshold : 0.
+ *    Hh(x, y)_k = the sum from 0.0f over i = -R..R ascending of
+ *    wn_|i| * B(clamp(x + i), y)_k;  Vv(x, y)_k = the same sum over j of
+ *    wn_|j| * Hh(x, clamp(y + j))_k (clamp: to the frame).
+ *    x_k = e_k + bloom_strength * Vv_k.  R = 0: x_k = e_k, and no blur plane is
+ *    allocated or launched.
+ * 6. Curve.  0: t = x.  1 (extended Reinhard): t = (x*(1.0f + x/(white*white))) / (1.0f + x).
+ *    2 (the ACES fit of Narkowicz): t = (x*(2.51f*x + 0.03f)) / (x*(2.43f*x + 0.59f) + 0.14f).
+ *    v = t < 1.0f ? t : 1.0f (a NaN, from +inf, becomes 1);  v = v > 0 ? v : 0.
+ * 7. Transfer.  0: u = v.  1: u = sqrtf(v).  2 (sRGB): i = (uint)(sqrtf(v)*4095.0f + 0.5f),
+ *    u = T[i];  T[i] is computed in double and rounded to f32:  l = (i/4095)^2,
+ *    T[i] = l <= 0.0031308 ? 12.92*l : 1.055*pow(l, 1/2.4) - 0.055
+ *    (surf_display_srgb_table).  Indexed by the square root, the table's error
+ *    stays below a tenth of an 8-bit code in the dark, steep part.
+ * 8. Quantise.  d = dither ? ((float)B8[y & 7][x & 7] + 0.5f) / 64.0f : 0.5f;
+ *    q = (uint)(u*255.0f + d), capped at 255;  alpha = 255;  the word is
+ *    r | g << 8 | b << 16 | a << 24, as surf_finalize_rgba8 packs it.
+ *    B8, the standard 8 x 8 Bayer matrix (surf_display_bayer8, row-major):
+ *       0 32  8 40  2 34 10 42
+ *      48 16 56 24 50 18 58 26
+ *      12 44  4 36 14 46  6 38
+ *      60 28 52 20 62 30 54 22
+ *       3 35 11 43  1 33  9 41
+ *      51 19 59 27 49 17 57 25
+ *      15 47  7 39 13 45  5 37
+ *      63 31 55 23 61 29 53 21
+ *
+ * Launches: the meter (a 256-bin histogram per block in LDS with integer LDS
+ * atomics, then one integer global atomic per non-empty bin per block, into
+ * one of 16 copies of the record so that the blocks do not all wait on the
+ * same addresses: the result does not depend on the order of arrival), the
+ * scale (one wave sums the copies, scans the bins and writes the meter record
+ * to device memory, where the following kernels read scale: no host
+ * synchronisation between meter and pack; the sRGB table is in constant
+ * memory), and
+ * either the fused pack (rules 1, 4, 6-8) or, with bloom, the horizontal pass
+ * and the vertical pass fused with the pack, on 32 x 8 pixel tiles staged in
+ * LDS with their halo of R.  Exposure adaptation over time is left to the
+ * caller: meter->scale is returned for it.  MEASUREMENTS "Display stage" has
+ * the costs. */
+typedef struct {
+    uint32_t exposure_mode;       /* 0 manual, 1 auto */
+    float exposure;               /* the manual linear scale; finite and > 0 */
+    float key, min_scale, max_scale;   /* finite, > 0, min_scale <= max_scale */
+    uint32_t bloom_radius;        /* 0 off, else 1..16 */
+    float bloom_threshold;        /* finite and >= 0 */
+    float bloom_strength;         /* finite and >= 0 */
+    uint32_t curve;               /* 0 none, 1 extended Reinhard, 2 ACES fit */
+    float white;                  /* finite and > 0 (curve 1's white point) */
+    uint32_t transfer;            /* 0 linear, 1 sqrt, 2 sRGB */
+    uint32_t dither;              /* 0 or 1 */
+} surf_display_params;
+/* Conventions, not measurements: exposure auto with the photographic key 0.18,
+ * min_scale 1/64, max_scale 64, exposure 1; bloom off (radius 0), threshold 1,
+ * strength 0.1; curve ACES, white 4; transfer sRGB; dither on. */
+int surf_display_default_params(surf_display_params* params);
+typedef struct {
+    uint32_t hist[256];
+    uint32_t counted, black, median_bin;
+    float scale;
+} surf_display_meter_result;
+/* The context form, on the context's accumulator (each pixel divided by its
+ * own .w); out_rgba8 height*width words, meter may be NULL.  Drains the
+ * stream.  SURF_ERR_INVALID for a NULL context, params or out_rgba8,
+ * parameters outside the ranges above, an accumulator nothing was rendered
+ * into since the last clear, and on a row shard -- the meter and the blur read
+ * the whole frame: assemble the shards' accumulators and call
+ * surf_display_image; SURF_ERR_OOM when a scratch image cannot be allocated. */
+int surf_display(surf_ctx* ctx, const surf_display_params* params, uint32_t* out_rgba8, surf_display_meter_result* meter);
+/* A host plane of any w x h frame (w*h in 1..2^27, w*h*4 floats): a filter's
+ * output (w = 1), an accumulator or a robust accumulator (w = the count).
+ * Needs no scene on the context. */
+int surf_display_image(surf_ctx* ctx, uint32_t w, uint32_t h, const float* rgba, const surf_display_params* params,
+                       uint32_t* out_rgba8, surf_display_meter_result* meter);
+/* ... the same from a plane on the context's device (w*h*16 bytes, e.g. what a
+ * filter's _copy_device form filled) to words on the device (w*h*4 bytes): no
+ * round trip through the host.  meter is a host pointer or NULL. */
+int surf_display_image_device(surf_ctx* ctx, uint32_t w, uint32_t h, const void* src_rgba_device, const surf_display_params* params,
+                              void* dst_rgba8_device, surf_display_meter_result* meter);
+/* The CPU twin; needs no device.  Bit-identical to surf_display_image. */
+int surf_display_image_host(uint32_t w, uint32_t h, const float* rgba, const surf_display_params* params, uint32_t* out_rgba8,
+                            surf_display_meter_result* meter);
+/* The two tables of the interface: T of rule 7 and B8 of rule 8 (row-major). */
+int surf_display_srgb_table(float out[4096]);
+int surf_display_bayer8(uint8_t out[64]);
+/* Diagnostics: device times (HIP events) of the last run's stages into
+ * kernel_ms[0..count): meter, scale, blur (the horizontal pass; 0 without
+ * bloom), pack (with bloom: the vertical pass fused with it). */
+int surf_debug_display_time(surf_ctx* ctx, float* kernel_ms, uint32_t count);
+
 /* ---- traversal entry points (kernel-level parity tests) ----
  * n world-space rays, o/d 3 floats each.  closest: depth starts at 1e30;
  * writes t,u,v (floats) and inst,prim (u32, ~0 on miss).  any: tmax per ray,

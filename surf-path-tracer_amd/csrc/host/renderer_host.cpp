@@ -365,6 +365,12 @@ std::vector<U32> WaveFrontRenderer::finalizeWeighted(bool display) {
     return out;
 }
 
+std::vector<U32> WaveFrontRenderer::display(const surf_display_params& params, surf_display_meter_result* meter) {
+    std::vector<U32> out((size_t)m_resolution.width * m_resolution.height);
+    check(surf_display(m_ctx, &params, out.data(), meter), m_ctx, "surf_display");
+    return out;
+}
+
 void WaveFrontRenderer::resetTemporal() { check(surf_temporal_reset(m_ctx), m_ctx, "surf_temporal_reset"); }
 
 std::vector<U32> WaveFrontRenderer::displayRGBA8() {

@@ -259,6 +259,15 @@ struct surf_ctx {
     PlaneGroup<1> em{"the error mask's counters"};
     PlaneGroup<3> emIn{"surf_error_mask_image's planes"};
     StageTimer<2> emTime;          /* mask kernel, compaction of the last run (surf_debug_error_mask_time) */
+    /* the display stage (surf_display*, host/display.hip): dpRec, the meter record's copies; dpTable: this context has
+     * queued the copy of the sRGB table to its device's constant memory; dpIn, the plane surf_display_image uploads; dpHh, the bloom's horizontal pass
+     * (allocated only with bloom on); dpOut, the RGBA8 words (4 B per pixel) of the forms that copy to the host */
+    PlaneGroup<1> dpRec{"the display stage's meter record"};
+    bool dpTable = false;
+    PlaneGroup<1> dpIn{"surf_display_image's plane"};
+    PlaneGroup<1> dpHh{"the bloom's plane"};
+    PlaneGroup<1> dpOut{"the display stage's words"};
+    StageTimer<4> dpTime;          /* meter, scale, blur, pack of the last run (surf_debug_display_time) */
     /* the active-pixel mask (surf_set_pixel_mask, surf_mask_from_noise; host/adaptive.hip):
      * pmOn: a mask that leaves some pixel out is set (an all-ones mask is "no
      * mask"); then pmMask holds its npx bytes, pmList the pmActive ascending
@@ -404,6 +413,8 @@ void freeNlm(surf_ctx* c);
 void freeRegress(surf_ctx* c);
 /* defined in host/error_mask.hip: surf_destroy's part for the error mask's images */
 void freeErrorMask(surf_ctx* c);
+/* defined in host/display.hip: surf_destroy's part for the display stage's images */
+void freeDisplay(surf_ctx* c);
 
 #define SURF_CHECK(ctx, call)                                                             \
     do {                                                                                  \

@@ -1203,6 +1203,7 @@ void surf_destroy(surf_ctx* c) {
     freeNlm(c);
     freeRegress(c);
     freeErrorMask(c);
+    freeDisplay(c);
     if (c->dRows) (void)hipFree(c->dRows);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);

@@ -30,6 +30,8 @@ Mirrors the reference interface for the hot path:
     .denoise_nlm()             dual-buffer non-local means on the buckets' two half images: no feature plane, an error estimate beside it
     .denoise_regress()         first-order regression of the two half images on the feature planes with those patch weights
     .render_adaptive_nlm()     the adaptive loop driven by that error estimate (.mask_from_nlm() builds its mask); returns the filtered image
+    .display()                 the display stage on the accumulator: metered exposure, bloom, tone curve, sRGB, dither -> RGBA8;
+                               .display_image(img) the same on any float RGBA image, display_image_host(img) its CPU twin
 """
 from __future__ import annotations
 
@@ -214,6 +216,24 @@ class AdaptiveNlmSummary(C.Structure):
                 ("samples", C.c_uint64), ("above", C.c_uint64), ("max_error", C.c_float), ("_pad2", C.c_uint32)]
 
 
+class DisplayParams(C.Structure):
+    """surf_display_params: exposure (mode, manual scale, the meter's key and limits), bloom, tone curve, transfer, dither."""
+    _fields_ = [("exposure_mode", C.c_uint32), ("exposure", C.c_float), ("key", C.c_float), ("min_scale", C.c_float),
+                ("max_scale", C.c_float), ("bloom_radius", C.c_uint32), ("bloom_threshold", C.c_float), ("bloom_strength", C.c_float),
+                ("curve", C.c_uint32), ("white", C.c_float), ("transfer", C.c_uint32), ("dither", C.c_uint32)]
+
+
+class DisplayMeterResult(C.Structure):
+    """surf_display_meter_result: the luminance histogram (8 bins per octave from 2^-16), the pixels in it, those below it,
+    the median's bin and the exposure scale applied."""
+    _fields_ = [("hist", C.c_uint32 * 256), ("counted", C.c_uint32), ("black", C.c_uint32), ("median_bin", C.c_uint32),
+                ("scale", C.c_float)]
+
+    def as_dict(self) -> dict:
+        return {"hist": np.array(self.hist, np.uint32), "counted": int(self.counted), "black": int(self.black),
+                "median_bin": int(self.median_bin), "scale": np.float32(self.scale)}
+
+
 _lib = None
 
 # Byte sizes of the reference records (include/surf_hip.h static_asserts).
@@ -349,6 +369,13 @@ def load() -> C.CDLL:
         "surf_adaptive_nlm_default_params": ([C.POINTER(AdaptiveNlmParams)], I32),
         "surf_render_adaptive_nlm": ([P, C.POINTER(AdaptiveNlmParams), P, P, P, U32, C.POINTER(AdaptiveNlmSummary)], I32),
         "surf_render_adaptive_nlm_copy_device": ([P, C.POINTER(AdaptiveNlmParams), P, P, P, U32, C.POINTER(AdaptiveNlmSummary)], I32),
+        "surf_display_default_params": ([C.POINTER(DisplayParams)], I32),
+        "surf_display": ([P, C.POINTER(DisplayParams), P, C.POINTER(DisplayMeterResult)], I32),
+        "surf_display_image": ([P, U32, U32, P, C.POINTER(DisplayParams), P, C.POINTER(DisplayMeterResult)], I32),
+        "surf_display_image_device": ([P, U32, U32, P, C.POINTER(DisplayParams), P, C.POINTER(DisplayMeterResult)], I32),
+        "surf_display_image_host": ([U32, U32, P, C.POINTER(DisplayParams), P, C.POINTER(DisplayMeterResult)], I32),
+        "surf_display_srgb_table": ([P], I32), "surf_display_bayer8": ([P], I32),
+        "surf_debug_display_time": ([P, C.POINTER(F), U32], I32),
         "surf_mesh_data": ([P, C.POINTER(P), C.POINTER(P), C.POINTER(U32)], I32),
         "surf_mesh_destroy": ([P], None),
         "surf_ref_sinf": ([F], F), "surf_ref_cosf": ([F], F), "surf_ref_expf": ([F], F),
@@ -863,6 +890,56 @@ def denoise_nlm_image_host(half0, half1, **params):
     p = nlm_params(**params)
     _check(load().surf_denoise_nlm_image_host(w, h, _ptr(a), _ptr(b), C.byref(p), _ptr(out), _ptr(err)), "surf_denoise_nlm_image_host")
     return out, err
+
+
+def display_default_params() -> DisplayParams:
+    """surf_display_default_params -- conventions, not measurements: exposure auto (key 0.18, scale within 1/64..64, manual
+    exposure 1), bloom off (radius 0, threshold 1, strength 0.1), the ACES curve (white 4), sRGB, dither on."""
+    p = DisplayParams()
+    _check(load().surf_display_default_params(C.byref(p)), "surf_display_default_params")
+    return p
+
+
+def display_params(**params) -> DisplayParams:
+    """display_default_params() with the given fields replaced."""
+    p = display_default_params()
+    kinds = {name: ctype for name, ctype in DisplayParams._fields_}
+    for name, v in params.items():
+        if name not in kinds:
+            raise TypeError(f"surf_display_params has no field {name!r}")
+        setattr(p, name, int(v) if kinds[name] is C.c_uint32 else float(v))
+    return p
+
+
+def _display_plane(img):
+    """(w, h, img, words): an (H, W, 4) float RGBA image as contiguous float32 and the (H, W) uint32 image it becomes."""
+    a = np.ascontiguousarray(img, dtype=np.float32)
+    if a.ndim != 3 or a.shape[-1] != 4:
+        raise ValueError(f"image {a.shape} is not (H, W, 4)")
+    return a.shape[1], a.shape[0], a, np.zeros(a.shape[:2], np.uint32)
+
+
+def display_image_host(img, **params):
+    """The CPU twin of Renderer.display_image (surf_display_image_host): (RGBA8 words (H, W) uint32, the meter's result
+    as a dict); bit-identical, no device."""
+    w, h, a, out = _display_plane(img)
+    p, m = display_params(**params), DisplayMeterResult()
+    _check(load().surf_display_image_host(w, h, _ptr(a), C.byref(p), _ptr(out), C.byref(m)), "surf_display_image_host")
+    return out, m.as_dict()
+
+
+def display_srgb_table() -> np.ndarray:
+    """The display stage's sRGB table, indexed by the square root (surf_display_srgb_table): 4096 float32."""
+    t = np.zeros(4096, np.float32)
+    _check(load().surf_display_srgb_table(_ptr(t)), "surf_display_srgb_table")
+    return t
+
+
+def display_bayer8() -> np.ndarray:
+    """The display stage's 8 x 8 Bayer matrix (surf_display_bayer8): (8, 8) uint8, [y, x]."""
+    b = np.zeros((8, 8), np.uint8)
+    _check(load().surf_display_bayer8(_ptr(b)), "surf_display_bayer8")
+    return b
 
 
 def regress_params(**params) -> RegressParams:
@@ -1663,6 +1740,38 @@ class Renderer:
         """Device milliseconds of the last error mask's launches (surf_debug_error_mask_time): mask kernel, compaction."""
         ms = (C.c_float * 2)()
         _check(load().surf_debug_error_mask_time(self._h, ms, 2), "surf_debug_error_mask_time", self._h)
+        return [float(v) for v in ms]
+
+    def display(self, **params):
+        """(RGBA8 words (H, W) uint32, the meter's result) of the display stage on this context's accumulator, each pixel
+        divided by its own sample count (surf_display; display_params' names): metered or manual exposure, optional bloom,
+        tone curve, transfer function, ordered dither.  Raises SURF_ERR_INVALID on a row shard (see display_image) and on an
+        accumulator nothing was rendered into."""
+        p, m = display_params(**params), DisplayMeterResult()
+        out = np.zeros((self.height, self.width), dtype=np.uint32)
+        _check(load().surf_display(self._h, C.byref(p), _ptr(out), C.byref(m)), "surf_display", self._h)
+        return out, m.as_dict()
+
+    def display_image(self, img, **params):
+        """The same on any host (H, W, 4) float RGBA image (surf_display_image): a filter's output (w = 1), an accumulator
+        or a robust accumulator (w = the count), e.g. one assembled from row shards."""
+        w, h, a, out = _display_plane(img)
+        p, m = display_params(**params), DisplayMeterResult()
+        _check(load().surf_display_image(self._h, w, h, _ptr(a), C.byref(p), _ptr(out), C.byref(m)), "surf_display_image", self._h)
+        return out, m.as_dict()
+
+    def display_image_device(self, src_device_ptr: int, width: int, height: int, dst_device_ptr: int, **params) -> dict:
+        """The same from a plane on this context's device (width*height*16 bytes, e.g. what copy_denoise_nlm_to filled) to
+        width*height words there (surf_display_image_device); returns the meter's result."""
+        p, m = display_params(**params), DisplayMeterResult()
+        _check(load().surf_display_image_device(self._h, width, height, C.c_void_p(src_device_ptr), C.byref(p),
+                                                C.c_void_p(dst_device_ptr), C.byref(m)), "surf_display_image_device", self._h)
+        return m.as_dict()
+
+    def debug_display_time(self) -> list:
+        """Device milliseconds of the last display run's stages (surf_debug_display_time): meter, scale, blur, pack."""
+        ms = (C.c_float * 4)()
+        _check(load().surf_debug_display_time(self._h, ms, 4), "surf_debug_display_time", self._h)
         return [float(v) for v in ms]
 
     def finalize_weighted(self, display: bool = False) -> np.ndarray:
