@@ -252,6 +252,15 @@ int surf_debug_issue_order(surf_ctx* ctx, uint32_t* heavy_pixels, uint32_t* perm
  * both 0 when k_connect walked every BLAS from global memory.  No reference
  * counterpart. */
 int surf_debug_connect_staging(surf_ctx* ctx, uint32_t* records, uint32_t* triangles);
+/* Diagnostics: the kernel variants the uploaded scene selects (1 or 0 each):
+ * trace and shading tables in LDS (at most 64 instances, materials, lights),
+ * k_extend's 16-bit traversal stack (fewer than 65,536 BLAS and TLAS nodes, no
+ * two-level lane walk, SURF_EXT_STACK16 not 0), the lane walk over the
+ * two-level records (SURF_LANEW, or a BVH past 256 MB), and whether the
+ * one-ray-per-wave engines may run (stack of at most 64 entries).  No
+ * reference counterpart. */
+int surf_debug_kernel_selection(surf_ctx* ctx, uint32_t* lds_tables, uint32_t* stack16, uint32_t* lane_two_level,
+                                uint32_t* wave_eligible);
 /* When enabled, per-kernel device times are measured with HIP events on the
  * render stream (slower: disables the graph replay). */
 int surf_set_profiling(surf_ctx* ctx, int enabled);

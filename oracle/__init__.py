@@ -43,6 +43,7 @@ def load():
     P, U32, I32, F, D = C.c_void_p, C.c_uint32, C.c_int, C.c_float, C.c_double
     sig = {
         "orc_scene_create": ([C.c_char_p, I32], P), "orc_scene_destroy": ([P], None),
+        "orc_scene_create_custom": ([U32, P, P, P, P, U32, P, U32, P, P, P], P),
         "orc_scene_mesh_tris": ([P, P, I32], I32),
         "orc_scene_instance_count": ([P], U32), "orc_scene_light_count": ([P], U32),
         "orc_scene_set_camera": ([P, U32, U32], None), "orc_camera_ubo": ([P, P], None),
@@ -100,6 +101,55 @@ class OracleScene:
         self._h = lib.orc_scene_create(assets_dir.encode(), variant)
         if not self._h:
             raise RuntimeError(f"oracle could not load the scene from {assets_dir}")
+
+    @classmethod
+    def custom(cls, meshes, materials, instances, background=None, view=None) -> "OracleScene":
+        """A caller's scene (orc_scene_create_custom).  meshes: per mesh (verts,
+        normals), two (n, 3, 3) float32 arrays: the stored v0, v1, v2 of each
+        triangle (a Triangle record's order) and n0, n1, n2; UVs are zero unless
+        every mesh brings a third (n, 6) array.
+        materials: dicts of materials()' seven fields (missing ones take
+        Material's defaults, material.h:6-19).  instances: (mesh index, material
+        index, M) with M a 4 x 4 array in mathematical layout (M[row][column]; it
+        is stored column major as glm does).  background / view: the keyword
+        arguments of set_background / set_view.  ValueError when the oracle
+        refuses the scene (an index out of range, a non-finite matrix, an empty
+        mesh, a tree deeper than 127)."""
+        lib = load()
+        cat = lambda k, w: (np.concatenate([np.asarray(m[k], np.float32).reshape(-1, w) for m in meshes]) if len(meshes)
+                            else np.zeros((0, w), np.float32))
+        tris = np.array([len(np.asarray(m[0]).reshape(-1, 3, 3)) for m in meshes], np.uint32)
+        verts, norms = cat(0, 9), cat(1, 9)
+        uvs = np.ascontiguousarray(cat(2, 6)) if len(meshes) and all(len(m) > 2 for m in meshes) else None
+        if uvs is not None and len(uvs) != len(verts):
+            raise ValueError("a mesh's vertex and UV arrays differ in length")
+        if verts.shape != norms.shape:
+            raise ValueError("a mesh's vertex and normal arrays differ in shape")
+        verts, norms = np.ascontiguousarray(verts), np.ascontiguousarray(norms)
+        mats = np.zeros((len(materials), 16), np.float32)
+        for r, m in zip(mats, materials):
+            unknown = [k for k in m if k not in ("emit", "refl", "refr", "ior", "emit_color", "albedo", "absorption")]
+            if unknown:
+                raise TypeError(f"unknown material field {unknown[0]!r}")
+            r[0], r[1], r[2], r[3] = m.get("emit", 0.0), m.get("refl", 0.0), m.get("refr", 0.0), m.get("ior", 1.0)
+            r[4:7], r[8:11], r[12:15] = (_f3(m.get(k, (0.0, 0.0, 0.0))) for k in ("emit_color", "albedo", "absorption"))
+        im = np.array([i[0] for i in instances], np.int64)
+        ia = np.array([i[1] for i in instances], np.int64)
+        if len(instances) and (im.min() < 0 or ia.min() < 0 or im.max() > 0xFFFFFFFF or ia.max() > 0xFFFFFFFF):
+            raise ValueError("instance index out of range")
+        im, ia = im.astype(np.uint32), ia.astype(np.uint32)
+        # M[row][column] -> column-major storage: element 4 * column + row
+        mm = np.ascontiguousarray(np.array([np.asarray(i[2], np.float32).reshape(4, 4).T for i in instances], np.float32).reshape(-1, 16))
+        h = lib.orc_scene_create_custom(len(tris), _p(tris), _p(verts), _p(norms), None if uvs is None else _p(uvs), len(mats), _p(mats), len(im), _p(im), _p(ia), _p(mm))
+        if not h:
+            raise ValueError("oracle refused the custom scene")
+        self = cls.__new__(cls)
+        self._h = h
+        if background is not None:
+            self.set_background(**background)
+        if view is not None:
+            self.set_view(**view)
+        return self
 
     def mesh_tris(self):
         out = np.zeros(8, np.uint32)

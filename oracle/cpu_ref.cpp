@@ -466,10 +466,16 @@ thread_local uint32_t* tVisitTris = nullptr;
 thread_local uint32_t* tVisitBaseN = nullptr;   /* per-instance arrays of the current ray */
 thread_local uint32_t* tVisitBaseT = nullptr;
 
+/* Traversal stack entries of blasTrace / tlasTrace.  The reference's stacks
+ * hold 64 (bvh.cpp:133, :658) and it checks neither; a walk pushes at most one
+ * entry per level, so 128 entries serve every tree of depth <= 127, the
+ * deepest orc_scene_create_custom accepts. */
+const uint32_t kTraceStack = 128;
+
 template <bool ANY>
 bool blasTrace(const Blas& B, V3 o, V3 d, float& depth, Hit& hit, uint32_t& stackMax) {
     const Bvh& b = B.bvh;
-    uint32_t stack[64]; uint32_t sp = 0;
+    uint32_t stack[kTraceStack]; uint32_t sp = 0;
     uint32_t ni = 0;
     bool any = false;
     for (;;) {
@@ -495,7 +501,7 @@ bool blasTrace(const Blas& B, V3 o, V3 d, float& depth, Hit& hit, uint32_t& stac
         if (dn == kFarAway) { if (sp == 0) break; ni = stack[--sp]; }
         else {
             ni = cn;
-            if (df != kFarAway) { if (sp >= 64) { fprintf(stderr, "oracle: BLAS stack overflow\n"); abort(); } stack[sp++] = cf; if (sp > stackMax) stackMax = sp; }
+            if (df != kFarAway) { if (sp >= kTraceStack) { fprintf(stderr, "oracle: BLAS stack overflow\n"); abort(); } stack[sp++] = cf; if (sp > stackMax) stackMax = sp; }
         }
     }
     return any;
@@ -523,7 +529,7 @@ struct Scene {
 template <bool ANY>
 bool tlasTrace(const Scene& S, V3 o, V3 d, float& depth, Hit& hit, uint32_t& stackMax) {
     const Bvh& b = S.tlas;
-    uint32_t stack[64]; uint32_t sp = 0;
+    uint32_t stack[kTraceStack]; uint32_t sp = 0;
     uint32_t ni = 0;
     bool any = false;
     for (;;) {
@@ -548,7 +554,10 @@ bool tlasTrace(const Scene& S, V3 o, V3 d, float& depth, Hit& hit, uint32_t& sta
         float dn = slab(b.nodes[cn].box, o, d, depth), df = slab(b.nodes[cf].box, o, d, depth);
         if (dn > df) { float t = dn; dn = df; df = t; uint32_t c = cn; cn = cf; cf = c; }
         if (dn == kFarAway) { if (sp == 0) break; ni = stack[--sp]; }
-        else { ni = cn; if (df != kFarAway) { stack[sp++] = cf; if (sp > stackMax) stackMax = sp; } }
+        else {
+            ni = cn;
+            if (df != kFarAway) { if (sp >= kTraceStack) { fprintf(stderr, "oracle: TLAS stack overflow\n"); abort(); } stack[sp++] = cf; if (sp > stackMax) stackMax = sp; }
+        }
     }
     return any;
 }
@@ -640,6 +649,56 @@ Scene* buildIndoor(const std::string& dir, int variant) {
     InstPrims P; P.inst = &S->inst;
     buildBvh(S->tlas, P, (uint32_t)S->inst.size());
     collectLights(*S);
+    return S;
+}
+
+/* A caller's scene from raw buffers, composed of the steps buildIndoor takes
+ * per mesh and instance (main.cpp:163-171, :204-341, scene.cpp:17-33): Triangle
+ * records from the stored vertices, one BvhBLAS per mesh, Instance(blas,
+ * material, M) with inverse(M) in f32, the TLAS over the instances, the light
+ * list.  nullptr for an empty mesh / instance / material list, an index out of
+ * range, a non-finite matrix element, or a tree deeper than kTraceStack - 1. */
+Scene* buildCustom(uint32_t nMeshes, const uint32_t* meshTris, const float* verts, const float* normals, const float* uvs,
+                   uint32_t nMats, const float* mats, uint32_t nInst, const uint32_t* instMesh, const uint32_t* instMat,
+                   const float* instM) {
+    if (nMeshes == 0 || nMats == 0 || nInst == 0) return nullptr;
+    for (uint32_t i = 0; i < nMeshes; ++i) if (meshTris[i] == 0) return nullptr;
+    for (uint32_t i = 0; i < nInst; ++i) {
+        if (instMesh[i] >= nMeshes || instMat[i] >= nMats) return nullptr;
+        for (int k = 0; k < 16; ++k) if (!std::isfinite(instM[16 * (size_t)i + k])) return nullptr;
+    }
+    Scene* S = new Scene();
+    size_t at = 0;
+    for (uint32_t i = 0; i < nMeshes; ++i) {
+        Mesh* m = new Mesh();
+        for (uint32_t t = 0; t < meshTris[i]; ++t, ++at) {
+            const float* v = verts + 9 * at; const float* n = normals + 9 * at;
+            /* makeTri(a, b, c) stores a in v1 and b in v0 (mesh.cpp:13-21): v holds the stored v0, v1, v2 */
+            m->tris.push_back(makeTri(mk(v[3], v[4], v[5]), mk(v[0], v[1], v[2]), mk(v[6], v[7], v[8])));
+            TriExt x; x.n0 = mk(n[0], n[1], n[2]); x.n1 = mk(n[3], n[4], n[5]); x.n2 = mk(n[6], n[7], n[8]);
+            for (int k = 0; k < 6; ++k) x.uv[k] = uvs ? uvs[6 * at + k] : 0.0f;
+            m->ext.push_back(x);
+        }
+        S->meshes.push_back(m);
+        Blas* b = new Blas(); b->mesh = m; TriPrims P; P.m = m; buildBvh(b->bvh, P, (uint32_t)m->tris.size()); S->blases.push_back(b);
+    }
+    for (uint32_t i = 0; i < nMats; ++i) {
+        const float* r = mats + 16 * (size_t)i;        /* orc_scene_export's 64-B record */
+        Material* m = new Material();
+        m->emit = r[0]; m->refl = r[1]; m->refr = r[2]; m->ior = r[3];
+        m->emitColor = mk(r[4], r[5], r[6]); m->albedo = mk(r[8], r[9], r[10]); m->absorption = mk(r[12], r[13], r[14]);
+        S->materials.push_back(m);
+    }
+    for (uint32_t i = 0; i < nInst; ++i) {
+        M4 M; memcpy(&M.c[0][0], instM + 16 * (size_t)i, sizeof M.c);      /* column major, as glm stores it */
+        S->inst.push_back(makeInstance(S->blases[instMesh[i]], S->materials[instMat[i]], M));
+    }
+    InstPrims P; P.inst = &S->inst;
+    buildBvh(S->tlas, P, (uint32_t)S->inst.size());
+    collectLights(*S);
+    bool deep = bvhDepth(S->tlas, 0) > kTraceStack - 1;
+    for (auto* b : S->blases) deep = deep || bvhDepth(b->bvh, 0) > kTraceStack - 1;
+    if (deep) { delete S; return nullptr; }
     return S;
 }
 
@@ -861,6 +920,16 @@ extern "C" {
 
 orc_scene* orc_scene_create(const char* dir, int variant) {
     Scene* s = buildIndoor(dir ? dir : ".", variant);
+    if (!s) return nullptr;
+    orc_scene* h = new orc_scene; h->s = s;
+    setCamera(*s, 1280, 720);
+    return h;
+}
+orc_scene* orc_scene_create_custom(uint32_t nMeshes, const uint32_t* meshTris, const float* verts, const float* normals, const float* uvs,
+                                   uint32_t nMats, const float* mats, uint32_t nInst, const uint32_t* instMesh,
+                                   const uint32_t* instMat, const float* instM) {
+    if (!meshTris || !verts || !normals || !mats || !instMesh || !instMat || !instM) return nullptr;
+    Scene* s = buildCustom(nMeshes, meshTris, verts, normals, uvs, nMats, mats, nInst, instMesh, instMat, instM);
     if (!s) return nullptr;
     orc_scene* h = new orc_scene; h->s = s;
     setCamera(*s, 1280, 720);

@@ -45,6 +45,23 @@ typedef struct {
  * materials (:173-202); orc_scene_set_view, orc_scene_set_background and
  * orc_scene_set_material below edit them. */
 orc_scene* orc_scene_create(const char* assets_dir, int variant);
+/* A caller's scene: n_meshes meshes of mesh_tris[i] triangles each, their
+ * records concatenated in mesh order -- verts: the stored v0, v1, v2 of each
+ * triangle (9 floats; the centroid is computed as Triangle::Triangle does),
+ * normals: n0, n1, n2 (9 floats), uvs: 6 floats, or NULL for zero UVs (no
+ * traversal or shading step reads them); materials as orc_scene_export's
+ * 64-B records (emit, refl, refr, ior, emitColor, albedo, absorption at 16-B
+ * strides); instances as (mesh index, material index, column-major 4x4 M).
+ * Built by the steps of main.cpp:163-341 and Scene::Scene (one BvhBLAS per
+ * mesh, Instance with inverse(M) in f32, the TLAS, the light list), with
+ * main.cpp's view and background until the setters below replace them.
+ * Export order is first use by the instances, as for the bundled scenes.
+ * NULL for an empty list or mesh, an index out of range, a non-finite matrix
+ * element, or a BLAS / TLAS deeper than 127 (the traversal stacks hold 128).
+ * NaN vertices are accepted: the builder's answer for them is defined. */
+orc_scene* orc_scene_create_custom(uint32_t n_meshes, const uint32_t* mesh_tris, const float* verts, const float* normals, const float* uvs,
+                                   uint32_t n_materials, const float* materials, uint32_t n_instances,
+                                   const uint32_t* inst_mesh, const uint32_t* inst_material, const float* inst_M);
 void orc_scene_destroy(orc_scene*);
 
 /* Mesh facts: triangles per loaded mesh (susanne, cube, lens, plane[, lattice]). */

@@ -217,6 +217,8 @@ SURF_HD float slabFinite(float mnx, float mny, float mnz, float mxx, float mxy, 
 }
 
 SURF_HD bool finite3(V3 v) { return fabsf(v.x) <= 3.40282347e38f && fabsf(v.y) <= 3.40282347e38f && fabsf(v.z) <= 3.40282347e38f; }
+/* finite3 with a bound: every coordinate within r (false on NaN) */
+SURF_HD bool within3(V3 v, float r) { return fabsf(v.x) <= r && fabsf(v.y) <= r && fabsf(v.z) <= r; }
 
 /* ---- Moller-Trumbore, mesh.cpp:23-62, with e1 = v1-v0, e2 = v2-v0 precomputed
  *      (the same f32 subtraction the reference performs per test). ---- */

@@ -69,6 +69,7 @@ struct DevScene {
     const float* wnodes;      /* two-level records (48 floats per BLAS node, see surf_upload_scene), or null */
     uint32_t nWnodes;         /* nodes in wnodes (every 192-B offset fits 32 bits) */
     uint32_t laneW;           /* the one-ray-per-lane traversal walks the two-level records too (HBM-resident BVHs) */
+    float cullRadius;         /* the instance world boxes cull only rays whose origin coordinates lie within it (buildInstanceTables) */
     uint32_t bgType;
     float bgColor[3], bgA[3], bgB[3];
     float cellLo[3], cellScale[3];   /* ray-order cells: the TLAS root box split in 2 per axis (scale 0: one cell) */

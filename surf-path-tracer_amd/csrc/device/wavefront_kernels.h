@@ -560,7 +560,7 @@ __device__ __forceinline__ bool traceScene(const DevScene& S, const TraceTables&
          * divisions and traversal when all its lanes do (coherent rays: the
          * shadow queue is ordered by light and origin cell). */
         const V3 rdw = mk3(1.0f / d.x, 1.0f / d.y, 1.0f / d.z);
-        const bool cullOk = finite3(o) && finite3(rdw);
+        const bool cullOk = within3(o, S.cullRadius) && finite3(rdw);   /* far origins: the world-box slab test rounds past the pad */
         const unsigned long long runMore = S.runMember & ~S.runHead;
         for (uint32_t k = 0; k < S.tlasLeafCount; ++k) {
             if (__builtin_expect((S.runMember >> k) & 1ull, 0)) {
@@ -1565,7 +1565,7 @@ __device__ __forceinline__ bool traceWaveTlas(const DevScene& S, const TraceTabl
                                               float& hv, uint32_t& hinst, uint32_t& hprim, float* rs, float4* pro, SegStats* ss) {
     const uint32_t lane = __lane_id();
     const V3 rdw = mk3(1.0f / d.x, 1.0f / d.y, 1.0f / d.z);
-    const bool cullOk = finite3(o) && finite3(rdw);
+    const bool cullOk = within3(o, S.cullRadius) && finite3(rdw);   /* far origins: the world-box slab test rounds past the pad */
     for (uint32_t b = 0; b < S.nInst; b += 64u)
         if (b + lane < S.nInst) (void)waveProEntry(Tt.inst[b + lane], o, d, rdw, cullOk, depth, pro + 4u * (b + lane));
     __builtin_amdgcn_wave_barrier();
@@ -1633,7 +1633,7 @@ __device__ __forceinline__ bool traceWave(const DevScene& S, const TraceTables& 
      * are culled by their world box too, which otherwise cost a triangle test
      * and its loads every segment */
     const V3 rdw = mk3(1.0f / d.x, 1.0f / d.y, 1.0f / d.z);
-    const bool cullOk = finite3(o) && finite3(rdw);
+    const bool cullOk = within3(o, S.cullRadius) && finite3(rdw);   /* far origins: the world-box slab test rounds past the pad */
     unsigned long long tP = 0;
     if (SURF_WALK_PROFILE) tP = profClock();
     bool keep = false;

@@ -78,6 +78,7 @@ struct InstanceTables {
     float4 hvLo[3], hvHi[3];
     uint32_t hvInst[3] = {0, 0, 0};
     unsigned long long runHead = 0, runMember = 0;
+    float cullRadius = FLT_MAX;
 };
 
 /* The heavy-instance boxes of the ray-order keys (kernel arguments). */
@@ -94,6 +95,7 @@ void setKeys(surf_ctx* c, DevScene& S, const InstanceTables& T) {
     S.keyMode = T.nHeavy ? c->keyMode : 0u;
     S.runHead = c->leafRun ? T.runHead : 0ull;
     S.runMember = c->leafRun ? T.runMember : 0ull;
+    S.cullRadius = T.cullRadius;
     /* the emitters' BLAS, when every light instance uses one BLAS and its
      * node records fit kLdsLightBlas bytes: k_connect stages them */
     S.sbNode0 = S.sbRecN = S.sbTri0 = S.sbTriN = 0u;
@@ -188,6 +190,12 @@ int buildInstanceTables(surf_ctx* c, const surf_gpu_instance* instances, uint32_
             if (ok) {
                 R.wlo = make_float4(flo[0], flo[1], flo[2], 1.0f);
                 R.whi = make_float4(fhi[0], fhi[1], fhi[2], 0.0f);
+                /* the kernels' slab test of this box computes (b - o) * (1 / d) in f32: each term is off by
+                 * up to 2^-23 (|b| + |o|) |1 / d|, and the pad gives pad |1 / d| of slack on the same axis.
+                 * |b| <= mag <= 1e4 pad; an origin within 2^20 pad keeps the error below pad / 4.  Rays
+                 * from farther away (at 1e17 from a unit box the three axes' terms differ by rounding
+                 * alone, and the test rejects rays the reference's walk accepts) skip the cull. */
+                T.cullRadius = std::min(T.cullRadius, (float)std::min(pad * 1048576.0, (double)FLT_MAX));
             }
         }
     }

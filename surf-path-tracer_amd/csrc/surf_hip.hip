@@ -1769,6 +1769,17 @@ int surf_debug_connect_staging(surf_ctx* c, uint32_t* records, uint32_t* triangl
     return SURF_OK;
 }
 
+int surf_debug_kernel_selection(surf_ctx* c, uint32_t* lds_tables, uint32_t* stack16, uint32_t* lane_two_level, uint32_t* wave_eligible) {
+    if (!c || !lds_tables || !stack16 || !lane_two_level || !wave_eligible) return SURF_ERR_INVALID;
+    if (!c->hasScene) return fail(c, SURF_ERR_NO_SCENE, "no scene uploaded");
+    const Variant v = variantOf(c);
+    *lds_tables = v.lds ? 1u : 0u;
+    *stack16 = v.sk16 ? 1u : 0u;
+    *lane_two_level = v.laneW ? 1u : 0u;
+    *wave_eligible = waveEligible(c) ? 1u : 0u;
+    return SURF_OK;
+}
+
 int surf_debug_segment_cycles(surf_ctx* c, const float* path12, uint32_t reps, uint64_t* cycles15) {
     if (!c || !path12 || !cycles15 || reps == 0) return SURF_ERR_INVALID;
     if (!c->hasScene) return fail(c, SURF_ERR_NO_SCENE, "no scene uploaded");

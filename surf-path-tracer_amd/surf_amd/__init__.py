@@ -264,6 +264,7 @@ def load() -> C.CDLL:
         "surf_debug_capped": ([P, P, U32, C.POINTER(C.c_uint64)], I32),
         "surf_debug_issue_order": ([P, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)], I32),
         "surf_debug_connect_staging": ([P, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)], I32),
+        "surf_debug_kernel_selection": ([P] + [C.POINTER(C.c_uint32)] * 4, I32),
         "surf_debug_segment_cycles": ([P, P, U32, P], I32),
         "surf_upload_scene": ([P, C.POINTER(SceneDesc)], I32),
         "surf_set_camera": ([P, P], I32),
@@ -1193,6 +1194,13 @@ class Renderer:
         a, t = C.c_uint32(), C.c_uint32()
         _check(load().surf_debug_connect_staging(self._h, C.byref(a), C.byref(t)), "surf_debug_connect_staging", self._h)
         return int(a.value), int(t.value)
+
+    def debug_kernel_selection(self) -> dict:
+        """The kernel variants the uploaded scene selects (surf_debug_kernel_selection):
+        lds_tables, stack16, lane_two_level, wave_eligible as booleans."""
+        v = [C.c_uint32() for _ in range(4)]
+        _check(load().surf_debug_kernel_selection(self._h, *[C.byref(x) for x in v]), "surf_debug_kernel_selection", self._h)
+        return dict(zip(("lds_tables", "stack16", "lane_two_level", "wave_eligible"), (bool(x.value) for x in v)))
 
     def debug_segment_cycles(self, origin, direction, throughput, seed: int, segment: int = 1, reps: int = 64):
         """Diagnostics: mean shader-clock cycles of one drain segment's pieces on
