@@ -350,6 +350,15 @@ public:
     /* which planes denoise() and denoiseSampled() read (surf_set_filter_guides): the first-hit
      * planes (the default) or the chain's at maxLinks; every other filter keeps the first-hit planes */
     void setFilterGuides(surf_guides guides, U32 maxLinks = 8);
+    /* the sampled feature buffers (surf_read_aov_sampled, which states their arithmetic): the
+     * first-hit features of the camera rays render() traces for frames first_sample ..
+     * first_sample + samples - 1, reduced per pixel; a float plane (position, normal or albedo),
+     * and an integer plane (id, matte key or matte count) */
+    std::vector<F32> readAOVSampled(surf_aovs plane, const surf_aov_sampled_params& params);
+    std::vector<U32> readAOVSampledIds(surf_aovs plane, const surf_aov_sampled_params& params);
+    /* ... as the planes denoise(), denoiseSampled() and the regression filter read
+     * (surf_set_filter_guides_sampled); setFilterGuides switches back */
+    void setFilterGuidesSampled(const surf_aov_sampled_params& params);
     /* the rendered radiance through the edge-avoiding a-trous filter (surf_denoise; width*height*4
      * floats, w = 1): the accumulator and the feature buffers of the camera and scene of the last
      * render() call; the accumulator is left untouched.  The form without arguments takes

@@ -415,6 +415,93 @@ typedef enum { SURF_GUIDES_FIRST_HIT = 0, SURF_GUIDES_CHAIN = 1 } surf_guides;
 int surf_set_filter_guides(surf_ctx* ctx, int guides, uint32_t max_links);
 int surf_get_filter_guides(const surf_ctx* ctx, int* guides, uint32_t* max_links);
 
+/* ---- sampled feature buffers: anti-aliased AOVs and id coverage mattes ----
+ * The first-hit planes come from one ray through the pixel's corner; the
+ * radiance in the accumulator is the mean over the jitter box and the lens.
+ * These planes reduce, per pixel, the first-hit features of the very camera
+ * rays the render traces at one sample per frame, so with samples = the frames
+ * rendered and first_sample = the first frame's index they describe the
+ * samples that sit in the accumulator.  No reference counterpart.  All
+ * arithmetic f32 and uncontracted, divisions IEEE, so a host restatement
+ * reproduces every plane bit for bit.  Per shard pixel, p = x + row * width
+ * over the whole frame (u32 wrap-around, as the render seeds), for
+ * s = 0 .. samples-1 in order:
+ *   1. seed = initSeed(p + 1799u * (first_sample + s))            (u32 wrap-around)
+ *   2. jy = rndRange(seed, -0.5, 0.5), then jx likewise; with a defocus angle
+ *      the lens disk: repeat sy = rndRange(seed, -1, 1), sx likewise, until
+ *      sx*sx + sy*sy <= 1; origin = position + (sx*diskU + sy*diskV);
+ *      u = ((float)x + jx) / width, v = ((float)row + jy) / height (as
+ *      multiplications by the reciprocals); d = normalize(((first_pixel +
+ *      u*u_vector) + v*v_vector) - origin): the render's primary ray
+ *   3. closest hit of (o, d) from depth 1e30
+ *   4. the sample's features are SURF_AOV_*'s expressions term for term:
+ *      P = o + t*d and t; the shading normal N turned against d; a = albedo,
+ *      or emission_strength * emission_color on an emitter, or the background
+ *      along d for a miss; the ids
+ * Running sums, f32 from 0.0f, ONE ADD PER SAMPLE IN SAMPLE ORDER (part of the
+ * interface): nHit (u32); sum P (xyz), sum t and sum N (xyz) over the hit
+ * samples; sum a (rgb) over ALL samples -- a miss adds the background.  Six
+ * planes of rows*width 16-byte records, shard row order like surf_read_aov's:
+ *   SURF_AOVS_POSITION    float4  nHit > 0: (sum P / (float)nHit, sum t / (float)nHit)
+ *                                 else (0, 0, 0, 1e30)
+ *   SURF_AOVS_NORMAL      float4  nHit > 0: (sum N / (float)nHit, 0) -- NOT renormalised:
+ *                                 a pixel that straddles a crease gets a short normal; else 0
+ *   SURF_AOVS_ALBEDO      float4  (sum a / (float)samples, (float)nHit / (float)samples):
+ *                                 w is the hit coverage, 0 exactly when every sample missed
+ *   SURF_AOVS_ID          uint4   sample 0's hit (instance, primitive, material index, nHit);
+ *                                 sample 0 missed: (~0, ~0, ~0, nHit)
+ *   SURF_AOVS_MATTE_KEY   uint4   the four highest-ranked keys
+ *   SURF_AOVS_MATTE_COUNT uint4   their sample counts (integers; coverage is
+ *                                 count / samples, left to the caller so it stays exact)
+ * The first three keep the first-hit planes' layout and their "albedo.w != 0
+ * means valid" convention: every filter reads them without change.
+ * The matte: a sample's key is its instance index (SURF_MATTE_INSTANCE) or its
+ * material index (SURF_MATTE_MATERIAL); a miss has key ~0 and is counted like
+ * any key.  A table keeps the first 8 distinct keys in order of first
+ * appearance, with their counts; a sample whose key is new once the table is
+ * full is not counted (its share is samples - sum of counts).  Ranks are
+ * ordered by count descending, ties by first appearance ascending; the four
+ * best go out, empty ranks are key ~0 with count 0.  With samples = 1 the
+ * matte is sample 0's key with count 1.
+ * Device buffers of their own, computed by one launch on the first read and
+ * cached until what drops surf_read_aov's planes (surf_set_camera,
+ * surf_upload_scene, surf_update_instances) or a read with other params.  A
+ * read never drains or changes the sample stream.  Row shards assemble to the
+ * frame (the seed uses the whole-frame pixel index).  Frames of more than one
+ * sample (samples_per_frame > 1) chain their RNG and are not described.
+ * Status codes as surf_read_aov; SURF_ERR_INVALID for a NULL pointer, a plane
+ * outside 0..5, samples 0 or above SURF_AOVS_MAX_SAMPLES, an unknown key or
+ * reserved != 0. */
+#define SURF_AOVS_MAX_SAMPLES 64
+typedef enum {
+    SURF_AOVS_POSITION = 0, SURF_AOVS_NORMAL = 1, SURF_AOVS_ALBEDO = 2, SURF_AOVS_ID = 3,
+    SURF_AOVS_MATTE_KEY = 4, SURF_AOVS_MATTE_COUNT = 5, SURF_AOVS_COUNT = 6
+} surf_aovs;
+typedef enum { SURF_MATTE_INSTANCE = 0, SURF_MATTE_MATERIAL = 1 } surf_matte_key;
+typedef struct {
+    uint32_t samples;       /* 1..SURF_AOVS_MAX_SAMPLES */
+    uint32_t first_sample;  /* frame index of sample 0 */
+    uint32_t key;           /* SURF_MATTE_INSTANCE or SURF_MATTE_MATERIAL */
+    uint32_t reserved;      /* 0 */
+} surf_aov_sampled_params;
+int surf_aov_sampled_default_params(surf_aov_sampled_params* p);   /* 16, 0, SURF_MATTE_INSTANCE, 0 */
+int surf_read_aov_sampled(surf_ctx* ctx, const surf_aov_sampled_params* p, int plane, void* out);
+int surf_copy_aov_sampled_device(surf_ctx* ctx, const surf_aov_sampled_params* p, int plane, void* dst_device);
+/* Diagnostics: device time (HIP events) of the last sampled-planes kernel launch, 0 before the first. */
+int surf_debug_aov_sampled_time(surf_ctx* ctx, float* kernel_ms);
+/* Makes the filters that honour surf_set_filter_guides -- surf_denoise,
+ * surf_denoise_sampled, surf_denoise_regress and their _copy_device forms --
+ * read POSITION / NORMAL / ALBEDO of these planes at *p (computed if need be,
+ * as a read computes them).  surf_get_filter_guides then reports
+ * SURF_GUIDES_SAMPLED (2) and p->samples in max_links;
+ * surf_set_filter_guides(ctx, 0 or 1, ...) switches back, and mode 2 stays
+ * unknown to it.  The temporal and variance-guided filters and the two mask
+ * builders keep the first-hit planes: they need reprojectable,
+ * per-pixel-exact planes.  The default stays first hit.  SURF_ERR_INVALID as
+ * surf_read_aov_sampled for the params. */
+#define SURF_GUIDES_SAMPLED 2
+int surf_set_filter_guides_sampled(surf_ctx* ctx, const surf_aov_sampled_params* p);
+
 /* ---- denoiser: edge-avoiding a-trous wavelet filter on the feature buffers ----
  * A pure post-process of the radiance (Dammertz et al. 2010, with albedo
  * demodulation): it reads the accumulator and the first-hit feature planes

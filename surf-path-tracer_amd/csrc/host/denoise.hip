@@ -79,7 +79,7 @@ int denoiseContext(surf_ctx* c, const surf_denoise_params* p, void* dst, hipMemc
     if (c->rows.size() != c->height)
         return fail(c, SURF_ERR_INVALID, "surf_denoise needs a context that owns every row of the frame: a spatial filter reads its "
                                          "neighbours' rows; assemble the shards' accumulators and feature planes and call surf_denoise_image");
-    void* const* g = nullptr;     /* the first-hit planes, or the chain's (surf_set_filter_guides) */
+    void* const* g = nullptr;     /* the first-hit planes, the chain's or the sampled ones (surf_set_filter_guides*) */
     int rc = guidePlanes(c, &g);
     if (rc) return rc;
     if ((rc = drainStream(c))) return rc;

@@ -59,7 +59,7 @@ int regressContext(surf_ctx* c, const surf_regress_params* p, void* out, void* o
     const float4 *pos = nullptr, *nrm = nullptr, *alb = nullptr;
     StillsCall call{who, 0, 0, nullptr, nullptr, out, outErr, kind};
     call.ready = [&]() -> int {
-        void* const* g = nullptr;     /* the first-hit planes, or the chain's (surf_set_filter_guides) */
+        void* const* g = nullptr;     /* the first-hit planes, the chain's or the sampled ones (surf_set_filter_guides*) */
         if (int rc = guidePlanes(c, &g)) return rc;
         pos = static_cast<const float4*>(g[SURF_AOV_POSITION]);
         nrm = static_cast<const float4*>(g[SURF_AOV_NORMAL]);

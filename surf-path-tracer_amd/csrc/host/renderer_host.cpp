@@ -141,6 +141,28 @@ void WaveFrontRenderer::setFilterGuides(surf_guides guides, U32 maxLinks) {
     check(surf_set_filter_guides(m_ctx, guides, maxLinks), m_ctx, "surf_set_filter_guides");
 }
 
+std::vector<F32> WaveFrontRenderer::readAOVSampled(surf_aovs plane, const surf_aov_sampled_params& params) {
+    if (plane != SURF_AOVS_POSITION && plane != SURF_AOVS_NORMAL && plane != SURF_AOVS_ALBEDO)
+        throw std::runtime_error("readAOVSampled: not a float plane (the id and matte planes are readAOVSampledIds)");
+    pushSceneAndCamera();
+    std::vector<F32> out((size_t)m_resolution.width * m_resolution.height * 4);
+    check(surf_read_aov_sampled(m_ctx, &params, plane, out.data()), m_ctx, "surf_read_aov_sampled");
+    return out;
+}
+
+std::vector<U32> WaveFrontRenderer::readAOVSampledIds(surf_aovs plane, const surf_aov_sampled_params& params) {
+    if (plane != SURF_AOVS_ID && plane != SURF_AOVS_MATTE_KEY && plane != SURF_AOVS_MATTE_COUNT)
+        throw std::runtime_error("readAOVSampledIds: not an integer plane (the float planes are readAOVSampled)");
+    pushSceneAndCamera();
+    std::vector<U32> out((size_t)m_resolution.width * m_resolution.height * 4);
+    check(surf_read_aov_sampled(m_ctx, &params, plane, out.data()), m_ctx, "surf_read_aov_sampled");
+    return out;
+}
+
+void WaveFrontRenderer::setFilterGuidesSampled(const surf_aov_sampled_params& params) {
+    check(surf_set_filter_guides_sampled(m_ctx, &params), m_ctx, "surf_set_filter_guides_sampled");
+}
+
 /* The filter reads the accumulator beside the feature buffers, so it keeps
  * the camera and the scene of the last render() call: those the accumulated
  * samples saw. */

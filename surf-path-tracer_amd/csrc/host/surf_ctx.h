@@ -116,6 +116,13 @@ struct surf_ctx {
     /* which planes surf_denoise and surf_denoise_sampled read (surf_set_filter_guides) */
     int guides = SURF_GUIDES_FIRST_HIT;
     uint32_t guideLinks = 8;
+    /* the sampled feature buffers (surf_read_aov_sampled): six planes of their
+     * own, valid until what clears aovValid or a read with other params */
+    void* aovSampled[SURF_AOVS_COUNT] = {};
+    bool aovSampledValid = false;
+    surf_aov_sampled_params aovSampledParams{};   /* the params the cached planes were traced with */
+    float aovSampledKernelMs = 0.0f;   /* device time of the last k_aov_sampled launch (surf_debug_aov_sampled_time) */
+    surf_aov_sampled_params guideSampled{};       /* the params of SURF_GUIDES_SAMPLED (surf_set_filter_guides_sampled) */
     /* the a-trous denoiser (surf_denoise*, host/denoise.hip): dn, the scratch
      * every a-trous filter runs in -- the two ping-pong levels, the packed
      * normal and position guides -- and, for surf_denoise_image, the four
@@ -391,7 +398,8 @@ void destroyGraph(surf_ctx* c);
 int drainStream(surf_ctx* c);
 int featurePlanes(surf_ctx* c);
 /* ... and for the two purely spatial context filters the planes surf_set_filter_guides chose,
- * computed: *planes is c->aov or c->aovChain */
+ * computed: *planes is c->aov, c->aovChain or c->aovSampled (whose first three planes are laid
+ * out as theirs) */
 int guidePlanes(surf_ctx* c, void* const** planes);
 /* defined in host/denoise.hip: PlaneGroup::grow's body -- `count` images of at
  * least npx records each (OOM message: "... of <what> ...") */

@@ -325,7 +325,7 @@ int sampledContext(surf_ctx* c, const surf_svgf_params* sp, void* dst, hipMemcpy
                                          "neighbours' rows; assemble the shards' accumulators, squares and feature planes and call "
                                          "surf_denoise_sampled_image");
     if (!c->sqOn) return fail(c, SURF_ERR_INVALID, "surf_denoise_sampled: sample squares are off (surf_set_sample_squares)");
-    void* const* g = nullptr;     /* the first-hit planes, or the chain's (surf_set_filter_guides) */
+    void* const* g = nullptr;     /* the first-hit planes, the chain's or the sampled ones (surf_set_filter_guides*) */
     int rc = guidePlanes(c, &g);
     if (rc) return rc;
     if ((rc = drainStream(c))) return rc;

@@ -19,6 +19,7 @@
 #include <mutex>
 
 #include "device/wavefront_kernels.h"
+#include "device/aov_sampled_kernels.h"
 
 namespace {
 
@@ -152,6 +153,7 @@ auto traceClosestKernel(const surf_ctx* c, const Variant& v) { return kernel(SUR
 auto traceAnyKernel(const surf_ctx* c, const Variant& v) { return kernel(SURF_PICK2(k_trace_any, v.lds, v.laneW), laneLds(c, kBlock, false, v.lds)); }
 auto aovKernel(const surf_ctx* c, const Variant& v) { return kernel(SURF_PICK2(k_aov, v.lds, v.laneW), laneLds(c, kBlock, false, v.lds)); }
 auto aovChainKernel(const surf_ctx* c, const Variant& v) { return kernel(SURF_PICK2(k_aov_chain, v.lds, v.laneW), laneLds(c, kBlock, false, v.lds)); }
+auto aovSampledKernel(const surf_ctx* c, const Variant& v) { return kernel(SURF_PICK2(k_aov_sampled, v.lds, v.laneW), laneLds(c, kBlock, false, v.lds)); }
 auto tailKernel(const surf_ctx* c, const Variant& v) { return kernel(v.lds ? k_tail<true> : k_tail<false>, laneLds(c, 64, false, v.lds)); }
 
 /* the one-ray-per-wave kernels over <LDS, W2> */
@@ -556,6 +558,44 @@ int ensureAovChain(surf_ctx* c, uint32_t maxLinks) {
     (void)hipEventElapsedTime(&c->aovChainKernelMs, c->ev0, c->ev1);
     c->aovChainLinks = maxLinks;
     c->aovChainValid = true;
+    return SURF_OK;
+}
+
+/* surf_aov_sampled_params as the header states them */
+bool aovSampledParamsOk(const surf_aov_sampled_params* p) {
+    return p && p->samples >= 1u && p->samples <= SURF_AOVS_MAX_SAMPLES && (p->key == SURF_MATTE_INSTANCE || p->key == SURF_MATTE_MATERIAL) &&
+           p->reserved == 0u;
+}
+
+/* The six sampled planes (k_aov_sampled), in device planes of their own: kept
+ * until what drops the first-hit planes, or a read with other params.  One
+ * launch on the render stream, as ensureAov. */
+int ensureAovSampled(surf_ctx* c, const surf_aov_sampled_params& q) {
+    if (!aovSampledParamsOk(&q)) return fail(c, SURF_ERR_INVALID, "sampled feature buffers: samples outside 1.." + std::to_string(SURF_AOVS_MAX_SAMPLES) + ", an unknown key or reserved != 0");
+    if (!c->hasScene) return fail(c, SURF_ERR_NO_SCENE, "no scene uploaded");
+    if (!c->hasCamera) return fail(c, SURF_ERR_NO_SCENE, "no camera set");
+    SURF_CHECK(c, hipSetDevice(c->device));
+    if (c->aovSampledValid && std::memcmp(&c->aovSampledParams, &q, sizeof q) == 0) return SURF_OK;
+    c->aovSampledValid = false;
+    for (void*& p : c->aovSampled)
+        if (!p && (hipMalloc(&p, (size_t)c->npx * 16) != hipSuccess || !p)) {
+            p = nullptr;
+            (void)hipGetLastError();
+            return fail(c, SURF_ERR_OOM, "hipMalloc of a feature plane (" + std::to_string((size_t)c->npx * 16) + " bytes) failed");
+        }
+    SURF_CHECK(c, hipEventRecord(c->ev0, c->stream));
+    const auto aov = aovSampledKernel(c, variantOf(c));
+    hipLaunchKernelGGL(aov.fn, dim3((c->npx + kBlock - 1) / kBlock), dim3(kBlock), aov.lds, c->stream, c->S, c->cam, (const uint32_t*)c->dRows, c->width, c->npx, q.samples, q.first_sample, q.key,
+                       static_cast<float4*>(c->aovSampled[SURF_AOVS_POSITION]), static_cast<float4*>(c->aovSampled[SURF_AOVS_NORMAL]),
+                       static_cast<float4*>(c->aovSampled[SURF_AOVS_ALBEDO]), static_cast<uint4*>(c->aovSampled[SURF_AOVS_ID]),
+                       static_cast<uint4*>(c->aovSampled[SURF_AOVS_MATTE_KEY]), static_cast<uint4*>(c->aovSampled[SURF_AOVS_MATTE_COUNT]),
+                       stackWords(c, kBlock));
+    SURF_CHECK(c, hipGetLastError());
+    SURF_CHECK(c, hipEventRecord(c->ev1, c->stream));
+    SURF_CHECK(c, hipEventSynchronize(c->ev1));
+    (void)hipEventElapsedTime(&c->aovSampledKernelMs, c->ev0, c->ev1);
+    c->aovSampledParams = q;
+    c->aovSampledValid = true;
     return SURF_OK;
 }
 
@@ -1037,6 +1077,10 @@ int ensureDrained(surf_ctx* c) {
 int surfhost::drainStream(surf_ctx* c) { return ensureDrained(c); }
 int surfhost::featurePlanes(surf_ctx* c) { return ensureAov(c); }
 int surfhost::guidePlanes(surf_ctx* c, void* const** planes) {
+    if (c->guides == SURF_GUIDES_SAMPLED) {
+        *planes = c->aovSampled;
+        return ensureAovSampled(c, c->guideSampled);
+    }
     const bool chain = c->guides == SURF_GUIDES_CHAIN;
     *planes = chain ? c->aovChain : c->aov;
     return chain ? ensureAovChain(c, c->guideLinks) : ensureAov(c);
@@ -1196,6 +1240,7 @@ void surf_destroy(surf_ctx* c) {
     for (auto& e : c->accEv) if (e) (void)hipEventDestroy(e);
     for (void*& p : c->aov) { if (p) (void)hipFree(p); p = nullptr; }
     for (void*& p : c->aovChain) { if (p) (void)hipFree(p); p = nullptr; }
+    for (void*& p : c->aovSampled) { if (p) (void)hipFree(p); p = nullptr; }
     freeDenoise(c);
     freeTemporal(c);
     freeAdaptive(c);
@@ -1360,6 +1405,7 @@ int surf_set_camera(surf_ctx* c, const surf_camera_ubo* u) {
     c->permValid = false;
     c->aovValid = false;
     c->aovChainValid = false;
+    c->aovSampledValid = false;
     c->camUbo = *u;
     c->hasCamera = true;
     destroyGraph(c);     /* camera is a kernel argument of the captured graph */
@@ -1609,7 +1655,45 @@ int surf_set_filter_guides(surf_ctx* c, int guides, uint32_t max_links) {
 int surf_get_filter_guides(const surf_ctx* c, int* guides, uint32_t* max_links) {
     if (!c || !guides || !max_links) return SURF_ERR_INVALID;
     *guides = c->guides;
-    *max_links = c->guideLinks;
+    *max_links = c->guides == SURF_GUIDES_SAMPLED ? c->guideSampled.samples : c->guideLinks;
+    return SURF_OK;
+}
+
+int surf_aov_sampled_default_params(surf_aov_sampled_params* p) {
+    if (!p) return SURF_ERR_INVALID;
+    *p = surf_aov_sampled_params{16u, 0u, SURF_MATTE_INSTANCE, 0u};
+    return SURF_OK;
+}
+
+/* surf_read_aov_sampled / surf_copy_aov_sampled_device */
+static int copyAovSampled(surf_ctx* c, const surf_aov_sampled_params* p, int plane, void* dst, hipMemcpyKind kind) {
+    if (!c || !p || !dst || plane < 0 || plane >= SURF_AOVS_COUNT) return SURF_ERR_INVALID;
+    int rc = ensureAovSampled(c, *p);
+    if (rc) return rc;
+    SURF_CHECK(c, hipMemcpyAsync(dst, c->aovSampled[plane], (size_t)c->npx * 16, kind, c->stream));
+    SURF_CHECK(c, hipStreamSynchronize(c->stream));
+    return SURF_OK;
+}
+
+int surf_read_aov_sampled(surf_ctx* c, const surf_aov_sampled_params* p, int plane, void* out) {
+    return copyAovSampled(c, p, plane, out, hipMemcpyDeviceToHost);
+}
+
+int surf_copy_aov_sampled_device(surf_ctx* c, const surf_aov_sampled_params* p, int plane, void* dst) {
+    return copyAovSampled(c, p, plane, dst, hipMemcpyDeviceToDevice);
+}
+
+int surf_debug_aov_sampled_time(surf_ctx* c, float* kernel_ms) {
+    if (!c || !kernel_ms) return SURF_ERR_INVALID;
+    *kernel_ms = c->aovSampledKernelMs;
+    return SURF_OK;
+}
+
+int surf_set_filter_guides_sampled(surf_ctx* c, const surf_aov_sampled_params* p) {
+    if (!c || !p) return SURF_ERR_INVALID;
+    if (!aovSampledParamsOk(p)) return fail(c, SURF_ERR_INVALID, "surf_set_filter_guides_sampled: samples outside 1.." + std::to_string(SURF_AOVS_MAX_SAMPLES) + ", an unknown key or reserved != 0");
+    c->guides = SURF_GUIDES_SAMPLED;
+    c->guideSampled = *p;
     return SURF_OK;
 }
 

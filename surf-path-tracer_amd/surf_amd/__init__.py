@@ -15,6 +15,8 @@ Mirrors the reference interface for the hot path:
     .aov()                     first-hit feature buffers (no reference counterpart)
     .aov_chain(max_links)      the same planes traced through mirrors and glass; .set_filter_guides("chain") guides
                                denoise() and denoise_sampled() with them (no reference counterpart)
+    .aov_sampled(samples)      the features of the camera rays render() traces, reduced per pixel: anti-aliased planes and an
+                               id coverage matte (matte_coverage); .set_filter_guides("sampled") guides the same filters
     .denoise()                 edge-avoiding a-trous filter on them (no reference counterpart)
     .temporal()                temporal accumulation with reprojection across cleared frames (no reference counterpart)
     .svgf()                    the same with luminance moments, their variance guiding the a-trous filter (no reference counterpart);
@@ -234,6 +236,11 @@ class DisplayMeterResult(C.Structure):
                 "median_bin": int(self.median_bin), "scale": np.float32(self.scale)}
 
 
+class AovSampledParams(C.Structure):
+    """surf_aov_sampled_params: the samples reduced per pixel, the frame index of the first, the matte's key."""
+    _fields_ = [("samples", C.c_uint32), ("first_sample", C.c_uint32), ("key", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 _lib = None
 
 # Byte sizes of the reference records (include/surf_hip.h static_asserts).
@@ -290,6 +297,11 @@ def load() -> C.CDLL:
         "surf_read_aov_chain": ([P, I32, U32, P], I32), "surf_copy_aov_chain_device": ([P, I32, U32, P], I32),
         "surf_debug_aov_chain_time": ([P, C.POINTER(F)], I32),
         "surf_set_filter_guides": ([P, I32, U32], I32), "surf_get_filter_guides": ([P, C.POINTER(I32), C.POINTER(U32)], I32),
+        "surf_aov_sampled_default_params": ([C.POINTER(AovSampledParams)], I32),
+        "surf_read_aov_sampled": ([P, C.POINTER(AovSampledParams), I32, P], I32),
+        "surf_copy_aov_sampled_device": ([P, C.POINTER(AovSampledParams), I32, P], I32),
+        "surf_debug_aov_sampled_time": ([P, C.POINTER(F)], I32),
+        "surf_set_filter_guides_sampled": ([P, C.POINTER(AovSampledParams)], I32),
         "surf_write_pfm": ([C.c_char_p, U32, U32, P], I32),
         "surf_denoise_default_params": ([C.POINTER(DenoiseParams)], I32),
         "surf_denoise": ([P, C.POINTER(DenoiseParams), P], I32),
@@ -567,6 +579,38 @@ def write_pfm(path: str, rgba: np.ndarray) -> None:
 AOV_PLANES = ("position", "normal", "albedo", "id")      # surf_aov order
 AOV_CHAIN_MAX_LINKS = 16                                 # SURF_AOV_CHAIN_MAX_LINKS
 FILTER_GUIDES = ("first_hit", "chain")                   # surf_guides order
+FILTER_GUIDES_SAMPLED = "sampled"                        # SURF_GUIDES_SAMPLED (2), set through surf_set_filter_guides_sampled
+AOVS_PLANES = ("position", "normal", "albedo", "id", "matte_key", "matte_count")   # surf_aovs order
+AOVS_MAX_SAMPLES = 64                                    # SURF_AOVS_MAX_SAMPLES
+MATTE_KEYS = ("instance", "material")                    # surf_matte_key order
+MATTE_MISS = 0xFFFFFFFF                                  # the key of a sample that missed, and of an empty rank
+
+
+def aov_sampled_params(samples=16, first_sample=0, key="instance") -> AovSampledParams:
+    """surf_aov_sampled_params, checked before the library sees them."""
+    if key not in MATTE_KEYS:
+        raise ValueError(f"matte key {key!r}: one of {MATTE_KEYS}")
+    n, f = int(samples), int(first_sample)
+    if n != samples or not 1 <= n <= AOVS_MAX_SAMPLES:
+        raise ValueError(f"samples {samples!r}: an integer in 1..{AOVS_MAX_SAMPLES}")
+    if f != first_sample or not 0 <= f <= 0xFFFFFFFF:
+        raise ValueError(f"first_sample {first_sample!r}: an unsigned 32-bit integer")
+    return AovSampledParams(n, f, MATTE_KEYS.index(key), 0)
+
+
+def matte_coverage(keys, counts, key: int, samples: int) -> np.ndarray:
+    """The coverage of one key from Renderer.aov_sampled()'s 'matte_key' and
+    'matte_count' planes: (H, W) float32, the key's count / samples where one
+    of the pixel's four ranks holds it (with a count above 0: an empty rank is
+    MATTE_MISS with count 0), else 0.  key = MATTE_MISS gives the share of the
+    samples that missed."""
+    keys, counts = np.asarray(keys, np.uint32), np.asarray(counts, np.uint32)
+    if keys.ndim != 3 or keys.shape[2] != 4 or counts.shape != keys.shape:
+        raise ValueError(f"matte planes {keys.shape} and {counts.shape} are not two (H, W, 4) images of one size")
+    if int(samples) < 1:
+        raise ValueError(f"samples {samples!r}: at least 1")
+    hits = np.where(keys == np.uint32(key), counts, np.uint32(0)).sum(axis=2, dtype=np.uint32)
+    return hits.astype(np.float32) / np.float32(samples)
 
 
 def _chain_links(max_links) -> int:
@@ -1324,20 +1368,54 @@ class Renderer:
         _check(load().surf_debug_aov_chain_time(self._h, C.byref(ms)), "surf_debug_aov_chain_time", self._h)
         return float(ms.value)
 
-    def set_filter_guides(self, guides: str = "first_hit", max_links: int = 8):
-        """Which planes denoise() and denoise_sampled() read (surf_set_filter_guides):
-        "first_hit" (the default) or "chain", aov_chain(max_links)'s.  temporal(),
-        svgf(), mask_from_noise() and render_adaptive() keep the first-hit planes."""
+    def aov_sampled(self, samples: int = 16, first_sample: int = 0, key: str = "instance") -> dict:
+        """The sampled feature buffers (surf_read_aov_sampled, which states the
+        arithmetic): the first-hit features of the camera rays render() traces for
+        frames first_sample .. first_sample + samples - 1 at one sample per frame,
+        reduced per pixel.  AOVS_PLANES as (rows, width, 4): 'position', 'normal'
+        and 'albedo' float32 (albedo.w = the hit coverage), 'id' (sample 0's ids,
+        w = the hit count), 'matte_key' and 'matte_count' uint32 (the four best of
+        the pixel's instance or material keys and their sample counts; see
+        matte_coverage).  Cached like aov(), per parameter set."""
+        q = aov_sampled_params(samples, first_sample, key)
+        out = {}
+        for k, name in enumerate(AOVS_PLANES):
+            a = np.zeros((len(self.rows), self.width, 4), dtype=np.float32 if k < 3 else np.uint32)
+            _check(load().surf_read_aov_sampled(self._h, C.byref(q), k, _ptr(a)), "surf_read_aov_sampled", self._h)
+            out[name] = a
+        return out
+
+    def copy_aov_sampled_to(self, plane: int, device_ptr: int, **params):
+        q = aov_sampled_params(**params)
+        _check(load().surf_copy_aov_sampled_device(self._h, C.byref(q), plane, C.c_void_p(device_ptr)), "surf_copy_aov_sampled_device", self._h)
+
+    def debug_aov_sampled_time(self) -> float:
+        """Device milliseconds of the last sampled-planes kernel launch (surf_debug_aov_sampled_time)."""
+        ms = C.c_float()
+        _check(load().surf_debug_aov_sampled_time(self._h, C.byref(ms)), "surf_debug_aov_sampled_time", self._h)
+        return float(ms.value)
+
+    def set_filter_guides(self, guides: str = "first_hit", max_links: int = 8, samples: int = 16, first_sample: int = 0):
+        """Which planes denoise(), denoise_sampled() and denoise_regress() read
+        (surf_set_filter_guides): "first_hit" (the default), "chain",
+        aov_chain(max_links)'s, or "sampled", aov_sampled(samples, first_sample)'s
+        (surf_set_filter_guides_sampled).  temporal(), svgf(), mask_from_noise()
+        and render_adaptive() keep the first-hit planes."""
+        if guides == FILTER_GUIDES_SAMPLED:
+            q = aov_sampled_params(samples, first_sample)
+            _check(load().surf_set_filter_guides_sampled(self._h, C.byref(q)), "surf_set_filter_guides_sampled", self._h)
+            return
         if guides not in FILTER_GUIDES:
-            raise ValueError(f"filter guides {guides!r}: one of {FILTER_GUIDES}")
+            raise ValueError(f"filter guides {guides!r}: one of {FILTER_GUIDES + (FILTER_GUIDES_SAMPLED,)}")
         max_links = _chain_links(max_links)
         _check(load().surf_set_filter_guides(self._h, FILTER_GUIDES.index(guides), max_links), "surf_set_filter_guides", self._h)
 
     def filter_guides(self) -> tuple:
-        """(guides, max_links) as set_filter_guides took them (surf_get_filter_guides)."""
+        """(guides, max_links) as set_filter_guides took them (surf_get_filter_guides);
+        with "sampled" guides the second member is their sample count."""
         g, n = C.c_int(), C.c_uint32()
         _check(load().surf_get_filter_guides(self._h, C.byref(g), C.byref(n)), "surf_get_filter_guides", self._h)
-        return FILTER_GUIDES[g.value], int(n.value)
+        return (FILTER_GUIDES + (FILTER_GUIDES_SAMPLED,))[g.value], int(n.value)
 
     def denoise(self, **params) -> np.ndarray:
         """The accumulated radiance through the edge-avoiding a-trous filter
