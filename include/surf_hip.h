@@ -131,6 +131,7 @@ typedef struct {
     uint32_t max_segments;     /* longest path seen (extension rays), diagnostics */
     uint64_t tail_survivors;   /* drain paths handed to the cooperative tail */
     uint32_t frame_window;     /* radiance ring slots (passes) of the current stream (surf_set_frame_batch), 0 before the first render */
+    uint64_t n_shadow_overflow; /* wavefront shadow rays queued in the overflow region: their order bin's region was full */
 } surf_stats;
 
 typedef struct surf_ctx surf_ctx;       /* one per HIP device */
@@ -252,6 +253,16 @@ int surf_debug_issue_order(surf_ctx* ctx, uint32_t* heavy_pixels, uint32_t* perm
  * both 0 when k_connect walked every BLAS from global memory.  No reference
  * counterpart. */
 int surf_debug_connect_staging(surf_ctx* ctx, uint32_t* records, uint32_t* triangles);
+/* Diagnostics: the shadow queue's order bin of n host rays under the context's
+ * key layout (SURF_SH_KEY: 16, 32 or 40 bins; 1 bin when the shadow order is
+ * off): o and d 3 floats per ray, tmax and the light slot one value per ray;
+ * keys[i] < *bins, the number of bins in use.  layout (25 floats, or NULL)
+ * receives what the key reads of the scene: the order cells' origin (3) and
+ * scale (3), the number of heavy instances (0..3), then each one's padded
+ * world box, lo (3) and hi (3), the heaviest first, zeros behind the last.
+ * Needs an uploaded scene.  No reference counterpart. */
+int surf_debug_shadow_keys(surf_ctx* ctx, uint32_t n, const float* o, const float* d, const float* tmax, const uint32_t* light,
+                           uint32_t* keys, uint32_t* bins, float* layout);
 /* Diagnostics: the kernel variants the uploaded scene selects (1 or 0 each):
  * trace and shading tables in LDS (at most 64 instances, materials, lights),
  * k_extend's 16-bit traversal stack (fewer than 65,536 BLAS and TLAS nodes, no

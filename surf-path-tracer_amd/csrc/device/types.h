@@ -103,11 +103,17 @@ struct Pool { float4* od; float4* T; uint8_t* key; };
 /* Shadow queue: od[2i] = (origin, tmax), od[2i + 1] = (direction, sample id)
  * -- the ray k_connect traverses is one 32-B piece of one cache line --
  * c[i] = (T * Ld, 0), read only for an unoccluded ray.  k_shade appends each
- * shadow ray straight into the region of its order bin (shadowKey: kShBins
+ * shadow ray straight into the region of its order bin (shadowKey: Q.bins
  * regions of `region` slots, then an overflow region of the pool's capacity
  * for a bin that outgrows its region), so k_connect reads the rays in bin
- * order sequentially: no sort pass and no gather through an order array. */
-constexpr uint32_t kShBins = 16;     /* shadow-ray order bins: light slot (mod 2) x octant cell */
+ * order sequentially: no sort pass and no gather through an order array.
+ * The key layouts (SURF_SH_KEY, shadowKey) use 16, 32 or 40 bins; kShBins is
+ * the most a layout may use, which sizes the LDS arrays and the cursor array.
+ * At most 63: one atomic instruction of k_shade's wave 0 reserves every bin
+ * and the continuations. */
+constexpr uint32_t kShBins = 40;
+constexpr uint32_t kShBinsBase = 16; /* layout 0: light slot (mod 2) x octant cell */
+static_assert(kShBins <= 63u, "k_shade reserves kShBins bins + the continuations in one wave instruction");
 /* Each bin's cursor and region are split by XCD (SURF_SH_XCDS parts, the
  * appending workgroup's HW_REG_XCC_ID) and the cursors lie SURF_SH_STRIDE words
  * apart: every workgroup iteration of k_shade reserves once per non-empty bin,
@@ -119,12 +125,16 @@ constexpr uint32_t kShBins = 16;     /* shadow-ray order bins: light slot (mod 2
 #define SURF_SH_STRIDE 32
 #endif
 constexpr uint32_t kShXcds = SURF_SH_XCDS, kShStride = SURF_SH_STRIDE;
-constexpr uint32_t kShSegs = kShBins * kShXcds + 1u;      /* queue segments: (bin, XCD) regions, then the overflow */
+constexpr uint32_t kShSegs = kShBins * kShXcds + 1u;      /* the most queue segments: (bin, XCD) regions, then the overflow */
 struct ShadowQ {
     float4* od; float4* c;
     uint32_t* cur;        /* [2 parities][kShSegs] cursors, kShStride words apart (may count past a region's end) */
     uint32_t region;      /* slots per (bin, XCD) region */
-    uint32_t bins;        /* kShBins, or 1: no shadow order (SURF_SORT=0/2) */
+    /* bins in use: 16, 32 or 40 (the key layout, shadowKey), or 1: no shadow
+     * order (SURF_SORT=0/2).  Segments 0 .. bins * kShXcds - 1 are the bins'
+     * regions, segment shOverflowSeg(bins) -- behind at least 16 bins -- is
+     * the overflow; the cursors behind it stay 0 */
+    uint32_t bins;
 };
 
 /* Device counters of the sample stream.  Double-buffered by phase parity so no
@@ -155,7 +165,8 @@ struct Counters {
     unsigned long long issued[2];    /* stream chains issued (first samples of (frame, pixel)), per parity */
     unsigned long long limit;        /* host-written issue limit (frame window) */
     unsigned long long baseFrame;    /* absolute frame index of stream frame 0 */
-    unsigned long long ev[16];       /* ext, hit, cont, shadow, acc, unocc, tail paths, capped paths, wavefront ext */
+    unsigned long long ev[16];       /* ext, hit, cont, shadow, acc, unocc, tail paths, capped paths, wavefront ext,
+                                        shadow rays queued in the overflow region */
     uint32_t capped[64];             /* sample ids of paths ended by the segment cap, slot blockIdx % 64 (diagnostics, ~0 = none) */
     /* event counts striped over kStripes cache lines (block b adds to stripe
      * b % kStripes): a counter shared by every block of a launch serializes its
@@ -165,7 +176,7 @@ struct Counters {
 };
 static_assert(offsetof(Counters, issued) == 56, "nActive fills the alignment gap in front of issued");
 constexpr uint32_t kStripes = 32;    /* frameDone and event-count stripes */
-constexpr int kEvents = 9;           /* event kinds counted (ev / evS index) */
+constexpr int kEvents = 10;          /* event kinds counted (ev / evS index) */
 
 /* Where a stream sample lives: radiance slot sid = (pass % window) * npx + pixel,
  * pass = the sample's index in the stream (frame * spp + its place in the

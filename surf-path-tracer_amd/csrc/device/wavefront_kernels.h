@@ -1777,15 +1777,54 @@ __device__ __forceinline__ uint8_t poolKey(const DevScene& S, uint32_t inst, flo
  * tools/order_probe2.py, last in commit 5a920ae):
  * 340 us shuffled, 277 sorted by light, 238 by light x octant cell, 286 by
  * light x 4x4x4 cells (too fine: the bins stop sharing paths through the BVH).
- * The pool's heavy-instance mask (of the segment [0, tmax)) x light x x/z
- * quadrant was measured slower: k_connect 147 -> 174 ms per C3 render. */
-__device__ __forceinline__ uint8_t shadowKey(const DevScene& S, uint32_t light, float4 o) {
+ * That is layout 0 (`bins` = 16).  The other two put the rays whose segment
+ * [0, tmax) meets a heavy instance's world box (heavyMask, 13 % of C3's) in
+ * bins of their own IN FRONT of the others, so the walks of the heavy BLASes
+ * gather in few waves and those waves are dispatched first:
+ *   32 bins: any heavy box x light x octant, then none x light x octant;
+ *   40 bins: three heavy classes -- more than one heavy instance, only the
+ *            heaviest, only the second or third -- x light x x/z quadrant
+ *            (24 bins), then none x light x octant.
+ * Lock-step model of the recorded C3 shadow rays (tools/lockstep_shadow.py),
+ * wave steps per 64 rays: 49.6, 36.1, 32.4.  Round 3 measured the mask
+ * ASCENDING x light x quadrant (the costly rays last, on the last-dispatched
+ * workgroups) in a k_connect that still sorted and gathered: 147 -> 174 ms
+ * per C3 render.  Heavy first on today's kernel (MEASUREMENTS "Shadow bins by
+ * heavy box"): k_connect 109.5 -> 97.8 ms (32 bins) and 94.6 ms (40 bins),
+ * k_shade 80.7 -> 83.4 ms for the mask, C3 535.0 -> 550.6 and 549.1 Mrays/s:
+ * 32 bins is the default.  o.w = tmax.  HV: `bins` is 32 or 40 -- a
+ * template parameter, so that layout 0's k_shade holds no code of the others
+ * (the kernel's register allocation is touchy: with the layout a run-time
+ * branch k_shade took 2 ms more per C3 render under layout 0).  Every result
+ * is < bins. */
+template <bool HV>
+__device__ __forceinline__ uint32_t shadowKey(const DevScene& S, uint32_t bins, uint32_t light, float4 o, float4 d) {
     uint32_t cell = 0;
     const float p[3] = {o.x, o.y, o.z};
 #pragma unroll
     for (int a = 0; a < 3; ++a)
         cell |= ((p[a] - S.cellLo[a]) * S.cellScale[a] >= 1.0f ? 1u : 0u) << a;
-    return (uint8_t)((light & 1u) * 8u + cell);
+    const uint32_t base = (light & 1u) * 8u + cell;
+    if constexpr (!HV) return base;
+    const uint32_t m = heavyMask(S, o, d, o.w);
+    if (bins == 2u * kShBinsBase) return m ? base : kShBinsBase + base;
+    if (!m) return 24u + base;
+    const uint32_t cls = (m & (m - 1u)) ? 0u : ((m & 1u) ? 1u : 2u);
+    return cls * 8u + (light & 1u) * 4u + (cell & 1u) + ((cell >> 1) & 2u);
+}
+/* The queue segment behind the bins' regions, the overflow: behind 16 regions
+ * for layout 0 and for the one bin of an unordered queue, else behind Q.bins. */
+__host__ __device__ __forceinline__ uint32_t shOverflowSeg(uint32_t bins) { return (bins > kShBinsBase ? bins : kShBinsBase) * kShXcds; }
+/* Diagnostics (surf_debug_shadow_keys): the order bin k_shade would give each
+ * of n host rays under the layout of `bins` bins. */
+__global__ __launch_bounds__(kBlock) void k_shadow_keys(DevScene S, uint32_t bins, const float* __restrict__ o, const float* __restrict__ d,
+                                                        const float* __restrict__ tmax, const uint32_t* __restrict__ light, uint32_t n,
+                                                        uint32_t* __restrict__ keys) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float4 o4 = make_float4(o[3u * i], o[3u * i + 1u], o[3u * i + 2u], tmax[i]);
+    const float4 d4 = make_float4(d[3u * i], d[3u * i + 1u], d[3u * i + 2u], 0.0f);
+    keys[i] = bins <= 1u ? 0u : (bins > kShBinsBase ? shadowKey<true>(S, bins, light[i], o4, d4) : shadowKey<false>(S, bins, light[i], o4, d4));
 }
 
 /* Rays to order: which = 0 the pool read by phase par, 1 its shadow queue. */
@@ -2272,7 +2311,8 @@ __device__ __forceinline__ void frameDoneAdd(uint32_t* frameDone, bool done, uin
     }
 }
 
-template <bool LDS_TABLES>
+/* HV: the shadow key's heavy-box layouts (Q.bins = 32 or 40; shadowKey) */
+template <bool LDS_TABLES, bool HV = false>
 __global__ __launch_bounds__(kBlock, SURF_SHADE_WAVES) void k_shade(DevScene S, Pool cur, Pool nxt, const float4* __restrict__ hitTUV,
                                                   const uint32_t* __restrict__ hitInst, ShadowQ Q,
                                                   float4* __restrict__ rad, uint32_t* __restrict__ frameDone,
@@ -2301,6 +2341,7 @@ __global__ __launch_bounds__(kBlock, SURF_SHADE_WAVES) void k_shade(DevScene S, 
     const uint32_t n = C->nIn[par];
     const uint32_t maxSeg = C->maxSeg, zeroCutoff = C->zeroCutoff, spp = C->spp;
     const uint32_t wv = threadIdx.x >> 6, nw = blockDim.x >> 6;
+    const uint32_t ovSeg = HV ? shOverflowSeg(Q.bins) : shOverflowSeg(kShBinsBase);   /* (a constant without the heavy layouts) */
     uint32_t it = 0;
     unsigned long long cHit = 0, cCont = 0, cSh = 0, cAcc = 0, cCap = 0;
     for (uint32_t base = blockIdx.x * blockDim.x; base < n; base += gridDim.x * blockDim.x, it ^= 1u) {
@@ -2329,16 +2370,16 @@ __global__ __launch_bounds__(kBlock, SURF_SHADE_WAVES) void k_shade(DevScene S, 
         if (laneId() == 0) sWave[it][wv] = (uint32_t)__popcll(mCont);
         /* the shadow ray's bin -- toward the same light from the same octant of
          * the scene -- and its rank among the iteration's rays of that bin */
-        const uint32_t kb = r.shadow ? (Q.bins > 1u ? shadowKey(S, r.light, r.so) : 0u) : kShBins;
+        const uint32_t kb = r.shadow ? (Q.bins > 1u ? shadowKey<HV>(S, Q.bins, r.light, r.so, r.sd) : 0u) : kShBins;
         uint32_t rk = 0;
         if (r.shadow) rk = atomicAdd(&sShCnt[it][kb], 1u);
         __syncthreads();
         if (threadIdx.x <= kShBins) {
             /* the iteration's reservations in ONE atomic instruction of wave 0
              * (a round trip each would serialize): lanes 0..kShBins-1 the
-             * non-empty shadow bins (this XCD's part of each), lane kShBins the
-             * continuations; shadow rays that do not fit their bin's region go
-             * to the overflow region */
+             * non-empty shadow bins (this XCD's part of each; the bins past
+             * Q.bins are always empty), lane kShBins the continuations; shadow
+             * rays that do not fit their bin's region go to the overflow region */
             const uint32_t t = threadIdx.x;
             const uint32_t seg = t * kShXcds + xccId();
             uint32_t tot = 0;
@@ -2355,7 +2396,7 @@ __global__ __launch_bounds__(kBlock, SURF_SHADE_WAVES) void k_shade(DevScene S, 
                 sBase[it] = b0;
             } else {
                 const uint32_t ok = b0 >= Q.region ? 0u : min(tot, Q.region - b0);
-                const uint32_t ov = ok < tot ? atomicAdd(shCursor(Q, par, kShSegs - 1u), tot - ok) : 0u;
+                const uint32_t ov = ok < tot ? atomicAdd(shCursor(Q, par, ovSeg), tot - ok) : 0u;
                 sShBase[it][t] = seg * Q.region + b0; sShOk[it][t] = ok; sShOv[it][t] = ov;
             }
         }
@@ -2370,7 +2411,7 @@ __global__ __launch_bounds__(kBlock, SURF_SHADE_WAVES) void k_shade(DevScene S, 
         }
         if (r.shadow) {
             const uint32_t ok = sShOk[it][kb];
-            const uint32_t js = rk < ok ? sShBase[it][kb] + rk : (kShSegs - 1u) * Q.region + sShOv[it][kb] + (rk - ok);
+            const uint32_t js = rk < ok ? sShBase[it][kb] + rk : ovSeg * Q.region + sShOv[it][kb] + (rk - ok);
             stS(&Q.od[2u * js], r.so); stS(&Q.od[2u * js + 1u], r.sd); stS(&Q.c[js], r.sc);
         }
         /* a path that ends here may still have this phase's shadow ray pending:
@@ -2388,10 +2429,10 @@ __global__ __launch_bounds__(kBlock, SURF_SHADE_WAVES) void k_shade(DevScene S, 
 }
 
 /* Where shadow ray i of the bin order lives: the (bin, XCD) regions in bin
- * order, then the overflow region (pre: the first ray index of each segment,
- * kShSegs + 1 entries, the last = the count). */
+ * order, then the overflow region (pre: the first ray index of each segment in
+ * use, shOverflowSeg + 2 entries, the last = the count). */
 __device__ __forceinline__ uint32_t shadowSlot(const ShadowQ& Q, const uint32_t* pre, uint32_t i) {
-    uint32_t lo = 0, hi = kShSegs;            /* pre[lo] <= i < pre[hi] */
+    uint32_t lo = 0, hi = shOverflowSeg(Q.bins) + 1u;   /* pre[lo] <= i < pre[hi] */
     while (hi - lo > 1u) {
         const uint32_t mid = (lo + hi) >> 1;
         if (i >= pre[mid]) lo = mid; else hi = mid;
@@ -2404,24 +2445,27 @@ __global__ __launch_bounds__(kBlock, STG ? 5 : SURF_TRACE_WAVES) void k_connect(
                                                     uint32_t stackWords) {
     extern __shared__ uint32_t lds[];
     __shared__ uint32_t sPre[kShSegs + 1];
+    const uint32_t nSegs = shOverflowSeg(Q.bins) + 1u;           /* the segments in use (<= kShSegs) */
     if (threadIdx.x < 64u) {
         /* first ray index of every queue segment: a wave scan of the cursors */
         uint32_t carry = 0;
         if (threadIdx.x == 0) sPre[0] = 0u;
-        for (uint32_t b0 = 0; b0 < kShSegs; b0 += 64u) {
+        for (uint32_t b0 = 0; b0 < nSegs; b0 += 64u) {
             const uint32_t b = b0 + threadIdx.x;
-            uint32_t v = b < kShSegs ? min(*shCursor(Q, par, b), b + 1u < kShSegs ? Q.region : 0xffffffffu) : 0u;
+            uint32_t v = b < nSegs ? min(*shCursor(Q, par, b), b + 1u < nSegs ? Q.region : 0xffffffffu) : 0u;
+            /* the rays that outgrew their bin's region (surf_stats.n_shadow_overflow): one thread per launch */
+            if (b + 1u == nSegs && v && blockIdx.x == 0) atomicAdd(&C->ev[9], (unsigned long long)v);
 #pragma unroll
             for (uint32_t off = 1; off < 64u; off <<= 1) {
                 const uint32_t t = __shfl_up(v, off);
                 if (threadIdx.x >= off) v += t;
             }
-            if (b < kShSegs) sPre[b + 1] = carry + v;
+            if (b < nSegs) sPre[b + 1] = carry + v;
             carry += (uint32_t)__shfl((int)v, 63);
         }
     }
     __syncthreads();
-    const uint32_t n = sPre[kShSegs];
+    const uint32_t n = sPre[nSegs];
     if (blockIdx.x * blockDim.x >= n) return;               /* no shadow rays for this block */
     /* STG: the emitters' BLAS node records (every unoccluded shadow ray walks
      * that BLAS down to its sampled triangle) staged after a stack of 16-bit
@@ -2555,7 +2599,7 @@ __global__ __launch_bounds__(kBlock) void k_regen(DevCamera cam, Pool nxt, float
                                                   uint32_t capacity, StreamGeom G, ShadowQ Q) {
     const RegenPlan R = regenPlan<MASKED>(C, par, capacity, G);
     const uint32_t gid = blockIdx.x * blockDim.x + threadIdx.x;
-    if (gid < kShSegs) *shCursor(Q, par ^ 1, gid) = 0u;      /* the next phase's shadow-queue cursors */
+    if (gid < kShSegs) *shCursor(Q, par ^ 1, gid) = 0u;      /* the next phase's shadow-queue cursors (all, in use or not) */
     for (uint32_t k = gid; k < R.nnew; k += gridDim.x * blockDim.x) regenSample<MASKED>(cam, nxt, rad, G, R, k);
     if (gid == 0) regenCounters(C, par, R);
 }
@@ -2574,7 +2618,7 @@ __global__ __launch_bounds__(kSortThreads) void k_regen_count(DevCamera cam, Poo
     if (threadIdx.x < kBins) h[threadIdx.x] = 0u;
     const RegenPlan R = regenPlan<MASKED>(C, par, capacity, G);
     const uint32_t gid = blockIdx.x * blockDim.x + threadIdx.x;
-    if (gid < kShSegs) *shCursor(Q, par ^ 1, gid) = 0u;      /* the next phase's shadow-queue cursors */
+    if (gid < kShSegs) *shCursor(Q, par ^ 1, gid) = 0u;      /* the next phase's shadow-queue cursors (all, in use or not) */
     __syncthreads();
     uint32_t a, b;
     sortChunk(R.cont + R.nnew, a, b);

@@ -353,6 +353,8 @@ struct surf_ctx {
     bool sortRays = true;          /* order each phase's rays by start instance (SURF_SORT=0: off) */
     bool sortPool = true;
     bool sortShadow = true;        /* ... and the shadow queue by light (SURF_SORT=2: pool only, 3: shadow queue only) */
+    uint32_t shKey = 1;            /* the shadow key's layout (shadowKey): 0 = 16 bins, 1 = 32 (default), 2 = 40 (SURF_SH_KEY) */
+    uint32_t shRegion = 0;         /* slots per shadow-queue region, 0: by the pool and the layout (SURF_SH_REGION, tests) */
     /* ray order: counts from k_regen_count (or k_bincount), then k_binscatter each phase */
     uint32_t* order = nullptr;
     uint32_t* binHist = nullptr;

@@ -138,7 +138,8 @@ auto extendKernel(const surf_ctx* c, const Variant& v) {
     return kernel(v.lds ? extendFn<true>(v) : extendFn<false>(v), laneLds(c, c->extBlock, v.sk16, v.lds) + c->extLdsPad);
 }
 
-auto shadeKernel(const Variant& v) { return v.lds ? k_shade<true> : k_shade<false>; }
+/* k_shade<LDS, HV>: HV with the shadow key's heavy-box layouts (SURF_SH_KEY 1, 2) */
+auto shadeKernel(const surf_ctx* c, const Variant& v) { return SURF_PICK2(k_shade, v.lds, c->Q.bins > kShBinsBase); }
 
 /* k_connect<LDS, LW, STG>: staged only over LDS tables and one-level records */
 auto connectKernel(const surf_ctx* c, const Variant& v) {
@@ -177,6 +178,11 @@ auto accumulateBucketsListKernel(const surf_ctx* c) { return SURF_PICK_BUCKETS(k
 /* k_regen<MASKED> / k_regen_count<MASKED>: a masked stream issues frame-major over the active list */
 auto regenKernel(const surf_ctx* c) { return c->streamMasked ? k_regen<true> : k_regen<false>; }
 auto regenCountKernel(const surf_ctx* c) { return c->streamMasked ? k_regen_count<true> : k_regen_count<false>; }
+/* shadow-queue order bins in use: the key layout's (SURF_SH_KEY, shadowKey), or 1 without a shadow order */
+uint32_t shadowBins(const surf_ctx* c) {
+    static const uint32_t kLayoutBins[3] = {kShBinsBase, 2u * kShBinsBase, kShBins};
+    return (c->sortRays && c->sortShadow) ? kLayoutBins[c->shKey] : 1u;
+}
 
 int allocWavefront(surf_ctx* c) {
     if (c->allocated) return SURF_OK;
@@ -213,12 +219,14 @@ int allocWavefront(surf_ctx* c) {
     }
     if ((rc = devAlloc(c, c->wfAllocs, &c->hitTUV, cap))) return rc;
     if ((rc = devAlloc(c, c->wfAllocs, &c->hitInst, cap))) return rc;
-    /* shadow queue: kShBins bin regions of a quarter pool each (a phase queues
-     * at most one shadow ray per path; C3 puts <= 30 % of them in one bin), then
-     * an overflow region of a whole pool */
-    c->Q.region = (uint32_t)((cap / (4 * kShXcds) + 255) / 256 * 256);
-    c->Q.bins = (c->sortRays && c->sortShadow) ? kShBins : 1u;
-    const size_t qslots = (size_t)(kShSegs - 1) * c->Q.region + cap;
+    /* shadow queue: the key layout's bin regions -- 16 of a quarter pool each
+     * (a phase queues at most one shadow ray per path; C3 puts <= 30 % of them
+     * in one bin), 32 of an eighth or 40 of a tenth: four pools of slots in
+     * every layout -- then an overflow region of a whole pool */
+    c->Q.bins = shadowBins(c);
+    const size_t perPool = (size_t)std::max(c->Q.bins, kShBinsBase) / 4 * kShXcds;    /* regions per pool of slots */
+    c->Q.region = (uint32_t)(((c->shRegion ? std::min<size_t>(c->shRegion, cap) : cap / perPool) + 255) / 256 * 256);
+    const size_t qslots = (size_t)shOverflowSeg(c->Q.bins) * c->Q.region + cap;
     if ((rc = devAlloc(c, c->wfAllocs, &c->Q.od, 2 * qslots))) return rc;
     if ((rc = devAlloc(c, c->wfAllocs, &c->Q.c, qslots))) return rc;
     if ((rc = devAlloc(c, c->wfAllocs, &c->Q.cur, (size_t)2 * kShSegs * kShStride))) return rc;
@@ -382,7 +390,7 @@ void launchPhase(surf_ctx* c, int ph, hipEvent_t* ev) {
                        cur, c->hitTUV, c->hitInst, (const Counters*)c->ctr, par, stackWords(c, c->extBlock), order);
     if (ev) (void)hipEventRecord(ev[2], s0);
     if (ovl && ph > 0) (void)hipStreamWaitEvent(s0, c->capEv[2 * (ph - 1) + 1], 0);   /* the previous phase's connect */
-    hipLaunchKernelGGL(shadeKernel(v), dim3(c->gridWork), dim3(kBlock), 0, s0, c->S, cur, c->pool[par ^ 1],
+    hipLaunchKernelGGL(shadeKernel(c, v), dim3(c->gridWork), dim3(kBlock), 0, s0, c->S, cur, c->pool[par ^ 1],
                        c->hitTUV, (const uint32_t*)c->hitInst, c->Q, c->rad, c->frameDone, c->npx, c->window, c->ctr, par, order,
                        c->cam, geom(c));
     if (ev) (void)hipEventRecord(ev[3], s0);
@@ -1143,6 +1151,8 @@ int createCtx(int dev, uint32_t w, uint32_t h, std::vector<uint32_t> rows, surf_
         c->sortPool = e[0] != '3';
         c->sortShadow = e[0] != '2';
     }
+    if (const char* e = std::getenv("SURF_SH_KEY")) c->shKey = e[0] == '1' ? 1u : (e[0] == '2' ? 2u : 0u);
+    if (const char* e = std::getenv("SURF_SH_REGION")) c->shRegion = (uint32_t)std::max(0, std::atoi(e));
     if (const char* e = std::getenv("SURF_CONNECT_GLOBAL")) c->connectGlobal = e[0] != '0';
     if (const char* e = std::getenv("SURF_EXT_STACK16")) c->extStack16 = e[0] != '0';
     if (const char* e = std::getenv("SURF_REGEN_COUNT")) c->regenCount = e[0] != '0';
@@ -1766,6 +1776,7 @@ int surf_get_stats(surf_ctx* c, surf_stats* out) {
     s.n_ext = ev[0]; s.n_hit = ev[1]; s.n_cont = ev[2]; s.n_shadow = ev[3]; s.n_acc = ev[4]; s.n_unocc = ev[5];
     s.tail_paths = ev[6];
     s.n_ext_wavefront = ev[8] - c->tailFirstRays;
+    s.n_shadow_overflow = ev[9];
     s.max_segments = std::max(c->segMaxBase, (c->streamActive && c->hctr) ? c->hctr->segMax : 0u);
     s.stack_depth = c->stackDepth;
     s.pool_capacity = c->capacity;
@@ -1843,6 +1854,40 @@ int surf_trace_any(surf_ctx* c, uint32_t n, const float* o, const float* d, cons
     hipError_t e = hipStreamSynchronize(c->stream);
     freeList(tmp);
     if (e != hipSuccess) return fail(c, SURF_ERR_HIP, std::string("trace_any: ") + hipGetErrorString(e));
+    return SURF_OK;
+}
+
+int surf_debug_shadow_keys(surf_ctx* c, uint32_t n, const float* o, const float* d, const float* tmax, const uint32_t* light,
+                           uint32_t* keys, uint32_t* bins, float* layout) {
+    if (!c || !bins || (n && (!o || !d || !tmax || !light || !keys))) return SURF_ERR_INVALID;
+    if (!c->hasScene) return fail(c, SURF_ERR_NO_SCENE, "no scene uploaded");
+    *bins = shadowBins(c);
+    if (layout) {
+        const DevScene& S = c->S;
+        for (int a = 0; a < 3; ++a) { layout[a] = S.cellLo[a]; layout[3 + a] = S.cellScale[a]; }
+        layout[6] = (float)S.nHeavy;
+        for (int h = 0; h < 3; ++h) {
+            const float b[6] = {S.hvLo[h].x, S.hvLo[h].y, S.hvLo[h].z, S.hvHi[h].x, S.hvHi[h].y, S.hvHi[h].z};
+            std::copy(b, b + 6, layout + 7 + 6 * h);
+        }
+    }
+    if (n == 0) return SURF_OK;
+    SURF_CHECK(c, hipSetDevice(c->device));
+    std::vector<void*> tmp;
+    float *dO, *dD, *dM; uint32_t *dL, *dK;
+    int rc;
+    if ((rc = devAlloc(c, tmp, &dO, 3 * (size_t)n)) || (rc = devAlloc(c, tmp, &dD, 3 * (size_t)n)) ||
+        (rc = devAlloc(c, tmp, &dM, n)) || (rc = devAlloc(c, tmp, &dL, n)) || (rc = devAlloc(c, tmp, &dK, n))) { freeList(tmp); return rc; }
+    (void)hipMemcpyAsync(dO, o, 12 * (size_t)n, hipMemcpyHostToDevice, c->stream);
+    (void)hipMemcpyAsync(dD, d, 12 * (size_t)n, hipMemcpyHostToDevice, c->stream);
+    (void)hipMemcpyAsync(dM, tmax, 4 * (size_t)n, hipMemcpyHostToDevice, c->stream);
+    (void)hipMemcpyAsync(dL, light, 4 * (size_t)n, hipMemcpyHostToDevice, c->stream);
+    hipLaunchKernelGGL(k_shadow_keys, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), 0, c->stream, c->S, *bins, (const float*)dO,
+                       (const float*)dD, (const float*)dM, (const uint32_t*)dL, n, dK);
+    (void)hipMemcpyAsync(keys, dK, 4 * (size_t)n, hipMemcpyDeviceToHost, c->stream);
+    const hipError_t e = hipStreamSynchronize(c->stream);
+    freeList(tmp);
+    if (e != hipSuccess) return fail(c, SURF_ERR_HIP, std::string("debug_shadow_keys: ") + hipGetErrorString(e));
     return SURF_OK;
 }
 

@@ -87,7 +87,7 @@ class Stats(C.Structure):
         ("launches_extend", C.c_uint64), ("n_ext_wavefront", C.c_uint64),
         ("stack_depth", C.c_uint32), ("pool_capacity", C.c_uint32),
         ("energy", C.c_float), ("max_segments", C.c_uint32), ("tail_survivors", C.c_uint64),
-        ("frame_window", C.c_uint32),
+        ("frame_window", C.c_uint32), ("n_shadow_overflow", C.c_uint64),
     ]
 
     def as_dict(self) -> dict:
@@ -273,6 +273,7 @@ def load() -> C.CDLL:
         "surf_debug_connect_staging": ([P, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)], I32),
         "surf_debug_kernel_selection": ([P] + [C.POINTER(C.c_uint32)] * 4, I32),
         "surf_debug_segment_cycles": ([P, P, U32, P], I32),
+        "surf_debug_shadow_keys": ([P, U32, P, P, P, P, P, C.POINTER(U32), P], I32),
         "surf_upload_scene": ([P, C.POINTER(SceneDesc)], I32),
         "surf_set_camera": ([P, P], I32),
         "surf_render": ([P, U32, U32, U32, U32], I32),
@@ -1245,6 +1246,32 @@ class Renderer:
         v = [C.c_uint32() for _ in range(4)]
         _check(load().surf_debug_kernel_selection(self._h, *[C.byref(x) for x in v]), "surf_debug_kernel_selection", self._h)
         return dict(zip(("lds_tables", "stack16", "lane_two_level", "wave_eligible"), (bool(x.value) for x in v)))
+
+    def debug_shadow_keys(self, origins, directions, tmax, lights):
+        """(keys, bins, layout): the shadow queue's order bin of each of n rays --
+        origins and directions (n, 3) float32, tmax (n,) float32, light slots
+        (n,) uint32 -- under this context's key layout (SURF_SH_KEY), the
+        number of bins in use, and what the key reads of the scene: cell_lo
+        (3,), cell_scale (3,), heavy_lo and heavy_hi (n_heavy, 3), the heaviest
+        instance first (surf_debug_shadow_keys)."""
+        fn = getattr(load(), "surf_debug_shadow_keys", None)
+        if fn is None or fn.argtypes is None:
+            raise RuntimeError("the loaded library (SURF_HIP_LIB) was built before surf_debug_shadow_keys existed: rebuild it")
+        o = np.ascontiguousarray(origins, np.float32).reshape(-1, 3)
+        d = np.ascontiguousarray(directions, np.float32).reshape(-1, 3)
+        t = np.ascontiguousarray(tmax, np.float32).reshape(-1)
+        li = np.ascontiguousarray(lights, np.uint32).reshape(-1)
+        n = len(o)
+        if not (len(d) == len(t) == len(li) == n):
+            raise ValueError("debug_shadow_keys: origins, directions, tmax and lights differ in length")
+        keys = np.zeros(n, np.uint32)
+        bins = C.c_uint32()
+        lay = np.zeros(25, np.float32)
+        _check(fn(self._h, n, _ptr(o), _ptr(d), _ptr(t), _ptr(li), _ptr(keys), C.byref(bins), _ptr(lay)), "surf_debug_shadow_keys", self._h)
+        nh = int(lay[6])
+        boxes = lay[7:].reshape(3, 2, 3)[:nh]
+        return keys, int(bins.value), {"cell_lo": lay[0:3].copy(), "cell_scale": lay[3:6].copy(),
+                                       "heavy_lo": boxes[:, 0].copy(), "heavy_hi": boxes[:, 1].copy()}
 
     def debug_segment_cycles(self, origin, direction, throughput, seed: int, segment: int = 1, reps: int = 64):
         """Diagnostics: mean shader-clock cycles of one drain segment's pieces on

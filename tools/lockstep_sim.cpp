@@ -28,14 +28,15 @@ int main(int argc, char** argv) {
         if (ANY) tmx[i] = raw[(size_t)RS * i + 6];
     }
     if (argc > 2 && std::string(argv[2]) == "mask") {
-        // membership of every ray: bit k = instance k's world box is hit within [0, inf)
+        // membership of every ray: bit k = instance k's world box is hit within [0, inf),
+        // or within the shadow segment [0, tmax) with LOCKSTEP_ANY
         const Bvh& T = S.tlas; const Node& root = T.nodes[0];
         std::vector<uint32_t> m(n, 0);
         for (uint32_t i = 0; i < n; ++i) {
             V3 o = mk(od[6*i], od[6*i+1], od[6*i+2]), d = mk(od[6*i+3], od[6*i+4], od[6*i+5]);
             for (uint32_t k = 0; k < root.cnt; ++k) {
                 uint32_t ii = T.idx[root.lf + k];
-                if (slab(S.inst[ii].bounds, o, d, kFarAway) != kFarAway) m[i] |= 1u << ii;
+                if (slab(S.inst[ii].bounds, o, d, tmx[i]) != kFarAway) m[i] |= 1u << ii;
             }
         }
         FILE* g = fopen(argv[3], "wb"); fwrite(m.data(), 4, n, g); fclose(g);
