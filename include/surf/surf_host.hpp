@@ -359,6 +359,11 @@ public:
     /* ... as the planes denoise(), denoiseSampled() and the regression filter read
      * (surf_set_filter_guides_sampled); setFilterGuides switches back */
     void setFilterGuidesSampled(const surf_aov_sampled_params& params);
+    /* ray-traced ambient occlusion (surf_read_ao, which states the arithmetic): the openness plane
+     * (bent normal, open share; width*height*4 floats) and the bits plane (sample mask, open count,
+     * valid flag; width*height*4 words) of the current camera and scene */
+    std::vector<F32> readAO(const surf_ao_params& params);
+    std::vector<U32> readAOBits(const surf_ao_params& params);
     /* the rendered radiance through the edge-avoiding a-trous filter (surf_denoise; width*height*4
      * floats, w = 1): the accumulator and the feature buffers of the camera and scene of the last
      * render() call; the accumulator is left untouched.  The form without arguments takes

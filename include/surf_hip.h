@@ -513,6 +513,71 @@ int surf_debug_aov_sampled_time(surf_ctx* ctx, float* kernel_ms);
 #define SURF_GUIDES_SAMPLED 2
 int surf_set_filter_guides_sampled(surf_ctx* ctx, const surf_aov_sampled_params* p);
 
+/* ---- ray-traced ambient occlusion and bent normals ----
+ * The utility pass next to depth, normal, albedo and the mattes: from every
+ * visible point, cosine-weighted any-hit rays of a given length; the share
+ * that escapes is the openness, their mean direction the bent normal.  No
+ * reference counterpart.  All arithmetic f32 and uncontracted, divisions IEEE,
+ * so a host restatement reproduces both planes bit for bit.
+ * The source planes of a shard pixel are the first-hit planes
+ * (SURF_AO_FIRST_HIT) or the chain's at max_links (SURF_AO_CHAIN), computed
+ * and cached exactly as a read of them would: P = position.xyz,
+ * N = normal.xyz, valid = (albedo.w != 0); p = x + row * width over the whole
+ * frame (u32 wrap-around, as the render seeds).  For a valid pixel, for
+ * s = 0 .. samples-1:
+ *   1. seed = initSeed((p + 1799u * (first_sample + s)) ^ SURF_AO_SEED_SALT)
+ *      (u32 wrap-around; the salt keeps the draws off the render's own streams)
+ *   2. R = the render's cosine-weighted direction about N from that seed: two
+ *      draws r0, r1 per try, r = sqrtf(r0), theta = 2pi * r1, the glibc-exact
+ *      sinf / cosf, dir = (r cos, r sin, sqrtf(1 - r0)) in the frame
+ *      B = normalize(cross(N, |N.x| > 1 - 1e-5 ? (0,1,0) : (1,0,0))),
+ *      T = cross(B, N): R = ((dir.x*T + dir.y*B) + dir.z*N); retried while
+ *      R.N == 0
+ *   3. O = P + bias * R (the render's continuation offset, bias in place of 1e-5)
+ *   4. occluded = any hit of (O, R) within depth `radius`: the shadow rays' walk
+ * nOpen = the number of unoccluded samples; S = the sum of the unoccluded R,
+ * f32 from 0.0f, ONE ADD PER UNOCCLUDED SAMPLE IN SAMPLE ORDER (part of the
+ * interface).  Two planes of rows*width 16-byte records, shard row order:
+ *   SURF_AO_OPENNESS  float4  valid: (S / (float)nOpen, (float)nOpen / (float)samples);
+ *                             xyz is 0 when nOpen == 0; the bent normal is NOT
+ *                             renormalised: its length tells how tight the open
+ *                             cone is.  invalid: (0, 0, 0, 1) -- the sky is open
+ *   SURF_AO_BITS      uint4   valid: (mask bits 0-31, bits 32-63, nOpen, 1), bit s
+ *                             set when sample s was unoccluded; invalid: (0, 0, 0, 0)
+ * samples is one of 1, 2, 4, 8, 16, 32, 64, deliberately: a pixel's rays then
+ * sit in one aligned lane group of a wave, and nOpen / samples is exact.
+ * Occlusion is binary: the any-hit walk returns no distance, and that is what
+ * makes it the fast walk; a distance falloff is not offered.  Shading normals
+ * are used, as the render uses them, so on smooth meshes a few rays start
+ * below the geometric surface and report the mesh itself; that is left as it
+ * is.  radius and bias are finite or +inf, radius > 0, bias >= 0.
+ * Device buffers of their own, computed by one launch on the first read and
+ * cached until what drops surf_read_aov's planes (surf_set_camera,
+ * surf_upload_scene, surf_update_instances) or a read with other params.  A
+ * read never drains or changes the sample stream.  Row shards assemble to the
+ * frame.  Status codes as surf_read_aov_sampled; SURF_ERR_INVALID for a NULL
+ * pointer, a plane outside 0..1, samples not one of the seven, a radius or
+ * bias outside its range, an unknown source, max_links above
+ * SURF_AOV_CHAIN_MAX_LINKS or reserved != 0. */
+#define SURF_AO_SEED_SALT 0x5AD0CC1Du
+#define SURF_AO_MAX_SAMPLES 64
+typedef enum { SURF_AO_OPENNESS = 0, SURF_AO_BITS = 1, SURF_AO_COUNT = 2 } surf_ao_plane;
+typedef enum { SURF_AO_FIRST_HIT = 0, SURF_AO_CHAIN = 1 } surf_ao_source;
+typedef struct {
+    uint32_t samples;       /* 1, 2, 4, 8, 16, 32 or 64 */
+    uint32_t first_sample;  /* index of sample 0 */
+    float radius;           /* the rays' length, > 0 */
+    float bias;             /* the origin's offset along the ray, >= 0 */
+    uint32_t source;        /* SURF_AO_FIRST_HIT or SURF_AO_CHAIN */
+    uint32_t max_links;     /* of the chain planes; ignored with SURF_AO_FIRST_HIT */
+    uint32_t reserved[2];   /* 0 */
+} surf_ao_params;
+int surf_ao_default_params(surf_ao_params* p);   /* 16, 0, 1.0f, 1e-5f, SURF_AO_FIRST_HIT, 8, 0, 0 */
+int surf_read_ao(surf_ctx* ctx, const surf_ao_params* p, int plane, void* out);
+int surf_copy_ao_device(surf_ctx* ctx, const surf_ao_params* p, int plane, void* dst_device);
+/* Diagnostics: device time (HIP events) of the last occlusion kernel launch, 0 before the first. */
+int surf_debug_ao_time(surf_ctx* ctx, float* kernel_ms);
+
 /* ---- denoiser: edge-avoiding a-trous wavelet filter on the feature buffers ----
  * A pure post-process of the radiance (Dammertz et al. 2010, with albedo
  * demodulation): it reads the accumulator and the first-hit feature planes

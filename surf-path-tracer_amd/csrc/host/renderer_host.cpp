@@ -163,6 +163,20 @@ void WaveFrontRenderer::setFilterGuidesSampled(const surf_aov_sampled_params& pa
     check(surf_set_filter_guides_sampled(m_ctx, &params), m_ctx, "surf_set_filter_guides_sampled");
 }
 
+std::vector<F32> WaveFrontRenderer::readAO(const surf_ao_params& params) {
+    pushSceneAndCamera();
+    std::vector<F32> out((size_t)m_resolution.width * m_resolution.height * 4);
+    check(surf_read_ao(m_ctx, &params, SURF_AO_OPENNESS, out.data()), m_ctx, "surf_read_ao");
+    return out;
+}
+
+std::vector<U32> WaveFrontRenderer::readAOBits(const surf_ao_params& params) {
+    pushSceneAndCamera();
+    std::vector<U32> out((size_t)m_resolution.width * m_resolution.height * 4);
+    check(surf_read_ao(m_ctx, &params, SURF_AO_BITS, out.data()), m_ctx, "surf_read_ao");
+    return out;
+}
+
 /* The filter reads the accumulator beside the feature buffers, so it keeps
  * the camera and the scene of the last render() call: those the accumulated
  * samples saw. */

@@ -88,6 +88,7 @@ void setKeys(surf_ctx* c, DevScene& S, const InstanceTables& T) {
     c->aovValid = false;                  /* ... and so do the feature buffers */
     c->aovChainValid = false;
     c->aovSampledValid = false;
+    c->aoValid = false;
     S.nHeavy = T.nHeavy;
     for (uint32_t h = 0; h < 3; ++h) {
         S.hvLo[h] = h < T.nHeavy ? T.hvLo[h] : make_float4(0, 0, 0, 0);

@@ -123,6 +123,13 @@ struct surf_ctx {
     surf_aov_sampled_params aovSampledParams{};   /* the params the cached planes were traced with */
     float aovSampledKernelMs = 0.0f;   /* device time of the last k_aov_sampled launch (surf_debug_aov_sampled_time) */
     surf_aov_sampled_params guideSampled{};       /* the params of SURF_GUIDES_SAMPLED (surf_set_filter_guides_sampled) */
+    /* ambient occlusion (surf_read_ao): two planes of their own, valid until
+     * what clears aovValid or a read with other params */
+    void* ao[SURF_AO_COUNT] = {};
+    bool aoValid = false;
+    surf_ao_params aoParams{};         /* the params the cached planes were traced with */
+    float aoKernelMs = 0.0f;           /* device time of the last k_ao launch (surf_debug_ao_time) */
+    bool aoRayMap = true;              /* A/B (SURF_AO_MAP): one lane per ray (1), one lane per pixel (0) */
     /* the a-trous denoiser (surf_denoise*, host/denoise.hip): dn, the scratch
      * every a-trous filter runs in -- the two ping-pong levels, the packed
      * normal and position guides -- and, for surf_denoise_image, the four

@@ -20,6 +20,7 @@
 
 #include "device/wavefront_kernels.h"
 #include "device/aov_sampled_kernels.h"
+#include "device/ao_kernels.h"
 
 namespace {
 
@@ -155,6 +156,13 @@ auto traceAnyKernel(const surf_ctx* c, const Variant& v) { return kernel(SURF_PI
 auto aovKernel(const surf_ctx* c, const Variant& v) { return kernel(SURF_PICK2(k_aov, v.lds, v.laneW), laneLds(c, kBlock, false, v.lds)); }
 auto aovChainKernel(const surf_ctx* c, const Variant& v) { return kernel(SURF_PICK2(k_aov_chain, v.lds, v.laneW), laneLds(c, kBlock, false, v.lds)); }
 auto aovSampledKernel(const surf_ctx* c, const Variant& v) { return kernel(SURF_PICK2(k_aov_sampled, v.lds, v.laneW), laneLds(c, kBlock, false, v.lds)); }
+/* k_ao<LDS, LW, RAY>: the lane mapping is the context's (SURF_AO_MAP) */
+template <bool RAY>
+auto aoFn(const Variant& v) {
+    return v.lds ? (v.laneW ? k_ao<true, true, RAY> : k_ao<true, false, RAY>) : (v.laneW ? k_ao<false, true, RAY> : k_ao<false, false, RAY>);
+}
+auto aoKernel(const surf_ctx* c, const Variant& v) { return kernel(c->aoRayMap ? aoFn<true>(v) : aoFn<false>(v), laneLds(c, kBlock, false, v.lds)); }
+static_assert(kAoSeedSalt == SURF_AO_SEED_SALT, "the kernel's salt is the header's");
 auto tailKernel(const surf_ctx* c, const Variant& v) { return kernel(v.lds ? k_tail<true> : k_tail<false>, laneLds(c, 64, false, v.lds)); }
 
 /* the one-ray-per-wave kernels over <LDS, W2> */
@@ -604,6 +612,50 @@ int ensureAovSampled(surf_ctx* c, const surf_aov_sampled_params& q) {
     (void)hipEventElapsedTime(&c->aovSampledKernelMs, c->ev0, c->ev1);
     c->aovSampledParams = q;
     c->aovSampledValid = true;
+    return SURF_OK;
+}
+
+/* surf_ao_params as the header states them */
+bool aoParamsOk(const surf_ao_params* p) {
+    const auto ranged = [](float v, bool zeroOk) { return !std::isnan(v) && (v > 0.0f || (zeroOk && v == 0.0f)); };
+    return p && p->samples >= 1u && p->samples <= SURF_AO_MAX_SAMPLES && (p->samples & (p->samples - 1u)) == 0u && ranged(p->radius, false) &&
+           ranged(p->bias, true) && (p->source == SURF_AO_FIRST_HIT || p->source == SURF_AO_CHAIN) &&
+           (p->source == SURF_AO_FIRST_HIT || p->max_links <= SURF_AOV_CHAIN_MAX_LINKS) && p->reserved[0] == 0u && p->reserved[1] == 0u;
+}
+
+/* The two occlusion planes (k_ao), in device planes of their own: kept until
+ * what drops the first-hit planes, or a read with other params.  The source
+ * planes first, as a read of them would compute them; then one launch on the
+ * render stream, as ensureAov. */
+int ensureAo(surf_ctx* c, const surf_ao_params& q) {
+    if (!aoParamsOk(&q))
+        return fail(c, SURF_ERR_INVALID, "ambient occlusion: samples not a power of two in 1.." + std::to_string(SURF_AO_MAX_SAMPLES) +
+                                             ", radius not > 0, bias not >= 0, an unknown source, max_links above SURF_AOV_CHAIN_MAX_LINKS or reserved != 0");
+    const bool chain = q.source == SURF_AO_CHAIN;
+    if (int rc = chain ? ensureAovChain(c, q.max_links) : ensureAov(c)) return rc;
+    if (c->aoValid && std::memcmp(&c->aoParams, &q, sizeof q) == 0) return SURF_OK;
+    c->aoValid = false;
+    for (void*& p : c->ao)
+        if (!p && (hipMalloc(&p, (size_t)c->npx * 16) != hipSuccess || !p)) {
+            p = nullptr;
+            (void)hipGetLastError();
+            return fail(c, SURF_ERR_OOM, "hipMalloc of an occlusion plane (" + std::to_string((size_t)c->npx * 16) + " bytes) failed");
+        }
+    void* const* src = chain ? c->aovChain : c->aov;
+    /* pixels per block: one per lane, or one per group of `samples` lanes */
+    const uint32_t perBlock = c->aoRayMap ? (uint32_t)kBlock / q.samples : (uint32_t)kBlock;
+    SURF_CHECK(c, hipEventRecord(c->ev0, c->stream));
+    const auto ao = aoKernel(c, variantOf(c));
+    hipLaunchKernelGGL(ao.fn, dim3((c->npx + perBlock - 1) / perBlock), dim3(kBlock), ao.lds, c->stream, c->S, (const uint32_t*)c->dRows, c->width, c->npx, q.samples, q.first_sample, q.radius, q.bias,
+                       static_cast<const float4*>(src[SURF_AOV_POSITION]), static_cast<const float4*>(src[SURF_AOV_NORMAL]),
+                       static_cast<const float4*>(src[SURF_AOV_ALBEDO]), static_cast<float4*>(c->ao[SURF_AO_OPENNESS]),
+                       static_cast<uint4*>(c->ao[SURF_AO_BITS]), stackWords(c, kBlock));
+    SURF_CHECK(c, hipGetLastError());
+    SURF_CHECK(c, hipEventRecord(c->ev1, c->stream));
+    SURF_CHECK(c, hipEventSynchronize(c->ev1));
+    (void)hipEventElapsedTime(&c->aoKernelMs, c->ev0, c->ev1);
+    c->aoParams = q;
+    c->aoValid = true;
     return SURF_OK;
 }
 
@@ -1172,6 +1224,7 @@ int createCtx(int dev, uint32_t w, uint32_t h, std::vector<uint32_t> rows, surf_
     if (const char* e = std::getenv("SURF_SVGF_LDS")) c->svVarStaged = std::atoi(e) != 0;
     if (const char* e = std::getenv("SURF_NLM_LDS")) c->nlStaged = std::atoi(e) != 0;
     if (const char* e = std::getenv("SURF_REGRESS_LDS")) c->rgStaged = std::atoi(e) != 0;
+    if (const char* e = std::getenv("SURF_AO_MAP")) c->aoRayMap = e[0] != '0';
     c->width = w;
     c->height = h;
     c->rows = std::move(rows);
@@ -1251,6 +1304,7 @@ void surf_destroy(surf_ctx* c) {
     for (void*& p : c->aov) { if (p) (void)hipFree(p); p = nullptr; }
     for (void*& p : c->aovChain) { if (p) (void)hipFree(p); p = nullptr; }
     for (void*& p : c->aovSampled) { if (p) (void)hipFree(p); p = nullptr; }
+    for (void*& p : c->ao) { if (p) (void)hipFree(p); p = nullptr; }
     freeDenoise(c);
     freeTemporal(c);
     freeAdaptive(c);
@@ -1416,6 +1470,7 @@ int surf_set_camera(surf_ctx* c, const surf_camera_ubo* u) {
     c->aovValid = false;
     c->aovChainValid = false;
     c->aovSampledValid = false;
+    c->aoValid = false;
     c->camUbo = *u;
     c->hasCamera = true;
     destroyGraph(c);     /* camera is a kernel argument of the captured graph */
@@ -1696,6 +1751,32 @@ int surf_copy_aov_sampled_device(surf_ctx* c, const surf_aov_sampled_params* p, 
 int surf_debug_aov_sampled_time(surf_ctx* c, float* kernel_ms) {
     if (!c || !kernel_ms) return SURF_ERR_INVALID;
     *kernel_ms = c->aovSampledKernelMs;
+    return SURF_OK;
+}
+
+int surf_ao_default_params(surf_ao_params* p) {
+    if (!p) return SURF_ERR_INVALID;
+    *p = surf_ao_params{16u, 0u, 1.0f, 1e-5f, SURF_AO_FIRST_HIT, 8u, {0u, 0u}};
+    return SURF_OK;
+}
+
+/* surf_read_ao / surf_copy_ao_device */
+static int copyAo(surf_ctx* c, const surf_ao_params* p, int plane, void* dst, hipMemcpyKind kind) {
+    if (!c || !p || !dst || plane < 0 || plane >= SURF_AO_COUNT) return SURF_ERR_INVALID;
+    int rc = ensureAo(c, *p);
+    if (rc) return rc;
+    SURF_CHECK(c, hipMemcpyAsync(dst, c->ao[plane], (size_t)c->npx * 16, kind, c->stream));
+    SURF_CHECK(c, hipStreamSynchronize(c->stream));
+    return SURF_OK;
+}
+
+int surf_read_ao(surf_ctx* c, const surf_ao_params* p, int plane, void* out) { return copyAo(c, p, plane, out, hipMemcpyDeviceToHost); }
+
+int surf_copy_ao_device(surf_ctx* c, const surf_ao_params* p, int plane, void* dst) { return copyAo(c, p, plane, dst, hipMemcpyDeviceToDevice); }
+
+int surf_debug_ao_time(surf_ctx* c, float* kernel_ms) {
+    if (!c || !kernel_ms) return SURF_ERR_INVALID;
+    *kernel_ms = c->aoKernelMs;
     return SURF_OK;
 }
 

@@ -15,6 +15,7 @@ Mirrors the reference interface for the hot path:
     .aov()                     first-hit feature buffers (no reference counterpart)
     .aov_chain(max_links)      the same planes traced through mirrors and glass; .set_filter_guides("chain") guides
                                denoise() and denoise_sampled() with them (no reference counterpart)
+    .ao(samples, radius)       ray-traced ambient occlusion and bent normals from the first-hit or chain planes
     .aov_sampled(samples)      the features of the camera rays render() traces, reduced per pixel: anti-aliased planes and an
                                id coverage matte (matte_coverage); .set_filter_guides("sampled") guides the same filters
     .denoise()                 edge-avoiding a-trous filter on them (no reference counterpart)
@@ -241,6 +242,12 @@ class AovSampledParams(C.Structure):
     _fields_ = [("samples", C.c_uint32), ("first_sample", C.c_uint32), ("key", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class AoParams(C.Structure):
+    """surf_ao_params: the rays per pixel, the index of the first, their length and origin offset, the source planes."""
+    _fields_ = [("samples", C.c_uint32), ("first_sample", C.c_uint32), ("radius", C.c_float), ("bias", C.c_float),
+                ("source", C.c_uint32), ("max_links", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
 _lib = None
 
 # Byte sizes of the reference records (include/surf_hip.h static_asserts).
@@ -303,6 +310,10 @@ def load() -> C.CDLL:
         "surf_copy_aov_sampled_device": ([P, C.POINTER(AovSampledParams), I32, P], I32),
         "surf_debug_aov_sampled_time": ([P, C.POINTER(F)], I32),
         "surf_set_filter_guides_sampled": ([P, C.POINTER(AovSampledParams)], I32),
+        "surf_ao_default_params": ([C.POINTER(AoParams)], I32),
+        "surf_read_ao": ([P, C.POINTER(AoParams), I32, P], I32),
+        "surf_copy_ao_device": ([P, C.POINTER(AoParams), I32, P], I32),
+        "surf_debug_ao_time": ([P, C.POINTER(F)], I32),
         "surf_write_pfm": ([C.c_char_p, U32, U32, P], I32),
         "surf_denoise_default_params": ([C.POINTER(DenoiseParams)], I32),
         "surf_denoise": ([P, C.POINTER(DenoiseParams), P], I32),
@@ -597,6 +608,30 @@ def aov_sampled_params(samples=16, first_sample=0, key="instance") -> AovSampled
     if f != first_sample or not 0 <= f <= 0xFFFFFFFF:
         raise ValueError(f"first_sample {first_sample!r}: an unsigned 32-bit integer")
     return AovSampledParams(n, f, MATTE_KEYS.index(key), 0)
+
+
+AO_PLANES = ("openness", "bits")                         # surf_ao_plane order
+AO_SOURCES = ("first_hit", "chain")                      # surf_ao_source order
+AO_SAMPLES = (1, 2, 4, 8, 16, 32, 64)                    # a pixel's rays fill an aligned lane group of a wave
+
+
+def ao_params(samples=16, radius=1.0, first_sample=0, bias=1e-5, source="first_hit", max_links=8) -> AoParams:
+    """surf_ao_params, checked before the library sees them."""
+    if source not in AO_SOURCES:
+        raise ValueError(f"source {source!r}: one of {AO_SOURCES}")
+    if isinstance(samples, bool) or samples not in AO_SAMPLES:
+        raise ValueError(f"samples {samples!r}: one of {AO_SAMPLES}")
+    f, links = int(first_sample), int(max_links)
+    if f != first_sample or not 0 <= f <= 0xFFFFFFFF:
+        raise ValueError(f"first_sample {first_sample!r}: an unsigned 32-bit integer")
+    if links != max_links or not 0 <= links <= AOV_CHAIN_MAX_LINKS:
+        raise ValueError(f"max_links {max_links!r}: an integer in 0..{AOV_CHAIN_MAX_LINKS}")
+    rad, b = np.float32(radius), np.float32(bias)
+    if not rad > 0.0:                                    # NaN fails every comparison
+        raise ValueError(f"radius {radius!r}: above 0 (inf allowed)")
+    if not b >= 0.0:
+        raise ValueError(f"bias {bias!r}: 0 or above")
+    return AoParams(int(samples), f, float(rad), float(b), AO_SOURCES.index(source), links, (C.c_uint32 * 2)(0, 0))
 
 
 def matte_coverage(keys, counts, key: int, samples: int) -> np.ndarray:
@@ -1420,6 +1455,35 @@ class Renderer:
         """Device milliseconds of the last sampled-planes kernel launch (surf_debug_aov_sampled_time)."""
         ms = C.c_float()
         _check(load().surf_debug_aov_sampled_time(self._h, C.byref(ms)), "surf_debug_aov_sampled_time", self._h)
+        return float(ms.value)
+
+    def ao(self, samples: int = 16, radius: float = 1.0, first_sample: int = 0, bias: float = 1e-5, source: str = "first_hit",
+           max_links: int = 8) -> dict:
+        """Ray-traced ambient occlusion and bent normals (surf_read_ao, which
+        states the arithmetic): `samples` cosine-weighted any-hit rays of length
+        `radius` from every visible point of aov() (source "first_hit") or
+        aov_chain(max_links) ("chain").  AO_PLANES as (rows, width, 4):
+        'openness' float32 (xyz the mean unoccluded direction, not renormalised;
+        w the unoccluded share, 1 on a miss pixel) and 'bits' uint32 (the sample
+        mask's two words, the open count, 1 on a valid pixel).  Cached like
+        aov(), per parameter set."""
+        q = ao_params(samples, radius, first_sample, bias, source, max_links)
+        out = {}
+        for k, name in enumerate(AO_PLANES):
+            a = np.zeros((len(self.rows), self.width, 4), dtype=np.float32 if k == 0 else np.uint32)
+            _check(load().surf_read_ao(self._h, C.byref(q), k, _ptr(a)), "surf_read_ao", self._h)
+            out[name] = a
+        return out
+
+    def copy_ao_to(self, plane: int, device_ptr: int, **params):
+        """One occlusion plane (index into AO_PLANES) into device memory of rows * width * 16 bytes (surf_copy_ao_device)."""
+        q = ao_params(**params)
+        _check(load().surf_copy_ao_device(self._h, C.byref(q), plane, C.c_void_p(device_ptr)), "surf_copy_ao_device", self._h)
+
+    def debug_ao_time(self) -> float:
+        """Device milliseconds of the last occlusion kernel launch (surf_debug_ao_time)."""
+        ms = C.c_float()
+        _check(load().surf_debug_ao_time(self._h, C.byref(ms)), "surf_debug_ao_time", self._h)
         return float(ms.value)
 
     def set_filter_guides(self, guides: str = "first_hit", max_links: int = 8, samples: int = 16, first_sample: int = 0):
