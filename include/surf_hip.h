@@ -272,6 +272,38 @@ int surf_debug_shadow_keys(surf_ctx* ctx, uint32_t n, const float* o, const floa
  * reference counterpart. */
 int surf_debug_kernel_selection(surf_ctx* ctx, uint32_t* lds_tables, uint32_t* stack16, uint32_t* lane_two_level,
                                 uint32_t* wave_eligible);
+/* Diagnostics: the kernels' libm (gExpf, gSinf, gCosf, gSinCosf of
+ * csrc/device/surf_math.h, the restatements of glibc's expf / sinf / cosf /
+ * sincosf) on the device, compiled as the render kernels use them, one lane
+ * per element of `in` (n floats).  out receives n floats, or for
+ * SURF_MATH_SINCOSF 2n: (sin, cos) per element.  Needs no scene.  The header
+ * states where each equals glibc bit for bit (expf everywhere, the others for
+ * |y| < 120).  No reference counterpart. */
+typedef enum { SURF_MATH_EXPF = 0, SURF_MATH_SINF = 1, SURF_MATH_COSF = 2, SURF_MATH_SINCOSF = 3 } surf_math_op;
+int surf_debug_math(surf_ctx* ctx, int op, uint32_t n, const float* in, float* out);
+/* ... and the same ops and output layout through the library's host build of
+ * the same source (no context, no device): which side a device mismatch is on. */
+int surf_debug_math_host(int op, uint32_t n, const float* in, float* out);
+/* Diagnostics: planted paths.  Path i starts at o[3i..] toward d[3i..] with RNG
+ * state seed[i] (as Renderer::trace is entered: throughput 1, no medium, the
+ * last bounce specular) and is traced to its end on the device with the
+ * render kernels' own device functions -- no camera, no seed derivation, no
+ * queues:
+ *   mode 0  one path per lane: the lane walk, shadePath<false> and the lane
+ *           any-hit walk -- what k_extend, k_shade and k_connect run;
+ *   mode 1  one path per wave: traceWave, shadePath<true> and the wave any-hit
+ *           walk with the context's table staging -- what the cooperative
+ *           drains run.  SURF_ERR_INVALID where surf_set_trace_mode(1) is.
+ * A path's contributions are added in the reference's order
+ * (renderer.cpp:338-444).  The throughput cutoff follows surf_set_zero_cutoff
+ * (automatic: on, a planted path being a one-sample frame).  max_segments caps
+ * the path as surf_render's does and must be 1..4096 (SURF_ERR_INVALID
+ * otherwise), so no planted path can run without end.
+ * out_energy_segments: 4 words per path -- the energy (3 floats) and the
+ * number of segments (u32 bits); out_seed[i]: the RNG state after the path's
+ * last draw.  Needs an uploaded scene.  No reference counterpart. */
+int surf_debug_trace_paths(surf_ctx* ctx, uint32_t n, const float* o, const float* d, const uint32_t* seed, uint32_t max_segments,
+                           int mode, float* out_energy_segments, uint32_t* out_seed);
 /* When enabled, per-kernel device times are measured with HIP events on the
  * render stream (slower: disables the graph replay). */
 int surf_set_profiling(surf_ctx* ctx, int enabled);

@@ -67,6 +67,9 @@ def load():
         "orc_set_zero_cutoff": ([I32], None),
         "orc_bvh_build": ([P, U32, P, P], U32),
         "orc_obj_load": ([C.c_char_p, P, P, C.c_uint64], C.c_long),
+        "orc_shade_census": ([P], None),
+        "orc_trace_paths": ([P, U32, P, P, P, U32, P], None),
+        "orc_libm_map": ([I32, C.c_uint64, P, P], I32),
     }
     for name, (args, res) in sig.items():
         fn = getattr(lib, name)
@@ -259,6 +262,19 @@ class OracleScene:
         load().orc_trace_visits(self._h, len(o), _p(o), _p(d), _p(nodes), _p(tris))
         return nodes, tris
 
+    def trace_paths(self, o, d, seeds, max_segments=0):
+        """Planted paths (orc_trace_paths): trace() from each origin, direction
+        and RNG state.  Returns (energy (n, 3) float32, segments (n,) uint32,
+        final seeds (n,) uint32); follows set_zero_cutoff."""
+        o = np.ascontiguousarray(o, np.float32).reshape(-1, 3)
+        d = np.ascontiguousarray(d, np.float32).reshape(-1, 3)
+        s = np.array(seeds, np.uint32).reshape(-1)
+        if not (len(o) == len(d) == len(s)):
+            raise ValueError("trace_paths: origins, directions and seeds differ in length")
+        out = np.zeros((len(o), 4), np.float32)
+        load().orc_trace_paths(self._h, len(o), _p(o), _p(d), _p(s), max_segments, _p(out))
+        return out[:, :3].copy(), out[:, 3].copy().view(np.uint32), s
+
     def update(self, dt: float):
         """GPUScene::update: rotate instance 3 by dt radians about +y, refit the TLAS."""
         load().orc_scene_update(self._h, dt)
@@ -298,6 +314,30 @@ class OracleScene:
 def set_zero_cutoff(on: bool):
     """Radiance-neutral early end of zero-throughput paths (default off = reference)."""
     load().orc_set_zero_cutoff(1 if on else 0)
+
+
+CENSUS = ("medium_segments", "exp_below_60", "exp_denormal", "exp_zero", "dielectric_outside", "tir_outside", "tir_inside",
+          "fresnel_reflect", "refract", "mirror", "diffuse", "rr_clamped", "rr_zero", "cutoff_kills", "cosine_retries")
+
+
+def shade_census() -> dict:
+    """The shading census (orc_shade_census) of every trace since the last call,
+    by name; reading resets it."""
+    out = np.zeros(len(CENSUS), np.uint64)
+    load().orc_shade_census(_p(out))
+    return {k: int(v) for k, v in zip(CENSUS, out)}
+
+
+LIBM_OPS = ("expf", "sinf", "cosf")
+
+
+def libm(op: str, x) -> np.ndarray:
+    """This machine's glibc expf / sinf / cosf over a float32 array (orc_libm_map)."""
+    x = np.ascontiguousarray(x, np.float32).reshape(-1)
+    out = np.empty_like(x)
+    rc = load().orc_libm_map(LIBM_OPS.index(op), len(x), _p(x), _p(out))
+    assert rc == 0, rc
+    return out
 
 
 def init_seed(s: int) -> int:

@@ -16,6 +16,7 @@
  */
 #include "cpu_ref.h"
 
+#include <atomic>
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
@@ -745,6 +746,26 @@ void primaryRay(const Scene& S, uint32_t& seed, float x, float y, V3& o, V3& d) 
     d = normalize(plane - origin);
 }
 
+/* Shading census (orc_shade_census): which branches of trace() the paths
+ * took.  Counting only -- no counter feeds back into a path.  Each thread
+ * counts in its own block and censusFlush() adds the block to the shared
+ * totals with atomic increments when the thread's share of a call is done. */
+enum {
+    kCsMediumSegments, kCsExpBelow60, kCsExpDenormal, kCsExpZero, kCsDielectricOutside, kCsTirOutside, kCsTirInside,
+    kCsFresnelReflect, kCsRefract, kCsMirror, kCsDiffuse, kCsRrClamped, kCsRrZero, kCsCutoffKills, kCsCosineRetries, kCsN
+};
+thread_local uint64_t tCensus[kCsN];
+std::atomic<uint64_t> gCensus[kCsN];
+void censusFlush() {
+    for (int k = 0; k < kCsN; ++k)
+        if (tCensus[k]) { gCensus[k].fetch_add(tCensus[k], std::memory_order_relaxed); tCensus[k] = 0; }
+}
+inline void censusExp(float arg, float res) {
+    if (arg < -60.0f) tCensus[kCsExpBelow60]++;
+    if (res != 0.0f && res < 1.17549435e-38f) tCensus[kCsExpDenormal]++;
+    if (arg < 0.0f && res == 0.0f) tCensus[kCsExpZero]++;
+}
+
 /* randomOnHemisphereCosineWeighted, surf_math.cpp:116-134 */
 V3 cosineSample(uint32_t& seed, V3 n) {
     for (;;) {
@@ -758,6 +779,7 @@ V3 cosineSample(uint32_t& seed, V3 n) {
         V3 T = cross(B, n);
         V3 out = ((dir.x * T) + (dir.y * B)) + (dir.z * n);
         if (!(dot(out, n) == 0.0f)) return out;
+        tCensus[kCsCosineRetries]++;
     }
 }
 
@@ -812,7 +834,10 @@ V3 trace(const Scene& S, uint32_t& seed, V3 o, V3 d, uint32_t maxSeg, Counters& 
             break;
         }
         V3 medium = splat(1.0f);
-        if (inMedium) { float nd = -depth; V3 a = m->absorption * nd; medium = mk(expf(a.x), expf(a.y), expf(a.z)); }   /* :354-356 */
+        if (inMedium) {
+            float nd = -depth; V3 a = m->absorption * nd; medium = mk(expf(a.x), expf(a.y), expf(a.z));   /* :354-356 */
+            tCensus[kCsMediumSegments]++; censusExp(a.x, medium.x); censusExp(a.y, medium.y); censusExp(a.z, medium.z);
+        }
         V3 I = o + depth * d;                                              /* Ray::hitPosition, ray.h:63-66 */
         /* Instance::normal (bvh.cpp:515-522) over Mesh::normal (mesh.h:63-68) */
         const TriExt& x = mesh->ext[h.prim];
@@ -827,11 +852,13 @@ V3 trace(const Scene& S, uint32_t& seed, V3 o, V3 d, uint32_t maxSeg, Counters& 
         bool nextMedium = inMedium;
         if (dot(d, N) > 0.0f) N = N * -1.0f;                               /* :367-368 */
         if (rng < m->refl) {                                               /* :370-375 */
+            tCensus[kCsMirror]++;
             R = reflect(d, N);
             lastSpecular = true;
             T = T * (m->albedo * medium);
         } else if (rng < (m->refl + m->refr)) {                            /* :376-404 */
             bool mustRefract = false;
+            if (!inMedium) tCensus[kCsDielectricOutside]++;
             R = reflect(d, N);
             float n1 = inMedium ? m->ior : 1.0f, n2 = inMedium ? 1.0f : m->ior;
             float ratio = n1 / n2;
@@ -844,11 +871,13 @@ V3 trace(const Scene& S, uint32_t& seed, V3 o, V3 d, uint32_t maxSeg, Counters& 
                 float fres = r0 + (1.0f - r0) * ((((c * c) * c) * c) * c);
                 mustRefract = rndF(seed) > fres;
                 if (mustRefract) R = (ratio * d) + ((ratio * cosI - sqrtf(fabsf(cos2))) * N);
-            }
+                tCensus[mustRefract ? kCsRefract : kCsFresnelReflect]++;
+            } else tCensus[inMedium ? kCsTirInside : kCsTirOutside]++;
             lastSpecular = true;
             T = T * (m->albedo * medium);
             nextMedium = mustRefract ? !inMedium : inMedium;
         } else {                                                           /* :405-455 */
+            tCensus[kCsDiffuse]++;
             R = cosineSample(seed, N);
             uint32_t nL = (uint32_t)S.lights.size();
             float cosT = dot(N, R);
@@ -894,6 +923,8 @@ V3 trace(const Scene& S, uint32_t& seed, V3 o, V3 d, uint32_t maxSeg, Counters& 
                 }
             }
             const float p = clampf(tmax(T.x, tmax(T.y, T.z)), 0.0f, 1.0f);   /* :446-448 */
+            if (tmax(T.x, tmax(T.y, T.z)) > 1.0f) tCensus[kCsRrClamped]++;
+            if (p == 0.0f) tCensus[kCsRrZero]++;
             if (p < rndF(seed)) break;
             float rr = 1.0f / p;
             float invPdf = 1.0f / pdf;
@@ -901,7 +932,7 @@ V3 trace(const Scene& S, uint32_t& seed, V3 o, V3 d, uint32_t maxSeg, Counters& 
             T = T * ((((cosT * invPdf) * brdf) * medium) * rr);
         }
         if (maxSeg != 0 && seg >= maxSeg) break;     /* C2 path-length cap */
-        if (gZeroCutoff && T.x < 1.17549435e-38f && T.y < 1.17549435e-38f && T.z < 1.17549435e-38f) break;
+        if (gZeroCutoff && T.x < 1.17549435e-38f && T.y < 1.17549435e-38f && T.z < 1.17549435e-38f) { tCensus[kCsCutoffKills]++; break; }
         C.cont++;
         o = I + kEps * R;                                                  /* :458-460 */
         d = R;
@@ -1086,6 +1117,7 @@ double orc_render_rows_spp(orc_scene* h, uint32_t W, uint32_t H, const uint32_t*
                 }
             }
         }
+        censusFlush();
         #pragma omp critical
         {
             tot.ext += C.ext; tot.hit += C.hit; tot.cont += C.cont; tot.sh += C.sh; tot.acc += C.acc; tot.unocc += C.unocc;
@@ -1168,6 +1200,7 @@ void orc_path_lengths(orc_scene* h, uint32_t W, uint32_t H, uint32_t frame, uint
             trace(S, seed, o, d, 0, C, nullptr, sm);
             out[p] = (uint32_t)(C.ext - e0);
         }
+        censusFlush();
     }
 }
 
@@ -1243,6 +1276,7 @@ void orc_record_rays(orc_scene* h, uint32_t W, uint32_t H, uint32_t frame, uint3
         primaryRay(S, seed, (float)x + jx, (float)y + jy, o, d);
         trace(S, seed, o, d, 0, C, &rec, sm);
     }
+    censusFlush();
     *nExt = rec.nExt; *nSh = rec.nSh;
 }
 
@@ -1305,6 +1339,38 @@ uint32_t orc_bvh_build(const float* tris, uint32_t n, uint32_t* idxOut, float* n
 }
 
 void orc_set_zero_cutoff(int on) { gZeroCutoff = on != 0; }
+
+/* The shading census since the last call, in the header's order; resets it. */
+void orc_shade_census(uint64_t* out15) {
+    for (int k = 0; k < kCsN; ++k) out15[k] = gCensus[k].exchange(0, std::memory_order_relaxed);
+}
+
+/* trace() as it stands from a caller's ray and RNG state: no camera, no seed
+ * derivation.  out: 4 words per path, the energy (3 floats) and the segment
+ * count (u32); seed: the state after the path's last draw. */
+void orc_trace_paths(const orc_scene* h, uint32_t n, const float* o, const float* d, uint32_t* seed, uint32_t maxSeg, float* out) {
+    const Scene& S = *h->s;
+    #pragma omp parallel
+    {
+        #pragma omp for schedule(dynamic, 16)
+        for (int64_t i = 0; i < (int64_t)n; ++i) {
+            Counters C; uint32_t sm = 0;
+            uint32_t sd = seed[i];
+            const V3 e = trace(S, sd, mk(o[3 * i], o[3 * i + 1], o[3 * i + 2]), mk(d[3 * i], d[3 * i + 1], d[3 * i + 2]), maxSeg, C, nullptr, sm);
+            const uint32_t segs = (uint32_t)C.maxSeg;
+            out[4 * i] = e.x; out[4 * i + 1] = e.y; out[4 * i + 2] = e.z; memcpy(out + 4 * i + 3, &segs, 4);
+            seed[i] = sd;
+        }
+        censusFlush();
+    }
+}
+
+/* This machine's glibc over an array: op 0 expf, 1 sinf, 2 cosf; -1 for another op. */
+int orc_libm_map(int op, uint64_t n, const float* in, float* out) {
+    if (op < 0 || op > 2) return -1;
+    for (uint64_t i = 0; i < n; ++i) out[i] = op == 0 ? expf(in[i]) : (op == 1 ? sinf(in[i]) : cosf(in[i]));
+    return 0;
+}
 
 uint32_t orc_init_seed(uint32_t s) { return seedOf(s); }
 uint32_t orc_random_u32(uint32_t* s) { return rndU(*s); }

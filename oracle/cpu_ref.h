@@ -158,6 +158,37 @@ void orc_bvh_depths(const orc_scene*, uint32_t* tlas_depth, uint32_t* max_blas_d
 /* Ends paths whose throughput is exactly zero (radiance-neutral; see cpu_ref.cpp).
  * Default off = reference semantics. */
 void orc_set_zero_cutoff(int on);
+
+/* Shading census: which branches of Renderer::trace's loop body the paths of
+ * every call since the last orc_shade_census took (renders, orc_trace_paths,
+ * orc_record_rays, orc_path_lengths; process-wide, kept with atomic
+ * increments).  Counting only: no arithmetic of trace() depends on it.
+ * Reads the 15 counters into out15 and resets them:
+ *   [0] medium_segments     shading events (non-emitter hits) with inMedium
+ *   [1] exp_below_60        absorption channels whose expf argument is < -60
+ *   [2] exp_denormal        ... whose expf result is nonzero and below FLT_MIN
+ *   [3] exp_zero            ... whose argument is < 0 and whose result is 0
+ *   [4] dielectric_outside  dielectric branch (renderer.cpp:376-404) taken outside a medium
+ *   [5] tir_outside         !(cos2 > 0) outside a medium (needs ior < 1)
+ *   [6] tir_inside          !(cos2 > 0) inside a medium
+ *   [7] fresnel_reflect     cos2 > 0 and the Fresnel draw reflects
+ *   [8] refract             cos2 > 0 and the Fresnel draw refracts
+ *   [9] mirror              mirror branch (:370-375)
+ *  [10] diffuse             diffuse branch (:405-455)
+ *  [11] rr_clamped          max(T) > 1 at the roulette (:446-448)
+ *  [12] rr_zero             roulette probability p == 0
+ *  [13] cutoff_kills        paths ended by orc_set_zero_cutoff's test
+ *  [14] cosine_retries      retries of randomOnHemisphereCosineWeighted's loop (dot(out, n) == 0) */
+void orc_shade_census(uint64_t* out15);
+/* Planted paths: Renderer::trace (this file's trace(), unchanged) from a
+ * caller's origin, direction (3 floats each) and RNG state per path, with no
+ * camera and no seed derivation.  max_segments as orc_render (0 = unbounded).
+ * out: 4 words per path -- the energy (3 floats) and the number of segments
+ * (extension rays, u32); seed[i] is replaced by the state after the path's
+ * last draw.  Follows orc_set_zero_cutoff. */
+void orc_trace_paths(const orc_scene*, uint32_t n, const float* o, const float* d, uint32_t* seed, uint32_t max_segments, float* out);
+/* This machine's glibc over an array: op 0 expf, 1 sinf, 2 cosf.  -1 for another op. */
+int orc_libm_map(int op, uint64_t n, const float* in, float* out);
 /* tinyobj-semantics OBJ load (Mesh(path)); -1 if unreadable. */
 long orc_obj_load(const char* path, float* tris_out, float* ext_out, uint64_t cap);
 /* Sequential BvhBLAS::build over n 64-B Triangles; returns nodesUsed. */

@@ -3578,4 +3578,112 @@ __global__ __launch_bounds__(64) void k_segment_cycles(DevScene S, float4 o4, fl
     }
 }
 
+/* Diagnostics (surf_debug_math): the kernels' libm on chosen inputs, one lane
+ * per element, the same device functions shadePath and cosineTry call.
+ * op 0 gExpf, 1 gSinf, 2 gCosf, 3 gSinCosf (out holds 2n: sin, cos). */
+__global__ __launch_bounds__(kBlock) void k_debug_math(uint32_t op, uint32_t n, const float* __restrict__ in, float* __restrict__ out) {
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+        const float x = in[i];
+        if (op == 0u) out[i] = gExpf(x);
+        else if (op == 1u) out[i] = gSinf(x);
+        else if (op == 2u) out[i] = gCosf(x);
+        else {
+            float sn, cs;
+            gSinCosf(x, sn, cs);
+            out[2u * (size_t)i] = sn; out[2u * (size_t)i + 1u] = cs;
+        }
+    }
+}
+
+/* Diagnostics (surf_debug_trace_paths): planted paths.  Path i enters
+ * Renderer::trace's loop at (o, d) with RNG state seed[i] -- throughput 1, no
+ * medium, the last bounce specular, segment 1 -- and runs to its end, or to
+ * maxSeg segments (1..4096, checked by the host: shadePath ends a path there,
+ * so neither loop below can spin).  Contributions are added in the reference's
+ * order: a bounce's light sample before the next segment's miss or emitter.
+ * outE[i] = (energy, segments), outSeed[i] = the state after the last draw. */
+__device__ __forceinline__ void plantedPath(const float* __restrict__ o, const float* __restrict__ d, const uint32_t* __restrict__ seed,
+                                            uint32_t i, float4& o4, float4& d4, float4& T4) {
+    o4 = make_float4(o[3 * (size_t)i], o[3 * (size_t)i + 1], o[3 * (size_t)i + 2], u2f(0u));
+    d4 = make_float4(d[3 * (size_t)i], d[3 * (size_t)i + 1], d[3 * (size_t)i + 2], u2f(kFlagSpecular | (1u << 2)));
+    T4 = make_float4(1.0f, 1.0f, 1.0f, u2f(seed[i]));
+}
+/* One path per lane: k_extend's walk, k_shade's shadePath, k_connect's any-hit walk. */
+template <bool LDS, bool LW = false>
+__global__ __launch_bounds__(kBlock) void k_debug_paths_lane(DevScene S, const float* __restrict__ o, const float* __restrict__ d,
+                                                             const uint32_t* __restrict__ seed, uint32_t n, uint32_t maxSeg,
+                                                             uint32_t zeroCutoff, float4* __restrict__ outE,
+                                                             uint32_t* __restrict__ outSeed, uint32_t stackWords) {
+    extern __shared__ uint32_t lds[];
+    __shared__ DevInstance sInst[LDS ? kLdsInst : 1];
+    __shared__ DevMaterial sMat[LDS ? kLdsMats : 1];
+    __shared__ uint2 sLights[LDS ? kLdsLights : 1];
+    const TraceTables Tt = traceTables<LDS>(S, lds, layout::laneTablesAt(stackWords, false));
+    ShadeTables Tb{S.inst, S.mats, S.lights};
+    if (LDS) {
+        stageTables(S, sInst, sMat, sLights);
+        Tb = ShadeTables{sInst, sMat, sLights};
+    }
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    float4 o4, d4, T4;
+    plantedPath(o, d, seed, i, o4, d4, T4);
+    V3 E = mk3(0.0f, 0.0f, 0.0f);
+    ShadeOut r;
+    for (;;) {
+        float depth = kFarAway, u = 0.0f, v = 0.0f;
+        uint32_t inst = kUnset, prim = kUnset;
+        const bool hit = traceScene<false, LW>(S, Tt, xyz(o4), xyz(d4), depth, u, v, inst, prim, lds + threadIdx.x, blockDim.x);
+        shadePath(S, Tb, o4, d4, T4, make_float4(depth, u, v, u2f(prim)), hit ? inst : kUnset, maxSeg, zeroCutoff, r);
+        if (r.addRad) E = add(E, r.radd);
+        if (r.shadow) {
+            float sdep = r.so.w, su = 0.0f, sv = 0.0f;
+            uint32_t si = kUnset, sp = kUnset;
+            if (!traceScene<true, LW>(S, Tt, xyz(r.so), xyz(r.sd), sdep, su, sv, si, sp, lds + threadIdx.x, blockDim.x)) E = add(E, xyz(r.sc));
+        }
+        if (!r.cont) break;
+        o4 = r.o; d4 = r.d; T4 = r.T;
+    }
+    outE[i] = make_float4(E.x, E.y, E.z, u2f(r.seg));
+    outSeed[i] = r.seedOut;
+}
+/* One path per wave (block), laid out as k_tail_coop and k_segment_cycles:
+ * traceWave, shadePath<true> evaluated by every lane, the wave any-hit walk;
+ * lane 0 writes. */
+template <bool LDS, bool W2>
+__global__ __launch_bounds__(64) void k_debug_paths_wave(DevScene S, const float* __restrict__ o, const float* __restrict__ d,
+                                                         const uint32_t* __restrict__ seed, uint32_t n, uint32_t maxSeg,
+                                                         uint32_t zeroCutoff, float4* __restrict__ outE,
+                                                         uint32_t* __restrict__ outSeed, uint32_t stackWords) {
+    extern __shared__ uint32_t lds[];
+    const TraceTables Tt = coopTrace<LDS>(S, lds, layout::waveTablesAt(stackWords, S.nInst, 1u));
+    const ShadeTables Tb = coopShade<LDS>(S, lds, layout::waveShadeAt(stackWords, S.nInst, 1u));
+    const uint32_t i = blockIdx.x;
+    if (i >= n) return;
+    float* rstk = reinterpret_cast<float*>(lds);
+    float4* pro = reinterpret_cast<float4*>(lds + layout::waveProAt(stackWords, S.nInst, 0u));
+    float4 o4, d4, T4;
+    plantedPath(o, d, seed, i, o4, d4, T4);
+    V3 E = mk3(0.0f, 0.0f, 0.0f);
+    ShadeOut r;
+    for (;;) {
+        float depth = kFarAway, u = 0.0f, v = 0.0f;
+        uint32_t inst = kUnset, prim = kUnset;
+        const bool hit = traceWave<false, W2>(S, Tt, xyz(o4), xyz(d4), depth, u, v, inst, prim, rstk, pro);
+        shadePath<true>(S, Tb, o4, d4, T4, make_float4(depth, u, v, u2f(prim)), hit ? inst : kUnset, maxSeg, zeroCutoff, r);
+        if (r.addRad) E = addU(E, r.radd);
+        if (r.shadow) {
+            float sdep = r.so.w, su = 0.0f, sv = 0.0f;
+            uint32_t si = kUnset, sp = kUnset;
+            if (!traceWave<true, W2>(S, Tt, xyz(r.so), xyz(r.sd), sdep, su, sv, si, sp, rstk, pro)) E = addU(E, xyz(r.sc));
+        }
+        if (!r.cont) break;
+        o4 = r.o; d4 = r.d; T4 = r.T;
+    }
+    if (threadIdx.x == 0) {
+        outE[i] = make_float4(E.x, E.y, E.z, u2f(r.seg));
+        outSeed[i] = r.seedOut;
+    }
+}
+
 }  // namespace surfdev

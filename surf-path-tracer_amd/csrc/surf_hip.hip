@@ -169,6 +169,9 @@ auto tailKernel(const surf_ctx* c, const Variant& v) { return kernel(v.lds ? k_t
 auto tailPairKernel(const surf_ctx* c, const Variant& v) { return kernel(SURF_PICK2(k_tail_pair, v.lds, v.w2), waveTailLds(c, 2u)); }
 auto tailCoopKernel(const surf_ctx* c, const Variant& v) { return kernel(SURF_PICK2(k_tail_coop, v.lds, v.w2), waveTailLds(c, 1u)); }
 auto segmentCyclesKernel(const surf_ctx* c, const Variant& v) { return kernel(SURF_PICK2(k_segment_cycles, v.lds, v.w2), waveTailLds(c, 1u)); }
+/* planted paths (surf_debug_trace_paths): the lane kernels' and the cooperative drain's variants and LDS */
+auto debugPathsLaneKernel(const surf_ctx* c, const Variant& v) { return kernel(SURF_PICK2(k_debug_paths_lane, v.lds, v.laneW), laneLds(c, kBlock, false, v.lds)); }
+auto debugPathsWaveKernel(const surf_ctx* c, const Variant& v) { return kernel(SURF_PICK2(k_debug_paths_wave, v.lds, v.w2), waveTailLds(c, 1u)); }
 auto traceClosestCoopKernel(const surf_ctx* c, const Variant& v) { return kernel(SURF_PICK2(k_trace_closest_coop, v.lds, v.w2), waveTraceLds(c)); }
 auto traceAnyCoopKernel(const surf_ctx* c, const Variant& v) { return kernel(SURF_PICK2(k_trace_any_coop, v.lds, v.w2), waveTraceLds(c)); }
 
@@ -2006,6 +2009,74 @@ int surf_debug_segment_cycles(surf_ctx* c, const float* path12, uint32_t reps, u
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     (void)hipFree(d);
     if (e != hipSuccess) return fail(c, SURF_ERR_HIP, std::string("segment cycles: ") + hipGetErrorString(e));
+    return SURF_OK;
+}
+
+int surf_debug_math(surf_ctx* c, int op, uint32_t n, const float* in, float* out) {
+    if (!c || op < SURF_MATH_EXPF || op > SURF_MATH_SINCOSF || (n && (!in || !out))) return SURF_ERR_INVALID;
+    if (n == 0) return SURF_OK;
+    SURF_CHECK(c, hipSetDevice(c->device));
+    const size_t per = op == SURF_MATH_SINCOSF ? 2 : 1;
+    std::vector<void*> tmp;
+    float *dIn, *dOut;
+    int rc;
+    if ((rc = devAlloc(c, tmp, &dIn, (size_t)n)) || (rc = devAlloc(c, tmp, &dOut, per * (size_t)n))) { freeList(tmp); return rc; }
+    (void)hipMemcpyAsync(dIn, in, 4 * (size_t)n, hipMemcpyHostToDevice, c->stream);
+    const uint32_t blocks = (uint32_t)std::min<size_t>(((size_t)n + kBlock - 1) / kBlock, 4096);    /* grid-stride beyond */
+    hipLaunchKernelGGL(k_debug_math, dim3(blocks), dim3(kBlock), 0, c->stream, (uint32_t)op, n, (const float*)dIn, dOut);
+    (void)hipMemcpyAsync(out, dOut, 4 * per * (size_t)n, hipMemcpyDeviceToHost, c->stream);
+    const hipError_t e = hipStreamSynchronize(c->stream);
+    freeList(tmp);
+    if (e != hipSuccess) return fail(c, SURF_ERR_HIP, std::string("debug_math: ") + hipGetErrorString(e));
+    return SURF_OK;
+}
+
+/* surf_debug_math's ops and output layout through the host build of the same source */
+int surf_debug_math_host(int op, uint32_t n, const float* in, float* out) {
+    if (op < SURF_MATH_EXPF || op > SURF_MATH_SINCOSF || (n && (!in || !out))) return SURF_ERR_INVALID;
+    for (size_t i = 0; i < n; ++i) {
+        if (op == SURF_MATH_EXPF) out[i] = surfdev::gExpf(in[i]);
+        else if (op == SURF_MATH_SINF) out[i] = surfdev::gSinf(in[i]);
+        else if (op == SURF_MATH_COSF) out[i] = surfdev::gCosf(in[i]);
+        else surfdev::gSinCosf(in[i], out[2 * i], out[2 * i + 1]);
+    }
+    return SURF_OK;
+}
+
+int surf_debug_trace_paths(surf_ctx* c, uint32_t n, const float* o, const float* d, const uint32_t* seed, uint32_t max_segments,
+                           int mode, float* out_energy_segments, uint32_t* out_seed) {
+    if (!c || (n && (!o || !d || !seed || !out_energy_segments || !out_seed))) return SURF_ERR_INVALID;
+    if (max_segments < 1u || max_segments > 4096u) return fail(c, SURF_ERR_INVALID, "debug_trace_paths: max_segments must be 1..4096");
+    if (mode < 0 || mode > 1) return fail(c, SURF_ERR_INVALID, "debug_trace_paths: mode must be 0 or 1");
+    if (!c->hasScene) return fail(c, SURF_ERR_NO_SCENE, "no scene uploaded");
+    if (mode == 1 && !waveEligible(c))
+        return fail(c, SURF_ERR_INVALID, "one-ray-per-wave traversal needs a BVH stack <= 64 entries");
+    if (n == 0) return SURF_OK;
+    SURF_CHECK(c, hipSetDevice(c->device));
+    std::vector<void*> tmp;
+    float *dO, *dD; uint32_t *dS, *dR; float4* dE;
+    int rc;
+    if ((rc = devAlloc(c, tmp, &dO, 3 * (size_t)n)) || (rc = devAlloc(c, tmp, &dD, 3 * (size_t)n)) || (rc = devAlloc(c, tmp, &dS, n)) ||
+        (rc = devAlloc(c, tmp, &dE, n)) || (rc = devAlloc(c, tmp, &dR, n))) { freeList(tmp); return rc; }
+    (void)hipMemcpyAsync(dO, o, 12 * (size_t)n, hipMemcpyHostToDevice, c->stream);
+    (void)hipMemcpyAsync(dD, d, 12 * (size_t)n, hipMemcpyHostToDevice, c->stream);
+    (void)hipMemcpyAsync(dS, seed, 4 * (size_t)n, hipMemcpyHostToDevice, c->stream);
+    const uint32_t cutoff = c->zeroCutoff != 0 ? 1u : 0u;       /* automatic (-1): on, as for one-sample frames */
+    const Variant v = variantOf(c);
+    if (mode == 1) {
+        const auto k = debugPathsWaveKernel(c, v);
+        hipLaunchKernelGGL(k.fn, dim3(n), dim3(64), k.lds, c->stream, c->S, (const float*)dO, (const float*)dD, (const uint32_t*)dS, n,
+                           max_segments, cutoff, dE, dR, recStackWords(c));
+    } else {
+        const auto k = debugPathsLaneKernel(c, v);
+        hipLaunchKernelGGL(k.fn, dim3((n + kBlock - 1) / kBlock), dim3(kBlock), k.lds, c->stream, c->S, (const float*)dO,
+                           (const float*)dD, (const uint32_t*)dS, n, max_segments, cutoff, dE, dR, stackWords(c, kBlock));
+    }
+    (void)hipMemcpyAsync(out_energy_segments, dE, 16 * (size_t)n, hipMemcpyDeviceToHost, c->stream);
+    (void)hipMemcpyAsync(out_seed, dR, 4 * (size_t)n, hipMemcpyDeviceToHost, c->stream);
+    const hipError_t e = hipStreamSynchronize(c->stream);
+    freeList(tmp);
+    if (e != hipSuccess) return fail(c, SURF_ERR_HIP, std::string("debug_trace_paths: ") + hipGetErrorString(e));
     return SURF_OK;
 }
 

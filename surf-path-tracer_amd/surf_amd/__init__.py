@@ -281,6 +281,8 @@ def load() -> C.CDLL:
         "surf_debug_kernel_selection": ([P] + [C.POINTER(C.c_uint32)] * 4, I32),
         "surf_debug_segment_cycles": ([P, P, U32, P], I32),
         "surf_debug_shadow_keys": ([P, U32, P, P, P, P, P, C.POINTER(U32), P], I32),
+        "surf_debug_math": ([P, I32, U32, P, P], I32),
+        "surf_debug_trace_paths": ([P, U32, P, P, P, U32, I32, P, P], I32),
         "surf_upload_scene": ([P, C.POINTER(SceneDesc)], I32),
         "surf_set_camera": ([P, P], I32),
         "surf_render": ([P, U32, U32, U32, U32], I32),
@@ -404,6 +406,7 @@ def load() -> C.CDLL:
         "surf_mesh_data": ([P, C.POINTER(P), C.POINTER(P), C.POINTER(U32)], I32),
         "surf_mesh_destroy": ([P], None),
         "surf_ref_sinf": ([F], F), "surf_ref_cosf": ([F], F), "surf_ref_expf": ([F], F),
+        "surf_debug_math_host": ([I32, U32, P, P], I32),
     }
     for name, (args, res) in sig.items():
         try:
@@ -610,6 +613,7 @@ def aov_sampled_params(samples=16, first_sample=0, key="instance") -> AovSampled
     return AovSampledParams(n, f, MATTE_KEYS.index(key), 0)
 
 
+MATH_OPS = ("expf", "sinf", "cosf", "sincosf")           # surf_math_op order
 AO_PLANES = ("openness", "bits")                         # surf_ao_plane order
 AO_SOURCES = ("first_hit", "chain")                      # surf_ao_source order
 AO_SAMPLES = (1, 2, 4, 8, 16, 32, 64)                    # a pixel's rays fill an aligned lane group of a wave
@@ -1325,6 +1329,35 @@ class Renderer:
         names = ("walk", "shade", "shadow_walk", "cosine", "light_sample", "normal", "checksum", "interior_cycles",
                  "leaf_cycles", "walks", "leaves", "triangles", "visits2", "prologue_cycles", "instance_loop_cycles")
         return {k: float(out[i]) / reps for i, k in enumerate(names) if k != "checksum"}
+
+    def debug_math(self, op: str, x) -> np.ndarray:
+        """Diagnostics: the kernels' libm on the device (surf_debug_math), one lane
+        per element of the float32 array x.  op: "expf", "sinf", "cosf" (n
+        results) or "sincosf" ((n, 2): sin, cos)."""
+        if op not in MATH_OPS:
+            raise ValueError(f"debug_math: op {op!r} is not one of {MATH_OPS}")
+        x = np.ascontiguousarray(x, np.float32).reshape(-1)
+        out = np.zeros((len(x), 2) if op == "sincosf" else len(x), np.float32)
+        _check(load().surf_debug_math(self._h, MATH_OPS.index(op), len(x), _ptr(x), _ptr(out)), "surf_debug_math", self._h)
+        return out
+
+    def debug_trace_paths(self, origins, directions, seeds, max_segments: int, mode: int = 0):
+        """Diagnostics: planted paths (surf_debug_trace_paths).  Path i starts at
+        origins[i] toward directions[i] ((n, 3) float32) with RNG state seeds[i]
+        and runs to its end or max_segments (1..4096) on the device: mode 0 one
+        path per lane (the wavefront kernels' device functions), mode 1 one
+        path per wave (the cooperative drain's).  Returns (energy (n, 3)
+        float32, segments (n,) uint32, final seeds (n,) uint32)."""
+        o = np.ascontiguousarray(origins, np.float32).reshape(-1, 3)
+        d = np.ascontiguousarray(directions, np.float32).reshape(-1, 3)
+        s = np.ascontiguousarray(seeds, np.uint32).reshape(-1)
+        if not (len(o) == len(d) == len(s)):
+            raise ValueError("debug_trace_paths: origins, directions and seeds differ in length")
+        out = np.zeros((len(o), 4), np.float32)
+        end = np.zeros(len(o), np.uint32)
+        _check(load().surf_debug_trace_paths(self._h, len(o), _ptr(o), _ptr(d), _ptr(s), max_segments, mode, _ptr(out), _ptr(end)),
+               "surf_debug_trace_paths", self._h)
+        return out[:, :3].copy(), out[:, 3].copy().view(np.uint32), end
 
     def set_zero_cutoff(self, on):
         """True / False, or None for the automatic default (on for 1-sample frames, off for multi-sample frames)."""

@@ -64,7 +64,7 @@ def chain_planes(osc, ubo: bytes, width: int, rows, max_links: int):
     nrm = np.zeros((n, 4), np.float32)
     alb = np.zeros((n, 4), np.float32)
     ids = np.tile(np.array([UNSET, UNSET, UNSET, 0], np.uint32), (n, 1))
-    info = {k: np.zeros(n, np.uint32) for k in ("reflect", "refract", "tir")}
+    info = {k: np.zeros(n, np.uint32) for k in ("reflect", "refract", "tir", "tir_outside")}
     info.update({k: np.zeros(n, bool) for k in ("exhausted", "ended_in_medium", "ended_after_exit", "ended_miss", "ended_emitter")})
     # the state of the pixels still active
     act = np.arange(n)
@@ -160,6 +160,7 @@ def chain_planes(osc, ubo: bytes, width: int, rows, max_links: int):
         info["reflect"][act[go & ~dielectric]] += 1
         info["refract"][act[go & refract]] += 1
         info["tir"][act[go & dielectric & ~refract]] += 1
+        info["tir_outside"][act[go & dielectric & ~refract & ~in_medium]] += 1      # an ior below 1: no bundled material
         just_exited = refract & in_medium
         in_medium = np.where(refract, ~in_medium, in_medium)
         # 6. advance

@@ -13,6 +13,13 @@ engines), cameraSample without a lens, a moved camera in k_regen, chainNext
 and classifyPixels, the mirror / dielectric / diffuse choice inside a medium,
 S.nLights == 0, and sampleNEE / k_connect with an emitter whose BLAS is large.
 
+Scenarios F to J keep the view and push the materials to their extremes
+(absorption into expf's denormal and zero range, an ior of 0.6 and of 3,
+refl + refr > 1 and refl == 1, a medium inside a heavy BLAS, albedo above 1,
+at 0 and below 0, a denormal emitter strength, a non-emitter with emit > 0):
+the branches of shadePath that one material table never takes.  Their
+conditions are floors on the oracle's shading census (CENSUS_FLOORS).
+
 Bar: bit-exact accumulator words and equal event counts, as
 tests/test_gpu_parity.py.  Each render's conditions (enough misses, shadow
 rays where they are expected, no path past 4096 segments) are asserted from
@@ -30,7 +37,7 @@ import surf_amd
 from test_gpu_aov import W as AW, H as AH, assert_planes_equal, camera_rays, expected_planes
 from test_gpu_aov_chain import chain_planes
 from test_gpu_parity import _assert_bitexact, _assert_counts
-from test_oracle_scene_edits import SCENARIOS, PatchedScene, check_conditions, edited_oracle
+from test_oracle_scene_edits import SCENARIOS, PatchedScene, check_conditions, edited_oracle, render_counted
 
 pytestmark = [pytest.mark.gpu, pytest.mark.timeout(900)]
 W, H, FRAMES = 64, 48, 3
@@ -70,11 +77,7 @@ def reference(scenes):
         key = (name, w, h, frames)
         if key not in done:
             o = scenes(name)[0]
-            oracle.set_zero_cutoff(True)
-            try:
-                c2, cnt, _ = o.render(w, h, frames)
-            finally:
-                oracle.set_zero_cutoff(False)
+            c2, cnt = render_counted(o, w, h, frames)
             miss = check_conditions(name, o, cnt, c2)
             c, _, _ = o.render(w, h, frames)
             assert np.array_equal(c.view(np.uint32), c2.view(np.uint32)), "cutoff changed the oracle's radiance"
@@ -131,7 +134,7 @@ def test_scenario_bitexact(scenes, reference, name, policy, coop, engine, monkey
 # ---- 2. multi-sample frames: chainNext after a miss, under a moved camera -------
 
 @pytest.mark.parametrize("engine", ["wavefront", "pair", "coop"])
-@pytest.mark.parametrize("name", ["A", "C"])
+@pytest.mark.parametrize("name", ["A", "C", "F", "H2", "H3"])
 def test_scenario_spp4_bitexact(scenes, name, engine, monkeypatch):
     """2 frames of 4 chained samples (orc_render_spp), the throughput cutoff on on
     both sides (the conditions are stated for it): in A almost every sample ends
@@ -142,11 +145,7 @@ def test_scenario_spp4_bitexact(scenes, name, engine, monkeypatch):
     the drain takes them and draws their remaining samples itself."""
     K, FR = 4, 2
     o = scenes(name)[0]
-    oracle.set_zero_cutoff(True)
-    try:
-        c, cnt, _ = o.render(W, H, FR, spp=K)
-    finally:
-        oracle.set_zero_cutoff(False)
+    c, cnt = render_counted(o, W, H, FR, spp=K)
     check_conditions(name, o, cnt, c)
     monkeypatch.setenv("SURF_TAIL_PAIR", "0" if engine == "coop" else "1")
     r = renderer(scenes, name, W, H, frame_batch=None if engine == "wavefront" else K)
@@ -252,6 +251,40 @@ def test_scenario_feature_planes_bitexact(scenes, name):
     try:
         assert_planes_equal(r.aov(), want, f"scenario {name} first hit")
         assert_planes_equal(r.aov_chain(8), chain, f"scenario {name} chain")
+    finally:
+        r.close()
+
+
+# Pixels (of 3,700) whose chain takes the link at least once, as the numpy restatement
+# counts them: (observed, floor asserted -- about half).
+EXTREME_LINKS = {
+    "G": {"tir_outside": (32, 16), "refract": (5, 2)},                       # ior 0.6: reflection on entry
+    "H": {"reflect": (836, 400), "refract": (40, 20)},                       # refl 1, and refl + refr > 1 either way round
+    "H3": {"tir_outside": (24, 12), "tir": (49, 24), "refract": (71, 35)},   # ior 0.7 through a heavy BLAS, absorbing
+}
+
+
+@pytest.mark.parametrize("name", list(EXTREME_LINKS))
+def test_extreme_material_feature_planes_bitexact(scenes, name):
+    """r.aov() and r.aov_chain(16) of G, H and H3.  The chain's delta rule
+    (include/surf_hip.h: a link where refl + refr >= 0.5, a dielectric one where
+    refl < refr, refraction where cos2 > 0 whichever side the ray is on) is the
+    numpy restatement's as it stood: total internal reflection on entry (an ior
+    below 1) is its `dielectric & ~refract` with the medium flag clear, counted
+    as tir_outside.  No bundled material reaches that, nor a mirror of
+    reflectivity 1, nor a dielectric whose refl + refr passes 1."""
+    o = scenes(name)[0]
+    ubo = o.camera_ubo(AW, AH)
+    want, _ = expected_planes(o, ubo, AW, range(AH))
+    chain, cinfo = chain_planes(o, ubo, AW, range(AH), 16)
+    for key, (_, floor) in EXTREME_LINKS[name].items():
+        took = int((cinfo[key] > 0).sum())
+        assert took >= floor, f"{name}: {took} pixels take a {key} link"
+    assert np.isfinite(chain["albedo"]).all() and np.isfinite(chain["position"][..., :3]).all()
+    r = renderer(scenes, name, AW, AH)
+    try:
+        assert_planes_equal(r.aov(), want, f"scenario {name} first hit")
+        assert_planes_equal(r.aov_chain(16), chain, f"scenario {name} chain")
     finally:
         r.close()
 

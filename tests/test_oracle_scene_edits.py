@@ -33,6 +33,13 @@ wall, 7 green wall):
   D  C with both emitters switched off: no lights, a sky-lit room.
   E  default view; Suzanne 0 becomes an emitter (strength 2, colour
      (1, 0.6, 0.3)): three lights, one with a 15,744-triangle BLAS.
+  F .. J  material extremes under the default view (EXTREMES; what each is
+     there for stands beside its floors in CENSUS_FLOORS): absorption that
+     drives expf into its denormal and zero range, an ior below 1 and one of
+     3, refl + refr > 1 and refl == 1, a medium inside a heavy BLAS, albedo
+     channels above 1, at 0 and below 0, an emitter strength that is a
+     denormal, and a non-emitter with emit > 0 and a black colour.  Their
+     conditions are counts of the oracle's shading census (oracle.shade_census).
 """
 import os
 
@@ -47,7 +54,7 @@ GOLDEN = os.path.join(os.path.dirname(__file__), "golden")
 UNSET = 0xFFFFFFFF
 F = np.float32
 
-M_CUBE_L, M_CUBE_R, M_SUZANNE0, M_LENS, M_WALL_GREEN = 1, 2, 3, 5, 7
+M_FLOOR, M_CUBE_L, M_CUBE_R, M_SUZANNE0, M_LENS, M_WALL_RED, M_WALL_GREEN = 0, 1, 2, 3, 5, 6, 7
 
 OUTSIDE = {"pos": (0.0, 6.0, -19.0), "target": (0.0, 6.0, -12.0)}
 PANE = {"refl": 0.0, "refr": 1.0, "ior": 1.0, "albedo": (1.0, 1.0, 1.0), "absorption": (0.0, 0.0, 0.0)}
@@ -63,7 +70,21 @@ SCENARIOS = {
     "C": {"materials": {M_WALL_GREEN: PANE, M_LENS: MIXED_LENS}},
     "D": {"materials": {M_WALL_GREEN: PANE, M_LENS: MIXED_LENS, M_CUBE_L: OFF, M_CUBE_R: OFF}},
     "E": {"materials": {M_SUZANNE0: {"emit": 2.0, "emit_color": (1.0, 0.6, 0.3)}}},
+    # material extremes (default view): what each is there for is in CENSUS_FLOORS
+    "F": {"materials": {M_LENS: {"absorption": (40.0, 8.0, 200.0)}}},
+    "G": {"materials": {M_LENS: {"ior": 0.6}}},
+    "G2": {"materials": {M_LENS: {"ior": 3.0}}},
+    "H": {"materials": {M_LENS: {"refl": 0.6, "refr": 0.9}, M_SUZANNE0: {"refl": 1.0},
+                        M_WALL_RED: {"refl": 0.3, "refr": 0.3, "ior": 1.0}}},
+    "H2": {"materials": {M_SUZANNE0: {"refl": 0.1, "refr": 0.9, "ior": 1.5, "albedo": (0.9, 0.9, 0.9),
+                                      "absorption": (30.0, 3.0, 120.0)}}},
+    "H3": {"materials": {M_SUZANNE0: {"refr": 1.0, "ior": 0.7, "absorption": (1.0, 0.1, 5.0)}}},
+    "I": {"materials": {M_SUZANNE0: {"albedo": (1.6, 1.2, 0.0)}, M_WALL_RED: {"albedo": (1.3, 0.1, 0.1)}}},
+    "I2": {"materials": {M_SUZANNE0: {"albedo": (-0.5, 0.5, 0.0)}, M_FLOOR: {"albedo": (0.0, 0.0, 0.0)}}},
+    "J": {"materials": {M_SUZANNE0: {"emit": 3.0, "emit_color": (0.0, 0.0, 0.0)},
+                        M_WALL_RED: {"emit": 1e-40, "emit_color": (1.0, 1.0, 1.0)}}},
 }
+EXTREMES = ("F", "G", "G2", "H", "H2", "H3", "I", "I2", "J")
 
 # include/surf_hip.h: surf_material and surf_background, byte offsets
 MATERIAL_AT = {"emit": (0, 1), "refl": (4, 1), "refr": (8, 1), "ior": (12, 1), "emit_color": (16, 3), "albedo": (32, 3),
@@ -142,21 +163,66 @@ def assert_buffers_equal(a, b, what):
 
 def render_counted(o, W, H, frames, spp=1):
     """The oracle's render with the throughput cutoff on (what the GPU traces by
-    default): (acc, counters)."""
+    default): (acc, counters).  counters["census"] is the shading census
+    (oracle.shade_census) of this render alone."""
     oracle.set_zero_cutoff(True)
     try:
+        oracle.shade_census()                       # reading resets it
         acc, cnt, _ = o.render(W, H, frames, spp=spp)
+        cnt["census"] = oracle.shade_census()
     finally:
         oracle.set_zero_cutoff(False)
     return acc, cnt
 
 
+# Census floors of the material-extreme scenarios: (what the scenario is there
+# for, the value the committed oracle reports at 64 x 48 x 3 with the cutoff on,
+# the floor asserted -- about half of it, so that the branch is well taken in
+# any render the GPU tests ask for; the 2 x 4-sample renders of F, H2 and H3
+# count more than the 3-frame ones in every row).
+CENSUS_FLOORS = {
+    # expf into the denormal and zero range: lens absorption (40, 8, 200)
+    "F": {"exp_denormal": (113, 50), "exp_zero": (400, 200), "exp_below_60": (636, 300)},
+    # total internal reflection on entry: an ior below 1
+    "G": {"tir_outside": (307, 150), "refract": (160, 80)},
+    "G2": {"tir_inside": (1468, 700), "fresnel_reflect": (197, 100)},
+    # refl + refr > 1 (the dielectric branch takes what the mirror leaves) and refl == 1
+    "H": {"mirror": (6675, 3000), "dielectric_outside": (1702, 800)},
+    # a medium inside a heavy BLAS
+    "H2": {"medium_segments": (1751, 800), "exp_zero": (433, 200), "tir_inside": (802, 400)},
+    "H3": {"tir_outside": (336, 150), "tir_inside": (330, 150)},
+    # albedo above 1: the roulette probability pinned at 1 under a growing throughput
+    # (cutoff_kills 0, brightest accumulator value 246)
+    "I": {"rr_clamped": (10595, 5000)},
+    # negative and zero albedo channels (negative radiance, asserted below)
+    "I2": {"cutoff_kills": (8874, 4000)},
+    # J: isLight's edge cases, asserted from the light list below
+    "J": {},
+}
+assert all(0 < floor <= seen for rows in CENSUS_FLOORS.values() for seen, floor in rows.values())
+
+
 def check_conditions(name, o, cnt, acc):
     """The conditions a scenario's render must meet to be worth a GPU run, from
-    the oracle's counters: what it is there to reach, and no path past 4096
-    segments (one that never ends must not reach a GPU)."""
+    the oracle's counters and census: what it is there to reach, a finite
+    accumulator, and no path past 4096 segments (one that never ends must not
+    reach a GPU).
+
+    No scenario puts a NaN in a material field: a NaN made by x86 arithmetic
+    and one made by gfx950 arithmetic differ in sign, so bit-for-bit equality
+    is undefined there."""
     miss = (cnt["n_ext"] - cnt["n_hit"]) / cnt["samples"]
     assert cnt["max_segments"] <= 4096, f"{name}: longest path {cnt['max_segments']} segments"
+    assert np.isfinite(acc).all(), f"{name}: a non-finite accumulator word"
+    if name in CENSUS_FLOORS:
+        census = cnt["census"]
+        for key, (_, floor) in CENSUS_FLOORS[name].items():
+            assert census[key] >= floor, f"{name}: {key} {census[key]} < {floor} ({census})"
+    if name == "I2":
+        assert (acc[..., :3] < 0).any(), "I2: no negative accumulator word"
+    if name == "J":
+        lights = np.frombuffer(o.export()["lights"], np.uint32).reshape(-1, 2)[:, 0].tolist()
+        assert o.light_count() == 3 and 3 not in lights and 6 in lights, lights
     if name in ("A", "B", "B2"):
         assert miss >= 0.25, f"{name}: {miss:.3f} misses per sample"
     if name in ("C", "D"):
@@ -249,7 +315,10 @@ def test_patched_buffers_equal_the_edited_export(product_scene, name):
                 at, n = MATERIAL_AT[k]
                 assert np.array_equal(mats[index, at // 4:at // 4 + n], np.asarray(v, np.float32).reshape(n)), (index, k)
         lights = np.frombuffer(want["lights"], np.uint32).reshape(-1, 2).tolist()
-        assert lights == {"D": [], "E": [[1, 188], [2, 188], [3, 15744]]}.get(name, [[1, 188], [2, 188]])
+        # J: Suzanne 0 (instance 3, emit 3 with a black colour) is no light; the red wall (instance 6, a
+        # denormal strength with colour 1) is one
+        assert lights == {"D": [], "E": [[1, 188], [2, 188], [3, 15744]],
+                          "J": [[1, 188], [2, 188], [6, 2]]}.get(name, [[1, 188], [2, 188]])
         bg = np.frombuffer(want["background"], np.uint32)
         assert bg[0] == spec.get("background", {}).get("type", 1)
     finally:
@@ -364,7 +433,8 @@ def test_moved_camera_rays_closest_equals_brute_force():
 
 # ---- 5. the scenarios reach what they are there for ----------------------------
 
-RUNS = [(n, 64, 48, 3, 1) for n in SCENARIOS] + [("A", 64, 48, 2, 4), ("C", 64, 48, 2, 4), ("A", 96, 64, 8, 1), ("C", 96, 64, 8, 1)]
+RUNS = ([(n, 64, 48, 3, 1) for n in SCENARIOS] + [(n, 64, 48, 2, 4) for n in ("A", "C", "F", "H2", "H3")] +
+        [("A", 96, 64, 8, 1), ("C", 96, 64, 8, 1)])
 
 
 @pytest.mark.parametrize("name,W,H,frames,spp", RUNS, ids=[f"{r[0]}-{r[1]}x{r[2]}x{r[3]}-spp{r[4]}" for r in RUNS])
@@ -375,6 +445,11 @@ def test_scenario_conditions(name, W, H, frames, spp):
     try:
         acc, cnt = render_counted(o, W, H, frames, spp)
         check_conditions(name, o, cnt, acc)
-        assert np.isfinite(acc).all() and (acc[..., :3] >= 0).all()
+        assert np.isfinite(acc).all()
+        assert name == "I2" or (acc[..., :3] >= 0).all()      # I2's albedo has a negative channel
+        if name in EXTREMES and spp == 1:
+            # what the GPU tests stand on: the cutoff leaves the radiance bits alone
+            plain, _, _ = o.render(W, H, frames)
+            assert np.array_equal(plain.view(np.uint32), acc.view(np.uint32)), f"{name}: the cutoff changed the oracle's radiance"
     finally:
         o.close()
