@@ -343,6 +343,9 @@ public:
      * width*height*4 values each): a float plane (position, normal or albedo), and the id plane */
     std::vector<F32> readAOV(surf_aov plane);
     std::vector<U32> readAOVIds();
+    /* ... and one of the four to a buffer of width*height*16 bytes on the renderer's device, with no host
+     * trip (surf_copy_aov_device): e.g. the position and normal planes for setSurfelSensorDevice */
+    void copyAOVDevice(surf_aov plane, void* dstDevice);
     /* the same planes traced through mirrors and glass to the first surface that is neither, or to
      * link maxLinks (surf_read_aov_chain, which defines the chain; 0..SURF_AOV_CHAIN_MAX_LINKS) */
     std::vector<F32> readAOVChain(surf_aov plane, U32 maxLinks = 8);
@@ -427,6 +430,15 @@ public:
      * where asked for, its active count. */
     void setPixelMask(const std::vector<uint8_t>& mask);
     std::vector<uint8_t> pixelMask(U32* activeCount = nullptr);
+    /* the surfel sensor (surf_set_surfel_sensor, whose header comment defines it): width*height float4
+     * records each, position and normal (w ignored; a (0, 0, 0) normal marks an invalid texel); render()
+     * then starts its samples at those points and the accumulator holds their light map.  The device form
+     * takes two pointers on the renderer's device (surf_set_surfel_sensor_device).  clearSurfelSensor:
+     * back to the camera.  surfelSensor: whether one is set and, where asked for, its valid texels. */
+    void setSurfelSensor(const std::vector<F32>& position, const std::vector<F32>& normal);
+    void setSurfelSensorDevice(const void* positionDevice, const void* normalDevice);
+    void clearSurfelSensor();
+    bool surfelSensor(U32* validTexels = nullptr);
     /* builds the mask from the noise estimate and sets it (surf_mask_from_noise); returns the active
      * count.  Needs setSampleSquares(true). */
     U32 maskFromNoise(const surf_adaptive_mask_params& params);

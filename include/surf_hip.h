@@ -1854,6 +1854,91 @@ int surf_display_bayer8(uint8_t out[64]);
  * bloom), pack (with bloom: the vertical pass fused with it). */
 int surf_debug_display_time(surf_ctx* ctx, float* kernel_ms, uint32_t count);
 
+/* ---- the surfel sensor: path-traced irradiance at the caller's texels (no reference counterpart) ----
+ * A context's samples start at its sensor.  After surf_create* that is the
+ * camera.  With a surfel sensor set, surf_render starts every sample at a
+ * surface point the caller gave -- a light-map texel, an irradiance probe's
+ * facet, a pixel's first hit -- and gathers the light that arrives there; the
+ * accumulator, the squares and bucket planes, the masks, the adaptive loops
+ * and every *_image filter then work on that light map as on any image.
+ *
+ * Definition.  All arithmetic is f32 and uncontracted.  Texel lp of the shard
+ * (rows*width, shard row order like the accumulator) has P = position[lp].xyz
+ * and N = normal[lp].xyz; both w components are ignored.  The texel is VALID
+ * iff N.x != 0 || N.y != 0 || N.z != 0 -- so a NaN normal component makes the
+ * texel valid -- and surf_read_aov's miss normal is (0, 0, 0): the first-hit
+ * position and normal planes can be handed in as they are.  N is used as
+ * given: the caller supplies a unit vector, the library does not normalize it.
+ * One degenerate input is refused (SURF_ERR_INVALID, nothing changes): a normal
+ * with a nonzero component whose squared length x*x + y*y + z*z, in f32, lies
+ * below FLT_MIN -- step 1's retry test dot(R, N) == 0 could then hold on every
+ * try and the sample never start.  A NaN or infinite component is not refused.
+ * Sample j of frame k of a valid texel is seeded as surf_render states above:
+ * seed = initSeed(p + 1799 * (first_sample_index + k*spp)) for j = 0, with
+ * p = x + row*width over the whole image; for j > 0 the seed is the state the
+ * previous sample's path left.  Then
+ *   1. R = cosineSample(seed, N): the path tracer's own
+ *      randomOnHemisphereCosineWeighted loop, with its retry;
+ *   2. o = P + 1e-5f * R, computed as add(P, lscl(kEps, R)): the continuation
+ *      origin of a diffuse bounce;
+ *   3. d = R;
+ *   4. the path enters Renderer::trace's loop exactly as a camera ray does:
+ *      throughput (1, 1, 1), no medium, last bounce specular, segment 1, RNG
+ *      state seed -- an emitter met on the first segment therefore counts;
+ *   5. (energy, 1) is accumulated per sample, in sample order.
+ * accumulator.rgb / w then estimates E / pi, with E the irradiance at P about
+ * N: the radiosity of a white diffuse texel.
+ *
+ * Validity and the mask.  An invalid texel is never issued: its accumulator,
+ * squares and bucket records stay untouched and its w does not advance,
+ * exactly like an inactive pixel of the mask.  The effective active set is
+ * mask AND valid: wherever the context's mask is set or built
+ * (surf_set_pixel_mask, surf_mask_from_noise, surf_mask_from_nlm, the reset by
+ * surf_clear_accumulator, both adaptive loops) an invalid texel's byte is
+ * forced to 0 before the compaction, and surf_get_pixel_mask reports the
+ * forced bytes.  An all-valid sensor with no mask takes the unmasked kernels
+ * and issue order.  With no valid texel at all surf_render returns SURF_OK and
+ * changes nothing.
+ *
+ * State.  The library copies both planes into buffers of its own (2 x 16 B
+ * and 1 B per texel, allocated on first use).  Setting or clearing a sensor
+ * drains and ends the open stream, as a mask change does, and sets the mask
+ * back to every (valid) texel.  The sensor survives surf_set_camera,
+ * surf_upload_scene, surf_update_instances and surf_clear_accumulator: the
+ * points are the caller's world-space data.  surf_render's requirements do not
+ * change: it still needs a scene and a camera.
+ *
+ * Scheduling (none of it affects results).  Under a sensor the permuted head
+ * of the stream, which classifies pixels by the camera's centre rays, is not
+ * used: issue is frame-major.  Surfel rays take the camera rays' pool key.
+ *
+ * What stays as it is.  surf_read_aov*, surf_read_ao and every filter keep
+ * describing the camera.  With a sensor set, the context forms of the guided
+ * filters (surf_denoise, surf_svgf, surf_denoise_sampled, surf_denoise_regress,
+ * surf_temporal_accumulate) make sense only when the surfels ARE those planes
+ * -- the view baked at its own first hits; nothing is refused.  The *_image
+ * forms, the noise estimate, the robust estimate, the non-local-means filter,
+ * both adaptive loops, surf_finalize_rgba8_weighted and the display stage
+ * operate on the light map as on any image.  surf_stats counts what was traced.
+ *
+ * Device side: the kernels that start a sample (k_regen, k_regen_count,
+ * k_shade and the three drain kernels) have a second instantiation that reads
+ * the texel's two 16-byte records in place of the camera; the camera's
+ * instantiations are unchanged. */
+#define SURF_SENSOR_CAMERA 0
+#define SURF_SENSOR_SURFELS 1
+/* position, normal: rows*width float4 records each, shard row order like the
+ * accumulator; host pointers.  NULL, NULL: back to the camera.  One NULL:
+ * SURF_ERR_INVALID (as for a NULL context, and for a nonzero normal whose
+ * squared length underflows, see above).  SURF_ERR_OOM when the copies cannot
+ * be allocated.  A call that fails before its copies leaves the sensor as it
+ * was; one whose copies fail leaves the context on the camera with no mask. */
+int surf_set_surfel_sensor(surf_ctx* ctx, const float* position, const float* normal);
+/* the same from device pointers on the context's device (e.g. what surf_copy_aov_device wrote) */
+int surf_set_surfel_sensor_device(surf_ctx* ctx, const void* position_device, const void* normal_device);
+/* *kind = SURF_SENSOR_CAMERA or SURF_SENSOR_SURFELS; *valid = valid texels (rows*width for the camera); either may be NULL */
+int surf_get_sensor(surf_ctx* ctx, int* kind, uint32_t* valid);
+
 /* ---- traversal entry points (kernel-level parity tests) ----
  * n world-space rays, o/d 3 floats each.  closest: depth starts at 1e30;
  * writes t,u,v (floats) and inst,prim (u32, ~0 on miss).  any: tmax per ray,

@@ -15,6 +15,14 @@ constexpr uint32_t kCompactBlock = 256;      /* pixels per block of the compacti
 
 #if defined(__HIPCC__) || defined(__HIP__)
 
+/* Before the compaction of a context's mask under a surfel sensor: mask[p] = 0
+ * where the texel is invalid (valid[p] == 0); every other byte is left as built. */
+static __global__ __launch_bounds__(kCompactBlock) void k_mask_and_valid(uint8_t* __restrict__ mask, const uint8_t* __restrict__ valid,
+                                                                         uint32_t n) {
+    const uint32_t p = blockIdx.x * kCompactBlock + threadIdx.x;
+    if (p < n && valid[p] == 0) mask[p] = 0;
+}
+
 /* Compaction, step 1: blk[b] = the nonzero bytes among pixels [256 b, 256 b + 256). */
 static __global__ __launch_bounds__(kCompactBlock) void k_compact_count(const uint8_t* __restrict__ mask, uint32_t n,
                                                                         uint32_t* __restrict__ blk) {

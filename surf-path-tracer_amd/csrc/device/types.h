@@ -188,6 +188,19 @@ struct StreamGeom {
     const uint32_t* perm;            /* local pixels, class A (Counters::permA of them) first; a masked stream's
                                         graph: the ascending active-pixel list (Counters::nActive of them) */
 };
+/* The stream geometry of a stream under a surfel sensor (surf_set_surfel_sensor):
+ * the same record and behind it the sensor's two planes, npx float4 records
+ * each in the shard's row order -- texel lp starts its samples at position[lp]
+ * about normal[lp] (surfelSample).  Only the SURFEL instantiations take this
+ * type: the camera kernels' arguments are what they were. */
+struct SurfelGeom : StreamGeom {
+    const float4* position;
+    const float4* normal;
+};
+/* the stream-geometry argument of a kernel instantiated for the camera (false) or for a surfel sensor (true) */
+template <bool SURFEL> struct GeomOf { using type = StreamGeom; };
+template <> struct GeomOf<true> { using type = SurfelGeom; };
+template <bool SURFEL> using Geom = typename GeomOf<SURFEL>::type;
 
 /* Record encodings the upload writes and the walks read */
 constexpr uint32_t kLeafTagC = 0x80000000u;   /* compact staged BLAS (blasAnyStaged): a child that is a leaf */

@@ -2286,15 +2286,45 @@ __device__ __forceinline__ void cameraSample(const DevCamera& cam, const StreamG
     T4 = make_float4(1.0f, 1.0f, 1.0f, u2f(seed));
 }
 
+/* The surfel sensor's sample (surf_set_surfel_sensor, include/surf_hip.h): the
+ * path record of sample `sid` at shard texel lp, which leaves P = position[lp]
+ * in a cosine-weighted direction R about N = normal[lp] -- drawn from `seed`
+ * with the diffuse bounce's own loop -- from shadePath's continuation origin
+ * P + kEps * R, and enters the path loop as a camera ray does: throughput 1,
+ * no medium, last bounce specular (an emitter met on the first segment
+ * counts), segment 1.  Each record is one 16-byte load; w is not looked at.
+ * cameraSample's signature: the camera is not read. */
+__device__ __forceinline__ void surfelSample(const DevCamera&, const SurfelGeom& G, uint32_t lp, uint32_t sid, uint32_t seed,
+                                             float4& o4, float4& d4, float4& T4) {
+    /* (the pools' streaming load: read once per sample, and as a whole record -- a plain load of a
+     * float4 whose w is unused compiles to 12-byte pieces) */
+    const float4 P4 = ldS(&G.position[lp]), N4 = ldS(&G.normal[lp]);
+    const V3 R = cosineSample(seed, xyz(N4));
+    const V3 O = add(xyz(P4), lscl(kEps, R));
+    o4 = make_float4(O.x, O.y, O.z, u2f(sid));
+    d4 = make_float4(R.x, R.y, R.z, u2f(kFlagSpecular | (1u << 2)));
+    T4 = make_float4(1.0f, 1.0f, 1.0f, u2f(seed));
+}
+/* SURFEL (a stream under a surfel sensor; threaded like MASKED, down from the
+ * kernels that start samples): which of the two draws a sample.  The camera
+ * instantiation is the code it was before the sensor existed. */
+template <bool SURFEL>
+__device__ __forceinline__ void sensorSample(const DevCamera& cam, const Geom<SURFEL>& G, uint32_t lp, uint32_t sid, uint32_t seed,
+                                             float4& o4, float4& d4, float4& T4) {
+    if constexpr (SURFEL) surfelSample(cam, G, lp, sid, seed, o4, d4, T4);
+    else cameraSample(cam, G, lp, sid, seed, o4, d4, T4);
+}
+
 /* The next sample of a multi-sample frame (Renderer::render's sample loop,
  * renderer.cpp:171-181): when the path of sample `sid` ended and its frame has
  * samples left for the pixel, the pixel's next camera sample -- radiance slot
  * sid + npx (the frame's samples occupy consecutive slots) -- drawn from the
  * RNG state the ended path left.  False for a frame's last sample. */
-__device__ __forceinline__ bool chainNext(const DevCamera& cam, const StreamGeom& G, uint32_t spp, uint32_t sid, uint32_t slot,
+template <bool SURFEL = false>
+__device__ __forceinline__ bool chainNext(const DevCamera& cam, const Geom<SURFEL>& G, uint32_t spp, uint32_t sid, uint32_t slot,
                                           uint32_t seed, float4& o4, float4& d4, float4& T4) {
     if (spp <= 1u || slot % spp == spp - 1u) return false;
-    cameraSample(cam, G, sid - slot * G.npx, sid + G.npx, seed, o4, d4, T4);
+    sensorSample<SURFEL>(cam, G, sid - slot * G.npx, sid + G.npx, seed, o4, d4, T4);
     return true;
 }
 
@@ -2311,13 +2341,14 @@ __device__ __forceinline__ void frameDoneAdd(uint32_t* frameDone, bool done, uin
     }
 }
 
-/* HV: the shadow key's heavy-box layouts (Q.bins = 32 or 40; shadowKey) */
-template <bool LDS_TABLES, bool HV = false>
+/* HV: the shadow key's heavy-box layouts (Q.bins = 32 or 40; shadowKey);
+ * SURFEL: a sample that ends is followed by the surfel sensor's next (chainNext) */
+template <bool LDS_TABLES, bool HV = false, bool SURFEL = false>
 __global__ __launch_bounds__(kBlock, SURF_SHADE_WAVES) void k_shade(DevScene S, Pool cur, Pool nxt, const float4* __restrict__ hitTUV,
                                                   const uint32_t* __restrict__ hitInst, ShadowQ Q,
                                                   float4* __restrict__ rad, uint32_t* __restrict__ frameDone,
                                                   uint32_t npx, uint32_t window, Counters* C, int par,
-                                                  const uint32_t* __restrict__ order, DevCamera cam, StreamGeom G) {
+                                                  const uint32_t* __restrict__ order, DevCamera cam, Geom<SURFEL> G) {
     if (blockIdx.x * blockDim.x >= C->nIn[par]) return;     /* nothing to shade in this block */
     __shared__ DevInstance sInst[LDS_TABLES ? kLdsInst : 1];
     __shared__ DevMaterial sMat[LDS_TABLES ? kLdsMats : 1];
@@ -2361,7 +2392,7 @@ __global__ __launch_bounds__(kBlock, SURF_SHADE_WAVES) void k_shade(DevScene S, 
             if (r.addRad) addRadiance(rad, sid, r.radd);
             /* the sample ended: its frame's next sample of this pixel takes its
              * place in the next pool (a camera ray, not a continuation) */
-            if (!r.cont && chainNext(cam, G, spp, sid, slot, r.seedOut, r.o, r.d, r.T)) {
+            if (!r.cont && chainNext<SURFEL>(cam, G, spp, sid, slot, r.seedOut, r.o, r.d, r.T)) {
                 r.next = true;
                 rad[sid + npx] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
             }
@@ -2544,8 +2575,8 @@ __device__ __forceinline__ RegenPlan regenPlan(const Counters* C, int par, uint3
     return R;
 }
 /* The k-th new chain's first sample into pool slot cont + k. */
-template <bool MASKED = false>
-__device__ __forceinline__ void regenSample(const DevCamera& cam, const Pool& nxt, float4* __restrict__ rad, const StreamGeom& G,
+template <bool MASKED = false, bool SURFEL = false>
+__device__ __forceinline__ void regenSample(const DevCamera& cam, const Pool& nxt, float4* __restrict__ rad, const Geom<SURFEL>& G,
                                             const RegenPlan& R, uint32_t k) {
     uint32_t lp;
     unsigned long long f;
@@ -2555,7 +2586,7 @@ __device__ __forceinline__ void regenSample(const DevCamera& cam, const Pool& nx
         const unsigned long long df = i / R.nA;
         lp = G.perm[(uint32_t)(i - df * R.nA)];
         f = R.f0 + df;
-    } else if (R.iss + k < R.endP) {
+    } else if (!SURFEL && R.iss + k < R.endP) {   /* (a sensor's stream has no permuted head) */
         const unsigned long long s = R.iss + k;
         if (s < R.endA) { f = s / R.nA; lp = G.perm[(uint32_t)(s - f * R.nA)]; }
         else { const unsigned long long j = s - R.endA; f = j / R.nB; lp = G.perm[R.nA + (uint32_t)(j - f * R.nB)]; }
@@ -2571,7 +2602,7 @@ __device__ __forceinline__ void regenSample(const DevCamera& cam, const Pool& nx
     const uint32_t p = (lp - rowi * G.width) + G.rows[rowi] * G.width;
     const uint32_t sid = slot * G.npx + lp;
     float4 o4, d4, T4;
-    cameraSample(cam, G, lp, sid, initSeed(p + (uint32_t)(R.base + pass) * 1799u), o4, d4, T4);
+    sensorSample<SURFEL>(cam, G, lp, sid, initSeed(p + (uint32_t)(R.base + pass) * 1799u), o4, d4, T4);
     const uint32_t slotIdx = R.cont + k;
     stS(&nxt.od[2u * (slotIdx)], o4);
     stS(&nxt.od[2u * (slotIdx) + 1u], d4);
@@ -2594,13 +2625,13 @@ __device__ __forceinline__ void regenCounters(Counters* C, int par, const RegenP
  * order: frame f's first sample is stream pass f * spp, seeded
  * initSeed(p + 1799 * (baseFrame + f * spp)) (renderer.cpp:169; baseFrame =
  * the sample count before the stream). */
-template <bool MASKED>
+template <bool MASKED, bool SURFEL = false>
 __global__ __launch_bounds__(kBlock) void k_regen(DevCamera cam, Pool nxt, float4* __restrict__ rad, Counters* C, int par,
-                                                  uint32_t capacity, StreamGeom G, ShadowQ Q) {
+                                                  uint32_t capacity, Geom<SURFEL> G, ShadowQ Q) {
     const RegenPlan R = regenPlan<MASKED>(C, par, capacity, G);
     const uint32_t gid = blockIdx.x * blockDim.x + threadIdx.x;
     if (gid < kShSegs) *shCursor(Q, par ^ 1, gid) = 0u;      /* the next phase's shadow-queue cursors (all, in use or not) */
-    for (uint32_t k = gid; k < R.nnew; k += gridDim.x * blockDim.x) regenSample<MASKED>(cam, nxt, rad, G, R, k);
+    for (uint32_t k = gid; k < R.nnew; k += gridDim.x * blockDim.x) regenSample<MASKED, SURFEL>(cam, nxt, rad, G, R, k);
     if (gid == 0) regenCounters(C, par, R);
 }
 
@@ -2611,9 +2642,9 @@ __global__ __launch_bounds__(kBlock) void k_regen(DevCamera cam, Pool nxt, float
  * samples (key kBins - 1), then writes the chunk's bin counts where k_bincount
  * would -- so the next phase's sort is k_binscatter alone, and one kernel
  * instead of two waits for CU slots beside k_connect. */
-template <bool MASKED>
+template <bool MASKED, bool SURFEL = false>
 __global__ __launch_bounds__(kSortThreads) void k_regen_count(DevCamera cam, Pool nxt, float4* __restrict__ rad, Counters* C, int par,
-                                                             uint32_t capacity, StreamGeom G, ShadowQ Q, uint32_t* __restrict__ hist) {
+                                                             uint32_t capacity, Geom<SURFEL> G, ShadowQ Q, uint32_t* __restrict__ hist) {
     __shared__ uint32_t h[kBins];
     if (threadIdx.x < kBins) h[threadIdx.x] = 0u;
     const RegenPlan R = regenPlan<MASKED>(C, par, capacity, G);
@@ -2625,7 +2656,7 @@ __global__ __launch_bounds__(kSortThreads) void k_regen_count(DevCamera cam, Poo
     uint32_t cam0 = 0u;
     for (uint32_t i = a + threadIdx.x; i < b; i += blockDim.x) {
         if (i < R.cont) atomicAdd(&h[nxt.key[i]], 1u);
-        else { regenSample<MASKED>(cam, nxt, rad, G, R, i - R.cont); ++cam0; }
+        else { regenSample<MASKED, SURFEL>(cam, nxt, rad, G, R, i - R.cont); ++cam0; }
     }
     if (cam0) atomicAdd(&h[kBins - 1u], cam0);
     __syncthreads();
@@ -2645,11 +2676,12 @@ __global__ __launch_bounds__(kSortThreads) void k_regen_count(DevCamera cam, Poo
 /* One path run to its end (or for `budget` segments, after which the
  * continuation goes to `sink`): extend -> shade -> connect per segment with
  * the wavefront kernels' device functions.  Returns whether the path ended. */
+template <bool SURFEL = false>
 __device__ __forceinline__ bool runPath(const DevScene& S, const TraceTables& Tt, const ShadeTables& Tb, float4 o4, float4 d4,
                                         float4 T4, uint32_t budget, const Sink& sink, float4* __restrict__ rad,
                                         uint32_t* __restrict__ frameDone, uint32_t npx, uint32_t window, Counters* C,
                                         uint32_t* stk, uint32_t stride, uint32_t firstCounted, const DevCamera& cam,
-                                        const StreamGeom& G) {
+                                        const Geom<SURFEL>& G) {
     const uint32_t maxSeg = C->maxSeg, zeroCutoff = C->zeroCutoff, spp = C->spp;
     const uint32_t st = blockIdx.x % kStripes;
     uint32_t slot = f2u(o4.w) / npx;
@@ -2684,7 +2716,7 @@ __device__ __forceinline__ bool runPath(const DevScene& S, const TraceTables& Tt
             atomicAdd(&frameDone[st * window + slot], 1u);
             ++nDone;
             /* the frame's next sample of this pixel continues on this lane */
-            if (chainNext(cam, G, spp, f2u(o4.w), slot, r.seedOut, o4, d4, T4)) { ++slot; E = mk3(0.0f, 0.0f, 0.0f); continue; }
+            if (chainNext<SURFEL>(cam, G, spp, f2u(o4.w), slot, r.seedOut, o4, d4, T4)) { ++slot; E = mk3(0.0f, 0.0f, 0.0f); continue; }
             break;
         }
         ++nCont;
@@ -2713,11 +2745,11 @@ __device__ __forceinline__ bool runPath(const DevScene& S, const TraceTables& Tt
  * budget, paths still alive after `budget` segments go to `surv` for the next
  * drain stage.  firstCounted: the first extension ray of each input path is
  * already in the event counts (regen counted it). */
-template <bool LDS_TABLES>
+template <bool LDS_TABLES, bool SURFEL = false>
 __global__ __launch_bounds__(64, SURF_TAIL_WAVES) void k_tail(DevScene S, Pool cur, uint32_t n, uint32_t lpw, float4* __restrict__ rad,
                                              uint32_t* __restrict__ frameDone, uint32_t npx, uint32_t window, Counters* C,
                                              uint32_t stackWords, uint32_t firstCounted, uint32_t budget, Pool surv,
-                                             DevCamera cam, StreamGeom G) {
+                                             DevCamera cam, Geom<SURFEL> G) {
     extern __shared__ uint32_t lds[];
     const TraceTables Tt = traceTables<LDS_TABLES>(S, lds, layout::laneTablesAt(stackWords, false));
     __shared__ DevInstance sInst[LDS_TABLES ? kLdsInst : 1];
@@ -2731,7 +2763,7 @@ __global__ __launch_bounds__(64, SURF_TAIL_WAVES) void k_tail(DevScene S, Pool c
     const uint32_t lane = threadIdx.x;
     const uint32_t i = blockIdx.x * lpw + lane;
     if (lane >= lpw || i >= n) return;
-    runPath(S, Tt, Tb, cur.od[2u * (i)], cur.od[2u * (i) + 1u], cur.T[i], budget, Sink{surv, &C->survN, C->survCap}, rad, frameDone, npx, window, C,
+    runPath<SURFEL>(S, Tt, Tb, cur.od[2u * (i)], cur.od[2u * (i) + 1u], cur.T[i], budget, Sink{surv, &C->survN, C->survCap}, rad, frameDone, npx, window, C,
             lds + threadIdx.x, blockDim.x, firstCounted, cam, G);
 }
 
@@ -2744,10 +2776,10 @@ __global__ __launch_bounds__(64, SURF_TAIL_WAVES) void k_tail(DevScene S, Pool c
  * (stackWords = 16 x depth words), then the trace tables; the shading tables
  * are read from global memory (wave-uniform reads): LDS copies would cap the
  * one-wave blocks at ~2 waves per SIMD. */
-template <bool LDS, bool W2 = false>
+template <bool LDS, bool W2 = false, bool SURFEL = false>
 __global__ __launch_bounds__(64, SURF_COOP_WAVES) void k_tail_coop(DevScene S, Pool cur, uint32_t n, float4* __restrict__ rad,
                                                   uint32_t* __restrict__ frameDone, uint32_t npx, uint32_t window, Counters* C,
-                                                  uint32_t stackWords, uint32_t firstCounted, DevCamera cam, StreamGeom G) {
+                                                  uint32_t stackWords, uint32_t firstCounted, DevCamera cam, Geom<SURFEL> G) {
     extern __shared__ uint32_t lds[];
     const TraceTables Tt = coopTrace<LDS>(S, lds, layout::waveTablesAt(stackWords, S.nInst, 1u));
     /* shading's instance / material / light tables in LDS too: a path's
@@ -2823,7 +2855,7 @@ __global__ __launch_bounds__(64, SURF_COOP_WAVES) void k_tail_coop(DevScene S, P
             }
             ++nDone;
             /* the frame's next sample of this pixel continues on this wave */
-            if (chainNext(cam, G, spp, f2u(o4.w), slot, r.seedOut, o4, d4, T4)) { ++slot; E = mk3(0.0f, 0.0f, 0.0f); continue; }
+            if (chainNext<SURFEL>(cam, G, spp, f2u(o4.w), slot, r.seedOut, o4, d4, T4)) { ++slot; E = mk3(0.0f, 0.0f, 0.0f); continue; }
             break;
         }
         ++nCont;
@@ -2880,11 +2912,11 @@ struct PairCounts { uint32_t ext, hit, cont, sh, acc, un, paths, samples; };   /
 
 /* One path of the queue on the calling wave (w); its shadow rays go to the
  * sibling while box.help[w] is set. */
-template <bool W2>
+template <bool W2, bool SURFEL = false>
 __device__ __forceinline__ void pairPath(const DevScene& S, const TraceTables& Tt, const ShadeTables& Tb, PairBox& box, uint32_t w,
                                          float4 o4, float4 d4, float4 T4, float4* __restrict__ rad, uint32_t* __restrict__ frameDone,
                                          uint32_t npx, uint32_t window, Counters* C, float* rstk, float4* pro, bool lead,
-                                         uint32_t& posted, PairCounts& pc, const DevCamera& cam, const StreamGeom& G) {
+                                         uint32_t& posted, PairCounts& pc, const DevCamera& cam, const Geom<SURFEL>& G) {
     const uint32_t maxSeg = C->maxSeg, zeroCutoff = C->zeroCutoff, spp = C->spp;
     uint32_t slot = f2u(o4.w) / npx;
     bool pend = false;                     /* a posted shadow ray awaits its answer */
@@ -2946,7 +2978,7 @@ __device__ __forceinline__ void pairPath(const DevScene& S, const TraceTables& T
                 atomicAdd(&frameDone[(blockIdx.x % kStripes) * window + slot], 1u);
             }
             /* the frame's next sample of this pixel continues on this wave */
-            if (chainNext(cam, G, spp, f2u(o4.w), slot, r.seedOut, o4, d4, T4)) { ++slot; E = mk3(0.0f, 0.0f, 0.0f); continue; }
+            if (chainNext<SURFEL>(cam, G, spp, f2u(o4.w), slot, r.seedOut, o4, d4, T4)) { ++slot; E = mk3(0.0f, 0.0f, 0.0f); continue; }
             break;
         }
         ++pc.cont;
@@ -2958,10 +2990,10 @@ __device__ __forceinline__ void pairPath(const DevScene& S, const TraceTables& T
     ++pc.paths;
 }
 
-template <bool LDS, bool W2 = false>
+template <bool LDS, bool W2 = false, bool SURFEL = false>
 __global__ __launch_bounds__(128, SURF_COOP_WAVES) void k_tail_pair(DevScene S, Pool cur, uint32_t n, float4* __restrict__ rad,
                                                    uint32_t* __restrict__ frameDone, uint32_t npx, uint32_t window, Counters* C,
-                                                   uint32_t stackWords, uint32_t firstCounted, DevCamera cam, StreamGeom G) {
+                                                   uint32_t stackWords, uint32_t firstCounted, DevCamera cam, Geom<SURFEL> G) {
     extern __shared__ uint32_t lds[];
     __shared__ PairBox box;
     /* LDS: [record stack | prologue table] per wave, then the trace tables and the shading tables */
@@ -2983,7 +3015,7 @@ __global__ __launch_bounds__(128, SURF_COOP_WAVES) void k_tail_pair(DevScene S, 
         if (lead) i = atomicAdd(&C->rowNext, 1u);
         i = __builtin_amdgcn_readfirstlane(i);
         if (i >= n) break;
-        pairPath<W2>(S, Tt, Tb, box, w, cur.od[2u * i], cur.od[2u * i + 1u], cur.T[i], rad, frameDone, npx, window, C, rstk, pro,
+        pairPath<W2, SURFEL>(S, Tt, Tb, box, w, cur.od[2u * i], cur.od[2u * i + 1u], cur.T[i], rad, frameDone, npx, window, C, rstk, pro,
                  lead, posted, pc, cam, G);
     }
     /* queue empty: leave the path loop, then serve the sibling's shadow rays

@@ -44,6 +44,7 @@ const char* frameError(uint32_t w, uint32_t h, const float* acc, const float* sq
 int runMask(surf_ctx* c, uint32_t w, uint32_t h, const float4* A, const float4* Q, const surf_adaptive_mask_params& P, uint8_t* mask,
             uint32_t* list, uint32_t* blk, uint32_t* count) {
     hipLaunchKernelGGL(k_adaptive_flags, tileGrid(w, h), dim3(256), 0, c->stream, A, Q, mask, (int)w, (int)h, ruleOf(P));
+    queueSensorValidity(c, mask);
     return compactMask(c, w * h, mask, list, blk, count);
 }
 
@@ -58,6 +59,24 @@ void surfhost::freeAdaptive(surf_ctx* c) {
     c->pmOn = false;
 }
 
+int surfhost::resetSensorMask(surf_ctx* c) {
+    c->pmOn = false;
+    c->pmActive = 0;
+    if (!sensorInvalid(c)) return SURF_OK;
+    if (int rc = ensureContextMask(c)) return rc;
+    std::vector<uint32_t> list;
+    list.reserve(c->ssValid);
+    for (uint32_t p = 0; p < c->npx; ++p)
+        if (c->ssValidHost[p]) list.push_back(p);
+    SURF_CHECK(c, hipMemcpyAsync(c->pmMask, c->ssValidHost.data(), c->npx, hipMemcpyHostToDevice, c->stream));
+    if (!list.empty())
+        SURF_CHECK(c, hipMemcpyAsync(c->pmList, list.data(), list.size() * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    SURF_CHECK(c, hipStreamSynchronize(c->stream));
+    c->pmOn = true;
+    c->pmActive = c->ssValid;
+    return SURF_OK;
+}
+
 extern "C" {
 
 int surf_set_pixel_mask(surf_ctx* c, const uint8_t* mask) {
@@ -65,13 +84,14 @@ int surf_set_pixel_mask(surf_ctx* c, const uint8_t* mask) {
     SURF_CHECK(c, hipSetDevice(c->device));
     int rc = endStream(c);                     /* a stream's pixels are fixed when it opens */
     if (rc) return rc;
-    if (!mask) { c->pmOn = false; c->pmActive = 0; return SURF_OK; }
+    if (!mask) return resetSensorMask(c);
+    const uint8_t* valid = sensorInvalid(c) ? c->ssValidHost.data() : nullptr;   /* a surfel sensor's invalid texels are never active */
     std::vector<uint8_t> bytes(c->npx);
     std::vector<uint32_t> list;
     list.reserve(c->npx);
     for (uint32_t p = 0; p < c->npx; ++p) {
-        bytes[p] = mask[p] ? 1 : 0;
-        if (mask[p]) list.push_back(p);
+        bytes[p] = mask[p] && (!valid || valid[p]) ? 1 : 0;
+        if (bytes[p]) list.push_back(p);
     }
     if (list.size() == c->npx) { c->pmOn = false; c->pmActive = 0; return SURF_OK; }   /* all ones: no mask */
     if ((rc = ensureContextMask(c))) return rc;

@@ -63,6 +63,7 @@ int runErrorMask(surf_ctx* c, uint32_t w, uint32_t h, const float4* out, const f
     hipLaunchKernelGGL(k_error_mask, tileGrid(w, h), dim3(256), 0, c->stream, out, err, A, mask, (int)w, (int)h, R,
                        stats ? emStats(c) : (ErrorStats*)nullptr);
     SURF_CHECK(c, c->emTime.mark(1, c->stream));
+    queueSensorValidity(c, mask);
     if ((rc = queueCompaction(c, npx, mask, list, blk))) return rc;
     SURF_CHECK(c, c->emTime.mark(2, c->stream));
     SURF_CHECK(c, hipMemcpyAsync(count, blk + compactBlocks(npx), sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));

@@ -52,6 +52,16 @@ int ensureImageMask(surf_ctx* c, size_t npx) {
     return SURF_OK;
 }
 
+/* a surfel sensor with invalid texels is set: they are never active, whatever sets or builds the context's mask */
+bool sensorInvalid(const surf_ctx* c) { return c->ssOn && c->ssValid < c->npx; }
+
+/* ... so behind the kernel that wrote the context's mask (any other mask is an image call's: left as built) and before its
+ * compaction, their bytes are forced to 0 */
+void queueSensorValidity(surf_ctx* c, uint8_t* mask) {
+    if (mask != c->pmMask || !sensorInvalid(c)) return;
+    hipLaunchKernelGGL(k_mask_and_valid, dim3(compactBlocks(c->npx)), dim3(kCompactBlock), 0, c->stream, mask, (const uint8_t*)c->ssValidDev, c->npx);
+}
+
 /* The ascending list of a byte mask of npx pixels, queued behind the kernel
  * that writes the mask: count, scan, scatter. */
 int queueCompaction(surf_ctx* c, uint32_t npx, const uint8_t* mask, uint32_t* list, uint32_t* blk) {

@@ -114,6 +114,11 @@ std::vector<F32> WaveFrontRenderer::readAOV(surf_aov plane) {
     return out;
 }
 
+void WaveFrontRenderer::copyAOVDevice(surf_aov plane, void* dstDevice) {
+    pushSceneAndCamera();
+    check(surf_copy_aov_device(m_ctx, plane, dstDevice), m_ctx, "surf_copy_aov_device");
+}
+
 std::vector<U32> WaveFrontRenderer::readAOVIds() {
     pushSceneAndCamera();
     std::vector<U32> out((size_t)m_resolution.width * m_resolution.height * 4);
@@ -330,6 +335,28 @@ std::vector<uint8_t> WaveFrontRenderer::pixelMask(U32* activeCount) {
     check(surf_get_pixel_mask(m_ctx, out.data(), &n), m_ctx, "surf_get_pixel_mask");
     if (activeCount) *activeCount = n;
     return out;
+}
+
+void WaveFrontRenderer::setSurfelSensor(const std::vector<F32>& position, const std::vector<F32>& normal) {
+    const size_t n = (size_t)m_resolution.width * m_resolution.height * 4;
+    if (position.size() != n || normal.size() != n)
+        throw std::runtime_error("setSurfelSensor: position and normal are not width*height*4 floats each");
+    check(surf_set_surfel_sensor(m_ctx, position.data(), normal.data()), m_ctx, "surf_set_surfel_sensor");
+}
+
+void WaveFrontRenderer::setSurfelSensorDevice(const void* positionDevice, const void* normalDevice) {
+    if (!positionDevice || !normalDevice) throw std::runtime_error("setSurfelSensorDevice: NULL device pointer");
+    check(surf_set_surfel_sensor_device(m_ctx, positionDevice, normalDevice), m_ctx, "surf_set_surfel_sensor_device");
+}
+
+void WaveFrontRenderer::clearSurfelSensor() { check(surf_set_surfel_sensor(m_ctx, nullptr, nullptr), m_ctx, "surf_set_surfel_sensor"); }
+
+bool WaveFrontRenderer::surfelSensor(U32* validTexels) {
+    int kind = 0;
+    uint32_t valid = 0;
+    check(surf_get_sensor(m_ctx, &kind, &valid), m_ctx, "surf_get_sensor");
+    if (validTexels) *validTexels = valid;
+    return kind == SURF_SENSOR_SURFELS;
 }
 
 U32 WaveFrontRenderer::maskFromNoise(const surf_adaptive_mask_params& params) {

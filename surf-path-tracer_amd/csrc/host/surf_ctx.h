@@ -298,6 +298,17 @@ struct surf_ctx {
     uint32_t* adImgList = nullptr;
     uint32_t* adImgBlk = nullptr;
     size_t adImgCap = 0;
+    /* the surfel sensor (surf_set_surfel_sensor*; surf_hip.hip): ssOn: samples start at the caller's texels, not at the
+     * camera -- the stream's kernels are the SURFEL instantiations (sensorKernels) and take surfelGeom's argument.  ssPlanes:
+     * the library's copies of the two planes (position, normal: npx records each), allocated on first use, kept when the
+     * sensor is cleared, freed in surf_destroy.  ssValidDev / ssValidHost: a byte per texel, 1 where its normal is not
+     * (0, 0, 0), ssValid of them: every mask set or built on the context is ANDed with it before its compaction, and while
+     * ssValid < npx "no mask" is the validity mask itself (resetSensorMask). */
+    bool ssOn = false;
+    PlaneGroup<2> ssPlanes{"the surfel sensor's planes"};
+    uint8_t* ssValidDev = nullptr;
+    std::vector<uint8_t> ssValidHost;
+    uint32_t ssValid = 0;
     hipEvent_t accEv[2] = {};      /* profiling: around each k_accumulate launch (surf_stats.ms_accum), created on first use */
     uint32_t* dRows = nullptr;
     Counters* ctr = nullptr;
@@ -422,6 +433,9 @@ void freeTemporal(surf_ctx* c);
 void freeSvgf(surf_ctx* c);
 /* defined in host/adaptive.hip: surf_destroy's part for the mask's buffers */
 void freeAdaptive(surf_ctx* c);
+/* defined in host/adaptive.hip, for whatever sets the context's mask back to "every pixel": under a surfel sensor with
+ * invalid texels that is the validity mask (bytes, list, count), else no mask at all.  Waits for its copies. */
+int resetSensorMask(surf_ctx* c);
 /* defined in host/robust.hip: surf_destroy's part for the robust estimate's images */
 void freeRobust(surf_ctx* c);
 /* defined in host/nlm.hip: surf_destroy's part for the stills filters' images */

@@ -17,6 +17,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <mutex>
+#include <type_traits>
 
 #include "device/wavefront_kernels.h"
 #include "device/aov_sampled_kernels.h"
@@ -127,6 +128,19 @@ Variant variantOf(const surf_ctx* c) {
 
 /* the four instantiations of a kernel template over two bools */
 #define SURF_PICK2(K, a, b) ((a) ? ((b) ? K<true, true> : K<true, false>) : ((b) ? K<false, true> : K<false, false>))
+/* ... and of one whose third argument, SF, is a compile-time constant at the call site */
+#define SURF_PICK2S(K, a, b, SF) ((a) ? ((b) ? K<true, true, SF> : K<true, false, SF>) : ((b) ? K<false, true, SF> : K<false, false, SF>))
+
+/* The sensor of the context's stream -- the camera, or the caller's surfels
+ * (surf_set_surfel_sensor) -- picks the SURFEL argument of every kernel that
+ * starts a sample (k_regen*, k_shade and the drains) and, with it, the type of
+ * the kernel's stream-geometry argument (Geom<SURFEL>): f(std::bool_constant<SURFEL>)
+ * launches with the selectors below and geomArg, both instantiated on it. */
+template <class F>
+void withSensor(const surf_ctx* c, F&& f) {
+    if (c->ssOn) f(std::true_type{});
+    else f(std::false_type{});
+}
 
 /* k_extend<LDS, LW, SK>: 6 of the 8 -- the two-level lane walk never takes a 16-bit stack */
 template <bool LDS>
@@ -140,7 +154,8 @@ auto extendKernel(const surf_ctx* c, const Variant& v) {
 }
 
 /* k_shade<LDS, HV>: HV with the shadow key's heavy-box layouts (SURF_SH_KEY 1, 2) */
-auto shadeKernel(const surf_ctx* c, const Variant& v) { return SURF_PICK2(k_shade, v.lds, c->Q.bins > kShBinsBase); }
+template <bool SF>
+auto shadeKernel(const surf_ctx* c, const Variant& v) { return SURF_PICK2S(k_shade, v.lds, c->Q.bins > kShBinsBase, SF); }
 
 /* k_connect<LDS, LW, STG>: staged only over LDS tables and one-level records */
 auto connectKernel(const surf_ctx* c, const Variant& v) {
@@ -163,11 +178,14 @@ auto aoFn(const Variant& v) {
 }
 auto aoKernel(const surf_ctx* c, const Variant& v) { return kernel(c->aoRayMap ? aoFn<true>(v) : aoFn<false>(v), laneLds(c, kBlock, false, v.lds)); }
 static_assert(kAoSeedSalt == SURF_AO_SEED_SALT, "the kernel's salt is the header's");
-auto tailKernel(const surf_ctx* c, const Variant& v) { return kernel(v.lds ? k_tail<true> : k_tail<false>, laneLds(c, 64, false, v.lds)); }
+template <bool SF>
+auto tailKernel(const surf_ctx* c, const Variant& v) { return kernel(v.lds ? k_tail<true, SF> : k_tail<false, SF>, laneLds(c, 64, false, v.lds)); }
 
 /* the one-ray-per-wave kernels over <LDS, W2> */
-auto tailPairKernel(const surf_ctx* c, const Variant& v) { return kernel(SURF_PICK2(k_tail_pair, v.lds, v.w2), waveTailLds(c, 2u)); }
-auto tailCoopKernel(const surf_ctx* c, const Variant& v) { return kernel(SURF_PICK2(k_tail_coop, v.lds, v.w2), waveTailLds(c, 1u)); }
+template <bool SF>
+auto tailPairKernel(const surf_ctx* c, const Variant& v) { return kernel(SURF_PICK2S(k_tail_pair, v.lds, v.w2, SF), waveTailLds(c, 2u)); }
+template <bool SF>
+auto tailCoopKernel(const surf_ctx* c, const Variant& v) { return kernel(SURF_PICK2S(k_tail_coop, v.lds, v.w2, SF), waveTailLds(c, 1u)); }
 auto segmentCyclesKernel(const surf_ctx* c, const Variant& v) { return kernel(SURF_PICK2(k_segment_cycles, v.lds, v.w2), waveTailLds(c, 1u)); }
 /* planted paths (surf_debug_trace_paths): the lane kernels' and the cooperative drain's variants and LDS */
 auto debugPathsLaneKernel(const surf_ctx* c, const Variant& v) { return kernel(SURF_PICK2(k_debug_paths_lane, v.lds, v.laneW), laneLds(c, kBlock, false, v.lds)); }
@@ -187,8 +205,10 @@ auto accumulateListKernel(const surf_ctx* c) { return c->sqOn ? k_accumulate_lis
 auto accumulateBucketsKernel(const surf_ctx* c) { return SURF_PICK_BUCKETS(k_accumulate_buckets, c->sqOn, c->bkM); }
 auto accumulateBucketsListKernel(const surf_ctx* c) { return SURF_PICK_BUCKETS(k_accumulate_buckets_list, c->sqOn, c->bkM); }
 /* k_regen<MASKED> / k_regen_count<MASKED>: a masked stream issues frame-major over the active list */
-auto regenKernel(const surf_ctx* c) { return c->streamMasked ? k_regen<true> : k_regen<false>; }
-auto regenCountKernel(const surf_ctx* c) { return c->streamMasked ? k_regen_count<true> : k_regen_count<false>; }
+template <bool SF>
+auto regenKernel(const surf_ctx* c) { return c->streamMasked ? k_regen<true, SF> : k_regen<false, SF>; }
+template <bool SF>
+auto regenCountKernel(const surf_ctx* c) { return c->streamMasked ? k_regen_count<true, SF> : k_regen_count<false, SF>; }
 /* shadow-queue order bins in use: the key layout's (SURF_SH_KEY, shadowKey), or 1 without a shadow order */
 uint32_t shadowBins(const surf_ctx* c) {
     static const uint32_t kLayoutBins[3] = {kShBinsBase, 2u * kShBinsBase, kShBins};
@@ -348,6 +368,12 @@ int ensureWindow(surf_ctx* c, uint64_t frames, uint32_t spp) {
 StreamGeom geom(const surf_ctx* c) {
     return StreamGeom{c->dRows, c->width, c->npx, c->window, c->streamMasked ? (const uint32_t*)c->pmList : (const uint32_t*)c->dPerm};
 }
+/* ... as the kernels of withSensor's choice take it: a sensor stream's carries the sensor's two planes */
+template <bool SF>
+Geom<SF> geomArg(const surf_ctx* c) {
+    if constexpr (SF) return SurfelGeom{geom(c), c->ssPlanes[0], c->ssPlanes[1]};
+    else return geom(c);
+}
 
 /* Counting sort of the pool (which 0) or shadow queue (which 1) of phase par
  * by its 4-bit key into c->order. */
@@ -387,12 +413,15 @@ void launchPhase(surf_ctx* c, int ph, hipEvent_t* ev) {
         order = c->order;
     }
     auto regen = [&]() {
-        if (fused)
-            hipLaunchKernelGGL(regenCountKernel(c), dim3(kSortBlocks), dim3(kSortThreads), 0, s0, c->cam, c->pool[par ^ 1], c->rad, c->ctr,
-                               par, c->capacity, geom(c), c->Q, c->binHist);
-        else
-            hipLaunchKernelGGL(regenKernel(c), dim3(c->gridRegen), dim3(kBlock), 0, s0, c->cam, c->pool[par ^ 1], c->rad, c->ctr, par,
-                               c->capacity, geom(c), c->Q);
+        withSensor(c, [&](auto sf) {
+            constexpr bool SF = decltype(sf)::value;
+            if (fused)
+                hipLaunchKernelGGL(regenCountKernel<SF>(c), dim3(kSortBlocks), dim3(kSortThreads), 0, s0, c->cam, c->pool[par ^ 1], c->rad,
+                                   c->ctr, par, c->capacity, geomArg<SF>(c), c->Q, c->binHist);
+            else
+                hipLaunchKernelGGL(regenKernel<SF>(c), dim3(c->gridRegen), dim3(kBlock), 0, s0, c->cam, c->pool[par ^ 1], c->rad, c->ctr,
+                                   par, c->capacity, geomArg<SF>(c), c->Q);
+        });
     };
     if (ev) (void)hipEventRecord(ev[1], s0);
     const Pool cur = c->pool[par];                 /* the pool k_extend / k_shade read */
@@ -401,9 +430,12 @@ void launchPhase(surf_ctx* c, int ph, hipEvent_t* ev) {
                        cur, c->hitTUV, c->hitInst, (const Counters*)c->ctr, par, stackWords(c, c->extBlock), order);
     if (ev) (void)hipEventRecord(ev[2], s0);
     if (ovl && ph > 0) (void)hipStreamWaitEvent(s0, c->capEv[2 * (ph - 1) + 1], 0);   /* the previous phase's connect */
-    hipLaunchKernelGGL(shadeKernel(c, v), dim3(c->gridWork), dim3(kBlock), 0, s0, c->S, cur, c->pool[par ^ 1],
-                       c->hitTUV, (const uint32_t*)c->hitInst, c->Q, c->rad, c->frameDone, c->npx, c->window, c->ctr, par, order,
-                       c->cam, geom(c));
+    withSensor(c, [&](auto sf) {
+        constexpr bool SF = decltype(sf)::value;
+        hipLaunchKernelGGL(shadeKernel<SF>(c, v), dim3(c->gridWork), dim3(kBlock), 0, s0, c->S, cur, c->pool[par ^ 1],
+                           c->hitTUV, (const uint32_t*)c->hitInst, c->Q, c->rad, c->frameDone, c->npx, c->window, c->ctr, par, order,
+                           c->cam, geomArg<SF>(c));
+    });
     if (ev) (void)hipEventRecord(ev[3], s0);
     /* k_regen before the fork (SURF_REGEN_FIRST): alone it takes ~17 us, beside
      * k_connect it waits for CU slots on the next phase's critical path */
@@ -671,7 +703,7 @@ int startStream(surf_ctx* c, uint64_t baseFrame, uint32_t maxSeg, uint32_t frame
     c->streamMasked = c->pmOn;
     c->streamPx = c->pmOn ? c->pmActive : c->npx;
     h.nActive = c->pmOn ? c->pmActive : 0u;
-    if (!c->pmOn && c->reorder && frames >= 2 && (uint64_t)frames * spp <= c->window && c->heavyInst.size()) {
+    if (!c->pmOn && !c->ssOn && c->reorder && frames >= 2 && (uint64_t)frames * spp <= c->window && c->heavyInst.size()) {
         int rc = classifyPixels(c);
         if (rc) return rc;
         if (c->permA > 0 && c->permA < c->npx) c->permFrames = frames;
@@ -890,9 +922,12 @@ int advance(surf_ctx* c, bool shortRun = false) {
  * phase boundary: pool 0 is the next to be extended, nothing else pending). */
 void launchTail(surf_ctx* c, Pool in, uint32_t n, uint32_t lpw, uint32_t firstCounted, uint32_t budget, Pool out) {
     const uint32_t blocks = (n + lpw - 1) / lpw;
-    const auto tail = tailKernel(c, variantOf(c));
-    hipLaunchKernelGGL(tail.fn, dim3(blocks), dim3(64), tail.lds, c->stream, c->S, in, n, lpw, c->rad, c->frameDone,
-                       c->npx, c->window, c->ctr, stackWords(c, 64), firstCounted, budget, out, c->cam, geom(c));
+    withSensor(c, [&](auto sf) {
+        constexpr bool SF = decltype(sf)::value;
+        const auto tail = tailKernel<SF>(c, variantOf(c));
+        hipLaunchKernelGGL(tail.fn, dim3(blocks), dim3(64), tail.lds, c->stream, c->S, in, n, lpw, c->rad, c->frameDone,
+                           c->npx, c->window, c->ctr, stackWords(c, 64), firstCounted, budget, out, c->cam, geomArg<SF>(c));
+    });
 }
 
 /* Finishes every path of pool 0 (counters at an even phase boundary: pool 0 is
@@ -930,22 +965,28 @@ int runTail(surf_ctx* c) {
             /* as many two-wave workgroups as are resident at once, each wave
              * taking paths from the queue; idle waves trace their sibling's
              * shadow rays once the queue is empty */
-            int per = 0;
-            const auto pair = tailPairKernel(c, v);
-            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, pair.fn, 128, pair.lds) != hipSuccess || per < 1)
-                per = 2 * SURF_COOP_WAVES;
-            const uint32_t blocks = std::max<uint32_t>(1u, std::min<uint32_t>((cnt + 1u) / 2u, c->cus * (uint32_t)per));
             SURF_CHECK(c, hipMemsetAsync(&c->ctr->rowNext, 0, sizeof(uint32_t), c->stream));
-            hipLaunchKernelGGL(pair.fn, dim3(blocks), dim3(128), pair.lds, c->stream, c->S, in, cnt, c->rad, c->frameDone,
-                               c->npx, c->window, c->ctr, recStackWords(c), firstCounted, c->cam, geom(c));
+            withSensor(c, [&](auto sf) {
+                constexpr bool SF = decltype(sf)::value;
+                int per = 0;
+                const auto pair = tailPairKernel<SF>(c, v);
+                if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, pair.fn, 128, pair.lds) != hipSuccess || per < 1)
+                    per = 2 * SURF_COOP_WAVES;
+                const uint32_t blocks = std::max<uint32_t>(1u, std::min<uint32_t>((cnt + 1u) / 2u, c->cus * (uint32_t)per));
+                hipLaunchKernelGGL(pair.fn, dim3(blocks), dim3(128), pair.lds, c->stream, c->S, in, cnt, c->rad, c->frameDone,
+                                   c->npx, c->window, c->ctr, recStackWords(c), firstCounted, c->cam, geomArg<SF>(c));
+            });
             SURF_CHECK(c, hipGetLastError());
             c->stats.tail_survivors += cnt;
             break;
         }
         if (waveEligible(c) && cnt <= c->coopAll) {
-            const auto coop = tailCoopKernel(c, v);
-            hipLaunchKernelGGL(coop.fn, dim3(cnt), dim3(64), coop.lds, c->stream, c->S, in, cnt, c->rad, c->frameDone,
-                               c->npx, c->window, c->ctr, recStackWords(c), firstCounted, c->cam, geom(c));
+            withSensor(c, [&](auto sf) {
+                constexpr bool SF = decltype(sf)::value;
+                const auto coop = tailCoopKernel<SF>(c, v);
+                hipLaunchKernelGGL(coop.fn, dim3(cnt), dim3(64), coop.lds, c->stream, c->S, in, cnt, c->rad, c->frameDone,
+                                   c->npx, c->window, c->ctr, recStackWords(c), firstCounted, c->cam, geomArg<SF>(c));
+            });
             SURF_CHECK(c, hipGetLastError());
             c->stats.tail_survivors += cnt;
             break;
@@ -1311,6 +1352,8 @@ void surf_destroy(surf_ctx* c) {
     freeDenoise(c);
     freeTemporal(c);
     freeAdaptive(c);
+    c->ssPlanes.free();
+    if (c->ssValidDev) (void)hipFree(c->ssValidDev);
     freeRobust(c);
     freeNlm(c);
     freeRegress(c);
@@ -1548,8 +1591,89 @@ int surf_clear_accumulator(surf_ctx* c) {
     std::memset(c->evBase, 0, sizeof c->evBase);
     c->segMaxBase = 0;
     c->tailFirstRays = 0;
-    c->pmOn = false;               /* the mask is back to "every pixel" */
-    c->pmActive = 0;
+    return resetSensorMask(c);     /* the mask is back to "every pixel" (every valid texel of a surfel sensor) */
+}
+
+/* surf_set_surfel_sensor*: the open stream ended, the
+ * validity bytes taken from the caller's normals (and the call refused before
+ * anything changes if one is unusable), the two planes copied into the
+ * context's own (kind: from the host or from the context's device), the graphs
+ * of the other sensor's kernels dropped and the mask set back to every valid
+ * texel. */
+static int setSensor(surf_ctx* c, const void* position, const void* normal, hipMemcpyKind kind, const char* who) {
+    if (!c) return fail(nullptr, SURF_ERR_INVALID, std::string(who) + ": ctx is NULL");
+    if (!position != !normal) return fail(c, SURF_ERR_INVALID, std::string(who) + ": one of position and normal is NULL");
+    SURF_CHECK(c, hipSetDevice(c->device));
+    int rc = endStream(c);                     /* a stream's sensor is fixed when it opens */
+    if (rc) return rc;
+    if (!position) {
+        if (c->ssOn) destroyGraph(c);          /* (captured with the surfel kernels) */
+        c->ssOn = false;
+        c->ssValid = 0;
+        return resetSensorMask(c);
+    }
+    const size_t npx = c->npx, bytes = npx * sizeof(float4);
+    /* validity first, from the caller's normals: nothing of the context changes before the planes are known to be usable */
+    std::vector<float4> n(npx);
+    if (kind == hipMemcpyHostToDevice) std::memcpy(n.data(), normal, bytes);
+    else {
+        SURF_CHECK(c, hipMemcpyAsync(n.data(), normal, bytes, hipMemcpyDeviceToHost, c->stream));
+        SURF_CHECK(c, hipStreamSynchronize(c->stream));
+    }
+    std::vector<uint8_t> validHost(npx);
+    uint32_t valid = 0;
+    for (size_t p = 0; p < npx; ++p) {
+        const bool v = n[p].x != 0.0f || n[p].y != 0.0f || n[p].z != 0.0f;   /* (a NaN component: valid) */
+        /* a nonzero normal whose squared length underflows: cosineSample's retry test dot(R, N) == 0 could hold on every try */
+        if (v && (n[p].x * n[p].x + n[p].y * n[p].y) + n[p].z * n[p].z < 1.17549435e-38f)
+            return fail(c, SURF_ERR_INVALID, std::string(who) + ": the normal of texel " + std::to_string(p) +
+                                                 " is nonzero but its squared length underflows (supply unit normals)");
+        validHost[p] = v ? 1 : 0;
+        valid += v ? 1u : 0u;
+    }
+    if ((rc = c->ssPlanes.grow(c, npx))) return rc;
+    if (!c->ssValidDev && hipMalloc((void**)&c->ssValidDev, npx) != hipSuccess) {
+        (void)hipGetLastError();
+        c->ssValidDev = nullptr;
+        return fail(c, SURF_ERR_OOM, std::string(who) + ": hipMalloc of " + std::to_string(npx) + " validity bytes failed");
+    }
+    /* from here the planes are overwritten: a copy that fails leaves the context on the camera, with no mask, not on
+     * new planes under the old validity */
+    const bool was = c->ssOn;
+    c->ssOn = false;
+    c->ssValid = 0;
+    const auto copies = [&]() -> int {
+        SURF_CHECK(c, hipMemcpyAsync(c->ssPlanes[0], position, bytes, kind, c->stream));
+        SURF_CHECK(c, hipMemcpyAsync(c->ssPlanes[1], normal, bytes, kind, c->stream));
+        SURF_CHECK(c, hipMemcpyAsync(c->ssValidDev, validHost.data(), npx, hipMemcpyHostToDevice, c->stream));
+        SURF_CHECK(c, hipStreamSynchronize(c->stream));
+        return SURF_OK;
+    };
+    if ((rc = copies())) {
+        if (was) destroyGraph(c);              /* (captured with the surfel kernels) */
+        const std::string why = c->err;
+        (void)resetSensorMask(c);              /* ssOn is off: every pixel */
+        return fail(c, rc, why);
+    }
+    if (!was) destroyGraph(c);                 /* (captured with the camera kernels) */
+    c->ssValidHost.swap(validHost);
+    c->ssOn = true;
+    c->ssValid = valid;
+    return resetSensorMask(c);
+}
+
+int surf_set_surfel_sensor(surf_ctx* c, const float* position, const float* normal) {
+    return setSensor(c, position, normal, hipMemcpyHostToDevice, "surf_set_surfel_sensor");
+}
+
+int surf_set_surfel_sensor_device(surf_ctx* c, const void* position_device, const void* normal_device) {
+    return setSensor(c, position_device, normal_device, hipMemcpyDeviceToDevice, "surf_set_surfel_sensor_device");
+}
+
+int surf_get_sensor(surf_ctx* c, int* kind, uint32_t* valid) {
+    if (!c) return fail(nullptr, SURF_ERR_INVALID, "surf_get_sensor: ctx is NULL");
+    if (kind) *kind = c->ssOn ? SURF_SENSOR_SURFELS : SURF_SENSOR_CAMERA;
+    if (valid) *valid = c->ssOn ? c->ssValid : c->npx;
     return SURF_OK;
 }
 

@@ -57,6 +57,9 @@ _STATUS = {
 }
 
 
+SENSOR_CAMERA, SENSOR_SURFELS = 0, 1    # surf_get_sensor's kinds
+
+
 class SurfError(RuntimeError):
     def __init__(self, code: int, what: str, detail: str):
         super().__init__(f"{what} failed: {_STATUS.get(code, code)}: {detail}")
@@ -361,6 +364,8 @@ def load() -> C.CDLL:
         "surf_noise_image": ([P, U32, P, P, C.POINTER(NoiseParams), P, C.POINTER(NoiseSummary)], I32),
         "surf_noise_image_host": ([U32, P, P, C.POINTER(NoiseParams), P, C.POINTER(NoiseSummary)], I32),
         "surf_set_pixel_mask": ([P, P], I32), "surf_get_pixel_mask": ([P, P, C.POINTER(U32)], I32),
+        "surf_set_surfel_sensor": ([P, P, P], I32), "surf_set_surfel_sensor_device": ([P, P, P], I32),
+        "surf_get_sensor": ([P, C.POINTER(I32), C.POINTER(U32)], I32),
         "surf_adaptive_default_mask_params": ([C.POINTER(AdaptiveMaskParams)], I32),
         "surf_adaptive_default_params": ([C.POINTER(AdaptiveParams)], I32),
         "surf_mask_from_noise": ([P, C.POINTER(AdaptiveMaskParams), C.POINTER(U32)], I32),
@@ -1885,6 +1890,57 @@ class Renderer:
         if m.size != len(self.rows) * self.width:
             raise ValueError(f"mask of {m.size} pixels for a shard of {len(self.rows) * self.width}")
         _check(load().surf_set_pixel_mask(self._h, _ptr(m)), "surf_set_pixel_mask", self._h)
+
+    def _surfel_planes(self, position, normal):
+        """The two planes of a surfel sensor checked before the library sees them: float32, (rows, W, 4) or flat with
+        rows*W*4 values each."""
+        n = len(self.rows) * self.width * 4
+        planes = []
+        for name, a in (("position", position), ("normal", normal)):
+            a = np.asarray(a)
+            if a.dtype != np.float32:
+                raise ValueError(f"set_surfel_sensor: {name} is {a.dtype}, not float32")
+            if a.size != n or (a.ndim != 1 and a.shape != (len(self.rows), self.width, 4)):
+                raise ValueError(f"set_surfel_sensor: {name} has shape {a.shape}, not ({len(self.rows)}, {self.width}, 4)")
+            planes.append(np.ascontiguousarray(a))
+        return planes
+
+    def set_surfel_sensor(self, position, normal):
+        """Starts this shard's samples at the caller's surface points (surf_set_surfel_sensor, which defines the sensor):
+        position and normal (rows, W, 4) float32 (w ignored); a texel whose normal is (0, 0, 0) is invalid and never
+        traced.  None, None: back to the camera.  accumulator() / w then estimates irradiance / pi at each texel."""
+        if position is None and normal is None:
+            _check(load().surf_set_surfel_sensor(self._h, None, None), "surf_set_surfel_sensor", self._h)
+            return
+        if position is None or normal is None:
+            raise ValueError("set_surfel_sensor: one of position and normal is None")
+        pos, nrm = self._surfel_planes(position, normal)
+        _check(load().surf_set_surfel_sensor(self._h, _ptr(pos), _ptr(nrm)), "surf_set_surfel_sensor", self._h)
+
+    def set_surfel_sensor_device(self, pos_ptr: int, nrm_ptr: int):
+        """The same from two device pointers on this context's device (surf_set_surfel_sensor_device), e.g. the planes
+        copy_aov_to wrote: rows*W float4 records each.  The library copies them."""
+        if not pos_ptr or not nrm_ptr:
+            raise ValueError("set_surfel_sensor_device: a device pointer is 0 (set_surfel_sensor(None, None) clears the sensor)")
+        _check(load().surf_set_surfel_sensor_device(self._h, C.c_void_p(pos_ptr), C.c_void_p(nrm_ptr)),
+               "surf_set_surfel_sensor_device", self._h)
+
+    def sensor(self):
+        """(kind, valid): SENSOR_CAMERA or SENSOR_SURFELS, and the valid texels (rows*W for the camera) (surf_get_sensor)."""
+        k, v = C.c_int(), C.c_uint32()
+        _check(load().surf_get_sensor(self._h, C.byref(k), C.byref(v)), "surf_get_sensor", self._h)
+        return int(k.value), int(v.value)
+
+    def bake(self, position, normal, frames: int, spp: int = 1, max_segments: int = 0, first_sample: int = 0) -> np.ndarray:
+        """Sets the surfel sensor, clears the accumulator, renders `frames` frames of `spp` samples and returns the
+        accumulator ((rows, W, 4): sum of energy, samples); the camera sensor is restored, the accumulator keeps the bake."""
+        self.set_surfel_sensor(position, normal)
+        try:
+            self.clear_accumulator()
+            self.render(frames, first_sample, max_segments, spp)
+            return self.accumulator()
+        finally:
+            self.set_surfel_sensor(None, None)
 
     def pixel_mask(self):
         """(mask (rows, W) uint8, active count) as set (surf_get_pixel_mask)."""
