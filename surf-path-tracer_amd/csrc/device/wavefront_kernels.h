@@ -3290,188 +3290,6 @@ __global__ __launch_bounds__(kBlock) void k_trace_any(DevScene S, const float* _
                               depth, u, v, inst, prim, lds + threadIdx.x, blockDim.x) ? 1 : 0;
 }
 
-/* First-hit feature buffers (AOVs, surf_read_aov): one lane per shard pixel lp
- * traces the pixel's unjittered camera ray -- through the pixel's corner
- * (x, row), from the camera position: no jitter and no lens sample, also for a
- * camera with a defocus angle, so the planes are sharp and carry no noise --
- * and writes four planar 16-byte records:
- *   pos[lp]  hit: (o + t d, t)                           miss: (0, 0, 0, 1e30)
- *   nrm[lp]  hit: (shadePath's N, 0), emitters included   miss: 0
- *   alb[lp]  hit: (albedo, 1); emitter: (strength * colour, 1)
- *                                                        miss: (background along d, 0)
- *   ids[lp]  hit: (instance, primitive, material, 0)     miss: (~0, ~0, ~0, 0)
- * The expressions are shadePath's / classifyPixels' term by term (f32, no
- * contraction), so a host restatement reproduces every plane bit for bit.
- * The tables are staged as k_trace_closest (dynamic LDS: stack, TraceInst,
- * TLAS order) and k_shade (static LDS) stage them, by every lane of the block
- * before the lanes past the last pixel leave.  Reads the scene and the camera
- * only: no Counters, no pool, nothing of the captured graph. */
-template <bool LDS, bool LW = false>
-__global__ __launch_bounds__(kBlock) void k_aov(DevScene S, DevCamera cam, const uint32_t* __restrict__ rows, uint32_t width,
-                                                uint32_t npx, float4* __restrict__ pos, float4* __restrict__ nrm,
-                                                float4* __restrict__ alb, uint4* __restrict__ ids, uint32_t stackWords) {
-    extern __shared__ uint32_t lds[];
-    __shared__ DevInstance sInst[LDS ? kLdsInst : 1];
-    __shared__ DevMaterial sMat[LDS ? kLdsMats : 1];
-    __shared__ uint2 sLights[LDS ? kLdsLights : 1];
-    const TraceTables Tt = traceTables<LDS>(S, lds, layout::laneTablesAt(stackWords, false));
-    ShadeTables Tb{S.inst, S.mats, S.lights};
-    if (LDS) {
-        stageTables(S, sInst, sMat, sLights);
-        Tb = ShadeTables{sInst, sMat, sLights};
-    }
-    const uint32_t lp = blockIdx.x * blockDim.x + threadIdx.x;
-    if (lp >= npx) return;
-    const uint32_t rowi = lp / width;
-    const uint32_t x = lp - rowi * width;
-    const uint32_t row = rows[rowi];
-    const float u = (float)x * cam.invW, v = (float)row * cam.invH;
-    const V3 o = ld3(cam.pos);
-    const V3 dir = sub(add(add(ld3(cam.firstPixel), lscl(u, ld3(cam.uVec))), lscl(v, ld3(cam.vVec))), o);
-    const float len2 = ((0.0f + dir.x * dir.x) + dir.y * dir.y) + dir.z * dir.z;
-    const float inv = 1.0f / sqrtf(len2);
-    const V3 d = scl(dir, inv);
-    float depth = kFarAway, hu = 0.0f, hv = 0.0f;
-    uint32_t inst = kUnset, prim = kUnset;
-    const bool hit = traceScene<false, LW>(S, Tt, o, d, depth, hu, hv, inst, prim, lds + threadIdx.x, blockDim.x);
-    float4 oP = make_float4(0.0f, 0.0f, 0.0f, kFarAway), oN = make_float4(0.0f, 0.0f, 0.0f, 0.0f), oA;
-    uint4 oI = make_uint4(kUnset, kUnset, kUnset, 0u);
-    if (hit) {
-        const DevInstance& I = Tb.inst[inst];
-        const DevMaterial& m = Tb.mats[I.material];
-        const V3 P = add(o, lscl(depth, d));
-        const V3 N = hitNormal(S, I, prim, hu, hv, d);
-        const bool isLight = m.emit > 0.0f && (m.ec[0] > 0.0f || m.ec[1] > 0.0f || m.ec[2] > 0.0f);
-        const V3 a = isLight ? lscl(m.emit, ld3(m.ec)) : ld3(m.albedo);
-        oP = make_float4(P.x, P.y, P.z, depth);
-        oN = make_float4(N.x, N.y, N.z, 0.0f);
-        oA = make_float4(a.x, a.y, a.z, 1.0f);
-        oI = make_uint4(inst, prim, I.material, 0u);
-    } else {
-        /* SceneBackground along d (scene.cpp:35-51), shadePath's miss */
-        V3 bg = mk3(0.0f, 0.0f, 0.0f);
-        if (S.bgType == 0u) bg = ld3(S.bgColor);
-        else if (S.bgType == 1u) {
-            const float a = 0.5f * (1.0f + d.y);
-            bg = add(lscl(a, ld3(S.bgB)), lscl(1.0f - a, ld3(S.bgA)));
-        }
-        oA = make_float4(bg.x, bg.y, bg.z, 0.0f);
-    }
-    pos[lp] = oP;
-    nrm[lp] = oN;
-    alb[lp] = oA;
-    ids[lp] = oI;
-}
-
-/* Feature buffers through mirrors and glass (surf_read_aov_chain): k_aov's
- * ray, followed through the delta interactions -- a material with
- * refl + refr >= 0.5 -- to the first surface that is not one, or to the
- * maxLinks-th link.  shadePath's arithmetic with its random choices replaced
- * by a fixed rule and no RNG at all: refl >= refr reflects; a dielectric
- * transmits whenever it can (no Fresnel draw) and reflects otherwise (total
- * internal reflection).  tint is the product of the links' albedo * medium,
- * L the path length summed along the chain, k the links followed:
- *   pos[lp]  surface: (P, L), the terminal point itself     miss: (0, 0, 0, 1e30)
- *   nrm[lp]  surface: (N, 0), turned against the last d     miss: 0
- *   alb[lp]  surface: ((tint * medium) * a, 1), a the albedo or, on an emitter
- *            (where medium = 1, as shadePath's emitter return absorbs nothing),
- *            strength * colour             miss: (tint * background along the last d, 0)
- *   ids[lp]  surface: (instance, primitive, material, k)    miss: (~0, ~0, ~0, k)
- * With maxLinks = 0 every plane is k_aov's bit for bit (1.0f * x is exact),
- * and at any maxLinks so is a pixel whose first hit is not delta.  Tables,
- * dynamic LDS and variants as k_aov; the lanes of a wave leave the loop one
- * by one, which traceScene allows (it holds no wave-wide operation). */
-template <bool LDS, bool LW = false>
-__global__ __launch_bounds__(kBlock) void k_aov_chain(DevScene S, DevCamera cam, const uint32_t* __restrict__ rows, uint32_t width,
-                                                      uint32_t npx, float4* __restrict__ pos, float4* __restrict__ nrm,
-                                                      float4* __restrict__ alb, uint4* __restrict__ ids, uint32_t stackWords,
-                                                      uint32_t maxLinks) {
-    extern __shared__ uint32_t lds[];
-    __shared__ DevInstance sInst[LDS ? kLdsInst : 1];
-    __shared__ DevMaterial sMat[LDS ? kLdsMats : 1];
-    __shared__ uint2 sLights[LDS ? kLdsLights : 1];
-    const TraceTables Tt = traceTables<LDS>(S, lds, layout::laneTablesAt(stackWords, false));
-    ShadeTables Tb{S.inst, S.mats, S.lights};
-    if (LDS) {
-        stageTables(S, sInst, sMat, sLights);
-        Tb = ShadeTables{sInst, sMat, sLights};
-    }
-    const uint32_t lp = blockIdx.x * blockDim.x + threadIdx.x;
-    if (lp >= npx) return;
-    const uint32_t rowi = lp / width;
-    const uint32_t x = lp - rowi * width;
-    const uint32_t row = rows[rowi];
-    const float u = (float)x * cam.invW, v = (float)row * cam.invH;
-    V3 o = ld3(cam.pos);
-    const V3 dir = sub(add(add(ld3(cam.firstPixel), lscl(u, ld3(cam.uVec))), lscl(v, ld3(cam.vVec))), o);
-    const float len2 = ((0.0f + dir.x * dir.x) + dir.y * dir.y) + dir.z * dir.z;
-    const float inv = 1.0f / sqrtf(len2);
-    V3 d = scl(dir, inv);
-    V3 tint = mk3(1.0f, 1.0f, 1.0f);
-    float L = 0.0f;
-    bool inMedium = false;
-    float4 oP = make_float4(0.0f, 0.0f, 0.0f, kFarAway), oN = make_float4(0.0f, 0.0f, 0.0f, 0.0f), oA = oN;
-    uint4 oI = make_uint4(kUnset, kUnset, kUnset, 0u);
-    /* at most maxLinks + 1 turns: the turn with k == maxLinks ends at its surface */
-    for (uint32_t k = 0; k <= maxLinks; ++k) {
-        float depth = kFarAway, hu = 0.0f, hv = 0.0f;
-        uint32_t inst = kUnset, prim = kUnset;
-        const bool hit = traceScene<false, LW>(S, Tt, o, d, depth, hu, hv, inst, prim, lds + threadIdx.x, blockDim.x);
-        if (!hit) {
-            /* SceneBackground along d (scene.cpp:35-51), shadePath's miss */
-            V3 bg = mk3(0.0f, 0.0f, 0.0f);
-            if (S.bgType == 0u) bg = ld3(S.bgColor);
-            else if (S.bgType == 1u) {
-                const float a = 0.5f * (1.0f + d.y);
-                bg = add(lscl(a, ld3(S.bgB)), lscl(1.0f - a, ld3(S.bgA)));
-            }
-            const V3 c = mul(tint, bg);
-            oA = make_float4(c.x, c.y, c.z, 0.0f);
-            oI.w = k;
-            break;
-        }
-        const DevInstance& I = Tb.inst[inst];
-        const DevMaterial& m = Tb.mats[I.material];
-        const bool isLight = m.emit > 0.0f && (m.ec[0] > 0.0f || m.ec[1] > 0.0f || m.ec[2] > 0.0f);
-        L = L + depth;
-        V3 medium = mk3(1.0f, 1.0f, 1.0f);
-        if (inMedium && !isLight) {
-            const float nd = -depth;
-            medium = mk3(gExpf(m.absorb[0] * nd), gExpf(m.absorb[1] * nd), gExpf(m.absorb[2] * nd));
-        }
-        const V3 P = add(o, lscl(depth, d));
-        const V3 N = hitNormal(S, I, prim, hu, hv, d);
-        const bool delta = (m.refl + m.refr) >= 0.5f;
-        if (isLight || !delta || k == maxLinks) {
-            const V3 a = isLight ? lscl(m.emit, ld3(m.ec)) : ld3(m.albedo);
-            const V3 c = mul(mul(tint, medium), a);
-            oP = make_float4(P.x, P.y, P.z, L);
-            oN = make_float4(N.x, N.y, N.z, 0.0f);
-            oA = make_float4(c.x, c.y, c.z, 1.0f);
-            oI = make_uint4(inst, prim, I.material, k);
-            break;
-        }
-        tint = mul(tint, mul(ld3(m.albedo), medium));
-        V3 R = sub(d, lscl(2.0f * dot(N, d), N));
-        if (!(m.refl >= m.refr)) {
-            const float n1f = inMedium ? m.ior : 1.0f, n2f = inMedium ? 1.0f : m.ior;
-            const float ratio = n1f / n2f;
-            const float cosI = -dot(d, N);
-            const float cos2 = 1.0f - (ratio * ratio) * (1.0f - cosI * cosI);
-            if (cos2 > 0.0f) {
-                R = add(lscl(ratio, d), lscl(ratio * cosI - sqrtf(fabsf(cos2)), N));
-                inMedium = !inMedium;
-            }
-        }
-        o = add(P, lscl(kEps, R));
-        d = R;
-    }
-    pos[lp] = oP;
-    nrm[lp] = oN;
-    alb[lp] = oA;
-    ids[lp] = oI;
-}
-
 /* Cooperative traversal entry points (one ray per 64-lane block, the
  * lanes-as-planes traversal of the cooperative tail): the same results as
  * k_trace_closest / k_trace_any, for parity tests and latency measurements. */

@@ -84,11 +84,7 @@ struct InstanceTables {
 /* The heavy-instance boxes of the ray-order keys (kernel arguments). */
 void setKeys(surf_ctx* c, DevScene& S, const InstanceTables& T) {
     c->heavyInst.assign(T.hvInst, T.hvInst + T.nHeavy);
-    c->permValid = false;                 /* the pixel classes follow the instances */
-    c->aovValid = false;                  /* ... and so do the feature buffers */
-    c->aovChainValid = false;
-    c->aovSampledValid = false;
-    c->aoValid = false;
+    dropDerivedPlanes(c);                 /* the pixel classes and the plane passes follow the instances */
     S.nHeavy = T.nHeavy;
     for (uint32_t h = 0; h < 3; ++h) {
         S.hvLo[h] = h < T.nHeavy ? T.hvLo[h] : make_float4(0, 0, 0, 0);

@@ -67,6 +67,19 @@ struct StageTimer {
     }
 };
 
+/* The cached planes of one per-pixel plane pass (first-hit, chain and sampled
+ * feature buffers, ambient occlusion): `count` device planes of npx 16-byte
+ * records, allocated on first use and freed with the context; valid until
+ * dropDerivedPlanes or a read with another key (the key is kept beside the
+ * record); ms is the device time of the pass's last launch
+ * (surf_debug_*_time).  ensurePlanes in surf_hip.hip is the one driver. */
+struct PassPlanes {
+    int count;
+    void* p[SURF_AOVS_COUNT] = {};   /* the most planes a pass has */
+    bool valid = false;
+    float ms = 0.0f;
+};
+
 struct surf_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -101,34 +114,25 @@ struct surf_ctx {
     bool reorder = true;
     bool permValid = false;
     uint32_t* dPerm = nullptr;
-    /* first-hit feature buffers (surf_read_aov): four planes of npx 16-byte
-     * records, allocated on first use; valid until the camera, the scene or
-     * the instances change (where permValid is cleared) */
-    void* aov[SURF_AOV_COUNT] = {};
-    bool aovValid = false;
-    float aovKernelMs = 0.0f;      /* device time of the last k_aov launch (surf_debug_aov_time) */
-    /* the same four planes traced through mirrors and glass (surf_read_aov_chain):
-     * planes of their own, valid until what clears aovValid or another max_links */
-    void* aovChain[SURF_AOV_COUNT] = {};
-    bool aovChainValid = false;
+    /* first-hit feature buffers (surf_read_aov, k_aov): valid until the camera,
+     * the scene or the instances change (dropDerivedPlanes) */
+    PassPlanes aov{SURF_AOV_COUNT};
+    /* the same four planes traced through mirrors and glass (surf_read_aov_chain,
+     * k_aov_chain): valid until then or another max_links */
+    PassPlanes aovChain{SURF_AOV_COUNT};
     uint32_t aovChainLinks = 0;    /* the max_links the cached planes were traced with */
-    float aovChainKernelMs = 0.0f; /* device time of the last k_aov_chain launch (surf_debug_aov_chain_time) */
     /* which planes surf_denoise and surf_denoise_sampled read (surf_set_filter_guides) */
     int guides = SURF_GUIDES_FIRST_HIT;
     uint32_t guideLinks = 8;
-    /* the sampled feature buffers (surf_read_aov_sampled): six planes of their
-     * own, valid until what clears aovValid or a read with other params */
-    void* aovSampled[SURF_AOVS_COUNT] = {};
-    bool aovSampledValid = false;
+    /* the sampled feature buffers (surf_read_aov_sampled, k_aov_sampled): valid
+     * until then or a read with other params */
+    PassPlanes aovSampled{SURF_AOVS_COUNT};
     surf_aov_sampled_params aovSampledParams{};   /* the params the cached planes were traced with */
-    float aovSampledKernelMs = 0.0f;   /* device time of the last k_aov_sampled launch (surf_debug_aov_sampled_time) */
     surf_aov_sampled_params guideSampled{};       /* the params of SURF_GUIDES_SAMPLED (surf_set_filter_guides_sampled) */
-    /* ambient occlusion (surf_read_ao): two planes of their own, valid until
-     * what clears aovValid or a read with other params */
-    void* ao[SURF_AO_COUNT] = {};
-    bool aoValid = false;
+    /* ambient occlusion (surf_read_ao, k_ao): valid until then or a read with
+     * other params */
+    PassPlanes ao{SURF_AO_COUNT};
     surf_ao_params aoParams{};         /* the params the cached planes were traced with */
-    float aoKernelMs = 0.0f;           /* device time of the last k_ao launch (surf_debug_ao_time) */
     bool aoRayMap = true;              /* A/B (SURF_AO_MAP): one lane per ray (1), one lane per pixel (0) */
     /* the a-trous denoiser (surf_denoise*, host/denoise.hip): dn, the scratch
      * every a-trous filter runs in -- the two ping-pong levels, the packed
@@ -414,13 +418,19 @@ void setGlobalError(const std::string& e);
 int endStream(surf_ctx* c);
 void destroyGraph(surf_ctx* c);
 /* ... and for the image-space filters (the .hip files of host/) what a read of the context
- * needs: the sample stream drained, the cached feature planes computed (c->aov) */
+ * needs: the sample stream drained, the cached feature planes computed (c->aov.p) */
 int drainStream(surf_ctx* c);
 int featurePlanes(surf_ctx* c);
 /* ... and for the two purely spatial context filters the planes surf_set_filter_guides chose,
- * computed: *planes is c->aov, c->aovChain or c->aovSampled (whose first three planes are laid
- * out as theirs) */
+ * computed: *planes is the planes of c->aov, c->aovChain or c->aovSampled (whose first three
+ * planes are laid out as theirs) */
 int guidePlanes(surf_ctx* c, void* const** planes);
+/* What follows the camera, the scene and the instances: the pixel classes of the issue order
+ * and the cached planes of every plane pass.  Whatever changes one of the three calls this. */
+inline void dropDerivedPlanes(surf_ctx* c) {
+    c->permValid = false;
+    for (PassPlanes* pp : {&c->aov, &c->aovChain, &c->aovSampled, &c->ao}) pp->valid = false;
+}
 /* defined in host/denoise.hip: PlaneGroup::grow's body -- `count` images of at
  * least npx records each (OOM message: "... of <what> ...") */
 int growImages(surf_ctx* c, float4** planes, int count, size_t& cap, size_t npx, const char* what);

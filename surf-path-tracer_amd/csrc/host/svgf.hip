@@ -175,10 +175,10 @@ int svgfContext(surf_ctx* c, const surf_temporal_params* p, const surf_svgf_para
     float4* const* next = c->tp.p + 3 * (c->tpCur ^ 1);
     SvgfPlanes pl{};
     pl.A = c->acc;
-    pl.P = static_cast<const float4*>(c->aov[SURF_AOV_POSITION]);
-    pl.N = static_cast<const float4*>(c->aov[SURF_AOV_NORMAL]);
-    pl.alb = static_cast<const float4*>(c->aov[SURF_AOV_ALBEDO]);
-    pl.ID = static_cast<const uint4*>(c->aov[SURF_AOV_ID]);
+    pl.P = static_cast<const float4*>(c->aov.p[SURF_AOV_POSITION]);
+    pl.N = static_cast<const float4*>(c->aov.p[SURF_AOV_NORMAL]);
+    pl.alb = static_cast<const float4*>(c->aov.p[SURF_AOV_ALBEDO]);
+    pl.ID = static_cast<const uint4*>(c->aov.p[SURF_AOV_ID]);
     if (have) {
         pl.pH = prev[0];
         pl.pP = prev[1];

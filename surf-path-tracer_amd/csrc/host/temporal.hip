@@ -122,9 +122,9 @@ int temporalContext(surf_ctx* c, const surf_temporal_params* p, const surf_denoi
                                            c->tpMotionHost);
     float4* const* prev = c->tp.p + 3 * c->tpCur;
     float4* const* next = c->tp.p + 3 * (c->tpCur ^ 1);
-    const float4* pos = static_cast<const float4*>(c->aov[SURF_AOV_POSITION]);
-    const float4* nrm = static_cast<const float4*>(c->aov[SURF_AOV_NORMAL]);
-    rc = runTemporal(c, c->width, c->height, c->acc, pos, nrm, static_cast<const uint4*>(c->aov[SURF_AOV_ID]), have ? prev[0] : nullptr,
+    const float4* pos = static_cast<const float4*>(c->aov.p[SURF_AOV_POSITION]);
+    const float4* nrm = static_cast<const float4*>(c->aov.p[SURF_AOV_NORMAL]);
+    rc = runTemporal(c, c->width, c->height, c->acc, pos, nrm, static_cast<const uint4*>(c->aov.p[SURF_AOV_ID]), have ? prev[0] : nullptr,
                      have ? prev[1] : nullptr, have ? reinterpret_cast<const TemporalGuide*>(prev[2]) : nullptr, K, c->tp[6], next[0],
                      next[1], reinterpret_cast<TemporalGuide*>(next[2]));
     if (rc) return rc;
@@ -135,7 +135,7 @@ int temporalContext(surf_ctx* c, const surf_temporal_params* p, const surf_denoi
     c->svHave = false;                /* this history carries no moments: the next surf_svgf_accumulate estimates spatially */
     const float4* res = c->tp[6];
     if (spatial) {
-        rc = denoisePlanes(c, c->width, c->height, c->tp[6], pos, nrm, static_cast<const float4*>(c->aov[SURF_AOV_ALBEDO]), *spatial, &res);
+        rc = denoisePlanes(c, c->width, c->height, c->tp[6], pos, nrm, static_cast<const float4*>(c->aov.p[SURF_AOV_ALBEDO]), *spatial, &res);
         if (rc) return rc;
     }
     SURF_CHECK(c, hipMemcpyAsync(dst, res, (size_t)c->npx * sizeof(float4), kind, c->stream));

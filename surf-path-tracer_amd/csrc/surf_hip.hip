@@ -20,8 +20,7 @@
 #include <type_traits>
 
 #include "device/wavefront_kernels.h"
-#include "device/aov_sampled_kernels.h"
-#include "device/ao_kernels.h"
+#include "device/plane_kernels.h"
 
 namespace {
 
@@ -553,63 +552,68 @@ int classifyPixels(surf_ctx* c) {
     return SURF_OK;
 }
 
-/* The four feature planes (k_aov), computed on first use and kept until the
- * camera, the scene or the instances change.  One launch on the render
- * stream, behind whatever replays are in flight: the kernel reads the scene
- * and the camera only, so the sample stream is neither drained nor touched. */
-int ensureAov(surf_ctx* c) {
+/* The driver of the per-pixel plane passes (device/plane_kernels.h): the
+ * preconditions, the cached return, the planes' allocation, one timed launch
+ * on the render stream and the marking valid.  A pass supplies `same` -- its
+ * cached key equals the request's -- and `launch`, its hipLaunchKernelGGL
+ * line; it validates its parameters before it calls this, and keeps its key
+ * once this returns SURF_OK.  The launch goes behind whatever replays are in
+ * flight: the kernels read the scene, the camera and source planes only, so
+ * the sample stream is neither drained nor touched. */
+template <class Same, class Launch>
+int ensurePlanes(surf_ctx* c, PassPlanes& pp, const char* what, Same same, Launch launch) {
     if (!c->hasScene) return fail(c, SURF_ERR_NO_SCENE, "no scene uploaded");
     if (!c->hasCamera) return fail(c, SURF_ERR_NO_SCENE, "no camera set");
     SURF_CHECK(c, hipSetDevice(c->device));
-    if (c->aovValid) return SURF_OK;
-    for (void*& p : c->aov)
-        if (!p && (hipMalloc(&p, (size_t)c->npx * 16) != hipSuccess || !p)) {
+    if (pp.valid && same()) return SURF_OK;
+    pp.valid = false;
+    for (int k = 0; k < pp.count; ++k)
+        if (void*& p = pp.p[k]; !p && (hipMalloc(&p, (size_t)c->npx * 16) != hipSuccess || !p)) {
             p = nullptr;
             (void)hipGetLastError();
-            return fail(c, SURF_ERR_OOM, "hipMalloc of a feature plane (" + std::to_string((size_t)c->npx * 16) + " bytes) failed");
+            return fail(c, SURF_ERR_OOM, std::string("hipMalloc of ") + what + " (" + std::to_string((size_t)c->npx * 16) + " bytes) failed");
         }
     SURF_CHECK(c, hipEventRecord(c->ev0, c->stream));
-    const auto aov = aovKernel(c, variantOf(c));
-    hipLaunchKernelGGL(aov.fn, dim3((c->npx + kBlock - 1) / kBlock), dim3(kBlock), aov.lds, c->stream, c->S, c->cam, (const uint32_t*)c->dRows, c->width, c->npx, static_cast<float4*>(c->aov[SURF_AOV_POSITION]),
-                       static_cast<float4*>(c->aov[SURF_AOV_NORMAL]), static_cast<float4*>(c->aov[SURF_AOV_ALBEDO]),
-                       static_cast<uint4*>(c->aov[SURF_AOV_ID]), stackWords(c, kBlock));
+    launch();
     SURF_CHECK(c, hipGetLastError());
     SURF_CHECK(c, hipEventRecord(c->ev1, c->stream));
     SURF_CHECK(c, hipEventSynchronize(c->ev1));
-    (void)hipEventElapsedTime(&c->aovKernelMs, c->ev0, c->ev1);
-    c->aovValid = true;
+    (void)hipEventElapsedTime(&pp.ms, c->ev0, c->ev1);
+    pp.valid = true;
     return SURF_OK;
+}
+
+/* plane k of a pass as the kernels take it */
+template <class T>
+T* planeOf(const PassPlanes& pp, int k) { return static_cast<T*>(pp.p[k]); }
+
+/* The four feature planes (k_aov), computed on first use and kept until the
+ * camera, the scene or the instances change. */
+int ensureAov(surf_ctx* c) {
+    PassPlanes& pp = c->aov;
+    return ensurePlanes(c, pp, "a feature plane", [] { return true; }, [&] {
+        const auto aov = aovKernel(c, variantOf(c));
+        hipLaunchKernelGGL(aov.fn, dim3((c->npx + kBlock - 1) / kBlock), dim3(kBlock), aov.lds, c->stream, c->S, c->cam, (const uint32_t*)c->dRows, c->width, c->npx,
+                           planeOf<float4>(pp, SURF_AOV_POSITION), planeOf<float4>(pp, SURF_AOV_NORMAL), planeOf<float4>(pp, SURF_AOV_ALBEDO),
+                           planeOf<uint4>(pp, SURF_AOV_ID), stackWords(c, kBlock));
+    });
 }
 
 /* The same planes traced through mirrors and glass (k_aov_chain), in device
  * planes of their own: kept until what drops the first-hit planes, or a read
- * with another max_links.  One launch on the render stream, as ensureAov. */
+ * with another max_links. */
 int ensureAovChain(surf_ctx* c, uint32_t maxLinks) {
     if (maxLinks > SURF_AOV_CHAIN_MAX_LINKS)
         return fail(c, SURF_ERR_INVALID, "max_links is above SURF_AOV_CHAIN_MAX_LINKS (" + std::to_string(SURF_AOV_CHAIN_MAX_LINKS) + ")");
-    if (!c->hasScene) return fail(c, SURF_ERR_NO_SCENE, "no scene uploaded");
-    if (!c->hasCamera) return fail(c, SURF_ERR_NO_SCENE, "no camera set");
-    SURF_CHECK(c, hipSetDevice(c->device));
-    if (c->aovChainValid && c->aovChainLinks == maxLinks) return SURF_OK;
-    c->aovChainValid = false;
-    for (void*& p : c->aovChain)
-        if (!p && (hipMalloc(&p, (size_t)c->npx * 16) != hipSuccess || !p)) {
-            p = nullptr;
-            (void)hipGetLastError();
-            return fail(c, SURF_ERR_OOM, "hipMalloc of a feature plane (" + std::to_string((size_t)c->npx * 16) + " bytes) failed");
-        }
-    SURF_CHECK(c, hipEventRecord(c->ev0, c->stream));
-    const auto aov = aovChainKernel(c, variantOf(c));
-    hipLaunchKernelGGL(aov.fn, dim3((c->npx + kBlock - 1) / kBlock), dim3(kBlock), aov.lds, c->stream, c->S, c->cam, (const uint32_t*)c->dRows, c->width, c->npx, static_cast<float4*>(c->aovChain[SURF_AOV_POSITION]),
-                       static_cast<float4*>(c->aovChain[SURF_AOV_NORMAL]), static_cast<float4*>(c->aovChain[SURF_AOV_ALBEDO]),
-                       static_cast<uint4*>(c->aovChain[SURF_AOV_ID]), stackWords(c, kBlock), maxLinks);
-    SURF_CHECK(c, hipGetLastError());
-    SURF_CHECK(c, hipEventRecord(c->ev1, c->stream));
-    SURF_CHECK(c, hipEventSynchronize(c->ev1));
-    (void)hipEventElapsedTime(&c->aovChainKernelMs, c->ev0, c->ev1);
-    c->aovChainLinks = maxLinks;
-    c->aovChainValid = true;
-    return SURF_OK;
+    PassPlanes& pp = c->aovChain;
+    const int rc = ensurePlanes(c, pp, "a feature plane", [&] { return c->aovChainLinks == maxLinks; }, [&] {
+        const auto aov = aovChainKernel(c, variantOf(c));
+        hipLaunchKernelGGL(aov.fn, dim3((c->npx + kBlock - 1) / kBlock), dim3(kBlock), aov.lds, c->stream, c->S, c->cam, (const uint32_t*)c->dRows, c->width, c->npx,
+                           planeOf<float4>(pp, SURF_AOV_POSITION), planeOf<float4>(pp, SURF_AOV_NORMAL), planeOf<float4>(pp, SURF_AOV_ALBEDO),
+                           planeOf<uint4>(pp, SURF_AOV_ID), stackWords(c, kBlock), maxLinks);
+    });
+    if (rc == SURF_OK) c->aovChainLinks = maxLinks;
+    return rc;
 }
 
 /* surf_aov_sampled_params as the header states them */
@@ -619,35 +623,19 @@ bool aovSampledParamsOk(const surf_aov_sampled_params* p) {
 }
 
 /* The six sampled planes (k_aov_sampled), in device planes of their own: kept
- * until what drops the first-hit planes, or a read with other params.  One
- * launch on the render stream, as ensureAov. */
+ * until what drops the first-hit planes, or a read with other params. */
 int ensureAovSampled(surf_ctx* c, const surf_aov_sampled_params& q) {
     if (!aovSampledParamsOk(&q)) return fail(c, SURF_ERR_INVALID, "sampled feature buffers: samples outside 1.." + std::to_string(SURF_AOVS_MAX_SAMPLES) + ", an unknown key or reserved != 0");
-    if (!c->hasScene) return fail(c, SURF_ERR_NO_SCENE, "no scene uploaded");
-    if (!c->hasCamera) return fail(c, SURF_ERR_NO_SCENE, "no camera set");
-    SURF_CHECK(c, hipSetDevice(c->device));
-    if (c->aovSampledValid && std::memcmp(&c->aovSampledParams, &q, sizeof q) == 0) return SURF_OK;
-    c->aovSampledValid = false;
-    for (void*& p : c->aovSampled)
-        if (!p && (hipMalloc(&p, (size_t)c->npx * 16) != hipSuccess || !p)) {
-            p = nullptr;
-            (void)hipGetLastError();
-            return fail(c, SURF_ERR_OOM, "hipMalloc of a feature plane (" + std::to_string((size_t)c->npx * 16) + " bytes) failed");
-        }
-    SURF_CHECK(c, hipEventRecord(c->ev0, c->stream));
-    const auto aov = aovSampledKernel(c, variantOf(c));
-    hipLaunchKernelGGL(aov.fn, dim3((c->npx + kBlock - 1) / kBlock), dim3(kBlock), aov.lds, c->stream, c->S, c->cam, (const uint32_t*)c->dRows, c->width, c->npx, q.samples, q.first_sample, q.key,
-                       static_cast<float4*>(c->aovSampled[SURF_AOVS_POSITION]), static_cast<float4*>(c->aovSampled[SURF_AOVS_NORMAL]),
-                       static_cast<float4*>(c->aovSampled[SURF_AOVS_ALBEDO]), static_cast<uint4*>(c->aovSampled[SURF_AOVS_ID]),
-                       static_cast<uint4*>(c->aovSampled[SURF_AOVS_MATTE_KEY]), static_cast<uint4*>(c->aovSampled[SURF_AOVS_MATTE_COUNT]),
-                       stackWords(c, kBlock));
-    SURF_CHECK(c, hipGetLastError());
-    SURF_CHECK(c, hipEventRecord(c->ev1, c->stream));
-    SURF_CHECK(c, hipEventSynchronize(c->ev1));
-    (void)hipEventElapsedTime(&c->aovSampledKernelMs, c->ev0, c->ev1);
-    c->aovSampledParams = q;
-    c->aovSampledValid = true;
-    return SURF_OK;
+    PassPlanes& pp = c->aovSampled;
+    const int rc = ensurePlanes(c, pp, "a feature plane", [&] { return std::memcmp(&c->aovSampledParams, &q, sizeof q) == 0; }, [&] {
+        const auto aov = aovSampledKernel(c, variantOf(c));
+        hipLaunchKernelGGL(aov.fn, dim3((c->npx + kBlock - 1) / kBlock), dim3(kBlock), aov.lds, c->stream, c->S, c->cam, (const uint32_t*)c->dRows, c->width, c->npx, q.samples, q.first_sample, q.key,
+                           planeOf<float4>(pp, SURF_AOVS_POSITION), planeOf<float4>(pp, SURF_AOVS_NORMAL), planeOf<float4>(pp, SURF_AOVS_ALBEDO),
+                           planeOf<uint4>(pp, SURF_AOVS_ID), planeOf<uint4>(pp, SURF_AOVS_MATTE_KEY), planeOf<uint4>(pp, SURF_AOVS_MATTE_COUNT),
+                           stackWords(c, kBlock));
+    });
+    if (rc == SURF_OK) c->aovSampledParams = q;
+    return rc;
 }
 
 /* surf_ao_params as the header states them */
@@ -660,37 +648,43 @@ bool aoParamsOk(const surf_ao_params* p) {
 
 /* The two occlusion planes (k_ao), in device planes of their own: kept until
  * what drops the first-hit planes, or a read with other params.  The source
- * planes first, as a read of them would compute them; then one launch on the
- * render stream, as ensureAov. */
+ * planes first, as a read of them would compute them. */
 int ensureAo(surf_ctx* c, const surf_ao_params& q) {
     if (!aoParamsOk(&q))
         return fail(c, SURF_ERR_INVALID, "ambient occlusion: samples not a power of two in 1.." + std::to_string(SURF_AO_MAX_SAMPLES) +
                                              ", radius not > 0, bias not >= 0, an unknown source, max_links above SURF_AOV_CHAIN_MAX_LINKS or reserved != 0");
     const bool chain = q.source == SURF_AO_CHAIN;
     if (int rc = chain ? ensureAovChain(c, q.max_links) : ensureAov(c)) return rc;
-    if (c->aoValid && std::memcmp(&c->aoParams, &q, sizeof q) == 0) return SURF_OK;
-    c->aoValid = false;
-    for (void*& p : c->ao)
-        if (!p && (hipMalloc(&p, (size_t)c->npx * 16) != hipSuccess || !p)) {
-            p = nullptr;
-            (void)hipGetLastError();
-            return fail(c, SURF_ERR_OOM, "hipMalloc of an occlusion plane (" + std::to_string((size_t)c->npx * 16) + " bytes) failed");
-        }
-    void* const* src = chain ? c->aovChain : c->aov;
-    /* pixels per block: one per lane, or one per group of `samples` lanes */
-    const uint32_t perBlock = c->aoRayMap ? (uint32_t)kBlock / q.samples : (uint32_t)kBlock;
-    SURF_CHECK(c, hipEventRecord(c->ev0, c->stream));
-    const auto ao = aoKernel(c, variantOf(c));
-    hipLaunchKernelGGL(ao.fn, dim3((c->npx + perBlock - 1) / perBlock), dim3(kBlock), ao.lds, c->stream, c->S, (const uint32_t*)c->dRows, c->width, c->npx, q.samples, q.first_sample, q.radius, q.bias,
-                       static_cast<const float4*>(src[SURF_AOV_POSITION]), static_cast<const float4*>(src[SURF_AOV_NORMAL]),
-                       static_cast<const float4*>(src[SURF_AOV_ALBEDO]), static_cast<float4*>(c->ao[SURF_AO_OPENNESS]),
-                       static_cast<uint4*>(c->ao[SURF_AO_BITS]), stackWords(c, kBlock));
-    SURF_CHECK(c, hipGetLastError());
-    SURF_CHECK(c, hipEventRecord(c->ev1, c->stream));
-    SURF_CHECK(c, hipEventSynchronize(c->ev1));
-    (void)hipEventElapsedTime(&c->aoKernelMs, c->ev0, c->ev1);
-    c->aoParams = q;
-    c->aoValid = true;
+    const PassPlanes& src = chain ? c->aovChain : c->aov;
+    PassPlanes& pp = c->ao;
+    const int rc = ensurePlanes(c, pp, "an occlusion plane", [&] { return std::memcmp(&c->aoParams, &q, sizeof q) == 0; }, [&] {
+        /* pixels per block: one per lane, or one per group of `samples` lanes */
+        const uint32_t perBlock = c->aoRayMap ? (uint32_t)kBlock / q.samples : (uint32_t)kBlock;
+        const auto ao = aoKernel(c, variantOf(c));
+        hipLaunchKernelGGL(ao.fn, dim3((c->npx + perBlock - 1) / perBlock), dim3(kBlock), ao.lds, c->stream, c->S, (const uint32_t*)c->dRows, c->width, c->npx, q.samples, q.first_sample, q.radius, q.bias,
+                           planeOf<const float4>(src, SURF_AOV_POSITION), planeOf<const float4>(src, SURF_AOV_NORMAL), planeOf<const float4>(src, SURF_AOV_ALBEDO),
+                           planeOf<float4>(pp, SURF_AO_OPENNESS), planeOf<uint4>(pp, SURF_AO_BITS), stackWords(c, kBlock));
+    });
+    if (rc == SURF_OK) c->aoParams = q;
+    return rc;
+}
+
+/* The body of the eight surf_read_* / surf_copy_*_device entry points of the
+ * plane passes: `ensure` computes the pass's planes (and reports through the
+ * context), then one copy of plane `plane` on the render stream. */
+template <class Ensure>
+int copyPlane(surf_ctx* c, bool argsOk, const PassPlanes surf_ctx::*pass, int plane, void* dst, hipMemcpyKind kind, Ensure ensure) {
+    if (!c || !argsOk || !dst || plane < 0 || plane >= (c->*pass).count) return SURF_ERR_INVALID;
+    if (int rc = ensure()) return rc;
+    SURF_CHECK(c, hipMemcpyAsync(dst, (c->*pass).p[plane], (size_t)c->npx * 16, kind, c->stream));
+    SURF_CHECK(c, hipStreamSynchronize(c->stream));
+    return SURF_OK;
+}
+
+/* ... and of their four surf_debug_*_time */
+int passTime(const surf_ctx* c, const PassPlanes surf_ctx::*pass, float* kernel_ms) {
+    if (!c || !kernel_ms) return SURF_ERR_INVALID;
+    *kernel_ms = (c->*pass).ms;
     return SURF_OK;
 }
 
@@ -1182,11 +1176,11 @@ int surfhost::drainStream(surf_ctx* c) { return ensureDrained(c); }
 int surfhost::featurePlanes(surf_ctx* c) { return ensureAov(c); }
 int surfhost::guidePlanes(surf_ctx* c, void* const** planes) {
     if (c->guides == SURF_GUIDES_SAMPLED) {
-        *planes = c->aovSampled;
+        *planes = c->aovSampled.p;
         return ensureAovSampled(c, c->guideSampled);
     }
     const bool chain = c->guides == SURF_GUIDES_CHAIN;
-    *planes = chain ? c->aovChain : c->aov;
+    *planes = chain ? c->aovChain.p : c->aov.p;
     return chain ? ensureAovChain(c, c->guideLinks) : ensureAov(c);
 }
 
@@ -1345,10 +1339,8 @@ void surf_destroy(surf_ctx* c) {
     if (c->sq) (void)hipFree(c->sq);
     if (c->bk) (void)hipFree(c->bk);
     for (auto& e : c->accEv) if (e) (void)hipEventDestroy(e);
-    for (void*& p : c->aov) { if (p) (void)hipFree(p); p = nullptr; }
-    for (void*& p : c->aovChain) { if (p) (void)hipFree(p); p = nullptr; }
-    for (void*& p : c->aovSampled) { if (p) (void)hipFree(p); p = nullptr; }
-    for (void*& p : c->ao) { if (p) (void)hipFree(p); p = nullptr; }
+    for (PassPlanes* pp : {&c->aov, &c->aovChain, &c->aovSampled, &c->ao})
+        for (void*& p : pp->p) { if (p) (void)hipFree(p); p = nullptr; }
     freeDenoise(c);
     freeTemporal(c);
     freeAdaptive(c);
@@ -1512,11 +1504,7 @@ int surf_set_camera(surf_ctx* c, const surf_camera_ubo* u) {
     k.diskU[0] = du.x; k.diskU[1] = du.y; k.diskU[2] = du.z;
     k.diskV[0] = dv.x; k.diskV[1] = dv.y; k.diskV[2] = dv.z;
     c->cam = k;
-    c->permValid = false;
-    c->aovValid = false;
-    c->aovChainValid = false;
-    c->aovSampledValid = false;
-    c->aoValid = false;
+    dropDerivedPlanes(c);
     c->camUbo = *u;
     c->hasCamera = true;
     destroyGraph(c);     /* camera is a kernel argument of the captured graph */
@@ -1787,52 +1775,24 @@ int surf_read_sample_buckets(surf_ctx* c, float* out) { return copyBuckets(c, ou
 int surf_copy_sample_buckets_device(surf_ctx* c, void* dst) { return copyBuckets(c, dst, hipMemcpyDeviceToDevice); }
 
 int surf_read_aov(surf_ctx* c, int plane, void* out) {
-    if (!c || !out || plane < 0 || plane >= SURF_AOV_COUNT) return SURF_ERR_INVALID;
-    int rc = ensureAov(c);
-    if (rc) return rc;
-    SURF_CHECK(c, hipMemcpyAsync(out, c->aov[plane], (size_t)c->npx * 16, hipMemcpyDeviceToHost, c->stream));
-    SURF_CHECK(c, hipStreamSynchronize(c->stream));
-    return SURF_OK;
+    return copyPlane(c, true, &surf_ctx::aov, plane, out, hipMemcpyDeviceToHost, [&] { return ensureAov(c); });
 }
 
 int surf_copy_aov_device(surf_ctx* c, int plane, void* dst) {
-    if (!c || !dst || plane < 0 || plane >= SURF_AOV_COUNT) return SURF_ERR_INVALID;
-    int rc = ensureAov(c);
-    if (rc) return rc;
-    SURF_CHECK(c, hipMemcpyAsync(dst, c->aov[plane], (size_t)c->npx * 16, hipMemcpyDeviceToDevice, c->stream));
-    SURF_CHECK(c, hipStreamSynchronize(c->stream));
-    return SURF_OK;
+    return copyPlane(c, true, &surf_ctx::aov, plane, dst, hipMemcpyDeviceToDevice, [&] { return ensureAov(c); });
 }
 
-int surf_debug_aov_time(surf_ctx* c, float* kernel_ms) {
-    if (!c || !kernel_ms) return SURF_ERR_INVALID;
-    *kernel_ms = c->aovKernelMs;
-    return SURF_OK;
-}
-
-/* surf_read_aov_chain / surf_copy_aov_chain_device */
-static int copyAovChain(surf_ctx* c, int plane, uint32_t maxLinks, void* dst, hipMemcpyKind kind) {
-    if (!c || !dst || plane < 0 || plane >= SURF_AOV_COUNT) return SURF_ERR_INVALID;
-    int rc = ensureAovChain(c, maxLinks);
-    if (rc) return rc;
-    SURF_CHECK(c, hipMemcpyAsync(dst, c->aovChain[plane], (size_t)c->npx * 16, kind, c->stream));
-    SURF_CHECK(c, hipStreamSynchronize(c->stream));
-    return SURF_OK;
-}
+int surf_debug_aov_time(surf_ctx* c, float* kernel_ms) { return passTime(c, &surf_ctx::aov, kernel_ms); }
 
 int surf_read_aov_chain(surf_ctx* c, int plane, uint32_t max_links, void* out) {
-    return copyAovChain(c, plane, max_links, out, hipMemcpyDeviceToHost);
+    return copyPlane(c, true, &surf_ctx::aovChain, plane, out, hipMemcpyDeviceToHost, [&] { return ensureAovChain(c, max_links); });
 }
 
 int surf_copy_aov_chain_device(surf_ctx* c, int plane, uint32_t max_links, void* dst) {
-    return copyAovChain(c, plane, max_links, dst, hipMemcpyDeviceToDevice);
+    return copyPlane(c, true, &surf_ctx::aovChain, plane, dst, hipMemcpyDeviceToDevice, [&] { return ensureAovChain(c, max_links); });
 }
 
-int surf_debug_aov_chain_time(surf_ctx* c, float* kernel_ms) {
-    if (!c || !kernel_ms) return SURF_ERR_INVALID;
-    *kernel_ms = c->aovChainKernelMs;
-    return SURF_OK;
-}
+int surf_debug_aov_chain_time(surf_ctx* c, float* kernel_ms) { return passTime(c, &surf_ctx::aovChain, kernel_ms); }
 
 int surf_set_filter_guides(surf_ctx* c, int guides, uint32_t max_links) {
     if (!c) return SURF_ERR_INVALID;
@@ -1857,29 +1817,15 @@ int surf_aov_sampled_default_params(surf_aov_sampled_params* p) {
     return SURF_OK;
 }
 
-/* surf_read_aov_sampled / surf_copy_aov_sampled_device */
-static int copyAovSampled(surf_ctx* c, const surf_aov_sampled_params* p, int plane, void* dst, hipMemcpyKind kind) {
-    if (!c || !p || !dst || plane < 0 || plane >= SURF_AOVS_COUNT) return SURF_ERR_INVALID;
-    int rc = ensureAovSampled(c, *p);
-    if (rc) return rc;
-    SURF_CHECK(c, hipMemcpyAsync(dst, c->aovSampled[plane], (size_t)c->npx * 16, kind, c->stream));
-    SURF_CHECK(c, hipStreamSynchronize(c->stream));
-    return SURF_OK;
-}
-
 int surf_read_aov_sampled(surf_ctx* c, const surf_aov_sampled_params* p, int plane, void* out) {
-    return copyAovSampled(c, p, plane, out, hipMemcpyDeviceToHost);
+    return copyPlane(c, p != nullptr, &surf_ctx::aovSampled, plane, out, hipMemcpyDeviceToHost, [&] { return ensureAovSampled(c, *p); });
 }
 
 int surf_copy_aov_sampled_device(surf_ctx* c, const surf_aov_sampled_params* p, int plane, void* dst) {
-    return copyAovSampled(c, p, plane, dst, hipMemcpyDeviceToDevice);
+    return copyPlane(c, p != nullptr, &surf_ctx::aovSampled, plane, dst, hipMemcpyDeviceToDevice, [&] { return ensureAovSampled(c, *p); });
 }
 
-int surf_debug_aov_sampled_time(surf_ctx* c, float* kernel_ms) {
-    if (!c || !kernel_ms) return SURF_ERR_INVALID;
-    *kernel_ms = c->aovSampledKernelMs;
-    return SURF_OK;
-}
+int surf_debug_aov_sampled_time(surf_ctx* c, float* kernel_ms) { return passTime(c, &surf_ctx::aovSampled, kernel_ms); }
 
 int surf_ao_default_params(surf_ao_params* p) {
     if (!p) return SURF_ERR_INVALID;
@@ -1887,25 +1833,15 @@ int surf_ao_default_params(surf_ao_params* p) {
     return SURF_OK;
 }
 
-/* surf_read_ao / surf_copy_ao_device */
-static int copyAo(surf_ctx* c, const surf_ao_params* p, int plane, void* dst, hipMemcpyKind kind) {
-    if (!c || !p || !dst || plane < 0 || plane >= SURF_AO_COUNT) return SURF_ERR_INVALID;
-    int rc = ensureAo(c, *p);
-    if (rc) return rc;
-    SURF_CHECK(c, hipMemcpyAsync(dst, c->ao[plane], (size_t)c->npx * 16, kind, c->stream));
-    SURF_CHECK(c, hipStreamSynchronize(c->stream));
-    return SURF_OK;
+int surf_read_ao(surf_ctx* c, const surf_ao_params* p, int plane, void* out) {
+    return copyPlane(c, p != nullptr, &surf_ctx::ao, plane, out, hipMemcpyDeviceToHost, [&] { return ensureAo(c, *p); });
 }
 
-int surf_read_ao(surf_ctx* c, const surf_ao_params* p, int plane, void* out) { return copyAo(c, p, plane, out, hipMemcpyDeviceToHost); }
-
-int surf_copy_ao_device(surf_ctx* c, const surf_ao_params* p, int plane, void* dst) { return copyAo(c, p, plane, dst, hipMemcpyDeviceToDevice); }
-
-int surf_debug_ao_time(surf_ctx* c, float* kernel_ms) {
-    if (!c || !kernel_ms) return SURF_ERR_INVALID;
-    *kernel_ms = c->aoKernelMs;
-    return SURF_OK;
+int surf_copy_ao_device(surf_ctx* c, const surf_ao_params* p, int plane, void* dst) {
+    return copyPlane(c, p != nullptr, &surf_ctx::ao, plane, dst, hipMemcpyDeviceToDevice, [&] { return ensureAo(c, *p); });
 }
+
+int surf_debug_ao_time(surf_ctx* c, float* kernel_ms) { return passTime(c, &surf_ctx::ao, kernel_ms); }
 
 int surf_set_filter_guides_sampled(surf_ctx* c, const surf_aov_sampled_params* p) {
     if (!c || !p) return SURF_ERR_INVALID;

@@ -1419,6 +1419,23 @@ class Renderer:
         buf = CameraUBO.from_buffer_copy(ubo)
         _check(load().surf_set_camera(self._h, buf), "surf_set_camera", self._h)
 
+    def _read_planes(self, entry: str, names, floats: int, *before, after=()) -> dict:
+        """The planes of one plane pass as {name: (rows, width, 4) array}: entry(handle,
+        *before, plane index, *after, out) per plane; the first `floats` planes are
+        float32, the rest uint32."""
+        out = {}
+        for k, name in enumerate(names):
+            a = np.zeros((len(self.rows), self.width, 4), dtype=np.float32 if k < floats else np.uint32)
+            _check(getattr(load(), entry)(self._h, *before, k, *after, _ptr(a)), entry, self._h)
+            out[name] = a
+        return out
+
+    def _debug_ms(self, entry: str) -> float:
+        """The one float a surf_debug_*_time of a single launch hands back."""
+        ms = C.c_float()
+        _check(getattr(load(), entry)(self._h, C.byref(ms)), entry, self._h)
+        return float(ms.value)
+
     def aov(self) -> dict:
         """First-hit feature buffers of this shard's rows (surf_read_aov; the plane
         definitions are in include/surf_hip.h): 'position', 'normal' and 'albedo'
@@ -1427,21 +1444,14 @@ class Renderer:
         until the camera, the scene or the instances change; the sample stream is
         not touched.  Row shards assemble like accumulators (assemble_shards
         works on float32: pass it the id plane as .view(np.float32))."""
-        out = {}
-        for k, name in enumerate(AOV_PLANES):
-            a = np.zeros((len(self.rows), self.width, 4), dtype=np.uint32 if name == "id" else np.float32)
-            _check(load().surf_read_aov(self._h, k, _ptr(a)), "surf_read_aov", self._h)
-            out[name] = a
-        return out
+        return self._read_planes("surf_read_aov", AOV_PLANES, 3)
 
     def copy_aov_to(self, plane: int, device_ptr: int):
         _check(load().surf_copy_aov_device(self._h, plane, C.c_void_p(device_ptr)), "surf_copy_aov_device", self._h)
 
     def debug_aov_time(self) -> float:
         """Device milliseconds of the last feature-buffer kernel launch (surf_debug_aov_time)."""
-        ms = C.c_float()
-        _check(load().surf_debug_aov_time(self._h, C.byref(ms)), "surf_debug_aov_time", self._h)
-        return float(ms.value)
+        return self._debug_ms("surf_debug_aov_time")
 
     def aov_chain(self, max_links: int = 8) -> dict:
         """The feature buffers traced through mirrors and glass (surf_read_aov_chain,
@@ -1451,12 +1461,7 @@ class Renderer:
         id.w is the number of links followed.  Cached like aov(), per max_links.
         Not for reprojection: the position is the real terminal point."""
         max_links = _chain_links(max_links)
-        out = {}
-        for k, name in enumerate(AOV_PLANES):
-            a = np.zeros((len(self.rows), self.width, 4), dtype=np.uint32 if name == "id" else np.float32)
-            _check(load().surf_read_aov_chain(self._h, k, max_links, _ptr(a)), "surf_read_aov_chain", self._h)
-            out[name] = a
-        return out
+        return self._read_planes("surf_read_aov_chain", AOV_PLANES, 3, after=(max_links,))
 
     def copy_aov_chain_to(self, plane: int, device_ptr: int, max_links: int = 8):
         max_links = _chain_links(max_links)
@@ -1464,9 +1469,7 @@ class Renderer:
 
     def debug_aov_chain_time(self) -> float:
         """Device milliseconds of the last chain kernel launch (surf_debug_aov_chain_time)."""
-        ms = C.c_float()
-        _check(load().surf_debug_aov_chain_time(self._h, C.byref(ms)), "surf_debug_aov_chain_time", self._h)
-        return float(ms.value)
+        return self._debug_ms("surf_debug_aov_chain_time")
 
     def aov_sampled(self, samples: int = 16, first_sample: int = 0, key: str = "instance") -> dict:
         """The sampled feature buffers (surf_read_aov_sampled, which states the
@@ -1478,12 +1481,7 @@ class Renderer:
         the pixel's instance or material keys and their sample counts; see
         matte_coverage).  Cached like aov(), per parameter set."""
         q = aov_sampled_params(samples, first_sample, key)
-        out = {}
-        for k, name in enumerate(AOVS_PLANES):
-            a = np.zeros((len(self.rows), self.width, 4), dtype=np.float32 if k < 3 else np.uint32)
-            _check(load().surf_read_aov_sampled(self._h, C.byref(q), k, _ptr(a)), "surf_read_aov_sampled", self._h)
-            out[name] = a
-        return out
+        return self._read_planes("surf_read_aov_sampled", AOVS_PLANES, 3, C.byref(q))
 
     def copy_aov_sampled_to(self, plane: int, device_ptr: int, **params):
         q = aov_sampled_params(**params)
@@ -1491,9 +1489,7 @@ class Renderer:
 
     def debug_aov_sampled_time(self) -> float:
         """Device milliseconds of the last sampled-planes kernel launch (surf_debug_aov_sampled_time)."""
-        ms = C.c_float()
-        _check(load().surf_debug_aov_sampled_time(self._h, C.byref(ms)), "surf_debug_aov_sampled_time", self._h)
-        return float(ms.value)
+        return self._debug_ms("surf_debug_aov_sampled_time")
 
     def ao(self, samples: int = 16, radius: float = 1.0, first_sample: int = 0, bias: float = 1e-5, source: str = "first_hit",
            max_links: int = 8) -> dict:
@@ -1506,12 +1502,7 @@ class Renderer:
         mask's two words, the open count, 1 on a valid pixel).  Cached like
         aov(), per parameter set."""
         q = ao_params(samples, radius, first_sample, bias, source, max_links)
-        out = {}
-        for k, name in enumerate(AO_PLANES):
-            a = np.zeros((len(self.rows), self.width, 4), dtype=np.float32 if k == 0 else np.uint32)
-            _check(load().surf_read_ao(self._h, C.byref(q), k, _ptr(a)), "surf_read_ao", self._h)
-            out[name] = a
-        return out
+        return self._read_planes("surf_read_ao", AO_PLANES, 1, C.byref(q))
 
     def copy_ao_to(self, plane: int, device_ptr: int, **params):
         """One occlusion plane (index into AO_PLANES) into device memory of rows * width * 16 bytes (surf_copy_ao_device)."""
@@ -1520,9 +1511,7 @@ class Renderer:
 
     def debug_ao_time(self) -> float:
         """Device milliseconds of the last occlusion kernel launch (surf_debug_ao_time)."""
-        ms = C.c_float()
-        _check(load().surf_debug_ao_time(self._h, C.byref(ms)), "surf_debug_ao_time", self._h)
-        return float(ms.value)
+        return self._debug_ms("surf_debug_ao_time")
 
     def set_filter_guides(self, guides: str = "first_hit", max_links: int = 8, samples: int = 16, first_sample: int = 0):
         """Which planes denoise(), denoise_sampled() and denoise_regress() read
@@ -1623,9 +1612,7 @@ class Renderer:
 
     def debug_temporal_time(self) -> float:
         """Device milliseconds of the last k_temporal launch (surf_debug_temporal_time)."""
-        ms = C.c_float()
-        _check(load().surf_debug_temporal_time(self._h, C.byref(ms)), "surf_debug_temporal_time", self._h)
-        return float(ms.value)
+        return self._debug_ms("surf_debug_temporal_time")
 
     def svgf(self, **params) -> np.ndarray:
         """One frame through the variance-guided filter (surf_svgf_accumulate): the
@@ -1692,9 +1679,7 @@ class Renderer:
 
     def debug_firefly_time(self) -> float:
         """Device milliseconds of the last k_firefly launch (surf_debug_firefly_time)."""
-        ms = C.c_float()
-        _check(load().surf_debug_firefly_time(self._h, C.byref(ms)), "surf_debug_firefly_time", self._h)
-        return float(ms.value)
+        return self._debug_ms("surf_debug_firefly_time")
 
     def debug_svgf_time(self) -> list:
         """Device milliseconds of the last svgf run's kernels (surf_debug_svgf_time):
@@ -1876,9 +1861,7 @@ class Renderer:
 
     def debug_robust_time(self) -> float:
         """Device milliseconds of the last k_robust launch (surf_debug_robust_time)."""
-        ms = C.c_float()
-        _check(load().surf_debug_robust_time(self._h, C.byref(ms)), "surf_debug_robust_time", self._h)
-        return float(ms.value)
+        return self._debug_ms("surf_debug_robust_time")
 
     def set_pixel_mask(self, mask):
         """The active-pixel mask of this shard (surf_set_pixel_mask): (rows, W) or flat, nonzero = active; None = every
