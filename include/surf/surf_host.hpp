@@ -439,6 +439,22 @@ public:
     void setSurfelSensorDevice(const void* positionDevice, const void* normalDevice);
     void clearSurfelSensor();
     bool surfelSensor(U32* validTexels = nullptr);
+    /* the light-map atlas (surf_atlas_*, whose header comment defines the three stages) on the renderer's scene.
+     * buildAtlas: the charts' UV layouts rasterized into one surfel per texel of a W x H atlas of its own size:
+     * position, normal (what setSurfelSensor takes when W x H is the renderer's frame), albedo, ids, the summary.
+     * buildAtlasDevice: the same into four planes on the renderer's device (NULL: not wanted).  finishAtlas: an
+     * accumulator-form plane and the build's albedo plane to the light map, its valid bytes into *valid.
+     * dilateAtlas: `iterations` gutter-fill passes; valid is read and replaced. */
+    struct AtlasPlanes {
+        std::vector<F32> position, normal, albedo;
+        std::vector<U32> ids;
+        surf_atlas_summary summary;
+    };
+    AtlasPlanes buildAtlas(const std::vector<surf_atlas_chart>& charts, U32 W, U32 H);
+    surf_atlas_summary buildAtlasDevice(const std::vector<surf_atlas_chart>& charts, U32 W, U32 H, void* positionDevice, void* normalDevice,
+                                        void* albedoDevice, void* idsDevice);
+    std::vector<F32> finishAtlas(U32 W, U32 H, const std::vector<F32>& acc, const std::vector<F32>& albedo, std::vector<uint8_t>* valid = nullptr);
+    std::vector<F32> dilateAtlas(U32 W, U32 H, const std::vector<F32>& rgba, std::vector<uint8_t>& valid, U32 iterations);
     /* builds the mask from the noise estimate and sets it (surf_mask_from_noise); returns the active
      * count.  Needs setSampleSquares(true). */
     U32 maskFromNoise(const surf_adaptive_mask_params& params);

@@ -1939,6 +1939,175 @@ int surf_set_surfel_sensor_device(surf_ctx* ctx, const void* position_device, co
 /* *kind = SURF_SENSOR_CAMERA or SURF_SENSOR_SURFELS; *valid = valid texels (rows*width for the camera); either may be NULL */
 int surf_get_sensor(surf_ctx* ctx, int* kind, uint32_t* valid);
 
+/* ---- the light-map atlas: UV rasterizer to surfels, finish, gutter fill (no reference counterpart) ----
+ * What stands between a mesh with UVs and a light-map texture, around the
+ * surfel sensor above: surf_atlas_build turns the UV layout of charts into one
+ * surfel per texel (the planes surf_set_surfel_sensor takes), surf_atlas_finish
+ * turns the baked accumulator into the texture, surf_atlas_dilate fills the
+ * gutters bilinear sampling reads at chart borders.  The atlas is W x H texels
+ * of its own, whatever the context's frame: the context supplies the device
+ * and the stream (a sharded context serves as well).  Each stage has a device
+ * form and a CPU twin (_host, no context) that agree bit for bit.  All
+ * arithmetic is f32, every operation rounded on its own, nothing contracted,
+ * in the order written.
+ *
+ * 1. surf_atlas_build.  Reads of the desc only triangles, tri_ext,
+ * triangle_count, instances, instance_count, materials, material_count: no BVH
+ * is needed.  Chart k maps the mesh of instance charts[k].instance; that mesh
+ * is the triangles from the instance's tri_offset up to the next larger
+ * tri_offset among the desc's instances, or triangle_count.
+ *
+ * Corner pairing.  A record keeps the reference's pairing (Triangle's
+ * constructor stores OBJ vertex 0 in v1, the extension stores corners in OBJ
+ * order): OBJ corner a is (v1, n0, uv0), corner b is (v0, n1, uv1), corner c
+ * is (v2, n2, uv2).  hu is the weight of v1, hv of v2, w = (1 - hu) - hv of
+ * v0: the Moller-Trumbore weights of the tracer, as in its normal
+ * hu n0 + hv n2 + w n1.
+ *
+ * Texel space.  For chart k and a record's uv (u, v):
+ *   X = (u*scale[0] + offset[0]) * (float)W,  Y = (v*scale[1] + offset[1]) * (float)H.
+ * A, B, C are the results for uv0, uv1, uv2.  Texel (x, y) has the centre
+ * c = ((float)x + 0.5f, (float)y + 0.5f); row y = 0 is v = 0.
+ *
+ * Skipped triangles.  det = (A.x-B.x)*(C.y-B.y) - (A.y-B.y)*(C.x-B.x).  A
+ * triangle with a non-finite coordinate among the six, or with det 0 or
+ * non-finite, is skipped: counted in skipped_triangles, covering nothing.
+ *
+ * Coverage.  For each edge (P, Q) of (A,B), (B,C), (C,A): the endpoints are put
+ * in canonical order (swapped when Q.x < P.x || (Q.x == P.x && Q.y < P.y)),
+ *   e = (Q.x-P.x)*(c.y-P.y) - (Q.y-P.y)*(c.x-P.x),
+ * e is negated if the endpoints were swapped, and negated again if det > 0.
+ * (With A = (0,0), B = (1,0), C = (0,1), det is -1 and the three e at the
+ * interior point (1/4, 1/4) are 1/4, 1/2, 1/4: a triangle with det < 0 has
+ * e >= 0 inside without the last negation, so det > 0 is the sense that
+ * flips.)  The centre is covered iff all three e >= 0 and it lies in the
+ * triangle's bounding box grown by one texel:
+ *   min(A.x,B.x,C.x) - 1.0f <= c.x <= max(A.x,B.x,C.x) + 1.0f, likewise y.
+ * The box is one condition more than "all three e >= 0": it is what the tile
+ * expansion culls by, and stating it makes that culling exact in f32 instead
+ * of an unproved superset.  In exact arithmetic the edge tests imply it.  In
+ * f32 it can exclude only a centre that lies more than one texel outside the
+ * triangle and that rounding in the edge functions admitted all the same,
+ * which takes coordinates of the order of 2^23 texels; a centre within a
+ * texel of a triangle -- every centre near a shared edge or vertex of a mesh
+ * inside the atlas -- is decided by the edge functions alone, so the box drops
+ * no centre between neighbours.  Negation is exact: two
+ * triangles sharing an edge with bit-identical endpoints evaluate the same
+ * number for it with opposite signs, so no centre between them is dropped and a
+ * centre exactly on the edge is covered by both.  A mirrored chart (a negative
+ * scale) covers what its unmirrored twin covers.  Partially covered texels
+ * whose centre is outside are not covered (no conservative rasterization).
+ *
+ * Owner.  Among the triangles covering a centre the lowest key wins; the key is
+ * first[k] + prim, first[k] the sum of the earlier charts' triangle counts,
+ * prim the triangle's index in its mesh.  cover is the number of covering
+ * triangles over all charts.  SURF_ERR_LIMIT when the charts hold 2^32 - 1
+ * triangles or more.
+ *
+ * Surfel of an owned texel.  e1 = A-B, e2 = C-B, q = c-B,
+ *   det' = e1.x*e2.y - e1.y*e2.x,
+ *   hu = (q.x*e2.y - q.y*e2.x)/det',  hv = (e1.x*q.y - e1.y*q.x)/det'
+ * (c = B + hu e1 + hv e2 solved by Cramer's rule; neither is clamped),
+ *   Po = v0 + (hu*(v1-v0) + hv*(v2-v0)) per component,
+ *   P = rows 0..2 of M (Po, 1), each row summed as (m0 x + m1 y) + (m2 z + m3 w),
+ *   N = the tracer's shading normal term for term: no = (hu n0 + hv n2) + w n1,
+ *       n4 = M (no, 0) with the same row sums, nn = (x*x + y*y) + (z*z + w*w)
+ *       over all four, N = n4.xyz * (1.0f / sqrtf(nn)) -- without the flip
+ *       against a ray.  flags bit 0 negates N.  If a component of N is then
+ *       not finite (the interpolated normal vanished), N = 0: the texel is
+ *       owned and never traced.
+ * Planes, 16-byte records, W*H each, row-major:
+ *   position  owned: (P, 1)                                    empty: 0
+ *   normal    owned: (N, 0)                                    empty: 0
+ *   albedo    owned: (albedo, 1); on an emitter -- strength > 0 and a colour
+ *             component > 0, surf_read_aov's test -- (strength * colour, 2)
+ *                                                              empty: 0
+ *   ids       owned: (chart, instance, primitive, cover)       empty: (~0, ~0, ~0, 0)
+ * An empty texel's zero normal is what the surfel sensor treats as invalid.
+ * Summary: covered = texels with cover >= 1, overlapped = texels with
+ * cover >= 2 (an overlapping UV layout is the usual mistake; shared edges that
+ * pass exactly through centres count too), skipped_triangles, triangles (all
+ * charts').
+ * SURF_ERR_INVALID: W or H 0 or above 16384; n_charts 0; a chart whose
+ * instance is out of range, whose instance's transform has a row 3 other than
+ * (0, 0, 0, 1) or offsets out of range; a non-finite scale or offset; a NULL
+ * desc, or NULL or empty triangles, tri_ext, instances or materials.
+ *
+ * Device side.  The result does not depend on the work mapping.  (a) one lane
+ * per triangle computes A, B, C, det and the 8 x 8-texel tiles its clipped
+ * bounding box touches, and one block scans the counts; (b) k_atlas_cover gives
+ * one wave to each (triangle, tile) item, lane l at texel (l & 7, l >> 3),
+ * with atomicMin on a u32 owner plane and atomicAdd on the cover plane -- both
+ * order-independent, so the planes are deterministic; (c) k_atlas_resolve, one
+ * lane per texel, recomputes the owner's surfel and counts the summary with one
+ * atomic per wave.  SURF_ATLAS_MAP=0 (read when the context is created) keeps
+ * the one-lane-per-triangle bounding-box walk as the A/B baseline: the same
+ * atomics, identical planes.  An expansion of 2^32 items or more takes that
+ * walk too.  The call uploads what it reads from the desc into buffers of its
+ * own and frees them. */
+typedef struct {
+    uint32_t instance;
+    uint32_t flags;             /* bit 0: flip the normal */
+    float scale[2], offset[2];
+} surf_atlas_chart;             /* 24 B */
+typedef struct { uint32_t covered, overlapped, skipped_triangles, triangles; } surf_atlas_summary;
+/* the four planes are host pointers, W*H*16 bytes each; any may be NULL, as may summary */
+int surf_atlas_build(surf_ctx* ctx, const surf_scene_desc* desc, const surf_atlas_chart* charts, uint32_t n_charts, uint32_t W, uint32_t H,
+                     float* position, float* normal, float* albedo, uint32_t* ids, surf_atlas_summary* summary);
+/* the same with the four planes device pointers on the context's device (desc, charts and summary stay on the host) */
+int surf_atlas_build_device(surf_ctx* ctx, const surf_scene_desc* desc, const surf_atlas_chart* charts, uint32_t n_charts, uint32_t W,
+                            uint32_t H, void* position_device, void* normal_device, void* albedo_device, void* ids_device,
+                            surf_atlas_summary* summary);
+/* the CPU twin */
+int surf_atlas_build_host(const surf_scene_desc* desc, const surf_atlas_chart* charts, uint32_t n_charts, uint32_t W, uint32_t H,
+                          float* position, float* normal, float* albedo, uint32_t* ids, surf_atlas_summary* summary);
+/* Charts on a grid, a pure host function: entry i of the list (instances NULL: instance i) gets cell i of a g x g grid,
+ * g the smallest integer with g*g >= n, column i % g, row i / g.  Cell (col, row) spans texels
+ * [col*W/g, (col+1)*W/g) x [row*H/g, (row+1)*H/g) in integer division, shrunk by margin_texels on every side to
+ * [lo, hi); the mesh's [0,1]^2 maps onto it: scale = (float)(hi - lo) / (float)side, offset = (float)lo / (float)side per
+ * axis (side W or H), flags 0.  SURF_ERR_INVALID when n is 0, out is NULL, W or H is 0 or above 16384, or the margins
+ * leave nothing of a cell. */
+int surf_atlas_grid_charts(uint32_t n_instances, const uint32_t* instances, uint32_t W, uint32_t H, uint32_t margin_texels,
+                           surf_atlas_chart* out);
+/* 2. surf_atlas_finish: accumulator to light-map texture, one lane per texel.
+ *   albedo.w == 2 (an emitter shows itself):  out = (albedo.rgb, 1), valid = 1
+ *   else acc.w > 0 and albedo.w == 1:         out = ((acc.r/acc.w)*albedo.r, (acc.g/acc.w)*albedo.g, (acc.b/acc.w)*albedo.b, 1), valid = 1
+ *   otherwise:                                out = 0, valid = 0
+ * acc is any plane in accumulator form, (sum of rgb, weight): surf_read_accumulator's, surf_robust_accumulator's out_acc,
+ * or a filter's output image with w set to 1 where it is meaningful (a filtered mean is the sum of one sample).  albedo is
+ * the build's plane.  out_valid is a byte per texel.  W*H records each; SURF_ERR_INVALID on a NULL argument or a size
+ * outside 1..16384. */
+int surf_atlas_finish(surf_ctx* ctx, uint32_t W, uint32_t H, const float* acc, const float* albedo, float* out_rgba, uint8_t* out_valid);
+int surf_atlas_finish_device(surf_ctx* ctx, uint32_t W, uint32_t H, const void* acc_device, const void* albedo_device, void* out_rgba_device,
+                             void* out_valid_device);
+int surf_atlas_finish_host(uint32_t W, uint32_t H, const float* acc, const float* albedo, float* out_rgba, uint8_t* out_valid);
+/* 3. surf_atlas_dilate: gutter fill.  Each iteration reads one buffer and writes another: a valid texel is copied as it
+ * is; an invalid texel with at least one valid 8-neighbour inside the image becomes the mean of those neighbours -- per
+ * channel the sum starts at 0 and runs in the order N, S, W, E, NW, NE, SW, SE (N is y - 1), then is divided by
+ * (float)count, w = 1 -- and is valid from the next iteration on; an invalid texel with no valid neighbour is 0 and
+ * stays invalid.  iterations 0..64; 0 copies.  The iterations are queued back to back with no trip to the host; the last
+ * one writes the caller's buffers.  An output may not be its own input.  SURF_ERR_INVALID otherwise as for finish. */
+int surf_atlas_dilate(surf_ctx* ctx, uint32_t W, uint32_t H, const float* rgba, const uint8_t* valid, uint32_t iterations, float* out_rgba,
+                      uint8_t* out_valid);
+int surf_atlas_dilate_device(surf_ctx* ctx, uint32_t W, uint32_t H, const void* rgba_device, const void* valid_device, uint32_t iterations,
+                             void* out_rgba_device, void* out_valid_device);
+int surf_atlas_dilate_host(uint32_t W, uint32_t H, const float* rgba, const uint8_t* valid, uint32_t iterations, float* out_rgba,
+                           uint8_t* out_valid);
+/* The chain on the device with buffers of the library's own on the context's device: surf_atlas_build_device at the
+ * context's width x height, surf_set_surfel_sensor_device from its planes, surf_clear_accumulator, surf_render(frames,
+ * first_sample_index, max_segments, samples_per_frame), the accumulator copied, the camera sensor restored (also when
+ * the render failed), surf_atlas_finish_device, surf_atlas_dilate_device, then lightmap (W*H*16 B), valid (W*H bytes)
+ * and, where not NULL, accumulator (W*H*16 B) and summary copied to the host.  The context's accumulator keeps the bake.
+ * Needs a scene and a camera, as surf_render does, and a context that owns every row.  SURF_ERR_INVALID: a sharded
+ * context, frames or samples_per_frame 0, iterations above 64, a NULL lightmap or valid, and whatever the build refuses. */
+int surf_atlas_bake(surf_ctx* ctx, const surf_scene_desc* desc, const surf_atlas_chart* charts, uint32_t n_charts, uint32_t frames,
+                    uint32_t first_sample_index, uint32_t max_segments, uint32_t samples_per_frame, uint32_t iterations, float* lightmap,
+                    uint8_t* valid, float* accumulator, surf_atlas_summary* summary);
+/* device times of the context's last runs, in ms: [0] the build's setup, scan and item-count readback, [1] its cover
+ * kernel, [2] its resolve, [3] the last finish, [4] the last dilate (all iterations); a build zeroes [3] and [4].
+ * *tile_map (may be NULL): 1 when the last build ran the tile mapping. */
+int surf_debug_atlas_time(surf_ctx* ctx, float* kernel_ms, uint32_t count, uint32_t* tile_map);
+
 /* ---- traversal entry points (kernel-level parity tests) ----
  * n world-space rays, o/d 3 floats each.  closest: depth starts at 1e30;
  * writes t,u,v (floats) and inst,prim (u32, ~0 on miss).  any: tmax per ray,

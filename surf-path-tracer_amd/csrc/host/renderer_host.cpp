@@ -349,6 +349,46 @@ void WaveFrontRenderer::setSurfelSensorDevice(const void* positionDevice, const 
     check(surf_set_surfel_sensor_device(m_ctx, positionDevice, normalDevice), m_ctx, "surf_set_surfel_sensor_device");
 }
 
+WaveFrontRenderer::AtlasPlanes WaveFrontRenderer::buildAtlas(const std::vector<surf_atlas_chart>& charts, U32 W, U32 H) {
+    const surf_scene_desc desc = m_scene.descriptor();
+    AtlasPlanes out{};
+    /* sized only for an atlas the library accepts: it refuses the others before it writes */
+    const size_t n = W && H && W <= 16384 && H <= 16384 ? (size_t)W * H * 4 : 4;
+    out.position.resize(n); out.normal.resize(n); out.albedo.resize(n); out.ids.resize(n);
+    check(surf_atlas_build(m_ctx, &desc, charts.data(), (U32)charts.size(), W, H, out.position.data(), out.normal.data(), out.albedo.data(),
+                           out.ids.data(), &out.summary), m_ctx, "surf_atlas_build");
+    return out;
+}
+
+surf_atlas_summary WaveFrontRenderer::buildAtlasDevice(const std::vector<surf_atlas_chart>& charts, U32 W, U32 H, void* positionDevice,
+                                                       void* normalDevice, void* albedoDevice, void* idsDevice) {
+    const surf_scene_desc desc = m_scene.descriptor();
+    surf_atlas_summary s{};
+    check(surf_atlas_build_device(m_ctx, &desc, charts.data(), (U32)charts.size(), W, H, positionDevice, normalDevice, albedoDevice, idsDevice, &s),
+          m_ctx, "surf_atlas_build_device");
+    return s;
+}
+
+std::vector<F32> WaveFrontRenderer::finishAtlas(U32 W, U32 H, const std::vector<F32>& acc, const std::vector<F32>& albedo, std::vector<uint8_t>* valid) {
+    const size_t npx = (size_t)W * H;
+    if (acc.size() != npx * 4 || albedo.size() != npx * 4) throw std::runtime_error("finishAtlas: acc and albedo are not W*H*4 floats each");
+    std::vector<F32> out(npx * 4);
+    std::vector<uint8_t> v(npx);
+    check(surf_atlas_finish(m_ctx, W, H, acc.data(), albedo.data(), out.data(), v.data()), m_ctx, "surf_atlas_finish");
+    if (valid) valid->swap(v);
+    return out;
+}
+
+std::vector<F32> WaveFrontRenderer::dilateAtlas(U32 W, U32 H, const std::vector<F32>& rgba, std::vector<uint8_t>& valid, U32 iterations) {
+    const size_t npx = (size_t)W * H;
+    if (rgba.size() != npx * 4 || valid.size() != npx) throw std::runtime_error("dilateAtlas: rgba is not W*H*4 floats or valid not W*H bytes");
+    std::vector<F32> out(npx * 4);
+    std::vector<uint8_t> v(npx);
+    check(surf_atlas_dilate(m_ctx, W, H, rgba.data(), valid.data(), iterations, out.data(), v.data()), m_ctx, "surf_atlas_dilate");
+    valid.swap(v);
+    return out;
+}
+
 void WaveFrontRenderer::clearSurfelSensor() { check(surf_set_surfel_sensor(m_ctx, nullptr, nullptr), m_ctx, "surf_set_surfel_sensor"); }
 
 bool WaveFrontRenderer::surfelSensor(U32* validTexels) {

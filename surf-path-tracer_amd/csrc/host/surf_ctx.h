@@ -286,6 +286,12 @@ struct surf_ctx {
     PlaneGroup<1> dpHh{"the bloom's plane"};
     PlaneGroup<1> dpOut{"the display stage's words"};
     StageTimer<4> dpTime;          /* meter, scale, blur, pack of the last run (surf_debug_display_time) */
+    /* the light-map atlas (surf_atlas_*, host/atlas.hip) keeps no buffer on the context: atlasTileMap, the cover kernel's
+     * work mapping (SURF_ATLAS_MAP: 1 one wave per (triangle, 8 x 8 tile), 0 one lane per triangle; the planes are the same);
+     * atTiles: the last build ran the tile mapping */
+    bool atlasTileMap = true;
+    bool atTiles = false;
+    StageTimer<5> atTime;          /* setup + scan, cover, resolve of the last build; the last finish; the last dilate (surf_debug_atlas_time) */
     /* the active-pixel mask (surf_set_pixel_mask, surf_mask_from_noise; host/adaptive.hip):
      * pmOn: a mask that leaves some pixel out is set (an all-ones mask is "no
      * mask"); then pmMask holds its npx bytes, pmList the pmActive ascending
@@ -456,6 +462,8 @@ void freeRegress(surf_ctx* c);
 void freeErrorMask(surf_ctx* c);
 /* defined in host/display.hip: surf_destroy's part for the display stage's images */
 void freeDisplay(surf_ctx* c);
+/* defined in host/atlas.hip: surf_destroy's part for the atlas stage's timer */
+void freeAtlas(surf_ctx* c);
 
 #define SURF_CHECK(ctx, call)                                                             \
     do {                                                                                  \

@@ -1263,6 +1263,7 @@ int createCtx(int dev, uint32_t w, uint32_t h, std::vector<uint32_t> rows, surf_
     if (const char* e = std::getenv("SURF_NLM_LDS")) c->nlStaged = std::atoi(e) != 0;
     if (const char* e = std::getenv("SURF_REGRESS_LDS")) c->rgStaged = std::atoi(e) != 0;
     if (const char* e = std::getenv("SURF_AO_MAP")) c->aoRayMap = e[0] != '0';
+    if (const char* e = std::getenv("SURF_ATLAS_MAP")) c->atlasTileMap = e[0] != '0';
     c->width = w;
     c->height = h;
     c->rows = std::move(rows);
@@ -1351,6 +1352,7 @@ void surf_destroy(surf_ctx* c) {
     freeRegress(c);
     freeErrorMask(c);
     freeDisplay(c);
+    freeAtlas(c);
     if (c->dRows) (void)hipFree(c->dRows);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
     if (c->ev1) (void)hipEventDestroy(c->ev1);

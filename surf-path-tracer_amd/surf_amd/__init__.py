@@ -35,6 +35,10 @@ Mirrors the reference interface for the hot path:
     .render_adaptive_nlm()     the adaptive loop driven by that error estimate (.mask_from_nlm() builds its mask); returns the filtered image
     .display()                 the display stage on the accumulator: metered exposure, bloom, tone curve, sRGB, dither -> RGBA8;
                                .display_image(img) the same on any float RGBA image, display_image_host(img) its CPU twin
+    .bake(pos, nrm, frames)    the surfel sensor: path-traced irradiance at the caller's texels
+    .atlas_build(scene, charts, W, H)  the light-map atlas: charts' UV layouts rasterized to one surfel per texel;
+                               .atlas_finish / .atlas_dilate turn the baked accumulator into the texture and fill its gutters,
+                               .bake_atlas(scene, charts, frames) runs all of it on the device; atlas_*_host are the CPU twins
 """
 from __future__ import annotations
 
@@ -251,6 +255,20 @@ class AoParams(C.Structure):
                 ("source", C.c_uint32), ("max_links", C.c_uint32), ("reserved", C.c_uint32 * 2)]
 
 
+class AtlasChart(C.Structure):
+    """surf_atlas_chart (24 B): the instance whose mesh the chart maps, flags (bit 0: flip the normal), and where the mesh's
+    uv lands in the atlas's [0,1]^2: uv * scale + offset."""
+    _fields_ = [("instance", C.c_uint32), ("flags", C.c_uint32), ("scale", C.c_float * 2), ("offset", C.c_float * 2)]
+
+
+class AtlasSummary(C.Structure):
+    """surf_atlas_summary: texels with cover >= 1, texels with cover >= 2, the triangles skipped, the triangles of all charts."""
+    _fields_ = [("covered", C.c_uint32), ("overlapped", C.c_uint32), ("skipped_triangles", C.c_uint32), ("triangles", C.c_uint32)]
+
+    def as_dict(self) -> dict:
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
 _lib = None
 
 # Byte sizes of the reference records (include/surf_hip.h static_asserts).
@@ -408,6 +426,16 @@ def load() -> C.CDLL:
         "surf_display_image_host": ([U32, U32, P, C.POINTER(DisplayParams), P, C.POINTER(DisplayMeterResult)], I32),
         "surf_display_srgb_table": ([P], I32), "surf_display_bayer8": ([P], I32),
         "surf_debug_display_time": ([P, C.POINTER(F), U32], I32),
+        "surf_atlas_build": ([P, C.POINTER(SceneDesc), P, U32, U32, U32, P, P, P, P, C.POINTER(AtlasSummary)], I32),
+        "surf_atlas_build_device": ([P, C.POINTER(SceneDesc), P, U32, U32, U32, P, P, P, P, C.POINTER(AtlasSummary)], I32),
+        "surf_atlas_build_host": ([C.POINTER(SceneDesc), P, U32, U32, U32, P, P, P, P, C.POINTER(AtlasSummary)], I32),
+        "surf_atlas_grid_charts": ([U32, P, U32, U32, U32, P], I32),
+        "surf_atlas_finish": ([P, U32, U32, P, P, P, P], I32), "surf_atlas_finish_device": ([P, U32, U32, P, P, P, P], I32),
+        "surf_atlas_finish_host": ([U32, U32, P, P, P, P], I32),
+        "surf_atlas_dilate": ([P, U32, U32, P, P, U32, P, P], I32), "surf_atlas_dilate_device": ([P, U32, U32, P, P, U32, P, P], I32),
+        "surf_atlas_dilate_host": ([U32, U32, P, P, U32, P, P], I32),
+        "surf_atlas_bake": ([P, C.POINTER(SceneDesc), P, U32, U32, U32, U32, U32, U32, P, P, P, C.POINTER(AtlasSummary)], I32),
+        "surf_debug_atlas_time": ([P, C.POINTER(F), U32, C.POINTER(U32)], I32),
         "surf_mesh_data": ([P, C.POINTER(P), C.POINTER(P), C.POINTER(U32)], I32),
         "surf_mesh_destroy": ([P], None),
         "surf_ref_sinf": ([F], F), "surf_ref_cosf": ([F], F), "surf_ref_expf": ([F], F),
@@ -1174,6 +1202,117 @@ def error_mask_image_host(out, err, acc, **params):
     _check(load().surf_error_mask_image_host(w, h, _ptr(o), _ptr(e), _ptr(a), C.byref(p), _ptr(mask), _ptr(lst), C.byref(n)),
            "surf_error_mask_image_host")
     return mask, lst[:n.value].copy()
+
+
+ATLAS_PLANES = ("position", "normal", "albedo", "ids")   # surf_atlas_build's planes
+ATLAS_MAX_SIDE = 16384
+ATLAS_MAX_ITERATIONS = 64
+
+
+def atlas_chart(instance: int, scale=(1.0, 1.0), offset=(0.0, 0.0), flip: bool = False) -> AtlasChart:
+    """One surf_atlas_chart."""
+    ch = AtlasChart()
+    ch.instance, ch.flags = int(instance), 1 if flip else 0
+    ch.scale[0], ch.scale[1] = float(scale[0]), float(scale[1])
+    ch.offset[0], ch.offset[1] = float(offset[0]), float(offset[1])
+    return ch
+
+
+def atlas_chart_array(charts):
+    """A ctypes array of the charts (AtlasChart records, or (instance, flags, sx, sy, ox, oy) rows) and their count."""
+    rows = list(charts)
+    arr = (AtlasChart * max(len(rows), 1))()
+    for k, ch in enumerate(rows):
+        if isinstance(ch, AtlasChart):
+            arr[k] = ch
+        else:
+            i, f, sx, sy, ox, oy = ch
+            arr[k] = atlas_chart(i, (sx, sy), (ox, oy))
+            arr[k].flags = int(f)
+    return arr, len(rows)
+
+
+def _atlas_desc(scene_or_desc) -> SceneDesc:
+    return scene_or_desc.desc() if isinstance(scene_or_desc, Scene) else scene_or_desc
+
+
+def _atlas_size(what: str, W: int, H: int):
+    if not (isinstance(W, (int, np.integer)) and isinstance(H, (int, np.integer))) or W < 0 or H < 0 or W >= 2 ** 32 or H >= 2 ** 32:
+        raise ValueError(f"{what}: W x H = {W!r} x {H!r} is not a pair of 32-bit sizes")
+
+
+def _atlas_out(W: int, H: int) -> dict:
+    out = {k: np.zeros((H, W, 4), np.float32) for k in ATLAS_PLANES[:3]}
+    out["ids"] = np.zeros((H, W, 4), np.uint32)
+    return out
+
+
+def atlas_grid_charts(instances, W: int, H: int, margin_texels: int = 0) -> list:
+    """Charts on a grid (surf_atlas_grid_charts): `instances` is a list of instance indices, or a count n for instances
+    0..n-1; entry i gets cell i of a g x g grid, g = ceil(sqrt(n)), shrunk by margin_texels on every side."""
+    _atlas_size("atlas_grid_charts", W, H)
+    ids = None if isinstance(instances, (int, np.integer)) else np.ascontiguousarray(instances, dtype=np.uint32)
+    n = int(instances) if ids is None else len(ids)
+    arr = (AtlasChart * max(n, 1))()
+    _check(load().surf_atlas_grid_charts(n, None if ids is None else _ptr(ids), W, H, margin_texels, arr), "surf_atlas_grid_charts")
+    return [AtlasChart.from_buffer_copy(arr[k]) for k in range(n)]
+
+
+def atlas_build_host(scene_or_desc, charts, W: int, H: int) -> dict:
+    """The CPU twin of Renderer.atlas_build (surf_atlas_build_host): the four planes (H, W, 4) and the summary."""
+    _atlas_size("atlas_build_host", W, H)
+    d, (arr, n), s = _atlas_desc(scene_or_desc), atlas_chart_array(charts), AtlasSummary()
+    ok = 0 < W <= ATLAS_MAX_SIDE and 0 < H <= ATLAS_MAX_SIDE
+    out = _atlas_out(W if ok else 1, H if ok else 1)
+    _check(load().surf_atlas_build_host(C.byref(d), arr, n, W, H, *(_ptr(out[k]) for k in ATLAS_PLANES), C.byref(s)), "surf_atlas_build_host")
+    out["summary"] = s.as_dict()
+    return out
+
+
+def _atlas_plane(what: str, a, H: int, W: int, dtype=np.float32) -> np.ndarray:
+    """A caller's (H, W, 4) plane (or (H, W) bytes) checked before the library sees it."""
+    a = np.asarray(a)
+    shape = (H, W, 4) if dtype == np.float32 else (H, W)
+    if a.dtype != dtype:
+        raise ValueError(f"{what} is {a.dtype}, not {np.dtype(dtype).name}")
+    if a.shape != shape:
+        raise ValueError(f"{what} has shape {a.shape}, not {shape}")
+    return np.ascontiguousarray(a)
+
+
+def _atlas_finish_args(acc, albedo):
+    acc = np.asarray(acc)
+    if acc.ndim != 3 or acc.shape[2] != 4:
+        raise ValueError(f"atlas_finish: acc has shape {acc.shape}, not (H, W, 4)")
+    H, W = acc.shape[:2]
+    a, b = _atlas_plane("atlas_finish: acc", acc, H, W), _atlas_plane("atlas_finish: albedo", albedo, H, W)
+    return W, H, a, b, np.zeros((H, W, 4), np.float32), np.zeros((H, W), np.uint8)
+
+
+def atlas_finish_host(acc, albedo):
+    """(light map (H, W, 4), valid (H, W) uint8) from an accumulator-form plane and the build's albedo plane
+    (surf_atlas_finish_host, the CPU twin of Renderer.atlas_finish)."""
+    W, H, a, b, out, valid = _atlas_finish_args(acc, albedo)
+    _check(load().surf_atlas_finish_host(W, H, _ptr(a), _ptr(b), _ptr(out), _ptr(valid)), "surf_atlas_finish_host")
+    return out, valid
+
+
+def _atlas_dilate_args(rgba, valid, iterations):
+    rgba = np.asarray(rgba)
+    if rgba.ndim != 3 or rgba.shape[2] != 4:
+        raise ValueError(f"atlas_dilate: rgba has shape {rgba.shape}, not (H, W, 4)")
+    H, W = rgba.shape[:2]
+    a, v = _atlas_plane("atlas_dilate: rgba", rgba, H, W), _atlas_plane("atlas_dilate: valid", valid, H, W, np.uint8)
+    if not 0 <= int(iterations) <= ATLAS_MAX_ITERATIONS:
+        raise ValueError(f"atlas_dilate: iterations {iterations} outside 0..{ATLAS_MAX_ITERATIONS}")
+    return W, H, a, v, np.zeros((H, W, 4), np.float32), np.zeros((H, W), np.uint8)
+
+
+def atlas_dilate_host(rgba, valid, iterations: int = 2):
+    """(rgba, valid) after `iterations` gutter-fill passes (surf_atlas_dilate_host, the CPU twin of Renderer.atlas_dilate)."""
+    W, H, a, v, out, ov = _atlas_dilate_args(rgba, valid, iterations)
+    _check(load().surf_atlas_dilate_host(W, H, _ptr(a), _ptr(v), int(iterations), _ptr(out), _ptr(ov)), "surf_atlas_dilate_host")
+    return out, ov
 
 
 def obj_load(path: str, threads: int = 0) -> tuple[np.ndarray, np.ndarray]:
@@ -2022,6 +2161,87 @@ class Renderer:
         ms = (C.c_float * 4)()
         _check(load().surf_debug_display_time(self._h, ms, 4), "surf_debug_display_time", self._h)
         return [float(v) for v in ms]
+
+    def atlas_build(self, scene_or_desc, charts, W: int, H: int) -> dict:
+        """Rasterizes the charts' UV layouts into one surfel per texel of a W x H atlas (surf_atlas_build, which defines
+        it): position, normal, albedo (H, W, 4) float32, ids (H, W, 4) uint32 = (chart, instance, primitive, cover), and
+        the summary.  scene_or_desc: a Scene or a SceneDesc (only triangles, tri_ext, instances and materials are read).
+        The atlas's size is its own; position and normal are what set_surfel_sensor / bake take."""
+        _atlas_size("atlas_build", W, H)
+        d, (arr, n), s = _atlas_desc(scene_or_desc), atlas_chart_array(charts), AtlasSummary()
+        ok = 0 < W <= ATLAS_MAX_SIDE and 0 < H <= ATLAS_MAX_SIDE
+        out = _atlas_out(W if ok else 1, H if ok else 1)
+        _check(load().surf_atlas_build(self._h, C.byref(d), arr, n, W, H, *(_ptr(out[k]) for k in ATLAS_PLANES), C.byref(s)),
+               "surf_atlas_build", self._h)
+        out["summary"] = s.as_dict()
+        return out
+
+    def atlas_build_to(self, scene_or_desc, charts, W: int, H: int, position_ptr: int = 0, normal_ptr: int = 0, albedo_ptr: int = 0,
+                       ids_ptr: int = 0) -> dict:
+        """The same into planes on this context's device, W*H*16 bytes each, 0: not wanted (surf_atlas_build_device);
+        returns the summary."""
+        _atlas_size("atlas_build_to", W, H)
+        d, (arr, n), s = _atlas_desc(scene_or_desc), atlas_chart_array(charts), AtlasSummary()
+        ptrs = [C.c_void_p(p or None) for p in (position_ptr, normal_ptr, albedo_ptr, ids_ptr)]
+        _check(load().surf_atlas_build_device(self._h, C.byref(d), arr, n, W, H, *ptrs, C.byref(s)), "surf_atlas_build_device", self._h)
+        return s.as_dict()
+
+    def atlas_finish(self, acc, albedo):
+        """(light map (H, W, 4), valid (H, W) uint8) from an accumulator-form plane -- accumulator(), robust()'s, a filter's
+        output with w = 1 -- and the build's albedo plane (surf_atlas_finish)."""
+        W, H, a, b, out, valid = _atlas_finish_args(acc, albedo)
+        _check(load().surf_atlas_finish(self._h, W, H, _ptr(a), _ptr(b), _ptr(out), _ptr(valid)), "surf_atlas_finish", self._h)
+        return out, valid
+
+    def atlas_finish_to(self, W: int, H: int, acc_ptr: int, albedo_ptr: int, out_ptr: int, valid_ptr: int):
+        """The same between planes on this context's device (surf_atlas_finish_device); valid is W*H bytes."""
+        _atlas_size("atlas_finish_to", W, H)
+        _check(load().surf_atlas_finish_device(self._h, W, H, *(C.c_void_p(p or None) for p in (acc_ptr, albedo_ptr, out_ptr, valid_ptr))),
+               "surf_atlas_finish_device", self._h)
+
+    def atlas_dilate(self, rgba, valid, iterations: int = 2):
+        """(rgba, valid) after `iterations` (0..64) gutter-fill passes: an invalid texel becomes the mean of its valid
+        8-neighbours (surf_atlas_dilate)."""
+        W, H, a, v, out, ov = _atlas_dilate_args(rgba, valid, iterations)
+        _check(load().surf_atlas_dilate(self._h, W, H, _ptr(a), _ptr(v), int(iterations), _ptr(out), _ptr(ov)), "surf_atlas_dilate", self._h)
+        return out, ov
+
+    def atlas_dilate_to(self, W: int, H: int, rgba_ptr: int, valid_ptr: int, iterations: int, out_ptr: int, out_valid_ptr: int):
+        """The same between planes on this context's device (surf_atlas_dilate_device)."""
+        _atlas_size("atlas_dilate_to", W, H)
+        _check(load().surf_atlas_dilate_device(self._h, W, H, C.c_void_p(rgba_ptr or None), C.c_void_p(valid_ptr or None), int(iterations),
+                                               C.c_void_p(out_ptr or None), C.c_void_p(out_valid_ptr or None)),
+               "surf_atlas_dilate_device", self._h)
+
+    def debug_atlas_time(self) -> dict:
+        """Device milliseconds of the last atlas runs (surf_debug_atlas_time): the build's setup (with the scan and the
+        item count's readback), cover and resolve, the last finish, the last dilate; and whether the build ran the tile mapping."""
+        ms, tiles = (C.c_float * 5)(), C.c_uint32()
+        _check(load().surf_debug_atlas_time(self._h, ms, 5, C.byref(tiles)), "surf_debug_atlas_time", self._h)
+        names = ("setup", "cover", "resolve", "finish", "dilate")
+        return {**{k: float(v) for k, v in zip(names, ms)}, "tile_map": bool(tiles.value)}
+
+    def bake_atlas(self, scene, charts, frames: int, iterations: int = 2, spp: int = 1, max_segments: int = 0,
+                   first_sample: int = 0) -> dict:
+        """A light map of this context's frame size with no host trip between the stages (surf_atlas_bake, in buffers of
+        the library's own on this context's device): atlas_build on the device, the surfel sensor set from its planes, the
+        accumulator cleared, `frames` frames rendered, finished and dilated `iterations` times.  The context must own every row (no shard); its width x height is the atlas.  Returns
+        lightmap (H, W, 4), valid (H, W), accumulator (H, W, 4) and the build's summary; the camera sensor is restored, the
+        accumulator keeps the bake."""
+        W, H = self.width, self.height
+        if len(self.rows) != H:
+            raise ValueError("bake_atlas: a row shard cannot bake an atlas: the context must own every row")
+        if not 0 <= int(iterations) <= ATLAS_MAX_ITERATIONS:
+            raise ValueError(f"bake_atlas: iterations {iterations} outside 0..{ATLAS_MAX_ITERATIONS}")
+        if int(frames) < 1 or int(spp) < 1:
+            raise ValueError("bake_atlas: frames and spp must be at least 1")
+        d, (arr, n), s = _atlas_desc(scene), atlas_chart_array(charts), AtlasSummary()
+        out = {"lightmap": np.zeros((H, W, 4), np.float32), "valid": np.zeros((H, W), np.uint8), "accumulator": np.zeros((H, W, 4), np.float32)}
+        _check(load().surf_atlas_bake(self._h, C.byref(d), arr, n, int(frames), first_sample, max_segments, int(spp), int(iterations),
+                                      _ptr(out["lightmap"]), _ptr(out["valid"]), _ptr(out["accumulator"]), C.byref(s)),
+               "surf_atlas_bake", self._h)
+        out["summary"] = s.as_dict()
+        return out
 
     def finalize_weighted(self, display: bool = False) -> np.ndarray:
         """RGBA8 with each pixel divided by its own sample count (surf_finalize_rgba8_weighted)."""
